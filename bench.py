@@ -109,6 +109,54 @@ def make_volume_gpu(torch, gdims, bdims, seed, kind="rm_volume"):
     return out.reshape(I * J * K, Z, Y, X)
 
 
+DUMP_SEED = 20240607
+DUMP_DECODED_SAMPLES = 6 << 20      # float32: 24 MiB
+DUMP_TREE_SAMPLES = 4 << 20         # float32: 16 MiB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, torch, bset, decoded):
+    """--dump-outputs: what one timed step hands its caller -- the decoded volume (`decoded`, uint8 on the device) and
+    the compressed trees of `bset` -- as float32 / float64 .npy files, so that two builds can be compared output for
+    output.  Outputs larger than the budget are sampled at positions drawn from a fixed seed (the same on every run)."""
+    rng = np.random.default_rng(DUMP_SEED)
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:   # a directory of run outputs: never source
+            f.write("*\n")
+    B = bset.num_bricks
+    # the decoded volume: every voxel, or a fixed sample of voxel indices (sorted: coalesced gather)
+    N = decoded.numel()
+    if N <= DUMP_DECODED_SAMPLES:
+        dec = decoded.cpu().numpy()
+    else:
+        idx = np.unique(rng.integers(0, N, DUMP_DECODED_SAMPLES, dtype=np.int64))
+        dec = decoded[torch.from_numpy(idx).to(decoded.device)].cpu().numpy()
+    # per brick: the tree's shape, its distance map and (a sample of) its stream bytes
+    infos = [bset.info(b) for b in range(B)]
+    info = np.array([[i["num_active_nodes"], i["tree_bytes"], i["max_tree_depth"], i["orig_tree_depth"]]
+                     for i in infos], np.float64)
+    dmap = np.concatenate([bset.distance_map(b) for b in range(B)])
+    sizes = np.array([i["tree_bytes"] for i in infos], np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    T = int(offs[-1])
+    pos = None if T <= DUMP_TREE_SAMPLES else np.unique(rng.integers(0, T, DUMP_TREE_SAMPLES, dtype=np.int64))
+    tree = []
+    for b in range(B):
+        t = bset.tree(b)
+        if pos is not None:
+            lo, hi = np.searchsorted(pos, [offs[b], offs[b + 1]])
+            t = t[pos[lo:hi] - offs[b]]
+        tree.append(t)
+    arrays = {"decoded": dec.astype(np.float32), "tree_info": info, "distance_map": dmap.astype(np.float32),
+              "tree": np.concatenate(tree).astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: run the same command line under torch.distributed.run
     (one rank per GPU, rendezvous on 127.0.0.1) as a child process and pass its output and exit code on."""
@@ -408,7 +456,12 @@ def main():
     ap.add_argument("--no-composite", action="store_true",
                     help="N > 1: skip the sort-last composited 1080p frames over RCCL (they run by default, after the timed "
                          "region, under the process group's timeout: a collective that fails ends the run non-zero)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0's decoded volume and "
+                         "compressed trees, sampled from a fixed seed beyond 64 MB in all) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks as children (torch.distributed.run) BEFORE this
@@ -547,6 +600,9 @@ def main():
         tt = torch.tensor([dt], device="cpu" if rehearsal else "cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) % NS           # the set (and output volume) of the last timed step
+        dump_outputs(args.dump_outputs, torch, sets[last], outs[last])
     total_vox = float(V) * (B_total if strong else B * world) * args.steps
     value = total_vox / dt / 1e6
     # the same steps without the contiguous copy of the compressed stream at the end of build() (vr_brickset_set_compaction:

@@ -35,6 +35,33 @@ def test_bench_prints_one_contract_line(pipeline):
     assert cb["host_cores"] >= 1 and cb["all_cores"]["threads_used"] >= 1 and cb["all_cores"]["value"] > 0
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs: the last timed step's decoded volume and trees as float .npy files (at most 64 MB in all), the
+    same from run to run with the same arguments; --steps sets the number of timed steps."""
+    import numpy as np
+    dumps = []
+    for r in range(2):
+        d = tmp_path / ("run%d" % r)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--bricks", "6", "--steps", "4", "--warmup", "1", "--no-cpu",
+               "--no-stream", "--no-extra-timing", "--pipeline", "3", "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+        j = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+        assert j["steps"] == 4 and j["ms_per_step"] > 0
+        files = sorted(f for f in os.listdir(d) if f.endswith(".npy"))
+        assert files == ["decoded.npy", "distance_map.npy", "tree.npy", "tree_info.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(d / f) for f in files})
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.array_equal(a, dumps[1][f]), f
+    info = dumps[0]["tree_info.npy"]
+    assert info.shape == (6, 4) and (info[:, 1] == np.ceil(info[:, 0] / 4)).all()      # tree bytes = ceil(tokens / 4)
+    assert dumps[0]["distance_map.npy"].size == (info[:, 2] + 1).sum()
+    assert dumps[0]["decoded.npy"].size > 0 and dumps[0]["tree.npy"].size > 0
+
+
 def test_gpus_flag_starts_that_many_ranks():
     """`python bench.py --gpus 2` with no launcher: the parent starts two ranks itself (torch.distributed.run on
     127.0.0.1) before touching a GPU.  VRHIP_BENCH_DRYRUN=1 keeps the ranks off the GPU (gloo), so the launch,
