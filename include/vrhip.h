@@ -136,6 +136,19 @@ vr_status vr_brickset_get_packed4(vr_brickset *bs, int32_t brick, uint8_t *dst_h
  * ancestor at depth min(cut_depth, depth of its terminal node).  Asynchronous on `stream`. */
 vr_status vr_brickset_decode(vr_brickset *bs, int32_t cut_depth, uint8_t *out_dev, void *stream);
 
+/* Per-brick progressive decode (view-dependent level of detail).  cuts_host[b] for every brick b of the set:
+ *   -1                      brick b is skipped: its X*Y*Z bytes of out_dev are left untouched
+ *   0 .. max_tree_depth     brick b is decoded exactly as vr_brickset_decode(bs, cuts_host[b], ...) decodes it
+ * Any other value -> VR_ERR_INVALID (nothing launched).  Asynchronous on `stream`; cuts_host may be reused as soon
+ * as the call returns.  The bricks are grouped by the kernel a uniform decode at their cut would use, one launch
+ * per non-empty group; skipped bricks cost nothing.
+ * Concurrency: each call has its own device lists, cut values and tables, taken from a ring of four per set.  Up to
+ * four calls may be in flight, back to back on one stream or on several streams, without a host synchronisation; a
+ * fifth waits on the host until the oldest has finished.  Calls on one set from several host threads at once are
+ * not supported (no call on a set is).  A set opened from a file, cut above the index level, fills the cut values on
+ * the host (as vr_brickset_decode does).  vr_brickset_last_timings reports the call's whole time as `decode`. */
+vr_status vr_brickset_decode_lod(vr_brickset *bs, const int32_t *cuts_host, uint8_t *out_dev, void *stream);
+
 /* MidRangeTree only (new: the reference builds the half-range stream, MidRangeTree.cpp:399-544, 871-982, but
  * never decodes it -- its levelCut, :984-1093, reads the mid stream alone): the same progressive
  * decode applied to the range stream, i.e. per voxel the half range of its terminal node's box as the
@@ -223,6 +236,31 @@ typedef struct vr_render_params {
  * Pixels not covered by the cube are white (main.cpp:392). */
 vr_status vr_raycast(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
                      const vr_render_params *params, float *rgba_dev, void *stream);
+
+/* Host-only (no device needed): choose cuts_out[b] for vr_brickset_decode_lod, for the bricks of a volume laid out
+ * as in vr_assemble_bricks (brick b at grid cell brick_ijk[3b..3b+2] of `grid`, each brick_dims voxels) and the frame
+ * vr_raycast draws with (cam, params).  pixel_tolerance > 0.  The rule:
+ *  - the volume is vr_raycast's unit cube: texture space [0,1]^3 = world [-0.5,0.5]^3, voxel size 1/G per axis,
+ *    G = grid * brick_dims (params->global_dims where non-zero).  Brick b covers [ijk*brick_dims, (ijk+1)*brick_dims)/G.
+ *  - its box is grown on every side by one voxel (the reach of a trilinear tap); in VR_RENDER_ISOSURFACE mode also by
+ *    0.01 + max|step_size| (the gradient's offset, and the second fetch / bisection points that may leave the cube
+ *    and read its clamped edge).
+ *  - culled (-1): the grown box lies wholly outside [box_min, box_max) on some axis, or all eight of its corners lie
+ *    outside one plane of the frame's frustum.  The frustum is vr_raycast's: f = normalize(front),
+ *    s = normalize(f x up), u = s x f, tanY = tan(fov/2), tanX = tanY * width / height (float, as vr_raycast); for a
+ *    point p with d = p - pos, z = d.f, x = d.s, y = d.u the planes are z >= z_near, |x| <= tanX z, |y| <= tanY z and
+ *    z <= z_far + (max_samples + 1) * max|step_size| (a ray enters the cube at depth <= z_far and marches on from
+ *    there).  Each test allows 1e-6 * (1 + |z|) for rounding.  If f is parallel to up (s = 0) the side planes are
+ *    not used.  No ray of the frame takes a sample or a tap from a culled brick.
+ *  - projected voxel size s = (height / 2 / tanY) * max_k(1/G_k) / max(dist, z_near), dist = distance from pos to
+ *    the grown box (0 inside it).
+ *  - levels dropped k = 0 if s >= pixel_tolerance, else min(orig_tree_depth, floor(3 log2(pixel_tolerance / s)))
+ *    (three tree levels halve the resolution on all three axes).
+ *  - cut = max_tree_depth if k == 0 (the grown-branch levels refine values, not space: kept only when no spatial
+ *    level is dropped), else orig_tree_depth - k. */
+vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *params, int32_t num_bricks,
+                        const int64_t brick_dims[3], const int64_t *brick_ijk, const int64_t grid[3],
+                        int32_t orig_tree_depth, int32_t max_tree_depth, float pixel_tolerance, int32_t *cuts_out);
 
 /* (min, max) of every skip_cell^3 cell of the volume, widened by the one voxel a trilinear fetch reaches beyond its
  * base voxel: grid_dev holds 2 bytes per cell, cells x fastest, ceil(dims / skip_cell) cells per axis.  Exact bounds of

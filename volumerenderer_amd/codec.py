@@ -126,6 +126,21 @@ class BrickSet:
               "vr_brickset_decode")
         return out
 
+    def decode_lod(self, cuts, out=None, stream=None):
+        """Per-brick progressive decode: cuts[b] = -1 leaves brick b's bytes of `out` untouched, 0 .. max_tree_depth
+        decodes it exactly as decode(cut_depth=cuts[b]) would (vr_brickset_decode_lod)."""
+        c = np.ascontiguousarray(np.asarray(cuts).reshape(-1), dtype=np.int32)
+        if c.size != self.num_bricks:
+            raise ValueError("decode_lod: %d cuts for %d bricks" % (c.size, self.num_bricks))
+        if out is None:
+            out = torch.empty(self.num_bricks * self.voxels_per_brick, dtype=torch.uint8, device="cuda")
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                and out.numel() == self.num_bricks * self.voxels_per_brick):
+            raise ValueError("bad output buffer")
+        check(self._L.vr_brickset_decode_lod(self._h, c.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out.data_ptr()),
+                                             _stream_ptr(stream)), "vr_brickset_decode_lod")
+        return out
+
     def decode_range(self, out=None, cut_depth=-1, stream=None):
         """MidRangeTree sets: the half-range stream decoded like the mid stream (vr_brickset_decode_range)."""
         if out is None:

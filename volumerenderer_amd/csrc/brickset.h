@@ -32,6 +32,30 @@ struct Switches {
     int forkBricks = 0;          // VRHIP_FORK_BRICKS (0: default)
 };
 
+// vr_brickset_decode_lod: the device state of one call.  Calls take the slots of a ring in turn; a call waits on the
+// host for its slot's previous call (its event) before rewriting anything in it, so up to VR_LOD_SLOTS calls of a set
+// may be queued, on one stream or several, without a host synchronisation, and none overwrites what another still reads.
+#define VR_LOD_SLOTS 4
+struct LodSlot {
+    int32_t *dev = nullptr;        // 3B: the cuts of all B bricks, then the class lists (together at most 2B entries)
+    int32_t *host = nullptr;       // 3B pinned: the same, staged for the copy
+    uint8_t *idxValCut = nullptr;  // B * nIdx: cut values of the bricks cut above depth Ds (first needed: allocated)
+    uint32_t *decTables = nullptr; // B * FD_TABLE_WORDS: k_decode_fine's tables at each brick's cut (first needed)
+    uint8_t *rankVals = nullptr;   // B * 2^D * 2: general-extent decode scratch (first needed)
+    hipEvent_t done = nullptr;     // recorded after the call's last launch
+    bool pending = false;
+};
+
+// one launch class of a per-brick decode (decode_launch's `lod` argument)
+struct LodClass {
+    const int32_t *list = nullptr; // device: the class's bricks (grid rows)
+    int n = 0;
+    const int32_t *cuts = nullptr; // device: the cuts of all B bricks
+    uint8_t *idxValCut = nullptr;
+    uint32_t *decTables = nullptr;
+    uint8_t *rankVals = nullptr;
+};
+
 struct BrickSet {
     int32_t B = 0;
     Switches sw;
@@ -116,13 +140,19 @@ struct BrickSet {
     float phasesMs[5] = {0, 0, 0, 0, 0};
     bool timingsPending = false, decodeTimingPending = false;
     void *lastStream = nullptr;
+    LodSlot lodSlot[VR_LOD_SLOTS];
+    int lodNext = 0;
 };
 
 // kd_encode.hip
 int encode_launch(BrickSet *bs, const uint8_t *voxDev, hipStream_t st);
 int compact_launch(BrickSet *bs, hipStream_t st);   // fused builds: contiguous stream(s) into Stream2::treeCompact
 // kd_decode.hip
-int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false);
+int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false,
+                  const LodClass *lod = nullptr);
+// per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
+int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st);
+void free_lod_slots(BrickSet *bs);
 int cut_values_from_stream(BrickSet *bs, const uint8_t *treeHost, int64_t numActive, const uint8_t *dmapHost, int cut,
                            std::vector<uint8_t> &vals);
 int build_index_from_stream(BrickSet *bs, int brick, const uint8_t *treeHost, int64_t numActive,

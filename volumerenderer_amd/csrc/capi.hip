@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -203,6 +204,7 @@ vr_status vr_brickset_destroy(vr_brickset *h)
 {
     if (!h) return VR_OK;
     BrickSet &b = h->s;
+    free_lod_slots(&b);
     free_encoder_buffers(b);
     free_stream2(b.mid);
     free_stream2(b.rng);
@@ -583,6 +585,113 @@ vr_status vr_brickset_decode(vr_brickset *h, int32_t cut_depth, uint8_t *out, vo
     }
     b.decodeTimingPending = true;
     b.lastStream = stream;
+    return VR_OK;
+}
+
+vr_status vr_brickset_decode_lod(vr_brickset *h, const int32_t *cuts, uint8_t *out, void *stream)
+{
+    if (!h || !cuts || !out) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    if (!b.built) return VR_ERR_STATE;
+    bool above = false;
+    for (int br = 0; br < b.B; ++br) {
+        if (cuts[br] < -1 || cuts[br] > b.maxDepth) return VR_ERR_INVALID;
+        above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
+    }
+    if (above && b.foreign) {
+        vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
+        if (rc != VR_OK) return rc;
+    }
+    const int rc = decode_lod_launch(&b, cuts, out, (hipStream_t)stream);
+    if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
+    b.decodeTimingPending = true;
+    b.lastStream = stream;
+    return VR_OK;
+}
+
+// The frame of vr_raycast (raymarch.hip raycast_launch): glm::lookAt basis and glm::perspectiveFov half-angle tangents,
+// the same float operations.  Every ray of the frame is dir = f + nx tanX s + ny tanY u, |nx|, |ny| < 1; its ray
+// parameter is the view depth d . f (d = point - pos), and its march starts at depth >= z_near.
+static void lod_cross3(const float *a, const float *b, float *o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+static void lod_norm3(float *v)
+{
+    float l = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (l > 0.0f) { v[0] /= l; v[1] /= l; v[2] /= l; } else { v[0] = v[1] = v[2] = 0.0f; }
+}
+
+vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *P, int32_t num_bricks, const int64_t brick_dims[3],
+                        const int64_t *brick_ijk, const int64_t grid[3], int32_t orig_tree_depth, int32_t max_tree_depth,
+                        float pixel_tolerance, int32_t *cuts_out)
+{
+    if (!cam || !P || !brick_dims || !brick_ijk || !grid || !cuts_out || num_bricks <= 0) return VR_ERR_INVALID;
+    if (!(pixel_tolerance > 0.0f) || P->width <= 0 || P->height <= 0) return VR_ERR_INVALID;
+    if (orig_tree_depth < 0 || max_tree_depth < orig_tree_depth) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) if (brick_dims[k] <= 0 || grid[k] <= 0) return VR_ERR_INVALID;
+    double G[3], vs[3], vmax = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        G[k] = P->global_dims[k] > 0 ? (double)P->global_dims[k] : (double)(grid[k] * brick_dims[k]);
+        vs[k] = 1.0 / G[k];
+        vmax = std::max(vmax, vs[k]);
+    }
+    // the reach beyond a brick's voxels of the samples and taps that read them: one voxel (a trilinear tap); in
+    // iso-surface mode also the gradient's 0.01 offset and one step (the second fetch and the bisection, whose points
+    // may lie outside the cube and read its clamped edge)
+    double grow[3], stepMax = 0.0;
+    for (int k = 0; k < 3; ++k) stepMax = std::max(stepMax, (double)fabsf(P->step_size[k]));
+    for (int k = 0; k < 3; ++k) grow[k] = vs[k] + (P->mode == VR_RENDER_ISOSURFACE ? 0.01 + stepMax : 0.0);
+    float f[3] = {cam->front[0], cam->front[1], cam->front[2]}, sv[3], u[3];
+    lod_norm3(f);
+    lod_cross3(f, cam->up, sv);
+    lod_norm3(sv);
+    lod_cross3(sv, f, u);
+    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
+    const float tanYf = tanf(0.5f * rad), tanXf = tanYf * (float)P->width / (float)P->height;
+    const double tanY = tanYf, tanX = tanXf;
+    const bool basis = (sv[0] != 0.0f || sv[1] != 0.0f || sv[2] != 0.0f);
+    // a ray marches at most max_samples + 1 steps past its entry point (at depth <= z_far)
+    const double zNear = cam->z_near, zFar = (double)cam->z_far + ((double)std::max(P->max_samples, 0) + 1.0) * stepMax;
+    const double eps = 1e-6;     // float rounding of the ray positions
+    const double focal = (double)P->height / 2.0 / tanY;
+    for (int i = 0; i < num_bricks; ++i) {
+        double lo[3], hi[3];        // the grown box, in the world space of vr_raycast's cube [-0.5, 0.5]^3
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = (double)(brick_ijk[3 * i + k] * brick_dims[k]) * vs[k] - grow[k] - 0.5;
+            hi[k] = (double)((brick_ijk[3 * i + k] + 1) * brick_dims[k]) * vs[k] + grow[k] - 0.5;
+        }
+        bool culled = false;
+        for (int k = 0; k < 3; ++k)       // [box_min, box_max) in texture space
+            if (hi[k] + 0.5 < (double)P->box_min[k] || lo[k] + 0.5 >= (double)P->box_max[k]) culled = true;
+        // frustum: all eight corners outside one plane (depth below z_near or above the far bound, |x| > tanX depth,
+        // |y| > tanY depth)
+        int outN = 0, outF = 0, outL = 0, outR = 0, outB = 0, outT = 0;
+        for (int c = 0; c < 8; ++c) {
+            const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
+            double d[3], z = 0.0, x = 0.0, y = 0.0;
+            for (int k = 0; k < 3; ++k) d[k] = p[k] - (double)cam->pos[k];
+            for (int k = 0; k < 3; ++k) { z += d[k] * f[k]; x += d[k] * sv[k]; y += d[k] * u[k]; }
+            const double tol = eps * (1.0 + fabs(z));
+            outN += z < zNear - tol;
+            outF += z > zFar + tol;
+            outR += x > tanX * z + tol; outL += -x > tanX * z + tol;
+            outT += y > tanY * z + tol; outB += -y > tanY * z + tol;
+        }
+        if (outN == 8 || outF == 8) culled = true;
+        if (basis && (outR == 8 || outL == 8 || outT == 8 || outB == 8)) culled = true;
+        if (culled) { cuts_out[i] = -1; continue; }
+        double q = 0.0;               // distance from the camera to the grown box
+        for (int k = 0; k < 3; ++k) {
+            const double e = std::max(std::max(lo[k] - (double)cam->pos[k], 0.0), (double)cam->pos[k] - hi[k]);
+            q += e * e;
+        }
+        const double s = focal * vmax / std::max(sqrt(q), zNear);
+        int k = 0;
+        if (s < (double)pixel_tolerance)
+            k = (int)std::min((double)orig_tree_depth, floor(3.0 * log2((double)pixel_tolerance / s)));
+        cuts_out[i] = k == 0 ? max_tree_depth : orig_tree_depth - k;
+    }
     return VR_OK;
 }
 

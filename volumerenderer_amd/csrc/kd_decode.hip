@@ -125,13 +125,25 @@ int build_general_geometry(BrickSet *bs)
     return launch_status("geometry");
 }
 
+// Per-brick decode (vr_brickset_decode_lod): grid row blockIdx.y decodes brick list[blockIdx.y] at its own cut
+// cuts[brick]; with both null (the uniform path) brick blockIdx.y at the launch-wide cut.  Both are workgroup-uniform:
+// one scalar load each, once per workgroup.
+__device__ __forceinline__ int lod_brick(const int32_t *list, unsigned row)
+{
+    return list ? __builtin_amdgcn_readfirstlane(list[row]) : (int)row;
+}
+__device__ __forceinline__ int lod_cut(const int32_t *cuts, int brick, int cut)
+{
+    return cuts ? __builtin_amdgcn_readfirstlane(cuts[brick]) : cut;
+}
+
 // out[voxel] = value of the leaf rank that owns it, if the box its terminal node writes still holds the voxel
 // (rankVals: value | branch nodes below the leaf << 8; 0 branch nodes = the leaf or an ancestor is pruned: whole box)
 __global__ void __launch_bounds__(256)
 k_owner_gather(const uint16_t *__restrict__ rankVals, int64_t leafStride, const uint32_t *__restrict__ owner,
-               const uint8_t *__restrict__ surv, int64_t voxels, uint8_t *__restrict__ out)
+               const uint8_t *__restrict__ surv, int64_t voxels, uint8_t *__restrict__ out, const int32_t *list)
 {
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(list, blockIdx.y);
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= voxels) return;
     const uint32_t e = rankVals[(int64_t)brick * leafStride + owner[v]];
@@ -168,6 +180,7 @@ struct DecodeArgs {
     int D, K, Ds;
     int cut;                    // progressive cut depth (maxTreeDepth = the reference's levelCut)
     const uint8_t *idxValCut;   // cut < Ds: scalar of every subtree's ancestor at depth `cut`
+    const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
 };
 
 // v1: one lane per subtree, direct byte stores.  RANK_OUT: the value of every leaf RANK goes to a.out (B * 2^D bytes,
@@ -176,14 +189,15 @@ template <bool RANK_OUT>
 __global__ void __launch_bounds__(64)
 k_decode_lane(DecodeArgs a)
 {
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(a.list, blockIdx.y);
+    const int cut = lod_cut(a.cuts, brick, a.cut);
     const int64_t s = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (s >= a.nIdx) return;
     const uint32_t off = a.idxOff[(int64_t)brick * a.nIdx + s];
-    const int val0 = a.cut < a.Ds ? a.idxValCut[(int64_t)brick * a.nIdx + s] : a.idxVal[(int64_t)brick * a.nIdx + s];
+    const int val0 = cut < a.Ds ? a.idxValCut[(int64_t)brick * a.nIdx + s] : a.idxVal[(int64_t)brick * a.nIdx + s];
     const uint8_t *dmapG = a.ctrls[brick].distanceMap;
     uint8_t dmap[VR_MAX_DEPTH + 8];
-    for (int q = 0; q <= a.D + VR_CHAIN_LEVELS; ++q) dmap[q] = q > a.cut ? 0 : dmapG[q];   // no refinement below the cut
+    for (int q = 0; q <= a.D + VR_CHAIN_LEVELS; ++q) dmap[q] = q > cut ? 0 : dmapG[q];   // no refinement below the cut
     int ox = 0, oy = 0, oz = 0;
     if (!RANK_OUT) rank_to_xyz(a.g, (uint32_t)(s << a.K), ox, oy, oz);
     uint8_t *O = RANK_OUT ? a.out + 2 * ((int64_t)brick * ((int64_t)1 << a.D) + (s << a.K))
@@ -270,6 +284,7 @@ struct TileArgs {
     const uint32_t *tables;     // BrickSet::decTables (k_decode_fine) / BrickSet::chainTab (k_decode_quad)
     const uint8_t *val3;        // BrickSet::idxVal3 (k_decode_quad only)
     uint8_t kqBit[8];           // k_decode_quad: bit i of a workgroup's ticket number = this bit of the tile's number
+    const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
 };
 
 #define DEC_WAVES 4
@@ -434,7 +449,8 @@ k_decode_tile(TileArgs a)
                                      // [129 + key]: second word (one bank further: both come with one ds_read2_b32)
     __shared__ uint32_t lutC1[256], lutC2[64];   // grown-branch tables: branch tokens 1-4 and 5-7
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(a.list, blockIdx.y);
+    const int cut = lod_cut(a.cuts, brick, a.cut);
     const int tileId = blockIdx.x * DEC_WAVES + wave;
     uint32_t *tile = tileS[wave];
     uint32_t *str = strS[wave];
@@ -446,7 +462,7 @@ k_decode_tile(TileArgs a)
         // [0] = 0: the subtree root keeps the value stored in the index; levels below a progressive cut
         // refine nothing (distance 0), so every voxel gets the scalar of its ancestor at the cut depth
         const int depth = t < 8 ? a.Ds + (t < 7 ? t : 0) : a.D + (t - 8);
-        dmS[t] = (t == 0 || depth > a.cut) ? 0 : dmap[depth];
+        dmS[t] = (t == 0 || depth > cut) ? 0 : dmap[depth];
     }
     __syncthreads();
     if (threadIdx.x < 128) {
@@ -499,7 +515,7 @@ k_decode_tile(TileArgs a)
     const int sc[3] = {tx * 32 + (lane & 31), ty * 2 + (lane >> 5), tz};   // subtree coords (units of 4 voxels)
     const uint32_t s = (a.spread[4 * sc[0]] | a.spread[a.g.X + 4 * sc[1]] | a.spread[a.g.X + a.g.Y + 4 * sc[2]]) >> 6;
     const uint32_t off = a.idxOff[(int64_t)brick * a.nIdx + s];
-    const int val0 = a.cut < a.Ds ? a.idxValCut[(int64_t)brick * a.nIdx + s] : a.idxVal[(int64_t)brick * a.nIdx + s];
+    const int val0 = cut < a.Ds ? a.idxValCut[(int64_t)brick * a.nIdx + s] : a.idxVal[(int64_t)brick * a.nIdx + s];
 
     // a tile whose 64 subtrees all lie under pruned nodes (constant regions) needs no walk: one value per
     // subtree goes to tile row 0 and the gather below reads every leaf from there
@@ -642,11 +658,12 @@ __device__ __forceinline__ void leaf_table(const uint8_t *dmS, uint32_t *lutL)
 #define FD_TABLE_WORDS (1024 + 64 + 4)
 
 __global__ void __launch_bounds__(256)
-k_fine_tables(const Ctrl *ctrls, int D, int Ds, int cut, uint32_t *tables)
+k_fine_tables(const Ctrl *ctrls, int D, int Ds, int cutAll, uint32_t *tables, const int32_t *list, const int32_t *cuts)
 {
     __shared__ uint8_t dmS[16];
     __shared__ uint32_t lutL[1024], lutC2[64];
-    const int brick = blockIdx.x;
+    const int brick = lod_brick(list, blockIdx.x);
+    const int cut = lod_cut(cuts, brick, cutAll);
     if (threadIdx.x < 16) {
         const uint8_t *dmap = ctrls[brick].distanceMap;
         const int t = threadIdx.x;
@@ -673,7 +690,8 @@ k_decode_fine(TileArgs a)
     uint32_t *lutL = tabS, *lutC2 = tabS + 1024;
     const uint8_t *dmS = (const uint8_t *)(tabS + 1088);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(a.list, blockIdx.y);
+    const int cut = lod_cut(a.cuts, brick, a.cut);
     const int tileId = blockIdx.x * FD_WAVES + wave;
     uint32_t *tile = tileS[wave];
     uint32_t *str = strS[wave];
@@ -686,7 +704,7 @@ k_decode_fine(TileArgs a)
         const int sc[3] = {tx * 32 + (lane & 31), ty * 2 + (lane >> 5), tz};
         const uint32_t s = (a.spread[4 * sc[0]] | a.spread[a.g.X + 4 * sc[1]] | a.spread[a.g.X + a.g.Y + 4 * sc[2]]) >> 6;
         off = a.idxOff[(int64_t)brick * a.nIdx + s];
-        val0 = a.cut < a.Ds ? a.idxValCut[(int64_t)brick * a.nIdx + s] : a.idxVal[(int64_t)brick * a.nIdx + s];
+        val0 = cut < a.Ds ? a.idxValCut[(int64_t)brick * a.nIdx + s] : a.idxVal[(int64_t)brick * a.nIdx + s];
         if (off != VR_IDX_DEAD) cv = *(const uint4 *)(a.fine + ((int64_t)brick * a.nIdx + s) * 16);
     }
     const unsigned long long liveMask = __ballot(off != VR_IDX_DEAD);
@@ -974,7 +992,8 @@ k_decode_quad(TileArgs a)
     uint32_t *chainS = sm.chain;
     uint32_t (*offS)[64] = sm.off;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(a.list, blockIdx.y);
+    const int cut = lod_cut(a.cuts, brick, a.cut);
     const int ntiles = a.tilesX * a.tilesY * a.tilesZ;
     const int tile0 = blockIdx.x * (QD_WAVES * QD_TPW);               // the workgroup's tiles: tile0 .. tile0 + 16 * QD_TPW - 1
     uint32_t *tile = sm.tile[wave];
@@ -1021,11 +1040,13 @@ k_decode_quad(TileArgs a)
     if (threadIdx.x < 12) {         // distances of depths D-2, D-1, D (0 below a progressive cut)
         const uint8_t *dmap = a.ctrls[brick].distanceMap;
         const int lv = threadIdx.x >> 2, tok = threadIdx.x & 3, depth = a.D - 2 + lv;
-        const int dist = depth <= a.cut ? dmap[depth] : 0;
+        const int dist = depth <= cut ? dmap[depth] : 0;
         (&sm.delta.d4[0])[threadIdx.x] = tok == 1 ? dist : (tok == 2 ? -dist : 0);
     }
     if (__syncthreads_or(any ? 1 : 0)) {
-        const uint4 *src = (const uint4 *)a.tables;
+        // per-brick decode: a.tables is the first of the set's chain tables, this brick's is the one for its refining levels
+        const int lv = cut - a.D < 0 ? 0 : (cut - a.D > VR_CHAIN_LEVELS ? VR_CHAIN_LEVELS : cut - a.D);
+        const uint4 *src = (const uint4 *)(a.cuts ? a.tables + (size_t)lv * QD_CHAIN_ENTRIES : a.tables);
         uint4 *dst = (uint4 *)chainS;
 #pragma unroll
         for (int i = 0; i < QD_CHAIN_ENTRIES / 4 / (64 * QD_WAVES); ++i) dst[i * 64 * QD_WAVES + threadIdx.x] = src[i * 64 * QD_WAVES + threadIdx.x];
@@ -1236,6 +1257,7 @@ struct RegionArgs {
     uint32_t xRead[2];          // 4 halfwords: image-word XOR of the gather's read k (the x bits above the two lowest)
     uint32_t blkX, blkY, blkZ;  // 6 x 5 bits each: bit k of x >> 4 (y >> 4, z >> 4) is this bit of the emit block's number (= leaf rank >> 12)
     int nreg;                   // regions of a brick
+    const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
     unsigned long long *dbg;    // RG_STAMP builds only: cycle sums (total, park, steps, barrier 1, gather, barrier 2)
 };
 
@@ -1369,13 +1391,14 @@ k_decode_region(RegionArgs a)
     __shared__ __attribute__((aligned(16))) Shared smw;
     RegionShared &sm = smw.t;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(a.list, blockIdx.y);
     const int G = (int)gridDim.x;
     const int nreg = a.nreg;
     int rid = (int)blockIdx.x;
     if (rid >= nreg) return;
     // ---- tables
     {
+        const int cut = lod_cut(a.cuts, brick, a.cut);
         const uint8_t *dmap = a.ctrls[brick].distanceMap;
         const int t = threadIdx.x;
         if (t < 192) {       // rank bits of the coordinates above the emit block (bit deposit, once per workgroup)
@@ -1406,16 +1429,16 @@ k_decode_region(RegionArgs a)
         {
             int distA[4], distB[3];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { const int depth = a.D + 1 + q; distA[q] = depth <= a.cut ? dmap[depth] : 0; }
+            for (int q = 0; q < 4; ++q) { const int depth = a.D + 1 + q; distA[q] = depth <= cut ? dmap[depth] : 0; }
 #pragma unroll
-            for (int q = 0; q < 3; ++q) { const int depth = a.D + 5 + q; distB[q] = depth <= a.cut ? dmap[depth] : 0; }
-            const int d6 = a.D <= a.cut ? dmap[a.D] : 0;
+            for (int q = 0; q < 3; ++q) { const int depth = a.D + 5 + q; distB[q] = depth <= cut ? dmap[depth] : 0; }
+            const int d6 = a.D <= cut ? dmap[a.D] : 0;
             for (int e = t; e < 1024; e += 64 * RG_WAVES) sm.leafA[e] = compose(e & 3, true, d6, distA, 4, (uint32_t)e >> 2);
             if (t < 64) sm.chainB[t] = compose(0, false, 0, distB, 3, (uint32_t)t);
         }
         if (t < 8) {
             const int lv = t >> 2, tok = t & 3, depth = a.D - 2 + lv;
-            const int dist = depth <= a.cut ? dmap[depth] : 0;
+            const int dist = depth <= cut ? dmap[depth] : 0;
             (lv ? sm.d5 : sm.d4)[tok] = tok == 1 ? dist : (tok == 2 ? -dist : 0);
         }
     }
@@ -1846,10 +1869,11 @@ static bool region_geometry(const BrickSet *bs, RegionArgs &a)
 
 // scalar of every depth-Ds subtree's ancestor at depth `cut` (< Ds), from the encoder's BFS codes
 __global__ void __launch_bounds__(256)
-k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *ctrls, int Ds, int cut, int64_t nIdx,
-             uint8_t *__restrict__ out)
+k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *ctrls, int Ds, int cutAll, int64_t nIdx,
+             uint8_t *__restrict__ out, const int32_t *list, const int32_t *cuts)
 {
-    const int brick = blockIdx.y;
+    const int brick = lod_brick(list, blockIdx.y);
+    const int cut = lod_cut(cuts, brick, cutAll);
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= nIdx) return;
     const uint8_t *Cb = codes + (int64_t)brick * codeStride;
@@ -1866,53 +1890,77 @@ k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *
     out[(int64_t)brick * nIdx + s] = (uint8_t)val;
 }
 
-int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream)
+// k_decode_fine / k_decode_quad / k_decode_region need every brick's per-4-leaf side-car
+static bool use_fine(const BrickSet *bs, bool rangeStream)
 {
-    hipEventRecord(bs->ev[5], st);
+    bool useFine = bs->fineIdx && (int)bs->fineHas.size() == bs->B && !rangeStream && !bs->sw.decodeWalk;
+    for (int i = 0; useFine && i < bs->B; ++i) useFine = bs->fineHas[(size_t)i] != 0;
+    return useFine;
+}
+
+// k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
+// at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
+static bool use_quad(const BrickSet *bs, bool useFine, int cut)
+{
+    return useFine && bs->idxVal3 && cut >= bs->D - 3 && !bs->sw.decodeFineV1;
+}
+
+int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream, const LodClass *lod)
+{
+    // lod: one class of a per-brick decode (decode_lod_launch): grid rows = the class's bricks, each at its own cut;
+    // `cut` is one of theirs (the kernel choice below depends on the class only).  The call's cut values, fine
+    // tables and rank scratch are its own (LodSlot), and the caller records the timing events around all classes.
+    if (lod && rangeStream) return -2;
+    if (!lod) hipEventRecord(bs->ev[5], st);
+    const unsigned rows = lod ? (unsigned)lod->n : (unsigned)bs->B;
+    const int32_t *list = lod ? lod->list : nullptr, *cuts = lod ? lod->cuts : nullptr;
     // MidRangeTree's second stream is emitted in lock step with the first (M.cpp:871-982): same token positions,
     // so the same side-car offsets serve it; only the scalars (its own codes, its own distanceMap) differ
     const Stream2 &sm = rangeStream ? bs->rng : bs->mid;
     const uint8_t *cutVals = nullptr, *idxVals = bs->idxVal;
-    if (cut < bs->Ds || rangeStream) {
+    if (lod) {
+        cutVals = lod->idxValCut;  // filled before the classes (k_cut_values over the bricks cut above Ds, or the host)
+    } else if (cut < bs->Ds || rangeStream) {
         if (!bs->idxValCut) return -2;
         if (!bs->foreign)
             hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), bs->B), dim3(256), 0, st,
-                               sm.codes, bs->codeStride, sm.ctrl, bs->Ds, cut < bs->Ds ? cut : bs->Ds, bs->nIdx, bs->idxValCut);
+                               sm.codes, bs->codeStride, sm.ctrl, bs->Ds, cut < bs->Ds ? cut : bs->Ds, bs->nIdx, bs->idxValCut,
+                               nullptr, nullptr);
         cutVals = bs->idxValCut;   // foreign streams: filled by the host from the bytes (capi)
         if (rangeStream) idxVals = bs->idxValCut;
     }
     TileArgs t;
     if (bs->generalGeom) {
         // general extents: rank-domain decode, then every voxel takes its owner leaf's value
-        if (!bs->rankVals && hipMalloc(&bs->rankVals, (size_t)bs->B * bs->leafStride * 2) != hipSuccess) return -3;
+        if (!lod && !bs->rankVals && hipMalloc(&bs->rankVals, (size_t)bs->B * bs->leafStride * 2) != hipSuccess) return -3;
+        uint8_t *rankVals = lod ? lod->rankVals : bs->rankVals;
         DecodeArgs a;
         a.tree = sm.tree; a.treeCap = bs->treeCap;
         a.idxBase = bs->idx64 ? bs->idxBase : nullptr; a.nBase = bs->nEmitBlk;
         a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
-        a.ctrls = sm.ctrl; a.lut = nullptr; a.out = bs->rankVals; a.g = bs->g;
+        a.ctrls = sm.ctrl; a.lut = nullptr; a.out = rankVals; a.g = bs->g;
         a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
-        a.cut = cut; a.idxValCut = cutVals;
-        hipLaunchKernelGGL(k_decode_lane<true>, dim3((unsigned)((bs->nIdx + 63) / 64), bs->B), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(k_owner_gather, dim3((unsigned)((bs->g.voxels + 255) / 256), bs->B), dim3(256), 0, st,
-                           (const uint16_t *)bs->rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out);
+        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts;
+        hipLaunchKernelGGL(k_decode_lane<true>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_owner_gather, dim3((unsigned)((bs->g.voxels + 255) / 256), rows), dim3(256), 0, st,
+                           (const uint16_t *)rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list);
     } else if (!bs->sw.decodeV1 && tile_geometry(bs, t)) {
         t.tree = sm.tree; t.treeCap = bs->treeCap;
         t.idxOff = bs->idxOff; t.idxVal = idxVals; t.nIdx = bs->nIdx;
         t.ctrls = sm.ctrl; t.out = out; t.g = bs->g; t.D = bs->D; t.Ds = bs->Ds;
         t.cut = cut; t.idxValCut = cutVals; t.spread = bs->spread;
+        t.list = list; t.cuts = cuts;
         const int ntiles = t.tilesX * t.tilesY * t.tilesZ;
         t.fine = bs->fineIdx;
         t.val3 = bs->idxVal3;
-        bool useFine = bs->fineIdx && (int)bs->fineHas.size() == bs->B && !rangeStream && !bs->sw.decodeWalk;
-        for (int i = 0; useFine && i < bs->B; ++i) useFine = bs->fineHas[(size_t)i] != 0;
-        // k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
-        // at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
-        const bool useQuad = useFine && bs->idxVal3 && cut >= bs->D - 3 && !bs->sw.decodeFineV1;
+        const bool useFine = use_fine(bs, rangeStream);
+        const bool useQuad = use_quad(bs, useFine, cut);
         RegionArgs r;
         if (useQuad && !bs->sw.decodeQuad && region_geometry(bs, r)) {
             r.tree = sm.tree; r.treeCap = bs->treeCap;
             r.idxOff = bs->idxOff; r.idxVal = idxVals; r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.nIdx = bs->nIdx;
             r.ctrls = sm.ctrl; r.out = out; r.spread = bs->spread; r.D = bs->D; r.cut = cut;
+            r.list = list; r.cuts = cuts;
             // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
             // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
             r.dbg = nullptr;
@@ -1929,8 +1977,8 @@ int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rang
             }
 #endif
             unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);
-            if ((int64_t)wgs * bs->B < 2048) wgs = (unsigned)std::min<int64_t>(r.nreg, (2048 + bs->B - 1) / bs->B);
-            hipLaunchKernelGGL(k_decode_region, dim3(wgs, bs->B), dim3(64 * RG_WAVES), 0, st, r);
+            if ((int64_t)wgs * rows < 2048) wgs = (unsigned)std::min<int64_t>(r.nreg, (2048 + rows - 1) / rows);
+            hipLaunchKernelGGL(k_decode_region, dim3(wgs, rows), dim3(64 * RG_WAVES), 0, st, r);
         } else if (useQuad) {
             const int levels = cut - bs->D < 0 ? 0 : (cut - bs->D > VR_CHAIN_LEVELS ? VR_CHAIN_LEVELS : cut - bs->D);
             // one table per number of refining levels, all written once: two decodes of one set on different streams at
@@ -1943,19 +1991,20 @@ int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rang
                 if (hipStreamSynchronize(st) != hipSuccess) return -1;
                 bs->chainTabReady = true;
             }
-            t.tables = bs->chainTab + (size_t)levels * QD_CHAIN_ENTRIES;
+            t.tables = bs->chainTab + (lod ? (size_t)0 : (size_t)levels * QD_CHAIN_ENTRIES);   // lod: the kernel picks per brick
             const int per = QD_WAVES * QD_TPW;
-            hipLaunchKernelGGL(k_decode_quad, dim3((unsigned)((ntiles + per - 1) / per), bs->B), dim3(64 * QD_WAVES), 0, st, t);
+            hipLaunchKernelGGL(k_decode_quad, dim3((unsigned)((ntiles + per - 1) / per), rows), dim3(64 * QD_WAVES), 0, st, t);
         } else {
-        if (useFine && !bs->decTables && hipMalloc(&bs->decTables, (size_t)bs->B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
-        t.tables = bs->decTables;
+        if (useFine && !lod && !bs->decTables && hipMalloc(&bs->decTables, (size_t)bs->B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
+        uint32_t *decTables = lod ? lod->decTables : bs->decTables;
+        t.tables = decTables;
         if (useFine)
-            hipLaunchKernelGGL(k_fine_tables, dim3(bs->B), dim3(256), 0, st, bs->mid.ctrl, bs->D, bs->Ds, cut, bs->decTables);
+            hipLaunchKernelGGL(k_fine_tables, dim3(rows), dim3(256), 0, st, bs->mid.ctrl, bs->D, bs->Ds, cut, decTables, list, cuts);
         if (useFine)
-            hipLaunchKernelGGL(k_decode_fine, dim3((unsigned)((ntiles + FD_WAVES - 1) / FD_WAVES), bs->B),
+            hipLaunchKernelGGL(k_decode_fine, dim3((unsigned)((ntiles + FD_WAVES - 1) / FD_WAVES), rows),
                                dim3(64 * FD_WAVES), 0, st, t);
         else
-            hipLaunchKernelGGL(k_decode_tile, dim3((unsigned)((ntiles + DEC_WAVES - 1) / DEC_WAVES), bs->B),
+            hipLaunchKernelGGL(k_decode_tile, dim3((unsigned)((ntiles + DEC_WAVES - 1) / DEC_WAVES), rows),
                                dim3(64 * DEC_WAVES), 0, st, t);
         }
     } else {
@@ -1965,11 +2014,110 @@ int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rang
         a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
         a.ctrls = sm.ctrl; a.lut = bs->lut; a.out = out; a.g = bs->g;
         a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
-        a.cut = cut; a.idxValCut = cutVals;
-        hipLaunchKernelGGL(k_decode_lane<false>, dim3((unsigned)((bs->nIdx + 63) / 64), bs->B), dim3(64), 0, st, a);
+        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts;
+        hipLaunchKernelGGL(k_decode_lane<false>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
+    }
+    if (!lod) hipEventRecord(bs->ev[6], st);
+    return launch_status("decode");
+}
+
+// ---- per-brick decode (vr_brickset_decode_lod)
+// The classes of decode_launch's choice, in launch order: region / quad, fine, tile, general extents, lane.
+enum { LOD_QUAD, LOD_FINE, LOD_TILE, LOD_GENERAL, LOD_LANE, LOD_CLASSES };
+
+// what the choice depends on besides the cut: the set's geometry and side-cars (once per call, not per brick)
+struct LodChoice {
+    int fixed;        // LOD_GENERAL / LOD_LANE, or -1: a tiled kernel, by the cut
+    bool useFine;
+    explicit LodChoice(const BrickSet *bs) : fixed(-1), useFine(false)
+    {
+        TileArgs t;
+        if (bs->generalGeom) fixed = LOD_GENERAL;
+        else if (bs->sw.decodeV1 || !tile_geometry(bs, t)) fixed = LOD_LANE;
+        else useFine = use_fine(bs, false);
+    }
+    int of(const BrickSet *bs, int cut) const
+    {
+        if (fixed >= 0) return fixed;
+        return use_quad(bs, useFine, cut) ? LOD_QUAD : (useFine ? LOD_FINE : LOD_TILE);
+    }
+};
+
+void free_lod_slots(BrickSet *bs)
+{
+    for (LodSlot &s : bs->lodSlot) {
+        if (s.done) { if (s.pending) hipEventSynchronize(s.done); hipEventDestroy(s.done); }
+        hipFree(s.dev); hipFree(s.idxValCut); hipFree(s.decTables); hipFree(s.rankVals);
+        if (s.host) hipHostFree(s.host);
+        s = LodSlot();
+    }
+}
+
+int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipStream_t st)
+{
+    const int B = bs->B;
+    LodSlot &s = bs->lodSlot[bs->lodNext];
+    // the slot's previous call (any stream) may still read its lists, cut values and tables
+    if (s.pending && hipEventSynchronize(s.done) != hipSuccess) return -1;
+    s.pending = false;
+    if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return -1;
+    if (!s.dev && hipMalloc(&s.dev, (size_t)3 * B * sizeof(int32_t)) != hipSuccess) return -3;
+    if (!s.host && hipHostMalloc(&s.host, (size_t)3 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return -3;
+    bs->lodNext = (bs->lodNext + 1) % VR_LOD_SLOTS;
+    // host image: cuts [0, B), bricks cut above Ds, then the classes' lists
+    int32_t *H = s.host;
+    const LodChoice choice(bs);
+    int nAbove = 0, nCls[LOD_CLASSES] = {0, 0, 0, 0, 0}, cutOf[LOD_CLASSES] = {0, 0, 0, 0, 0};
+    std::vector<int> cls((size_t)B, -1);
+    for (int b = 0; b < B; ++b) {
+        H[b] = cutsHost[b];
+        if (cutsHost[b] < 0) continue;
+        if (cutsHost[b] < bs->Ds) H[B + nAbove++] = b;
+        cls[(size_t)b] = choice.of(bs, cutsHost[b]);
+        ++nCls[cls[(size_t)b]];
+        cutOf[cls[(size_t)b]] = cutsHost[b];
+    }
+    int first[LOD_CLASSES], at = B + nAbove;
+    for (int c = 0; c < LOD_CLASSES; ++c) { first[c] = at; at += nCls[c]; }
+    {
+        int fill[LOD_CLASSES];
+        for (int c = 0; c < LOD_CLASSES; ++c) fill[c] = first[c];
+        for (int b = 0; b < B; ++b) if (cls[(size_t)b] >= 0) H[fill[cls[(size_t)b]]++] = b;
+    }
+    if (at == B) return 0;              // every brick skipped: nothing to launch
+    if (nAbove && !s.idxValCut && hipMalloc(&s.idxValCut, (size_t)B * bs->nIdx) != hipSuccess) return -3;
+    if ((nCls[LOD_FINE] || nCls[LOD_QUAD]) && !s.decTables && hipMalloc(&s.decTables, (size_t)B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
+    if (nCls[LOD_GENERAL] && !s.rankVals && hipMalloc(&s.rankVals, (size_t)B * bs->leafStride * 2) != hipSuccess) return -3;
+    if (nAbove && bs->foreign) {
+        // ancestor scalars at each brick's cut, from the stream bytes kept at set_tree/open time (as vr_brickset_decode)
+        std::vector<uint8_t> vals;
+        for (int i = 0; i < nAbove; ++i) {
+            const int br = H[B + i];
+            vals.assign((size_t)bs->nIdx, 0);
+            if (br < (int)bs->hostTree.size() && !bs->hostTree[br].empty() &&
+                cut_values_from_stream(bs, bs->hostTree[br].data(), (int64_t)bs->hostCtrl[br].numActive,
+                                       bs->hostCtrl[br].distanceMap, cutsHost[br], vals) != 0)
+                return -4;
+            if (hipMemcpy(s.idxValCut + (size_t)br * bs->nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+        }
+    }
+    hipEventRecord(bs->ev[5], st);
+    if (hipMemcpyAsync(s.dev, H, (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (nAbove && !bs->foreign)
+        hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), nAbove), dim3(256), 0, st,
+                           bs->mid.codes, bs->codeStride, bs->mid.ctrl, bs->Ds, 0, bs->nIdx, s.idxValCut, s.dev + B, s.dev);
+    int rc = 0;
+    for (int c = 0; c < LOD_CLASSES && rc == 0; ++c) {
+        if (!nCls[c]) continue;
+        LodClass L;
+        L.list = s.dev + first[c]; L.n = nCls[c]; L.cuts = s.dev;
+        L.idxValCut = s.idxValCut; L.decTables = s.decTables; L.rankVals = s.rankVals;
+        rc = decode_launch(bs, out, cutOf[c], st, false, &L);
     }
     hipEventRecord(bs->ev[6], st);
-    return launch_status("decode");
+    hipEventRecord(s.done, st);
+    s.pending = true;
+    return rc;
 }
 
 // Foreign stream, progressive cut above the index level: scalar of every depth-Ds subtree's ancestor at

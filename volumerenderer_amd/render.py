@@ -130,6 +130,20 @@ def disassemble_bricks(volume, brick_dims, brick_ijk, grid, out=None, stream=Non
     return out
 
 
+def select_lod(cam, params, brick_dims, brick_ijk, grid, orig_tree_depth, max_tree_depth, pixel_tolerance=1.0):
+    """Per-brick cuts for BrickSet.decode_lod for the frame raycast(cam, params) draws (vr_lod_select, host only):
+    -1 for bricks no ray of the frame reads, coarser cuts for bricks whose voxels project below pixel_tolerance
+    pixels.  Bricks as in assemble_bricks.  Returns an int32 numpy array."""
+    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
+    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    ijk = np.ascontiguousarray(brick_ijk, np.int64).reshape(-1, 3)
+    cuts = np.empty(ijk.shape[0], np.int32)
+    check(_lib.lib().vr_lod_select(C.byref(cam), C.byref(params), int(ijk.shape[0]), bd,
+                                   ijk.ctypes.data_as(C.POINTER(C.c_int64)), g, int(orig_tree_depth), int(max_tree_depth),
+                                   float(pixel_tolerance), cuts.ctypes.data_as(C.POINTER(C.c_int32))), "vr_lod_select")
+    return cuts
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}

@@ -7,7 +7,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .render import default_camera, default_params, raycast
+from .render import assemble_bricks, default_camera, default_params, raycast, select_lod
 
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
@@ -80,6 +80,27 @@ class HeadlessViewer:
     def draw(self, volume, dims, brick_dims=(256, 256, 128), mode=_lib.RENDER_COMPOSITE, out=None):
         P = default_params(self.width, self.height, brick_dims, mode, float(self.currIsoVal) / 255.0)
         return raycast(volume, dims, self.camera(), P, out)
+
+    def draw_lod(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, out=None):
+        """One frame from a BrickSet: select_lod for this frame's camera, decode_lod, assemble, ray-cast.  The bricks
+        are decoded into a buffer this viewer owns and kept across frames: a brick culled in this frame keeps (and
+        shows nowhere) whatever an earlier frame decoded into it.  Returns (frame, cuts)."""
+        import torch
+        bd = tuple(int(q) for q in bset.dims)
+        g = tuple(int(q) for q in grid)
+        info = bset.info(0)
+        P = default_params(self.width, self.height, bd, mode, float(self.currIsoVal) / 255.0)
+        cam = self.camera()
+        cuts = select_lod(cam, P, bd, brick_ijk, g, info["orig_tree_depth"], info["max_tree_depth"], pixel_tolerance)
+        n = bset.num_bricks * bset.voxels_per_brick
+        if getattr(self, "_lodBricks", None) is None or self._lodBricks.numel() != n:
+            self._lodBricks = torch.zeros(n, dtype=torch.uint8, device="cuda")
+            self._lodVol = None
+        bset.decode_lod(cuts, out=self._lodBricks)
+        self._lodVol = assemble_bricks(self._lodBricks, bd, brick_ijk, g, out=self._lodVol)
+        vol = self._lodVol
+        dims = (g[0] * bd[0], g[1] * bd[1], g[2] * bd[2])
+        return raycast(vol, dims, cam, P, out), cuts
 
     @staticmethod
     def dump_ppm(path, rgba):
