@@ -303,6 +303,24 @@ vr_status vr_compositor_create_from_comm(vr_compositor **out, void *nccl_comm, i
 vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
                                   const vr_render_params *params, float *rgba_dev, void *stream);
 vr_status vr_compositor_destroy(vr_compositor *c);
+/* The transport seam: vr_compositor_composite's exchange is four point-to-point calls, made through this table.  RCCL
+ * is the built-in table (ctx = the ncclComm_t) that the two constructors above install.  With
+ * vr_compositor_create_with_transport the caller brings its own: every member gets `ctx` back, count is in floats,
+ * stream is the one passed to vr_compositor_composite, and 0 means success.  The semantics are NCCL's grouped
+ * point-to-point model -- send / recv only between group_start and group_end, the k-th send from p to r matches the
+ * k-th recv on r from p, and the copies are ordered on `stream` (on both sides) without a host synchronisation.  The
+ * seam exists so that the whole exchange can be tested on one GPU (tests/loopback_transport.cpp); a host may also use
+ * it for another transport.  The compositor never destroys a caller's transport or ctx.
+ * VR_ERR_INVALID for a null table or member, world < 1, a rank out of range or height < world; then
+ * VR_ERR_NO_DEVICE without a GPU. */
+typedef struct vr_transport {
+    int32_t (*group_start)(void *ctx);
+    int32_t (*group_end)(void *ctx);
+    int32_t (*send)(void *ctx, const float *buf, int64_t count, int32_t peer, void *stream);
+    int32_t (*recv)(void *ctx, float *buf, int64_t count, int32_t peer, void *stream);
+} vr_transport;
+vr_status vr_compositor_create_with_transport(vr_compositor **out, const vr_transport *t, void *ctx, int32_t rank,
+                                              int32_t world, int32_t width, int32_t height);
 
 /* ---- streams, events, pinned host memory (what include/vrhip/TimestepStreamer.hpp overlaps the stages of a timestep
  * stream with: main.cpp:242-290 runs them one after another).  Streams and events travel as void*. */

@@ -50,6 +50,18 @@ def test_argument_validation_and_no_cpu_fallback(L):
     assert L.vr_brickset_create(None, 1, dims, 1, 2, 0) == -1           # VR_ERR_INVALID
     assert L.vr_brickset_create(C.byref(h), 1, dims, -1, 2, 0) == -1    # negative tolerance
     assert L.vr_brickset_create(C.byref(h), 1, bad, 1, 2, 0) == -7      # VR_ERR_UNSUPPORTED
+    # vr_compositor_create_with_transport: argument checks first, whatever the device
+    noop = C.CFUNCTYPE(C.c_int32, C.c_void_p)(lambda ctx: 0)
+    xfer = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)(lambda *a: 0)
+    table = (C.c_void_p * 4)(*[C.cast(f, C.c_void_p) for f in (noop, noop, xfer, xfer)])
+    for k in range(4):                                                   # one null member at a time
+        holed = (C.c_void_p * 4)(*table)
+        holed[k] = None
+        assert L.vr_compositor_create_with_transport(C.byref(h), holed, None, 0, 2, 64, 48) == -1
+    assert L.vr_compositor_create_with_transport(C.byref(h), None, None, 0, 2, 64, 48) == -1     # no table
+    assert L.vr_compositor_create_with_transport(None, table, None, 0, 2, 64, 48) == -1
+    for rank, world, w, hh in ((0, 0, 64, 48), (2, 2, 64, 48), (-1, 2, 64, 48), (0, 5, 64, 4), (0, 2, 0, 48)):
+        assert L.vr_compositor_create_with_transport(C.byref(h), table, None, rank, world, w, hh) == -1, (rank, world, w, hh)
     if n.value == 0:
         # CPU-only box: every compute entry point must fail loudly
         assert L.vr_brickset_create(C.byref(h), 1, dims, 1, 2, 0) == -2  # VR_ERR_NO_DEVICE
@@ -58,6 +70,8 @@ def test_argument_validation_and_no_cpu_fallback(L):
         assert L.vr_query_error(buf, buf, 16, buf, None) == -2
         assert L.vr_measure_error(buf, buf, 16, None, None, None) == -2
         assert L.vr_composite_over(buf, buf, 1, None) == -2
+        assert L.vr_compositor_create_with_transport(C.byref(h), table, None, 0, 2, 64, 48) == -2
+        assert L.vr_compositor_create_with_transport(C.byref(h), table, None, 0, 1, 64, 1) == -2
 
 
 def test_product_never_imports_oracle():
@@ -69,3 +83,21 @@ def test_product_never_imports_oracle():
                     txt = open(os.path.join(dp, f), errors="ignore").read()
                     for needle in ("import oracle", "from oracle", "liboracle", "oracle/"):
                         assert needle not in txt, "%s references the oracle (%s)" % (f, needle)
+
+
+def test_loopback_transport_compiles(tmp_path):
+    """The loopback vr_transport the GPU compositor tests run the exchange with is plain C++ on the HIP runtime API:
+    it builds with g++ and -Werror here too, and exports what those tests call."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_compositor import build_loopback
+    so = build_loopback(tmp_path)
+    lb = C.CDLL(so)
+    for name in ("lb_create", "lb_destroy", "lb_rank_ctx", "lb_transport", "lb_fail_at", "lb_count_delta", "lb_log_size",
+                 "lb_log_entry", "lb_log_clear", "lb_errors"):
+        assert hasattr(lb, name), name
+    src = open(os.path.join(ROOT, "tests", "loopback_transport.cpp")).read()
+    code = "\n".join(line.split("//")[0] for line in src.splitlines())
+    for sync in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize", "hipStreamQuery", "hipMemcpy("):
+        assert sync not in code, "the fake must not synchronise (%s)" % sync
+

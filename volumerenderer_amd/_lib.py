@@ -86,6 +86,7 @@ SIGNATURES = {
     "vr_rccl_unique_id": (_I32, [_P]),
     "vr_compositor_create": (_I32, [C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
     "vr_compositor_create_from_comm": (_I32, [C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
+    "vr_compositor_create_with_transport": (_I32, [C.POINTER(_P), _P, _P, _I32, _I32, _I32, _I32]),
     "vr_compositor_composite": (_I32, [_P, _P, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
     "vr_compositor_destroy": (_I32, [_P]),
     "vr_stream_create": (_I32, [C.POINTER(_P)]),

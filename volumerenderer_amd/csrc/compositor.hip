@@ -9,6 +9,9 @@
 //
 // RCCL is bound at run time (dlopen of the copy already in the process -- PyTorch brings its own -- or of
 // librccl.so.1), so libvrhip.so loads and every single-GPU entry point works where RCCL is absent.
+//
+// The four point-to-point calls go through a per-compositor transport table (vr_transport): RCCL is the built-in
+// one, a host (or a test, tests/loopback_transport.cpp) may bring its own with vr_compositor_create_with_transport.
 #include "../../include/vrhip.h"
 #include "kd_common.h"
 #include <dlfcn.h>
@@ -74,12 +77,27 @@ bool nccl_ok(ncclResult_t e, const char *what)
     return false;
 }
 
+// the built-in transport: ctx = the compositor's ncclComm_t
+int32_t rccl_group_start(void *) { return nccl_ok(rccl().GroupStart(), "ncclGroupStart") ? 0 : 1; }
+int32_t rccl_group_end(void *) { return nccl_ok(rccl().GroupEnd(), "ncclGroupEnd") ? 0 : 1; }
+int32_t rccl_send(void *ctx, const float *buf, int64_t count, int32_t peer, void *stream)
+{
+    return nccl_ok(rccl().Send(buf, (size_t)count, ncclFloat, peer, (ncclComm_t)ctx, (hipStream_t)stream), "ncclSend") ? 0 : 1;
+}
+int32_t rccl_recv(void *ctx, float *buf, int64_t count, int32_t peer, void *stream)
+{
+    return nccl_ok(rccl().Recv(buf, (size_t)count, ncclFloat, peer, (ncclComm_t)ctx, (hipStream_t)stream), "ncclRecv") ? 0 : 1;
+}
+const vr_transport kRcclTransport = {rccl_group_start, rccl_group_end, rccl_send, rccl_recv};
+
 } // namespace
 
 struct vr_compositor {
     int rank = 0, world = 1, W = 0, H = 0;
     ncclComm_t comm = nullptr;
     bool ownComm = false;
+    vr_transport t = kRcclTransport;
+    void *ctx = nullptr;        // what t's members get: comm for RCCL, the caller's ctx otherwise
     float *recv = nullptr;      // world * (my tile's pixels) * 4
     float *tile = nullptr;      // my finished tile
 };
@@ -124,6 +142,7 @@ vr_status vr_compositor_create(vr_compositor **out, const uint8_t id[128], int32
         memcpy(&u, id, 128);
         if (!nccl_ok(rccl().CommInitRank(&c->comm, world, u, rank), "ncclCommInitRank")) { delete c; return VR_ERR_NO_DEVICE; }
         c->ownComm = true;
+        c->ctx = c->comm;
     }
     const vr_status rc = compositor_alloc(c);
     if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
@@ -142,6 +161,25 @@ vr_status vr_compositor_create_from_comm(vr_compositor **out, void *nccl_comm, i
     if (!c) return VR_ERR_OOM;
     c->rank = rank; c->world = world; c->W = width; c->H = height;
     c->comm = (ncclComm_t)nccl_comm;
+    c->ctx = c->comm;
+    const vr_status rc = compositor_alloc(c);
+    if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
+    *out = c;
+    return VR_OK;
+}
+
+vr_status vr_compositor_create_with_transport(vr_compositor **out, const vr_transport *t, void *ctx, int32_t rank,
+                                              int32_t world, int32_t width, int32_t height)
+{
+    if (!out || !t || !t->group_start || !t->group_end || !t->send || !t->recv) return VR_ERR_INVALID;
+    if (world < 1 || rank < 0 || rank >= world || width <= 0 || height < world) return VR_ERR_INVALID;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VR_ERR_NO_DEVICE;
+    vr_compositor *c = new (std::nothrow) vr_compositor();
+    if (!c) return VR_ERR_OOM;
+    c->rank = rank; c->world = world; c->W = width; c->H = height;
+    c->t = *t;
+    c->ctx = ctx;
     const vr_status rc = compositor_alloc(c);
     if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
     *out = c;
@@ -167,21 +205,21 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
     const int64_t frame = (int64_t)c->W * c->H;
     if (c->world == 1)
         return vr::composite_slabs_launch(partial_dev, 1, frame, 0, axis, cam, params, rgba_dev, st) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
-    Rccl &R = rccl();
+    const vr_transport &T = c->t;
     int myLo, myHi;
     rows_of(c->H, c->rank, c->world, myLo, myHi);
     const size_t npix = (size_t)(myHi - myLo) * c->W;
     // ---- tile t of my partial image to rank t, my tile of every rank's image to me (slab order = rank order)
-    if (!nccl_ok(R.GroupStart(), "ncclGroupStart")) return VR_ERR_NO_DEVICE;
+    if (T.group_start(c->ctx) != 0) return VR_ERR_NO_DEVICE;
     bool ok = true;
     for (int peer = 0; peer < c->world && ok; ++peer) {
         if (peer == c->rank) continue;
         int lo, hi;
         rows_of(c->H, peer, c->world, lo, hi);
-        ok = ok && nccl_ok(R.Send(partial_dev + (size_t)lo * c->W * 4, (size_t)(hi - lo) * c->W * 4, ncclFloat, peer, c->comm, st), "ncclSend");
-        ok = ok && nccl_ok(R.Recv(c->recv + (size_t)peer * npix * 4, npix * 4, ncclFloat, peer, c->comm, st), "ncclRecv");
+        ok = ok && T.send(c->ctx, partial_dev + (size_t)lo * c->W * 4, (int64_t)(hi - lo) * c->W * 4, peer, st) == 0;
+        ok = ok && T.recv(c->ctx, c->recv + (size_t)peer * npix * 4, (int64_t)npix * 4, peer, st) == 0;
     }
-    ok = nccl_ok(R.GroupEnd(), "ncclGroupEnd") && ok;
+    ok = T.group_end(c->ctx) == 0 && ok;
     if (!ok) return VR_ERR_NO_DEVICE;
     if (hipMemcpyAsync(c->recv + (size_t)c->rank * npix * 4, partial_dev + (size_t)myLo * c->W * 4, npix * 4 * sizeof(float),
                        hipMemcpyDeviceToDevice, st) != hipSuccess) return VR_ERR_NO_DEVICE;
@@ -189,15 +227,15 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
     float *dst = c->rank == 0 ? rgba_dev + (size_t)myLo * c->W * 4 : c->tile;
     if (vr::composite_slabs_launch(c->recv, c->world, (int64_t)npix, (int64_t)myLo * c->W, axis, cam, params, dst, st) != 0) return VR_ERR_NO_DEVICE;
     // ---- the finished tiles to rank 0
-    if (!nccl_ok(R.GroupStart(), "ncclGroupStart")) return VR_ERR_NO_DEVICE;
-    if (c->rank != 0) ok = nccl_ok(R.Send(c->tile, npix * 4, ncclFloat, 0, c->comm, st), "ncclSend");
+    if (T.group_start(c->ctx) != 0) return VR_ERR_NO_DEVICE;
+    if (c->rank != 0) ok = T.send(c->ctx, c->tile, (int64_t)npix * 4, 0, st) == 0;
     else
         for (int peer = 1; peer < c->world && ok; ++peer) {
             int lo, hi;
             rows_of(c->H, peer, c->world, lo, hi);
-            ok = nccl_ok(R.Recv(rgba_dev + (size_t)lo * c->W * 4, (size_t)(hi - lo) * c->W * 4, ncclFloat, peer, c->comm, st), "ncclRecv");
+            ok = T.recv(c->ctx, rgba_dev + (size_t)lo * c->W * 4, (int64_t)(hi - lo) * c->W * 4, peer, st) == 0;
         }
-    ok = nccl_ok(R.GroupEnd(), "ncclGroupEnd") && ok;
+    ok = T.group_end(c->ctx) == 0 && ok;
     return ok ? VR_OK : VR_ERR_NO_DEVICE;
 }
 

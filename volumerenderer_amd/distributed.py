@@ -83,17 +83,33 @@ def _compositor(group, world, rank, W, H):
     return h
 
 
+def _check_image(t, what, shape=None):
+    if t.dtype != torch.float32:
+        raise ValueError("%s must be float32, not %s" % (what, t.dtype))
+    if t.dim() != 3 or t.shape[2] != 4 or (shape is not None and tuple(t.shape) != shape):
+        raise ValueError("%s must be shaped %s, not %s" % (what, shape or "(H, W, 4)", tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+
+
 def composite_sort_last(partial, cam, params, axis=2, group=None, combine=None, out=None):
     """partial: this rank's (c, tau, covered, 0) image [H][W][4] float32 (rank r holds slab r along
     `axis`).  Returns the finished RGBA frame [H][W][4] on rank 0 (None elsewhere).
 
     Device tensors take the C-ABI compositor (vr_compositor_composite: grouped RCCL send/recv, k_composite_slabs,
-    gather -- what a C++ host calls).  With an injected `combine` (the CPU tests: gloo, the oracle's combine) the same
-    exchange runs over torch.distributed point-to-point operations."""
+    gather -- what a C++ host calls); it reads `partial` (and writes `out`) through raw pointers, so anything but a
+    contiguous float32 (H, W, 4) device tensor raises ValueError before any C call.  With an injected `combine` (the
+    CPU tests: gloo, the oracle's combine) the same exchange runs over torch.distributed point-to-point operations."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
-    H, W = partial.shape[0], partial.shape[1]
     if combine is None and partial.is_cuda:
+        # the C ABI reads (and writes) dense float32 [H][W][4] through raw pointers: anything else is refused here
+        _check_image(partial, "partial")
+        H, W = partial.shape[0], partial.shape[1]
+        if rank == 0 and out is not None:
+            _check_image(out, "out", (H, W, 4))
+            if out.device != partial.device:
+                raise ValueError("out must be on %s, not %s" % (partial.device, out.device))
         from . import _lib
         from .codec import _stream_ptr
         from ._lib import check
@@ -105,6 +121,7 @@ def composite_sort_last(partial, cam, params, axis=2, group=None, combine=None, 
                                                  C.c_void_p(frame.data_ptr()) if rank == 0 else None, _stream_ptr()),
               "vr_compositor_composite")
         return frame
+    H, W = partial.shape[0], partial.shape[1]
     combine = combine or _gpu_combine
     rows = tile_rows(H, world)
     if world == 1:
