@@ -190,7 +190,9 @@ vr_status vr_query_error(const uint8_t *decoded_dev, const uint8_t *original_dev
  * without a brick are left untouched; the reference sizes its array by numBricks, VolumeReader.h:163-168,
  * and overruns it for sparse brick lists -- not reproduced).  64-bit indices (the reference's 32-bit ones wrap above
  * 2^32 voxels, VolumeReader.h:171).  vr_disassemble_bricks is the inverse (global
- * volume -> contiguous bricks), used to feed per-brick trees. */
+ * volume -> contiguous bricks), used to feed per-brick trees.  Either buffer may start at any byte (16-byte vector
+ * copies where both are 16-byte aligned, byte copies otherwise: no reliance on the hardware's tolerance of misaligned
+ * vector loads). */
 vr_status vr_assemble_bricks(const uint8_t *bricks_dev, int32_t num_bricks, const int64_t brick_dims[3],
                              const int64_t *brick_ijk, const int64_t grid[3], uint8_t *volume_dev, void *stream);
 vr_status vr_disassemble_bricks(const uint8_t *volume_dev, int32_t num_bricks, const int64_t brick_dims[3],
@@ -233,7 +235,9 @@ typedef struct vr_render_params {
 
 /* volume_dev: X*Y*Z uint8 (the 3-D texture contents, GL_RED/GL_UNSIGNED_BYTE, GL_LINEAR,
  * clamp-to-edge: VolumeReader.h:114-127).  rgba_dev: height*width*4 float32, row 0 = top.
- * Pixels not covered by the cube are white (main.cpp:392). */
+ * Pixels not covered by the cube are white (main.cpp:392).  VR_ERR_INVALID (nothing launched) for any dims[k] <= 0 or
+ * >= 2^31, width or height <= 0, max_samples < 0 or an unknown mode.  volume_dev and skip_grid_dev may start at any
+ * byte. */
 vr_status vr_raycast(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
                      const vr_render_params *params, float *rgba_dev, void *stream);
 
@@ -266,7 +270,7 @@ vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *params, in
  * base voxel: grid_dev holds 2 bytes per cell, cells x fastest, ceil(dims / skip_cell) cells per axis.  Exact bounds of
  * the DECODED voxels: MidRangeTree's half-range stream would give bounds of the original data one level above, but the
  * decoded scalar of an internal node is a prediction with no error bound, so mid +- range at a coarse cut is not a safe
- * bracket (vr_brickset_decode_range remains available for previews). */
+ * bracket (vr_brickset_decode_range remains available for previews).  Both buffers may start at any byte. */
 vr_status vr_skip_grid_build(const uint8_t *volume_dev, const int64_t dims[3], int32_t skip_cell, uint8_t *grid_dev,
                              void *stream);
 

@@ -62,8 +62,19 @@ def test_argument_validation_and_no_cpu_fallback(L):
     assert L.vr_compositor_create_with_transport(None, table, None, 0, 2, 64, 48) == -1
     for rank, world, w, hh in ((0, 0, 64, 48), (2, 2, 64, 48), (-1, 2, 64, 48), (0, 5, 64, 4), (0, 2, 0, 48)):
         assert L.vr_compositor_create_with_transport(C.byref(h), table, None, rank, world, w, hh) == -1, (rank, world, w, hh)
+    # vr_raycast: extents checked before the device (tex3d would clamp to -1 and read before the volume; >= 2^31 would
+    # be narrowed to int), as vr_skip_grid_build does
+    from volumerenderer_amd import render as R
+    cam, P = R.default_camera(), R.default_params(8, 8, (16, 16, 16))
+    vol = (C.c_uint8 * 64)()
+    img = (C.c_float * (8 * 8 * 4))()
+    for d in ((0, 16, 16), (16, -1, 16), (16, 16, -(1 << 40)), (1 << 31, 1, 1), (1, 1 << 31, 1), (1, 1, 1 << 40), (-1, -1, 1)):
+        assert L.vr_raycast(vol, (C.c_int64 * 3)(*d), C.byref(cam), C.byref(P), img, None) == -1, d
+        assert L.vr_skip_grid_build(vol, (C.c_int64 * 3)(*d), 8, vol, None) == -1, d
     if n.value == 0:
         # CPU-only box: every compute entry point must fail loudly
+        assert L.vr_raycast(vol, (C.c_int64 * 3)(4, 4, 4), C.byref(cam), C.byref(P), img, None) == -2
+        assert L.vr_raycast(vol, (C.c_int64 * 3)(1, 1, 1), C.byref(cam), C.byref(P), img, None) == -2
         assert L.vr_brickset_create(C.byref(h), 1, dims, 1, 2, 0) == -2  # VR_ERR_NO_DEVICE
         assert L.vr_set_device(0) == -2
         buf = (C.c_uint8 * 16)()

@@ -21,7 +21,7 @@ import time
 import numpy as np
 import pytest
 
-from refmarch import march_composite, march_partial, rays
+from refmarch import march_composite, march_partial, rays, view_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -114,22 +114,6 @@ def slab_setup(axis, world, r, dims=DIMS):
     sl = [slice(None)] * 3
     sl[2 - axis] = slice(a0, a1)
     return bmin, bmax, org, sub, tuple(sl)
-
-
-def view_dir(cam, w, h, axis):
-    """dir[axis] per pixel exactly as the kernels compute it (float32 basis, float32 pixel arithmetic)."""
-    front, up, fov = cam[2], cam[3], cam[4]
-    f = np.asarray(front, np.float32)
-    f = f / np.float32(np.sqrt(np.sum(f * f, dtype=np.float32)))
-    s = np.cross(f, np.asarray(up, np.float32)).astype(np.float32)
-    s = s / np.float32(np.sqrt(np.sum(s * s, dtype=np.float32)))
-    u = np.cross(s, f).astype(np.float32)
-    ty = np.float32(math.tan(np.float32(0.5) * np.float32(fov) * np.float32(0.01745329251994329576923690768489)))
-    tx = ty * np.float32(w) / np.float32(h)
-    px, py = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
-    nx = np.float32(2) * (px + np.float32(0.5)) / np.float32(w) - np.float32(1)
-    ny = np.float32(1) - np.float32(2) * (py + np.float32(0.5)) / np.float32(h)
-    return f[axis] + nx * tx * s[axis] + ny * ty * u[axis]
 
 
 def combine64(parts, ascending):

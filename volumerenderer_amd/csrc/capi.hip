@@ -987,6 +987,8 @@ vr_status vr_raycast(const uint8_t *vol, const int64_t dims[3], const vr_camera 
 {
     if (!vol || !dims || !cam || !P || !rgba) return VR_ERR_INVALID;
     if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
+    // tex3d clamps to [0, X-1] (-1 for X = 0) and the launch narrows the extents to int
+    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return raycast_launch(vol, dims, cam, P, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }

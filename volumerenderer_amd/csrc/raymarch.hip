@@ -26,6 +26,8 @@ struct Tex {
 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// a 16-bit word at any byte address (gfx950: still one global_load_ushort)
+typedef uint16_t __attribute__((aligned(1))) u16u;
 
 // texture(volume, p).r : R8 normalised, GL_LINEAR, clamp-to-edge, float32 weights
 __device__ __forceinline__ float tex3d(const Tex &t, float px, float py, float pz)
@@ -43,7 +45,6 @@ __device__ __forceinline__ float tex3d(const Tex &t, float px, float py, float p
     const uint8_t *r2 = t.v + sy * ya + sz * zb, *r3 = t.v + sy * yb + sz * zb;
     // the two x taps of a row are neighbouring bytes except at a clamped edge: one (unaligned) 16-bit load
     // per row instead of two byte loads; at an edge both taps are the same voxel
-    typedef uint16_t __attribute__((aligned(1))) u16u;
     const bool pairx = xb == xa + 1;
     const int xl = pairx ? xa : (xa < xb ? xa : xb);
     uint32_t q0, q1, q2, q3;
@@ -77,7 +78,8 @@ __device__ __forceinline__ bool inside(float x, float y, float z)
 struct SkipGrid { const uint8_t *g; int S, nx, ny, nz; };
 
 __global__ void __launch_bounds__(256)
-k_skip_grid(const uint8_t *__restrict__ vol, int X, int Y, int Z, int S, int nx, int ny, int nz, uint8_t *__restrict__ grid)
+k_skip_grid(const uint8_t *__restrict__ vol, int X, int Y, int Z, int S, int nx, int ny, int nz, uint8_t *__restrict__ grid,
+            bool volAligned8)
 {
     // one wave per cell: a lane takes whole x-rows of the cell's (S+1)^2 (y, z) columns -- S + 1 consecutive bytes,
     // fetched as aligned 8-byte pieces where the row allows it -- then a wave min / max
@@ -88,7 +90,7 @@ k_skip_grid(const uint8_t *__restrict__ vol, int X, int Y, int Z, int S, int nx,
     const int x0 = cx * S, y0 = cy * S, z0 = cz * S;
     const int ex = min(S + 1, X - x0), ey = min(S + 1, Y - y0), ez = min(S + 1, Z - z0);
     uint32_t mn = 255, mx = 0;
-    const bool wide = (S & 7) == 0 && (X & 7) == 0;          // rows start 8-byte aligned
+    const bool wide = volAligned8 && (S & 7) == 0 && (X & 7) == 0;          // rows start 8-byte aligned
     for (int r = lane; r < ey * ez; r += 64) {
         const uint8_t *row = vol + (int64_t)x0 + (int64_t)X * ((y0 + r % ey) + (int64_t)Y * (z0 + r / ey));
         int i = 0;
@@ -165,7 +167,7 @@ __device__ __forceinline__ uint32_t skip_bounds(const SkipGrid &sg, const Tex &t
     const int x0 = clampi((int)floorf(px * (float)t.GX - 0.5f), 0, t.GX - 1), y0 = clampi((int)floorf(py * (float)t.GY - 0.5f), 0, t.GY - 1),
               z0 = clampi((int)floorf(pz * (float)t.GZ - 0.5f), 0, t.GZ - 1);
     const int64_t c = (x0 / sg.S) + (int64_t)sg.nx * ((y0 / sg.S) + (int64_t)sg.ny * (z0 / sg.S));
-    return *(const uint16_t *)(sg.g + 2 * c);
+    return *(const u16u *)(sg.g + 2 * c);       // the grid may start at any byte of a caller's allocation
 }
 
 struct RayArgs {
@@ -359,8 +361,9 @@ k_composite_slabs(SlabArgs a)
     a.out[i] = o;
 }
 
-// Brick <-> global volume placement (VolumeReader.h:172-211), 16-byte rows segments.
-template <bool TO_VOLUME>
+// Brick <-> global volume placement (VolumeReader.h:172-211), 16-byte rows segments: one vector copy each where both
+// buffers start 16-byte aligned, sixteen byte copies otherwise (offset views of a caller's allocation).
+template <bool TO_VOLUME, bool ALIGNED>
 __global__ void __launch_bounds__(256)
 k_assemble(const uint8_t *src, uint8_t *dst, int nbricks, int64_t X, int64_t Y, int64_t Z, const int64_t *ijk,
            int64_t I, int64_t J)
@@ -374,8 +377,12 @@ k_assemble(const uint8_t *src, uint8_t *dst, int nbricks, int64_t X, int64_t Y, 
         int64_t xq = q % xv, y = (q / xv) % Y, z = q / (xv * Y);
         int64_t bo = (int64_t)b * X * Y * Z + xq * 16 + X * (y + Y * z);
         int64_t go = (i * X + xq * 16) + GX * ((j * Y + y) + GY * (k * Z + z));
-        if (TO_VOLUME) *(uint4 *)(dst + go) = *(const uint4 *)(src + bo);
-        else *(uint4 *)(dst + bo) = *(const uint4 *)(src + go);
+        const int64_t so = TO_VOLUME ? bo : go, doff = TO_VOLUME ? go : bo;
+        if (ALIGNED) *(uint4 *)(dst + doff) = *(const uint4 *)(src + so);
+        else {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) dst[doff + c] = src[so + c];
+        }
     }
 }
 
@@ -466,7 +473,7 @@ int skip_grid_launch(const uint8_t *vol, const int64_t dims[3], int S, uint8_t *
         return launch_status("skip_grid");
     }
     hipLaunchKernelGGL(k_skip_grid, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, vol, (int)dims[0], (int)dims[1], (int)dims[2], S,
-                       nx, ny, nz, grid);
+                       nx, ny, nz, grid, ((uintptr_t)vol & 7u) == 0u);
     return launch_status("skip_grid");
 }
 
@@ -507,12 +514,10 @@ int assemble_launch(bool toVolume, const uint8_t *src, uint8_t *dst, int nb, con
     int64_t total = bd[0] / 16 * bd[1] * bd[2];
     unsigned gx = (unsigned)((total + 255) / 256);
     if (gx > 4096) gx = 4096;
-    if (toVolume)
-        hipLaunchKernelGGL(k_assemble<true>, dim3(gx, nb), dim3(256), 0, st, src, dst, nb, bd[0], bd[1], bd[2], ijkDev,
-                           grid[0], grid[1]);
-    else
-        hipLaunchKernelGGL(k_assemble<false>, dim3(gx, nb), dim3(256), 0, st, src, dst, nb, bd[0], bd[1], bd[2], ijkDev,
-                           grid[0], grid[1]);
+    const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0u;
+    auto kern = toVolume ? (aligned ? k_assemble<true, true> : k_assemble<true, false>)
+                         : (aligned ? k_assemble<false, true> : k_assemble<false, false>);
+    hipLaunchKernelGGL(kern, dim3(gx, nb), dim3(256), 0, st, src, dst, nb, bd[0], bd[1], bd[2], ijkDev, grid[0], grid[1]);
     return launch_status("raymarch");
 }
 int measure_error_launch(const uint8_t *a, const uint8_t *b, int64_t n, int *maxErrDev, unsigned long long *sumDev,

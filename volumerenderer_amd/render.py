@@ -44,15 +44,44 @@ def default_params(width=1600, height=1200, brick_dims=(256, 256, 128), mode=_li
     return P
 
 
+def _check_buf(t, what, dtype, numel, device):
+    """The C ABI reads and writes through raw pointers: a buffer it is handed must be a contiguous `dtype` tensor of
+    exactly `numel` elements on `device`, or the wrapper raises ValueError before anything is launched (as
+    distributed.composite_sort_last does)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a torch tensor, not %s" % (what, type(t).__name__))
+    if t.dtype != dtype:
+        raise ValueError("%s must be %s, not %s" % (what, dtype, t.dtype))
+    if t.device != device:
+        raise ValueError("%s must be on %s, not %s" % (what, device, t.device))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+    if t.numel() != numel:
+        raise ValueError("%s must hold %d elements, not %d" % (what, numel, t.numel()))
+
+
+def _skip_grid_bytes(dims, cell):
+    n = 2
+    for q in dims:
+        n *= (int(q) + int(cell) - 1) // int(cell)
+    return n
+
+
 def build_skip_grid(volume, dims, cell=8, out=None, stream=None):
     """(min, max) per cell^3 voxels (+1 voxel reach of a trilinear fetch) of a device volume: 2 bytes per cell.
     Attach to render params with use_skip_grid(); the frame stays bit-identical, the marcher just does not fetch
     samples the grid proves irrelevant."""
     v = _as_dev_u8(volume)
     d = (C.c_int64 * 3)(*[int(q) for q in dims])
-    n = [(int(q) + cell - 1) // cell for q in dims]
+    if v.numel() != d[0] * d[1] * d[2]:
+        raise ValueError("volume size does not match dims")
+    if not 1 <= int(cell) <= 64:
+        raise ValueError("cell must be 1..64, not %d" % int(cell))
+    nbytes = _skip_grid_bytes(dims, cell)
     if out is None:
-        out = torch.empty(2 * n[0] * n[1] * n[2], dtype=torch.uint8, device="cuda")
+        out = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+    else:
+        _check_buf(out, "out", torch.uint8, nbytes, v.device)
     check(_lib.lib().vr_skip_grid_build(C.c_void_p(v.data_ptr()), d, int(cell), C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
           "vr_skip_grid_build")
     return out
@@ -69,24 +98,46 @@ def raycast(volume, dims, cam, params, out=None, stream=None):
     """volume: CUDA uint8 (X*Y*Z, x fastest). Returns float32 CUDA [H][W][4], row 0 = top."""
     v = _as_dev_u8(volume)
     d = (C.c_int64 * 3)(*[int(q) for q in dims])
-    if v.numel() != d[0] * d[1] * d[2]:
+    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
         raise ValueError("volume size does not match dims")
+    if params.skip_grid_dev and params.skip_cell > 0:
+        # the grid must describe THIS volume at THIS cell size, or skip_bounds reads past it
+        g = getattr(params, "_keep_grid", None)
+        if g is None or g.data_ptr() != params.skip_grid_dev:
+            raise ValueError("attach skip grids with use_skip_grid()")
+        _check_buf(g, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), v.device)
     if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device="cuda")
+        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=v.device)
+    else:
+        _check_buf(out, "out", torch.float32, params.height * params.width * 4, v.device)
     check(_lib.lib().vr_raycast(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params),
                                 C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast")
     return out
 
 
 def composite_over(front, back, stream=None):
+    """front = front OVER back, in place; both contiguous float32 (c, tau, covered, 0) images of the same size."""
+    if not isinstance(front, torch.Tensor) or not front.is_cuda:
+        raise ValueError("front must be a CUDA tensor")
+    if front.numel() == 0 or front.numel() % 4:
+        raise ValueError("front must hold whole (c, tau, covered, 0) pixels, not %d floats" % front.numel())
+    _check_buf(front, "front", torch.float32, front.numel(), front.device)
+    _check_buf(back, "back", torch.float32, front.numel(), front.device)
     check(_lib.lib().vr_composite_over(C.c_void_p(front.data_ptr()), C.c_void_p(back.data_ptr()),
                                        front.numel() // 4, _stream_ptr(stream)), "vr_composite_over")
     return front
 
 
 def composite_finish(partial, out=None, stream=None):
+    if not isinstance(partial, torch.Tensor) or not partial.is_cuda:
+        raise ValueError("partial must be a CUDA tensor")
+    if partial.numel() == 0 or partial.numel() % 4:
+        raise ValueError("partial must hold whole (c, tau, covered, 0) pixels, not %d floats" % partial.numel())
+    _check_buf(partial, "partial", torch.float32, partial.numel(), partial.device)
     if out is None:
         out = torch.empty_like(partial)
+    else:
+        _check_buf(out, "out", torch.float32, partial.numel(), partial.device)
     check(_lib.lib().vr_composite_finish(C.c_void_p(partial.data_ptr()), C.c_void_p(out.data_ptr()),
                                          partial.numel() // 4, _stream_ptr(stream)), "vr_composite_finish")
     return out
