@@ -367,12 +367,10 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
 
 /* ---- debugging switches (new) ----------------------------------------------------------------------------------
  * Which kernel serves a call is decided by the set's geometry and by a few switches kept IN THE HANDLE: they are
- * initialised from the environment (VRHIP_DECODE_WALK, VRHIP_DECODE_FINE_V1, VRHIP_DECODE_QUAD, VRHIP_DECODE_V1,
- * VRHIP_NO_FUSED_EMIT, VRHIP_NO_SKIP_BLOCKS, VRHIP_NOSWZ, VRHIP_MR_SERIAL, VRHIP_FORK_BRICKS) once, when the set is
- * created, and changed afterwards only through this call -- never by the environment at launch time.  Names:
- * "decode_walk", "decode_fine_v1", "decode_quad", "decode_v1", "no_skip_blocks", "noswz", "mr_serial",
- * "fork_bricks" (0..4), "no_fused_emit" (before the first build only: VR_ERR_STATE afterwards).  Results never
- * depend on a switch; the tests use them to check the kernels against each other.
+ * initialised from the environment (VRHIP_DECODE_WALK, VRHIP_DECODE_FINE_V1, VRHIP_DECODE_QUAD, VRHIP_NO_SKIP_BLOCKS)
+ * once, when the set is created, and changed afterwards only through this call -- never by the environment at launch
+ * time.  Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks"; any other name is VR_ERR_INVALID.
+ * Results never depend on a switch; the tests use them to check the kernels against each other.
  * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1". */
 vr_status vr_brickset_set_switch(vr_brickset *bs, const char *name, int32_t value);
 vr_status vr_debug_set(const char *name, int32_t value);

@@ -291,22 +291,21 @@ def test_progressive_cut_matches_oracle(vr, oracle, tmp_path):
             assert np.array_equal(got, ref.levelCutProgressive(cut)), "foreign cut %d" % cut
 
 
-def test_fused_emit_equals_two_pass_emit(vr, oracle, monkeypatch):
-    """The default D >= 12 path (k_prune_emit12 + k_concat12) and the older per-quad emitter kept behind
-    VRHIP_NO_FUSED_EMIT must produce the same bytes, index and statistics."""
+def test_fused_emit_matches_oracle(vr, oracle):
+    """Bricks of D >= 12 are built by k_prune_emit12 + k_index12 / k_concat12.  Three 32x64x32 volumes (smooth,
+    noise, a stretched sphere) each match the oracle in everything check_case compares, and the three built as one
+    batched set give the three single-brick results."""
     rng = np.random.default_rng(21)
     vols = [rm_like((32, 64, 32)), rng.integers(0, 256, (32, 64, 32), dtype=np.uint8), oracle.gen_sphere(32, 3).repeat(2, axis=1)]
-    res = []
-    for env in (None, "1"):
-        if env: monkeypatch.setenv("VRHIP_NO_FUSED_EMIT", env)
-        bs = vr.BrickSet(len(vols), (32, 64, 32), 1, 2)
-        bs.build(np.stack(vols))
-        dec = bs.decode().cpu().numpy()
-        res.append([(bs.tree(i).tobytes(), tuple(sorted(bs.info(i).items()))) for i in range(len(vols))] + [dec.tobytes()])
-    monkeypatch.delenv("VRHIP_NO_FUSED_EMIT")
-    assert res[0] == res[1]
-    ref = oracle.OracleTree(vols[1].copy(), tolerance=1, max_epochs=2).build()
-    assert res[0][1][0] == ref.tree.tobytes()
+    single = []
+    for v in vols:
+        _, bs = check_case(vr, oracle, v, 1, 2)
+        single.append((bs.tree(0).tobytes(), bs.info(0), list(bs.distance_map(0)), bs.decode().cpu().numpy().tobytes()))
+    bs = vr.BrickSet(len(vols), (32, 64, 32), 1, 2)
+    bs.build(np.stack(vols))
+    dec = bs.decode().cpu().numpy().reshape(len(vols), -1)
+    for i in range(len(vols)):
+        assert (bs.tree(i).tobytes(), bs.info(i), list(bs.distance_map(i)), dec[i].tobytes()) == single[i], "brick %d" % i
 
 
 def test_midrange_file_roundtrip(vr, oracle, tmp_path):

@@ -17,19 +17,14 @@ struct Stream2 {              // one 2-bit stream (mid, or MidRangeTree's half-r
                                     // BrickSet::brickOff[b] (compact_launch; at the end of build() unless compaction was turned off)
 };
 
-// Debugging / experiment switches.  Read from the environment (VRHIP_<NAME>) ONCE, when a set is created, or set
-// explicitly with vr_brickset_set_switch -- never in a launch path: the kernels a handle uses do not change behind
-// the caller's back, and buffers sized under one setting are not used under another.
+// Debugging switches: each runs one kernel in place of another on the same data, for the tests to compare.  Read from
+// the environment (VRHIP_<NAME>) ONCE, when a set is created, or set explicitly with vr_brickset_set_switch -- never
+// in a launch path: the kernels a handle uses do not change behind the caller's back.
 struct Switches {
-    bool decodeV1 = false;       // VRHIP_DECODE_V1: k_decode_lane for everything
     bool decodeWalk = false;     // VRHIP_DECODE_WALK: k_decode_tile (no per-4-leaf counts)
     bool decodeFineV1 = false;   // VRHIP_DECODE_FINE_V1: round 1's k_decode_fine
     bool decodeQuad = false;     // VRHIP_DECODE_QUAD: round 2's k_decode_quad instead of k_decode_region
-    bool noFusedEmit = false;    // VRHIP_NO_FUSED_EMIT
     bool noSkipBlocks = false;   // VRHIP_NO_SKIP_BLOCKS
-    bool noSwz = false;          // VRHIP_NOSWZ
-    bool mrSerial = false;       // VRHIP_MR_SERIAL
-    int forkBricks = 0;          // VRHIP_FORK_BRICKS (0: default)
 };
 
 // vr_brickset_decode_lod: the device state of one call.  Calls take the slots of a ring in turn; a call waits on the
@@ -46,16 +41,6 @@ struct LodSlot {
     bool pending = false;
 };
 
-// one launch class of a per-brick decode (decode_launch's `lod` argument)
-struct LodClass {
-    const int32_t *list = nullptr; // device: the class's bricks (grid rows)
-    int n = 0;
-    const int32_t *cuts = nullptr; // device: the cuts of all B bricks
-    uint8_t *idxValCut = nullptr;
-    uint32_t *decTables = nullptr;
-    uint8_t *rankVals = nullptr;
-};
-
 struct BrickSet {
     int32_t B = 0;
     Switches sw;
@@ -70,7 +55,7 @@ struct BrickSet {
     int64_t reconStride = 0;  // bytes per brick of a reconstruction buffer: 2^D, or 2^(D-1) in a leafless build
     // A fused build (k_prune_emit12) never stores the leaf level's codes and reconstruction: its leaf-level fills only
     // sum errors, and the prune recomputes both from (truth, parent's reconstruction, the distances the level loop ended
-    // with: Ctrl::finalReconDist / finalCodesDist).  Decided when the encoder's buffers are allocated (first build).
+    // with: Ctrl::finalReconDist / finalCodesDist).  Set from leafless_build() when the encoder's buffers are allocated.
     bool leafless = false;
     int64_t treeCap = 0;      // bytes per brick reserved for the preorder stream
     int64_t nIdx = 0;         // 2^Ds index entries per brick
@@ -144,12 +129,15 @@ struct BrickSet {
     int lodNext = 0;
 };
 
+// Every D >= 12 brick is built by k_prune_emit12; with a level loop that runs, such a build keeps nothing of the leaf
+// level (BrickSet::leafless).
+inline bool leafless_build(const BrickSet &b) { return b.D >= 12 && b.maxEpochs >= 1; }
+
 // kd_encode.hip
 int encode_launch(BrickSet *bs, const uint8_t *voxDev, hipStream_t st);
 int compact_launch(BrickSet *bs, hipStream_t st);   // fused builds: contiguous stream(s) into Stream2::treeCompact
 // kd_decode.hip
-int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false,
-                  const LodClass *lod = nullptr);
+int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false);
 // per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
 int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st);
 void free_lod_slots(BrickSet *bs);

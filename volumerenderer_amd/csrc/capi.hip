@@ -141,10 +141,8 @@ static void free_encoder_buffers(BrickSet &b)
 static vr_status alloc_encoder_buffers(BrickSet &b)
 {
     const size_t B = (size_t)b.B;
-    // a fused build (k_prune_emit12: D >= 12, 64-leaf index granularity, not switched off) with a level loop that runs
-    // keeps nothing of the leaf level: codes and reconstruction arrays end one level higher (BrickSet::leafless).
-    // The switch is final here: vr_brickset_set_switch("no_fused_emit") is refused after the first build.
-    b.leafless = b.D >= 12 && b.K == 6 && !b.sw.noFusedEmit && b.maxEpochs >= 1;
+    // a leafless build's codes and reconstruction arrays end one level above the leaves
+    b.leafless = leafless_build(b);
     b.reconStride = b.leafless ? b.leafStride / 2 : b.leafStride;
     b.codeStride = b.leafless ? b.leafStride / 4 + 16 : ((b.heapStride + 15) / 16) * 4;
     HIPCHK(hipMalloc(&b.mid.temp, B * (size_t)b.heapStride));
@@ -238,15 +236,10 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
     b.B = num_bricks;
     {   // the VRHIP_* debugging switches are read here, once per set (brickset.h Switches)
         Switches &w = b.sw;
-        w.decodeV1 = getenv("VRHIP_DECODE_V1") != nullptr;
         w.decodeWalk = getenv("VRHIP_DECODE_WALK") != nullptr;
         w.decodeFineV1 = getenv("VRHIP_DECODE_FINE_V1") != nullptr;
         w.decodeQuad = getenv("VRHIP_DECODE_QUAD") != nullptr;
-        w.noFusedEmit = getenv("VRHIP_NO_FUSED_EMIT") != nullptr;
         w.noSkipBlocks = getenv("VRHIP_NO_SKIP_BLOCKS") != nullptr;
-        w.noSwz = getenv("VRHIP_NOSWZ") != nullptr;
-        w.mrSerial = getenv("VRHIP_MR_SERIAL") != nullptr;
-        if (const char *e = getenv("VRHIP_FORK_BRICKS")) { const long v = strtol(e, nullptr, 10); w.forkBricks = v >= 1 && v <= 4 ? (int)v : 0; }
     }
     make_geom(b.g, dims);
     b.D = b.g.D;
@@ -320,19 +313,11 @@ vr_status vr_brickset_set_switch(vr_brickset *h, const char *name, int32_t value
     if (!h || !name) return VR_ERR_INVALID;
     Switches &w = h->s.sw;
     const bool on = value != 0;
-    if (!strcmp(name, "decode_v1")) w.decodeV1 = on;
-    else if (!strcmp(name, "decode_walk")) w.decodeWalk = on;
+    if (!strcmp(name, "decode_walk")) w.decodeWalk = on;
     else if (!strcmp(name, "decode_fine_v1")) w.decodeFineV1 = on;
     else if (!strcmp(name, "decode_quad")) w.decodeQuad = on;
     else if (!strcmp(name, "no_skip_blocks")) w.noSkipBlocks = on;
-    else if (!strcmp(name, "noswz")) w.noSwz = on;
-    else if (!strcmp(name, "mr_serial")) w.mrSerial = on;
-    else if (!strcmp(name, "fork_bricks")) { if (value < 0 || value > 4) return VR_ERR_INVALID; w.forkBricks = value; }
-    else if (!strcmp(name, "no_fused_emit")) {
-        // the emitter decides the layout of the stream buffer and which side-cars exist: only before the first build
-        if (h->s.built) return VR_ERR_STATE;
-        w.noFusedEmit = on;
-    } else return VR_ERR_INVALID;
+    else return VR_ERR_INVALID;
     return VR_OK;
 }
 
@@ -369,7 +354,7 @@ vr_status vr_brickset_build(vr_brickset *h, const uint8_t *vox, void *stream)
     BrickSet &b = h->s;
     // (vr_brickset_set_max_epochs(0) <-> >= 1 between two builds changes what the level loop keeps of the leaf level:
     // the encoder's arrays are made again for the other mode)
-    if (b.encoderReady && b.leafless != (b.D >= 12 && b.K == 6 && !b.sw.noFusedEmit && b.maxEpochs >= 1)) {
+    if (b.encoderReady && b.leafless != leafless_build(b)) {
         HIPCHK(hipDeviceSynchronize());
         free_encoder_buffers(b);
     }

@@ -369,20 +369,13 @@ __device__ __forceinline__ void tile_gather(const TileArgs &a, const uint32_t *t
 }
 
 
-#ifndef QD_NT
-#define QD_NT 1
-#endif
 // decoded voxels are written once and not read again by this launch: streaming stores keep them from displacing the
 // stream and side-car lines the neighbouring tiles are about to read
 __device__ __forceinline__ void store_out16(uint8_t *p, uint4 v)
 {
-#if QD_NT
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     u32x4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
     __builtin_nontemporal_store(t, (u32x4 *)p);
-#else
-    *(uint4 *)p = v;
-#endif
 }
 
 // the same gather with wide LDS reads (k_decode_quad).  A 16-byte row piece = the voxels x = 16c .. 16c+15 of one (y, z)
@@ -878,22 +871,11 @@ k_decode_fine(TileArgs a)
 //     its parent's scalar through selects, never through exec-mask branches;
 //   * the workgroup's front end (index pre-pass into LDS, two tickets per wave, ticket order by emit block, per-level
 //     delta tables) and what bounds the launch are described at the kernel and in DESIGN.md 3.3.
-#ifndef QD_WAVES
 #define QD_WAVES 16
-#endif
-#ifndef QD_KEYMASK
-#define QD_KEYMASK 0xFFFCu      // (timing experiments only: a smaller mask fakes a smaller table)
-#endif
-#ifndef QD_TPW
 #define QD_TPW 16           // tiles per wave: amortises the table copy
-#endif
 #define QD_TS 68            // tile row stride in words (as FD_TS)
-#ifndef QD_PF
 #define QD_PF 4             // steps the stream-word requests run ahead
-#endif
-#ifndef QD_CHAIN_ENTRIES
 #define QD_CHAIN_ENTRIES 16384
-#endif
 
 // entry: byte 0 = A (int8), byte 2 = LO, byte 3 = HI; `levels` = branch levels at or above the cut (7: levelCut at
 // full depth; fewer: progressive cut inside the branch, deeper levels refine nothing)
@@ -945,7 +927,7 @@ __device__ __forceinline__ int qd_leaf(uint32_t yl, int V5, const int *delta6, c
     // branch tokens = bits 2..15.  (Measured on gfx950: a two-operand VALU instruction takes 2 cycles of the SIMD,
     // a three-operand or byte-select (SDWA) one 4 -- scratch/mb/valu_rate.hip -- so the three byte selects below cost
     // what six plain instructions would; reading the entry's bytes with three LDS reads instead was 27 % slower.)
-    const uint32_t ent = *(const uint32_t *)((const char *)chainS + (ym & QD_KEYMASK));
+    const uint32_t ent = *(const uint32_t *)((const char *)chainS + (ym & 0xFFFCu));
     // The leaf's own step clamps to [0, 255] (R.cpp:783-787) before the branch's composed clamp-add f runs; f is
     // monotone with f(0) = LO and f(255) = HI, and f(v) = min(max(v + A, LO), HI) on [0, 255], so
     // f(clamp(x, 0, 255)) = min(max(x + A, LO), HI) for every x: the inner clamp needs no instruction.
@@ -972,9 +954,7 @@ __device__ __forceinline__ uint32_t qd_pair(uint32_t y, uint32_t yh, uint32_t de
     return (uint32_t)v1 | ((uint32_t)v2 << 8);
 }
 
-#ifndef QD_MINW
 #define QD_MINW 1
-#endif
 __global__ void __launch_bounds__(64 * QD_WAVES, QD_MINW)
 k_decode_quad(TileArgs a)
 {
@@ -1111,13 +1091,8 @@ k_decode_quad(TileArgs a)
             const bool stepDead = ((uint32_t)(liveMask >> (lane & 60)) & 15u) == 0u;     // my step's four blocks are all dead
             const uint32_t deadW = stepDead ? rep : val0;
             uint32_t run = 0;
-#ifdef RG_KO_PARK           // (timing experiments)
-#pragma unroll
-            for (int gg = 0; gg < 1; ++gg) {
-#else
 #pragma unroll
             for (int gg = 0; gg < 16; ++gg) {
-#endif
                 const uint32_t cgg = (cw[gg >> 2] >> (8 * (gg & 3))) & 255u;
                 const int own = gg == 0 ? 4 : (gg & 1 ? 0 : (gg & 2 ? 1 : (gg & 4 ? 2 : 3)));
                 const uint32_t vgg = (sw[gg >> 3] >> (8 * ((gg >> 1) & 3))) & 255u;
@@ -1214,18 +1189,10 @@ k_decode_quad(TileArgs a)
 // step q >> 6, and bits 2-4 XORed with the step's low three bits, so that the step accesses (64 consecutive words),
 // the park stores (one 64-leaf block per lane) and the gather's 16-byte reads (with the block images 4 words apart in
 // the banks) are all conflict-free or two-way.
-#ifndef RG_NP
 #define RG_NP 4             // ring pieces of 1 KiB per wave
-#endif
-#ifndef RG_MINW
 #define RG_MINW 4           // waves per SIMD asked of the register allocator (4: two workgroups per CU, 6: three)
-#endif
-#ifndef RG_PER
 #define RG_PER 16           // regions per workgroup
-#endif
-#ifndef RG_WAVES
 #define RG_WAVES 8          // emit blocks (waves) of a region along x: 8 = whole 128-byte lines, 4 = 64-byte half lines
-#endif
 #define RG_LW (RG_WAVES == 8 ? 3 : 2)
 #define RG_REGX (16 * RG_WAVES)
 #define RG_BLK_WORDS 1028
@@ -1258,7 +1225,6 @@ struct RegionArgs {
     uint32_t blkX, blkY, blkZ;  // 6 x 5 bits each: bit k of x >> 4 (y >> 4, z >> 4) is this bit of the emit block's number (= leaf rank >> 12)
     int nreg;                   // regions of a brick
     const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
-    unsigned long long *dbg;    // RG_STAMP builds only: cycle sums (total, park, steps, barrier 1, gather, barrier 2)
 };
 
 __device__ __forceinline__ uint32_t wave_incl_scan_max_dpp(uint32_t v)
@@ -1330,9 +1296,6 @@ __device__ __forceinline__ uint32_t rg_pair(uint32_t y, uint32_t yh, uint32_t de
 __device__ __forceinline__ uint32_t rg_quad(uint32_t pw, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t p0, uint32_t p1,
                                             const RegionShared &sm)
 {
-#ifdef RG_KO_COMPUTE        // (timing experiments: the step's arithmetic replaced by an XOR of its inputs)
-    return pw ^ w0 ^ w1 ^ w2 ^ w3 ^ p0;
-#endif
     const uint32_t b = (pw >> 7) & 30u;                    // bit of my first token in w0
     const int V3 = (int)(pw & 255u);
     const uint32_t dead = ((pw >> 24) & 1u) - 1u;           // all ones <=> my root does not exist
@@ -1371,9 +1334,7 @@ __device__ __forceinline__ void rg_vm_wait(uint32_t n)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_" SUFFIX " %1, off\n\ts_mov_b32 m0, %0" \
                  : "=&s"(keep_) : "v"(gptr), "s"(ldsByte) : "memory"); } while (0)
 
-#ifndef RG_IDXD
 #define RG_IDXD 3           // regions the index entries run ahead
-#endif
 
 __global__ void __launch_bounds__(64 * RG_WAVES, RG_MINW)
 k_decode_region(RegionArgs a)
@@ -1541,16 +1502,7 @@ k_decode_region(RegionArgs a)
     for (int d = 0; d < RG_IDXD; ++d) if (rid + d * G < nreg) request_index(rid + d * G, d);
     stage(rid, 0);
     int slot = 0;           // index slot of the current region
-#ifdef RG_STAMP             // (diagnostic build: where a wave's cycles go; never timed)
-    unsigned long long tAcc[6] = {0, 0, 0, 0, 0, 0}, tPiece = 0;
-#define RG_T(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tAcc[i] += now_ - tLast; tLast = now_; } while (0)
-    unsigned long long tLast = __builtin_amdgcn_s_memtime();
-    const unsigned long long tStart = tLast;
-#else
-#define RG_T(i) do { } while (0)
-#endif
     for (; rid < nreg; rid += G) {
-        RG_T(5);
         if (liveMask == 0ull) {
             // an emit block under pruned nodes: one value per 64-leaf block, no stream, no further side-car
             const uint32_t rep = valC * 0x01010101u;
@@ -1571,13 +1523,8 @@ k_decode_region(RegionArgs a)
             const bool stepDead = ((uint32_t)(liveMask >> (lane & 60)) & 15u) == 0u;
             const uint32_t deadW = stepDead ? valC * 0x01010101u : valC;
             uint32_t run = liveL ? offC - wbase * 16u : 0u;
-#ifdef RG_KO_PARK           // (timing experiments)
-#pragma unroll
-            for (int gg = 0; gg < 1; ++gg) {
-#else
 #pragma unroll
             for (int gg = 0; gg < 16; ++gg) {
-#endif
                 const uint32_t cgg = (cw[gg >> 2] >> (8 * (gg & 3))) & 255u;
                 const int own = gg == 0 ? 4 : (gg & 1 ? 0 : (gg & 2 ? 1 : (gg & 4 ? 2 : 3)));
                 const uint32_t vgg = (sw2[gg >> 3] >> (8 * ((gg >> 1) & 3))) & 255u;
@@ -1586,7 +1533,6 @@ k_decode_region(RegionArgs a)
                 run += cgg;
             }
             const uint32_t mEnd = wave_incl_scan_max_dpp(liveL ? run : 0u);       // end of the last live block up to mine
-            RG_T(1);
             // the side-cars are in registers: their ring slots take the string's pieces 2 and 3
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             for (uint32_t p = 2; p < (uint32_t)RG_NP && p < totalPieces; ++p) { issue_piece(wbase, p); ++issued; }
@@ -1601,13 +1547,7 @@ k_decode_region(RegionArgs a)
                 // the pieces this trip reads must have landed
                 const uint32_t need = (((endTok + 15u) >> 4) + 255u) >> 8;
                 if (need > landed) {
-#ifdef RG_STAMP
-                    const unsigned long long w0_ = __builtin_amdgcn_s_memtime();
-#endif
                     rg_vm_wait(ops - mark_of_piece(need - 1u));
-#ifdef RG_STAMP
-                    tPiece += __builtin_amdgcn_s_memtime() - w0_;
-#endif
                     landed = need;
                     while (guardNext < need) {     // a piece has landed on the ring's first slot: its first four words again behind the last slot
                         if (lane < 4) ringW[RG_NP * 256 + lane] = ringW[lane];
@@ -1638,7 +1578,6 @@ k_decode_region(RegionArgs a)
                 while (issued < totalPieces && 256u * (issued - (RG_NP - 1)) <= consumedWord) { issue_piece(wbase, issued); ++issued; }
             }
         }
-        RG_T(2);
         // ---- where this region's voxels go
         const uint32_t rxC = (uint32_t)rid & ((1u << a.lrx) - 1u), ryC = ((uint32_t)rid >> a.lrx) & ((1u << a.lry) - 1u), rzC = (uint32_t)rid >> (a.lrx + a.lry);
         uint8_t *O = a.out + (int64_t)brick * a.voxels + ((int64_t)rzC * 16 * a.Y + (int64_t)ryC * 16) * a.X + (int64_t)rxC * RG_REGX + (lane & (RG_WAVES - 1)) * 16;
@@ -1646,14 +1585,9 @@ k_decode_region(RegionArgs a)
         // lands before the next region's piece for the same slot: loads return in issue order)
         slot = slot + 1 == RG_IDXD ? 0 : slot + 1;
         if (rid + G < nreg) stage(rid + G, slot);
-        RG_T(2);
         rg_barrier();           // every block of the region is decoded
-        RG_T(3);
         // ---- gather: a 16-byte row piece of emit block c = lane & 7 per lane, eight whole 128-byte lines per store.
         // All reads of the image first (they are independent), then the byte picks and the stores.
-#ifdef RG_KO_GATHER         // (timing experiments)
-        if (false)
-#endif
         {
             const uint32_t *img = sm.buf + (lane & (RG_WAVES - 1)) * RG_BLK_WORDS;
             const uint32_t xr1 = a.xRead[0] >> 16, xr2 = a.xRead[1] & 0xFFFFu, xr3 = a.xRead[1] >> 16;
@@ -1680,12 +1614,8 @@ k_decode_region(RegionArgs a)
                     const uint32_t sel = b0 | (b1 << 8) | ((4u + b0) << 16) | ((4u + b1) << 24);
                     const uint4 o4 = make_uint4(__builtin_amdgcn_perm(P[it].y, P[it].x, sel), __builtin_amdgcn_perm(P[it].w, P[it].z, sel),
                                                 __builtin_amdgcn_perm(Q[it].y, Q[it].x, sel), __builtin_amdgcn_perm(Q[it].w, Q[it].z, sel));
-#ifdef RG_KO_STORE          // (timing experiments: no store; the count of operations must stay right)
-                    asm volatile("" :: "v"(o4.x), "v"(o4.y), "v"(o4.z), "v"(o4.w));
-#else
                     store_out16(O + ooI[it], o4);
                     ++ops;
-#endif
                 }
             } else {                 // jx == 2: four x-neighbours in four words
 #pragma unroll
@@ -1705,28 +1635,14 @@ k_decode_region(RegionArgs a)
                             return __builtin_amdgcn_perm(__builtin_amdgcn_perm(u.w, u.z, sel), __builtin_amdgcn_perm(u.y, u.x, sel), 0x05040100u);
                         };
                         const uint4 o4 = make_uint4(mk(P[k]), mk(Q[k]), mk(R[k]), mk(T[k]));
-#ifdef RG_KO_STORE
-                        asm volatile("" :: "v"(o4.x), "v"(o4.y), "v"(o4.z), "v"(o4.w));
-#else
                         store_out16(O + ooI[2 * h + k], o4);
                         ++ops;
-#endif
                     }
                 }
             }
         }
-        RG_T(4);
         rg_barrier();           // the image is free for the next region's park
     }
-#ifdef RG_STAMP
-    RG_T(5);
-    if (lane == 0 && a.dbg) {
-        atomicAdd(&a.dbg[0], __builtin_amdgcn_s_memtime() - tStart);
-        for (int i = 1; i < 6; ++i) atomicAdd(&a.dbg[i], tAcc[i]);
-        atomicAdd(&a.dbg[6], 1ull);
-        atomicAdd(&a.dbg[7], tPiece);
-    }
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (no LDS-DMA may outlive the workgroup's LDS)
 }
 
@@ -1890,27 +1806,59 @@ k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *
     out[(int64_t)brick * nIdx + s] = (uint8_t)val;
 }
 
-// k_decode_fine / k_decode_quad / k_decode_region need every brick's per-4-leaf side-car
-static bool use_fine(const BrickSet *bs, bool rangeStream)
-{
-    bool useFine = bs->fineIdx && (int)bs->fineHas.size() == bs->B && !rangeStream && !bs->sw.decodeWalk;
-    for (int i = 0; useFine && i < bs->B; ++i) useFine = bs->fineHas[(size_t)i] != 0;
-    return useFine;
-}
+// ---- the choice of decode kernel.  The kernels, in the order a per-brick decode launches its classes:
+enum class DecodeKernel { REGION, QUAD, FINE, TILE, GENERAL, LANE };
+constexpr int DECODE_KERNELS = (int)DecodeKernel::LANE + 1;
 
-// k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
-// at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
-static bool use_quad(const BrickSet *bs, bool useFine, int cut)
-{
-    return useFine && bs->idxVal3 && cut >= bs->D - 3 && !bs->sw.decodeFineV1;
-}
+// What the choice depends on besides the cut: the set's geometry, the per-4-leaf side-cars and the switches.  Worked
+// out once per call (a per-brick decode classifies every brick with one plan); kernel() is the only place a kernel is
+// chosen.
+struct DecodePlan {
+    const BrickSet *bs;
+    bool tiled = false;     // tile geometry: k_decode_tile and the kernels built on it
+    bool fine = false;      // every brick has the per-4-leaf side-car (k_decode_fine / quad / region)
+    bool region = false;    // region geometry, and k_decode_quad was not asked for instead
+    TileArgs t;             // (geometry part: tile_geometry)
+    RegionArgs r;           // (geometry part: region_geometry)
 
-int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream, const LodClass *lod)
+    DecodePlan(const BrickSet *b, bool rangeStream) : bs(b)
+    {
+        if (bs->generalGeom) return;
+        tiled = tile_geometry(bs, t);
+        if (!tiled) return;
+        fine = bs->fineIdx && (int)bs->fineHas.size() == bs->B && !rangeStream && !bs->sw.decodeWalk;
+        for (int i = 0; fine && i < bs->B; ++i) fine = bs->fineHas[(size_t)i] != 0;
+        region = fine && !bs->sw.decodeQuad && region_geometry(bs, r);
+    }
+
+    DecodeKernel kernel(int cut) const
+    {
+        if (bs->generalGeom) return DecodeKernel::GENERAL;
+        if (!tiled) return DecodeKernel::LANE;
+        // k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
+        // at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
+        if (fine && bs->idxVal3 && cut >= bs->D - 3 && !bs->sw.decodeFineV1)
+            return region ? DecodeKernel::REGION : DecodeKernel::QUAD;
+        return fine ? DecodeKernel::FINE : DecodeKernel::TILE;
+    }
+};
+
+// one launch class of a per-brick decode (launch_decode's `lod` argument)
+struct LodClass {
+    const int32_t *list = nullptr; // device: the class's bricks (grid rows)
+    int n = 0;
+    const int32_t *cuts = nullptr; // device: the cuts of all B bricks
+    uint8_t *idxValCut = nullptr;
+    uint32_t *decTables = nullptr;
+    uint8_t *rankVals = nullptr;
+};
+
+// One launch of kernel k.  lod: one class of a per-brick decode (decode_lod_launch): grid rows = the class's bricks,
+// each at its own cut; `cut` is one of theirs (the kernel is the class's).  The call's cut values, fine tables and rank
+// scratch are its own (LodSlot), and the caller records the timing events around all classes.
+static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, uint8_t *out, int cut, hipStream_t st,
+                         bool rangeStream, const LodClass *lod)
 {
-    // lod: one class of a per-brick decode (decode_lod_launch): grid rows = the class's bricks, each at its own cut;
-    // `cut` is one of theirs (the kernel choice below depends on the class only).  The call's cut values, fine
-    // tables and rank scratch are its own (LodSlot), and the caller records the timing events around all classes.
-    if (lod && rangeStream) return -2;
     if (!lod) hipEventRecord(bs->ev[5], st);
     const unsigned rows = lod ? (unsigned)lod->n : (unsigned)bs->B;
     const int32_t *list = lod ? lod->list : nullptr, *cuts = lod ? lod->cuts : nullptr;
@@ -1929,8 +1877,19 @@ int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rang
         cutVals = bs->idxValCut;   // foreign streams: filled by the host from the bytes (capi)
         if (rangeStream) idxVals = bs->idxValCut;
     }
-    TileArgs t;
-    if (bs->generalGeom) {
+    const auto tile_args = [&]() {
+        TileArgs t = plan.t;
+        t.tree = sm.tree; t.treeCap = bs->treeCap;
+        t.idxOff = bs->idxOff; t.idxVal = idxVals; t.nIdx = bs->nIdx;
+        t.ctrls = sm.ctrl; t.out = out; t.g = bs->g; t.D = bs->D; t.Ds = bs->Ds;
+        t.cut = cut; t.idxValCut = cutVals; t.spread = bs->spread;
+        t.list = list; t.cuts = cuts;
+        t.fine = bs->fineIdx;
+        t.val3 = bs->idxVal3;
+        return t;
+    };
+    switch (k) {
+    case DecodeKernel::GENERAL: {
         // general extents: rank-domain decode, then every voxel takes its owner leaf's value
         if (!lod && !bs->rankVals && hipMalloc(&bs->rankVals, (size_t)bs->B * bs->leafStride * 2) != hipSuccess) return -3;
         uint8_t *rankVals = lod ? lod->rankVals : bs->rankVals;
@@ -1944,70 +1903,58 @@ int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rang
         hipLaunchKernelGGL(k_decode_lane<true>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_owner_gather, dim3((unsigned)((bs->g.voxels + 255) / 256), rows), dim3(256), 0, st,
                            (const uint16_t *)rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list);
-    } else if (!bs->sw.decodeV1 && tile_geometry(bs, t)) {
-        t.tree = sm.tree; t.treeCap = bs->treeCap;
-        t.idxOff = bs->idxOff; t.idxVal = idxVals; t.nIdx = bs->nIdx;
-        t.ctrls = sm.ctrl; t.out = out; t.g = bs->g; t.D = bs->D; t.Ds = bs->Ds;
-        t.cut = cut; t.idxValCut = cutVals; t.spread = bs->spread;
-        t.list = list; t.cuts = cuts;
+        break;
+    }
+    case DecodeKernel::REGION: {
+        RegionArgs r = plan.r;
+        r.tree = sm.tree; r.treeCap = bs->treeCap;
+        r.idxOff = bs->idxOff; r.idxVal = idxVals; r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.nIdx = bs->nIdx;
+        r.ctrls = sm.ctrl; r.out = out; r.spread = bs->spread; r.D = bs->D; r.cut = cut;
+        r.list = list; r.cuts = cuts;
+        // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
+        // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
+        unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);
+        if ((int64_t)wgs * rows < 2048) wgs = (unsigned)std::min<int64_t>(r.nreg, (2048 + rows - 1) / rows);
+        hipLaunchKernelGGL(k_decode_region, dim3(wgs, rows), dim3(64 * RG_WAVES), 0, st, r);
+        break;
+    }
+    case DecodeKernel::QUAD: {
+        TileArgs t = tile_args();
         const int ntiles = t.tilesX * t.tilesY * t.tilesZ;
-        t.fine = bs->fineIdx;
-        t.val3 = bs->idxVal3;
-        const bool useFine = use_fine(bs, rangeStream);
-        const bool useQuad = use_quad(bs, useFine, cut);
-        RegionArgs r;
-        if (useQuad && !bs->sw.decodeQuad && region_geometry(bs, r)) {
-            r.tree = sm.tree; r.treeCap = bs->treeCap;
-            r.idxOff = bs->idxOff; r.idxVal = idxVals; r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.nIdx = bs->nIdx;
-            r.ctrls = sm.ctrl; r.out = out; r.spread = bs->spread; r.D = bs->D; r.cut = cut;
-            r.list = list; r.cuts = cuts;
-            // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
-            // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
-            r.dbg = nullptr;
-#ifdef RG_STAMP
-            {
-                static unsigned long long *dbgDev = nullptr;
-                if (!dbgDev) { hipMalloc(&dbgDev, 64); hipMemset(dbgDev, 0, 64); }
-                unsigned long long h[8];
-                hipMemcpy(h, dbgDev, 64, hipMemcpyDeviceToHost);
-                if (h[6]) fprintf(stderr, "[rg stamp] waves %llu  cycles/wave: total %.0f park %.0f steps+stage %.0f (of it waiting for string pieces %.0f) barrier1 %.0f gather %.0f barrier2+top %.0f\n", h[6],
-                                  (double)h[0] / h[6], (double)h[1] / h[6], (double)h[2] / h[6], (double)h[7] / h[6], (double)h[3] / h[6], (double)h[4] / h[6], (double)h[5] / h[6]);
-                hipMemset(dbgDev, 0, 64);
-                r.dbg = dbgDev;
-            }
-#endif
-            unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);
-            if ((int64_t)wgs * rows < 2048) wgs = (unsigned)std::min<int64_t>(r.nreg, (2048 + rows - 1) / rows);
-            hipLaunchKernelGGL(k_decode_region, dim3(wgs, rows), dim3(64 * RG_WAVES), 0, st, r);
-        } else if (useQuad) {
-            const int levels = cut - bs->D < 0 ? 0 : (cut - bs->D > VR_CHAIN_LEVELS ? VR_CHAIN_LEVELS : cut - bs->D);
-            // one table per number of refining levels, all written once: two decodes of one set on different streams at
-            // different cuts never rewrite a table the other is reading
-            if (!bs->chainTab && hipMalloc(&bs->chainTab, (size_t)(VR_CHAIN_LEVELS + 1) * QD_CHAIN_ENTRIES * 4) != hipSuccess) return -3;
-            if (!bs->chainTabReady) {
-                for (int lv = 0; lv <= VR_CHAIN_LEVELS; ++lv)
-                    hipLaunchKernelGGL(k_chain_table, dim3(QD_CHAIN_ENTRIES / 256), dim3(256), 0, st, lv, bs->chainTab + (size_t)lv * QD_CHAIN_ENTRIES);
-                // (the first use may come from any stream: make the tables visible to all of them before going on)
-                if (hipStreamSynchronize(st) != hipSuccess) return -1;
-                bs->chainTabReady = true;
-            }
-            t.tables = bs->chainTab + (lod ? (size_t)0 : (size_t)levels * QD_CHAIN_ENTRIES);   // lod: the kernel picks per brick
-            const int per = QD_WAVES * QD_TPW;
-            hipLaunchKernelGGL(k_decode_quad, dim3((unsigned)((ntiles + per - 1) / per), rows), dim3(64 * QD_WAVES), 0, st, t);
-        } else {
+        const int levels = cut - bs->D < 0 ? 0 : (cut - bs->D > VR_CHAIN_LEVELS ? VR_CHAIN_LEVELS : cut - bs->D);
+        // one table per number of refining levels, all written once: two decodes of one set on different streams at
+        // different cuts never rewrite a table the other is reading
+        if (!bs->chainTab && hipMalloc(&bs->chainTab, (size_t)(VR_CHAIN_LEVELS + 1) * QD_CHAIN_ENTRIES * 4) != hipSuccess) return -3;
+        if (!bs->chainTabReady) {
+            for (int lv = 0; lv <= VR_CHAIN_LEVELS; ++lv)
+                hipLaunchKernelGGL(k_chain_table, dim3(QD_CHAIN_ENTRIES / 256), dim3(256), 0, st, lv, bs->chainTab + (size_t)lv * QD_CHAIN_ENTRIES);
+            // (the first use may come from any stream: make the tables visible to all of them before going on)
+            if (hipStreamSynchronize(st) != hipSuccess) return -1;
+            bs->chainTabReady = true;
+        }
+        t.tables = bs->chainTab + (lod ? (size_t)0 : (size_t)levels * QD_CHAIN_ENTRIES);   // lod: the kernel picks per brick
+        const int per = QD_WAVES * QD_TPW;
+        hipLaunchKernelGGL(k_decode_quad, dim3((unsigned)((ntiles + per - 1) / per), rows), dim3(64 * QD_WAVES), 0, st, t);
+        break;
+    }
+    case DecodeKernel::FINE:
+    case DecodeKernel::TILE: {
+        TileArgs t = tile_args();
+        const int ntiles = t.tilesX * t.tilesY * t.tilesZ;
+        const bool useFine = k == DecodeKernel::FINE;
         if (useFine && !lod && !bs->decTables && hipMalloc(&bs->decTables, (size_t)bs->B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
         uint32_t *decTables = lod ? lod->decTables : bs->decTables;
         t.tables = decTables;
-        if (useFine)
+        if (useFine) {
             hipLaunchKernelGGL(k_fine_tables, dim3(rows), dim3(256), 0, st, bs->mid.ctrl, bs->D, bs->Ds, cut, decTables, list, cuts);
-        if (useFine)
             hipLaunchKernelGGL(k_decode_fine, dim3((unsigned)((ntiles + FD_WAVES - 1) / FD_WAVES), rows),
                                dim3(64 * FD_WAVES), 0, st, t);
-        else
+        } else
             hipLaunchKernelGGL(k_decode_tile, dim3((unsigned)((ntiles + DEC_WAVES - 1) / DEC_WAVES), rows),
                                dim3(64 * DEC_WAVES), 0, st, t);
-        }
-    } else {
+        break;
+    }
+    case DecodeKernel::LANE: {
         DecodeArgs a;
         a.tree = sm.tree; a.treeCap = bs->treeCap;
         a.idxBase = nullptr; a.nBase = 0;
@@ -2016,32 +1963,18 @@ int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rang
         a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
         a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts;
         hipLaunchKernelGGL(k_decode_lane<false>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
+        break;
+    }
     }
     if (!lod) hipEventRecord(bs->ev[6], st);
     return launch_status("decode");
 }
 
-// ---- per-brick decode (vr_brickset_decode_lod)
-// The classes of decode_launch's choice, in launch order: region / quad, fine, tile, general extents, lane.
-enum { LOD_QUAD, LOD_FINE, LOD_TILE, LOD_GENERAL, LOD_LANE, LOD_CLASSES };
-
-// what the choice depends on besides the cut: the set's geometry and side-cars (once per call, not per brick)
-struct LodChoice {
-    int fixed;        // LOD_GENERAL / LOD_LANE, or -1: a tiled kernel, by the cut
-    bool useFine;
-    explicit LodChoice(const BrickSet *bs) : fixed(-1), useFine(false)
-    {
-        TileArgs t;
-        if (bs->generalGeom) fixed = LOD_GENERAL;
-        else if (bs->sw.decodeV1 || !tile_geometry(bs, t)) fixed = LOD_LANE;
-        else useFine = use_fine(bs, false);
-    }
-    int of(const BrickSet *bs, int cut) const
-    {
-        if (fixed >= 0) return fixed;
-        return use_quad(bs, useFine, cut) ? LOD_QUAD : (useFine ? LOD_FINE : LOD_TILE);
-    }
-};
+int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream)
+{
+    const DecodePlan plan(bs, rangeStream);
+    return launch_decode(bs, plan, plan.kernel(cut), out, cut, st, rangeStream, nullptr);
+}
 
 void free_lod_slots(BrickSet *bs)
 {
@@ -2066,28 +1999,28 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
     bs->lodNext = (bs->lodNext + 1) % VR_LOD_SLOTS;
     // host image: cuts [0, B), bricks cut above Ds, then the classes' lists
     int32_t *H = s.host;
-    const LodChoice choice(bs);
-    int nAbove = 0, nCls[LOD_CLASSES] = {0, 0, 0, 0, 0}, cutOf[LOD_CLASSES] = {0, 0, 0, 0, 0};
+    const DecodePlan plan(bs, false);
+    int nAbove = 0, nCls[DECODE_KERNELS] = {}, cutOf[DECODE_KERNELS] = {};
     std::vector<int> cls((size_t)B, -1);
     for (int b = 0; b < B; ++b) {
         H[b] = cutsHost[b];
         if (cutsHost[b] < 0) continue;
         if (cutsHost[b] < bs->Ds) H[B + nAbove++] = b;
-        cls[(size_t)b] = choice.of(bs, cutsHost[b]);
+        cls[(size_t)b] = (int)plan.kernel(cutsHost[b]);
         ++nCls[cls[(size_t)b]];
         cutOf[cls[(size_t)b]] = cutsHost[b];
     }
-    int first[LOD_CLASSES], at = B + nAbove;
-    for (int c = 0; c < LOD_CLASSES; ++c) { first[c] = at; at += nCls[c]; }
+    int first[DECODE_KERNELS], at = B + nAbove;
+    for (int c = 0; c < DECODE_KERNELS; ++c) { first[c] = at; at += nCls[c]; }
     {
-        int fill[LOD_CLASSES];
-        for (int c = 0; c < LOD_CLASSES; ++c) fill[c] = first[c];
+        int fill[DECODE_KERNELS];
+        for (int c = 0; c < DECODE_KERNELS; ++c) fill[c] = first[c];
         for (int b = 0; b < B; ++b) if (cls[(size_t)b] >= 0) H[fill[cls[(size_t)b]]++] = b;
     }
     if (at == B) return 0;              // every brick skipped: nothing to launch
     if (nAbove && !s.idxValCut && hipMalloc(&s.idxValCut, (size_t)B * bs->nIdx) != hipSuccess) return -3;
-    if ((nCls[LOD_FINE] || nCls[LOD_QUAD]) && !s.decTables && hipMalloc(&s.decTables, (size_t)B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
-    if (nCls[LOD_GENERAL] && !s.rankVals && hipMalloc(&s.rankVals, (size_t)B * bs->leafStride * 2) != hipSuccess) return -3;
+    if ((nCls[(int)DecodeKernel::REGION] || nCls[(int)DecodeKernel::QUAD] || nCls[(int)DecodeKernel::FINE]) && !s.decTables && hipMalloc(&s.decTables, (size_t)B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
+    if (nCls[(int)DecodeKernel::GENERAL] && !s.rankVals && hipMalloc(&s.rankVals, (size_t)B * bs->leafStride * 2) != hipSuccess) return -3;
     if (nAbove && bs->foreign) {
         // ancestor scalars at each brick's cut, from the stream bytes kept at set_tree/open time (as vr_brickset_decode)
         std::vector<uint8_t> vals;
@@ -2107,12 +2040,12 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
         hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), nAbove), dim3(256), 0, st,
                            bs->mid.codes, bs->codeStride, bs->mid.ctrl, bs->Ds, 0, bs->nIdx, s.idxValCut, s.dev + B, s.dev);
     int rc = 0;
-    for (int c = 0; c < LOD_CLASSES && rc == 0; ++c) {
+    for (int c = 0; c < DECODE_KERNELS && rc == 0; ++c) {
         if (!nCls[c]) continue;
         LodClass L;
         L.list = s.dev + first[c]; L.n = nCls[c]; L.cuts = s.dev;
         L.idxValCut = s.idxValCut; L.decTables = s.decTables; L.rankVals = s.rankVals;
-        rc = decode_launch(bs, out, cutOf[c], st, false, &L);
+        rc = launch_decode(bs, plan, (DecodeKernel)c, out, cutOf[c], st, false, &L);
     }
     hipEventRecord(bs->ev[6], st);
     hipEventRecord(s.done, st);

@@ -88,62 +88,36 @@ k_pyramid(Geom g, int dLeaf, int L, const uint8_t *__restrict__ vox, const uint8
     }
 }
 
-#ifndef ENC_NT
-#define ENC_NT 1
-#endif
 // level arrays are written by one whole-volume pass and read by the next: nothing of them survives in a cache until
 // then, so the large stores stream past it
 __device__ __forceinline__ void st16(void *p, uint4 v)
 {
-#if ENC_NT
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     u32x4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
     __builtin_nontemporal_store(t, (u32x4 *)p);
-#else
-    *(uint4 *)p = v;
-#endif
 }
 __device__ __forceinline__ void st8(void *p, uint2 v)
 {
-#if ENC_NT
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     u32x2 t; t.x = v.x; t.y = v.y;
     __builtin_nontemporal_store(t, (u32x2 *)p);
-#else
-    *(uint2 *)p = v;
-#endif
 }
 __device__ __forceinline__ void st4(void *p, uint32_t v)
 {
-#if ENC_NT
     __builtin_nontemporal_store(v, (uint32_t *)p);
-#else
-    *(uint32_t *)p = v;
-#endif
 }
 
-#ifndef ENC_NTL
-#define ENC_NTL 1
-#endif
 __device__ __forceinline__ uint4 ld16(const void *p)
 {
-#if ENC_NTL
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 t = __builtin_nontemporal_load((const u32x4 *)p);
     return make_uint4(t.x, t.y, t.z, t.w);
-#else
-    return *(const uint4 *)p;
-#endif
 }
 __device__ __forceinline__ uint2 ld8(const void *p)
 {
-#if ENC_NTL
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     const u32x2 t = __builtin_nontemporal_load((const u32x2 *)p);
     return make_uint2(t.x, t.y);
-#else
-    return *(const uint2 *)p;
-#endif
 }
 
 // Bottom 12 levels in one block: the 4096 leaves under one depth-(D-12) node form a
@@ -553,11 +527,7 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
     vr_s16x2 hmin = h[0];
 #pragma unroll
     for (int k = 1; k < 8; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
-#ifdef EST_NO_HBIG          // (timing experiments)
-    const bool hBig = false;
-#else
     const bool hBig = __ballot(min((int)hmin.x, (int)hmin.y) < Tbase + nc - 1) == 0ull;
-#endif
 #pragma unroll 1
     for (int ci = 0; ci < nc; ++ci) {
         const int Th = Tbase + ci;
@@ -789,9 +759,7 @@ __device__ __forceinline__ void leaf_pair_encode(uint32_t tword, int tsel, uint3
     codes2 = take & pk_u(pk_s(c.up) + pk_s(0x00020002u));                   // up ? 1 : 2 (per-lane wrap)
 }
 
-#ifndef FILL_ITERS
 #define FILL_ITERS 8        // chunks of 4096 nodes per workgroup of k_fill16 (large levels)
-#endif
 template <bool STORE>     // false (the leaf level of a leafless build): errors only -- k_prune_emit12 recomputes codes and reconstruction
 __global__ void __launch_bounds__(256)
 k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, uint8_t *__restrict__ codes, int64_t heapStride,
@@ -1303,191 +1271,6 @@ __global__ void k_chain_lut(int tol, int nsteps, uint32_t *__restrict__ lut)
     const int zr = __syncthreads_count(m0 <= 127 && lastKeep);
     if (m0 == 0) lut[256] = (uint32_t)zr;
 }
-__device__ __forceinline__ uint32_t chain_mirror(uint32_t ch) { return ch ^ (((ch ^ (ch >> 1)) & 0x1555u) * 3u); }   // add <-> sub
-
-// Leaf prune + the 12 levels above it in one block (the level-synchronous kernels above
-// stay for small bricks and for the levels nearer the root): 16 leaves per thread as
-// 16-byte loads, pruned flags carried upwards in LDS, each level's codes read-modified-
-// written in place.  Equal to the serial recursion (R.cpp:596-629) because a node only
-// depends on its two children.
-__global__ void __launch_bounds__(256)
-k_prune12(int D, int tol, Ctrl *ctrls, const uint8_t *__restrict__ temp, uint8_t *__restrict__ codes,
-          uint8_t *__restrict__ codesRange, int64_t heapStride, int64_t codeStride, ReconBufs rb, int64_t leafStride,
-          int maxDepth, uint32_t *__restrict__ subTok, int64_t nEmitBlk, unsigned long long *__restrict__ blockL1,
-          const uint32_t *__restrict__ chainLut)
-{
-    __shared__ uint32_t lutS[256];
-    __shared__ uint8_t fl[2][2048];
-    __shared__ uint16_t cnt[2][2048];      // tokens a (live) subtree emits, carried upwards with the flags
-    __shared__ uint8_t lv[2048], lvOld[2048];     // codes of the block's nodes at depths D-12 .. D-2, heap order
-    const int brick = blockIdx.y, t = threadIdx.x;
-    Ctrl &c = ctrls[brick];
-    if (c.constBrick) return;
-    const uint32_t base = blockIdx.x << 12;
-    uint8_t *Cb = codes + (int64_t)brick * codeStride;
-    uint8_t *CR = codesRange ? codesRange + (int64_t)brick * codeStride : nullptr;
-    // every global load of the block is issued before any is looked at (one memory round trip)
-    const uint32_t lutV = chainLut[t];
-    uint32_t lvB[8];
-    int lvSh[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int h = q * 256 + (t ? t : (q ? 0 : 1));           // heap index inside the block (index 0 is unused)
-        const int lq = 31 - __clz(h);
-        const int64_t ni = ((int64_t)1 << (D - 12 + lq)) + (((int64_t)blockIdx.x) << lq) + (h - (1 << lq));
-        lvB[q] = Cb[ni >> 2];
-        lvSh[q] = (int)(ni & 3) * 2;
-    }
-    const int64_t li = ((int64_t)1 << D) + base + t * 16;
-    uint32_t cpk = *(const uint32_t *)(Cb + (li >> 2));       // my 16 leaf codes, packed
-    const uint4 tv = *(const uint4 *)(temp + (int64_t)brick * heapStride + li);
-    const uint4 rv = *(const uint4 *)(rb.b[c.par] + (int64_t)brick * leafStride + base + t * 16);
-    lutS[t] = lutV;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int h = q * 256 + t;
-        const uint8_t cv0 = (uint8_t)((lvB[q] >> lvSh[q]) & 3u);
-        if (h) { lv[h] = cv0; lvOld[h] = cv0; }
-    }
-    const uint32_t tw[4] = {tv.x, tv.y, tv.z, tv.w}, rw[4] = {rv.x, rv.y, rv.z, rv.w};
-    // Sibling leaves 2j, 2j+1 share a packed 16-bit register pair.  State of a leaf: m = |truth - recon|,
-    // sg = 0xFFFF where truth < recon.  One step of the grown branch with distance d (encodeNode with the
-    // leaf's own reconstruction as parent, kd_common.h): x = min(d - m, sg ? t : 255 - t); taken iff |x| < m;
-    // then m = |x| and the side flips iff x > 0.
-    const uint32_t tol2 = (uint32_t)tol * 0x10001u;
-    uint32_t T2[8], m[8], sg[8], act[8], nt[8];
-    uint32_t wa = 0, wb = 0, bothMask = 0, anyAct = 0;
-    vr_s16x2 mxB = (vr_s16x2)(0);
-    __syncthreads();                      // lutS
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t sel = (j & 1) ? 0x0c030c02u : 0x0c010c00u;
-        T2[j] = __builtin_amdgcn_perm(0, tw[j >> 1], sel);
-        const vr_s16x2 dl = pk_s(T2[j]) - pk_s(__builtin_amdgcn_perm(0, rw[j >> 1], sel));
-        const vr_s16x2 mm = pk_abs(dl);
-        m[j] = pk_u(mm);
-        sg[j] = pk_u(dl >> 15);
-        mxB = __builtin_elementwise_max(mxB, mm);
-        const uint32_t lt = pk_u((mm - pk_s(tol2)) >> 15);                                     // err < tol
-        const uint32_t cl2 = ((cpk >> (4 * j)) & 3u) | (((cpk >> (4 * j + 2)) & 3u) << 16);     // the pair's codes
-        const uint32_t isz = pk_u((pk_s(cl2) - pk_s(0x00010001u)) >> 15), is3 = pk_u((pk_s(0x00020002u) - pk_s(cl2)) >> 15);
-        const uint32_t newp = isz & lt;                                                        // R.cpp:618-626
-        const uint32_t pruned = newp | is3;
-        if (j < 4) wa |= (newp & 0x000C0003u) << (4 * j); else wb |= (newp & 0x000C0003u) << (4 * (j - 4));
-        bothMask |= ((pruned & (pruned >> 16)) & 1u) << j;
-        // an unpruned leaf is always live (pruning is closed downwards): its code, then the grown branch --
-        // from the table unless a clamp could matter (m > min(t, 255 - t)), then step by step below
-        const vr_s16x2 lim = __builtin_elementwise_min(pk_s(T2[j]), pk_s(T2[j] ^ 0x00FF00FFu));
-        const uint32_t viol = pk_u((lim - mm) >> 15);
-        const uint32_t e0 = lutS[m[j] & 255u], e1 = lutS[(m[j] >> 16) & 255u];
-        const uint32_t useL = ~pruned & ~viol;
-        nt[j] = 0x00010001u + (useL & __builtin_amdgcn_perm(e1, e0, 0x0c050c01u));                // the two counts
-        m[j] = (useL & __builtin_amdgcn_perm(e1, e0, 0x0c040c00u)) | (~useL & m[j]);               // the two final errors
-        act[j] = ~pruned & viol;
-        anyAct |= act[j];
-    }
-    cpk |= ((wa | (wa >> 16)) & 0xFFFFu) | ((wb | (wb >> 16)) << 16);
-    const int nsteps = maxDepth - D;      // distanceMap[D+1..] = 64, 32, .., 1 (R.cpp:23,94-97)
-    for (int i = 0; i < nsteps; ++i) {
-        if (__ballot(anyAct != 0) == 0ull) break;        // wave-uniform: every branch of the wave has ended
-        const uint32_t d2 = (uint32_t)(64 >> i) * 0x10001u;
-        anyAct = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const vr_s16x2 mm = pk_s(m[j]);
-            const uint32_t gt = pk_u((pk_s(tol2) - mm) >> 15);                                 // err > tol: grow
-            nt[j] = pk_u(pk_s(nt[j]) - pk_s(act[j]));                                          // a code or the terminator
-            const uint32_t go = act[j] & gt;
-            const uint32_t lim = (sg[j] & T2[j]) | (~sg[j] & (T2[j] ^ 0x00FF00FFu));
-            const vr_s16x2 x = __builtin_elementwise_min(pk_s(d2) - mm, pk_s(lim));
-            const vr_s16x2 nx = (vr_s16x2)(0) - x, ax = __builtin_elementwise_max(x, nx);
-            const uint32_t take = go & pk_u((ax - mm) >> 15);
-            m[j] = (take & pk_u(ax)) | (~take & m[j]);
-            sg[j] ^= take & pk_u(nx >> 15);
-            act[j] = go;
-            anyAct |= go;
-        }
-    }
-    vr_s16x2 mxA = (vr_s16x2)(0), l1p = (vr_s16x2)(0);   // encoder's own statistics after branch growth,
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {                         // over every leaf (R.cpp:115-129)
-        mxA = __builtin_elementwise_max(mxA, pk_s(m[j]));
-        l1p += pk_s(m[j]);
-    }
-    int maxErr = max((int)mxB.x, (int)mxB.y), maxAfter = max((int)mxA.x, (int)mxA.y);
-    const uint32_t l1After = (uint32_t)((int)l1p.x + (int)l1p.y);
-    uint32_t pr = 0;            // pruned flags of sibling pairs: bit k <=> both leaves 2k, 2k+1 pruned
-    pr = bothMask;
-    *(uint32_t *)(Cb + (li >> 2)) = cpk;
-    if (CR) {
-        uint32_t q = *(const uint32_t *)(CR + (li >> 2));
-        q |= (cpk & (cpk >> 1) & 0x55555555u) * 3u;     // every pruned leaf: range code 3 as well (M.cpp:864-865)
-        *(uint32_t *)(CR + (li >> 2)) = q;
-    }
-    unsigned long long l1w = l1After;
-    for (int o = 32; o > 0; o >>= 1) {
-        int u = __shfl_xor(maxErr, o); maxErr = u > maxErr ? u : maxErr;
-        int w = __shfl_xor(maxAfter, o); maxAfter = w > maxAfter ? w : maxAfter;
-        l1w += __shfl_xor(l1w, o);
-    }
-    if ((t & 63) == 0)      // one record per wave = 1024 leaves
-        blockL1[(int64_t)brick * nEmitBlk + (size_t)blockIdx.x * 4 + (t >> 6)] = stat_pack(l1w, maxErr, maxAfter);
-    // level D-1: 8 nodes per thread, children flags in registers
-    {
-        const int64_t ni = ((int64_t)1 << (D - 1)) + (base >> 1) + t * 8;
-        uint32_t v = *(const uint16_t *)(Cb + (ni >> 2)), vr = CR ? *(const uint16_t *)(CR + (ni >> 2)) : 0u;   // 8 codes
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const bool both = (pr >> k) & 1u;
-            const int code = (int)((v >> (2 * k)) & 3u);
-            const bool p = both && code == 0;
-            if (p) { v |= 3u << (2 * k); vr |= 3u << (2 * k); }
-            const bool f3 = p || code == 3;
-            fl[1][t * 8 + k] = (uint8_t)(f3 ? 1 : 0);
-            cnt[1][t * 8 + k] = (uint16_t)(f3 ? 1u : 1u + (nt[k] & 0xFFFFu) + (nt[k] >> 16));
-        }
-        *(uint16_t *)(Cb + (ni >> 2)) = (uint16_t)v;
-        if (CR) *(uint16_t *)(CR + (ni >> 2)) = (uint16_t)vr;
-    }
-    __syncthreads();
-    // levels D-2 .. D-12 of this block (2047 codes) were fetched into LDS up front (one memory
-    // round trip instead of eleven dependent ones); prune them there and write them back once
-    for (int l = 2; l <= 12; ++l) {
-        const int m = 4096 >> l, src = (l - 1) & 1, dst = l & 1;
-        const int hb = 1 << (12 - l);               // heap base of this level inside the block
-        for (int i = t; i < m; i += 256) {
-            const bool both = fl[src][2 * i] && fl[src][2 * i + 1];
-            const int code = lv[hb + i];
-            const bool p = both && code == 0;
-            if (p) lv[hb + i] = 3;
-            const bool f3 = p || code == 3;
-            fl[dst][i] = (uint8_t)(f3 ? 1 : 0);
-            const uint32_t cn = f3 ? 1u : 1u + cnt[src][2 * i] + cnt[src][2 * i + 1];
-            cnt[dst][i] = (uint16_t)cn;
-            if (l == 10 && subTok) subTok[(int64_t)brick * nEmitBlk + (size_t)blockIdx.x * 4 + i] = cn;   // one emit block
-        }
-        __syncthreads();
-    }
-    // write the block's levels back packed: levels with >= 4 nodes own whole bytes (plain stores of
-    // every byte); the top two levels (1 and 2 nodes) share bytes with neighbouring blocks -> atomic OR
-    for (int hb4 = 1 + t; hb4 < 512; hb4 += 256) {     // heap bytes 1..511 <-> heap nodes 4..2047
-        const int h = hb4 * 4;
-        const int lq = 31 - __clz(h);                   // depth below the block root (>= 2)
-        const int64_t gi = ((int64_t)1 << (D - 12 + lq)) + (((int64_t)blockIdx.x) << lq) + (h - (1 << lq));
-        const uint8_t pk = (uint8_t)(lv[h] | (lv[h + 1] << 2) | (lv[h + 2] << 4) | (lv[h + 3] << 6));
-        const uint8_t po = (uint8_t)(lvOld[h] | (lvOld[h + 1] << 2) | (lvOld[h + 2] << 4) | (lvOld[h + 3] << 6));
-        if (pk != po) {
-            Cb[gi >> 2] = pk;
-            if (CR) CR[gi >> 2] |= (uint8_t)(pk ^ po);   // newly pruned nodes: range code 3 as well (byte owned by me)
-        }
-    }
-    if (t >= 1 && t < 4 && lv[t] != lvOld[t]) {          // heap nodes 1..3: the block root and its children
-        const int lq = 31 - __clz(t);
-        const int64_t gi = ((int64_t)1 << (D - 12 + lq)) + (((int64_t)blockIdx.x) << lq) + (t - (1 << lq));
-        cset3(Cb, gi);
-        if (CR) cset3(CR, gi);
-    }
-}
 
 // ---------------------------------------------------------------- convert ----
 // Tokens owned by leaf rank r, in stream order: the live internal nodes whose first
@@ -1578,7 +1361,7 @@ struct EmitArgs {
     unsigned long long *idxBase;    // stay relative to their 4096-leaf block and idxBase[block] holds the block's stream offset
     unsigned long long *blockL1;   // per-block sum |recon - temp| after growth (reduced by k_emit_stats)
     uint8_t *blockAlive, *blockVal; // k_block_alive: flags, scalar above the block
-    unsigned long long *blockSpine; // k_block_alive: tokens above depth D-10 owned by the block's first rank
+    unsigned long long *blockSpine; // k_block_alive: tokens above depth D-12 owned by the block's first rank
     unsigned long long *blockSpineR; // ... the same tokens of MidRangeTree's range stream
     int64_t nEmitBlk;
     uint8_t *tree, *treeR;
@@ -1621,7 +1404,7 @@ __device__ __forceinline__ uint32_t block4_excl_scan_u32(uint32_t v, uint32_t *s
 
 // ---- prune + block-local emit (VolumeKdtree streams with D >= 12: K = 6, Ds = D-6) --------------
 // One block owns a depth-(D-12) subtree: 4096 leaves, 16 per thread.  It prunes the twelve levels
-// bottom-up like k_prune12 (the four above the leaves in registers, the other eight in LDS), and then,
+// bottom-up (the four above the leaves in registers, the other eight in LDS), and then,
 // top-down, writes the subtree's own preorder token string -- assuming its root is live -- into LDS
 // and from there into the block's slot of the brick's stream buffer: slot b starts at word b * PE_WORDS
 // (a block's string is at most 4095 + 8 * 4096 tokens = 9216 bytes).  That block-gapped buffer IS what the decoders
@@ -1783,11 +1566,7 @@ k_prune_emit12(PruneEmitArgs a)
     const int nsteps = a.maxDepth - D;    // distanceMap[D+1..] = 64, 32, .., 1 (R.cpp:23,94-97)
     // a wave whose 1024 leaves all carry code 0 and are reproduced exactly (constant regions) prunes them all:
     // one '3' per leaf, no branches, no statistics to add
-#ifdef PE_KO_LEAF
-    const bool busy = false;
-#else
     const bool busy = __ballot(!plain) != 0ull;
-#endif
     if (!busy) {
         bothMask = 0x5555u;
 #pragma unroll
@@ -1831,11 +1610,7 @@ k_prune_emit12(PruneEmitArgs a)
             act[jj] = ~pruned & viol;
             anyAct |= act[jj];
         }
-#ifdef PE_KO_STEP
-        for (int i = 0; i < 0; ++i) {
-#else
         for (int i = 0; i < nsteps; ++i) {    // exact stepping for the leaves the table does not cover
-#endif
             if (__ballot(anyAct != 0) == 0ull) break;
             const uint32_t d2 = (uint32_t)(64 >> i) * 0x10001u;
             anyAct = 0;
@@ -2020,11 +1795,7 @@ k_prune_emit12(PruneEmitArgs a)
     uint32_t bitpos = 2u * pos;
     pe_put(W, bitpos, (unsigned long long)S, ns);
     bitpos += 2u * (uint32_t)ns;
-#ifdef PE_KO_COMPOSE
-    if (false) {
-#else
     if (alive) {
-#endif
         // preorder of my 31-node subtree; internal tokens wait in (pb, pn) and leave with the next leaf-pair piece
         unsigned long long pb = a4;
         int pn = 1;
@@ -2080,11 +1851,7 @@ k_prune_emit12(PruneEmitArgs a)
     // build sits right behind it (the decoders fetch whole words past a run's end; what they fetch there is never used)
     const uint32_t nw = min((tot + 15u) / 16u + 1u, (uint32_t)PE_WORDS);
     uint32_t *slot = (uint32_t *)((RANGE ? a.gapR : a.gap) + (int64_t)brick * a.treeCap) + (size_t)blk * PE_WORDS;
-#ifndef PE_KO_COPY
     for (uint32_t i = t; i < nw; i += 256u) slot[i] = W[i];
-#else
-    if (t == 0) slot[0] = W[0] + nw;
-#endif
 }
 
 
@@ -2264,142 +2031,12 @@ k_emit_write(EmitArgs a)
     }
 }
 
-// ---- emit, 4 leaf ranks per thread (VolumeKdtree streams with D >= 12) -----------------
-// Thread t of a block owns ranks r0..r0+3 (r0 = 4t): the spine above the quad (first leaf
-// r0), the depth-(D-2) node, both depth-(D-1) nodes and the four leaves with their grown
-// branches -- at most D+1+32 tokens, assembled in a 128-bit register string.  Leaf arrays
-// are read as dwords; one block = 1024 ranks.
-#define EMIT4_RANKS 1024
-#define EMIT4_LDS_WORDS 640     // >= (1024*8 + 1023 + 28 + 15) / 16
-
-struct Str128 { unsigned long long lo, hi; int n; };
-struct Quad { Str128 s; int preDs, aliveAtDs, zeroRun; };
-
-// inner: codes of the block's internal nodes at depths D-10 .. D-3, heap-ordered (node (l, i) at (1<<l)+i)
-// lutS: k_chain_lut's table (LDS copy)
-// What a thread reads from memory for its quad, fetched in one batch before anything is looked at
-struct QuadIn { uint32_t quadB, pairB, clb, tl, rl; };
-__device__ __forceinline__ QuadIn quad_load(const uint8_t *__restrict__ Cb, const uint8_t *__restrict__ Tb,
-                                            const uint8_t *__restrict__ Rl, int D, uint32_t r0)
-{
-    QuadIn q;
-    q.quadB = Cb[(((int64_t)1 << (D - 2)) + (r0 >> 2)) >> 2];      // byte holding the depth-(D-2) code
-    q.pairB = Cb[(((int64_t)1 << (D - 1)) + (r0 >> 1)) >> 2];      // 4 packed depth-(D-1) codes
-    q.clb = Cb[(((int64_t)1 << D) + r0) >> 2];                      // my four leaf codes = one byte
-    q.tl = *(const uint32_t *)(Tb + ((int64_t)1 << D) + r0);
-    q.rl = *(const uint32_t *)(Rl + r0);
-    return q;
-}
-
-__device__ inline Quad quad_tokens(const QuadIn &in, const uint8_t *inner, const uint32_t *lutS, bool rootLive,
-                                   unsigned long long upSpine, int D, int maxDepth, int tol, int Ds, uint32_t r0)
-{
-    Quad Q;
-    Q.s.lo = Q.s.hi = 0; Q.s.n = 0; Q.preDs = 0; Q.aliveAtDs = 0; Q.zeroRun = 0;
-    const uint32_t lr = r0 & 1023u;                                  // rank inside the block
-    const int quadCode = (int)((in.quadB >> (((r0 >> 2) & 3u) * 2u)) & 3u);
-    const uint32_t pk2 = (in.pairB >> (((r0 >> 1) & 3u) * 2u)) & 15u;                // mine: two of the four
-    const uint32_t pair = (pk2 & 3u) | ((pk2 >> 2) << 8);
-    const uint32_t clb = in.clb;
-    const uint32_t cl = (clb & 3u) | (((clb >> 2) & 3u) << 8) | (((clb >> 4) & 3u) << 16) | (((clb >> 6) & 3u) << 24);
-    const uint32_t tl = in.tl, rl = in.rl;
-    // The thread's string = spine (the live ancestors above the quad node whose first leaf is r0; at most
-    // D-2 <= 26 tokens, one 64-bit word) followed by the quad node's subtree, composed bottom-up from
-    // fixed-shape pieces: leaf = code + branch (<= 8 tokens), half = pair node + two leaves (<= 17 tokens),
-    // quad = node + two halves (<= 35 tokens).  Three wide shifts per thread instead of one per token.
-    bool alive;
-    int j;
-    unsigned long long S = 0;
-    int ns = 0;
-    if (lr == 0) {                            // first rank of the block: the spine above depth D-10 comes precomputed
-        ns = (int)(upSpine >> 56);
-        S = upSpine & 0x00FFFFFFFFFFFFFFull;
-        alive = rootLive;
-        j = D - 10;
-    } else {
-        const int c0 = __ffs((int)lr) - 1;    // 2..9
-        j = D - c0;                           // first spine depth (> D-10)
-        const int l = j - 1 - (D - 10);       // parent level inside the block
-        alive = inner[(1 << l) + (lr >> (D - j + 1))] != 3;
-    }
-    for (; alive && j <= D - 3; ++j) {         // spine down to the quad node's parent
-        if (j == Ds) { Q.preDs = ns; Q.aliveAtDs = 1; }
-        const int l = j - (D - 10);
-        const uint32_t code = inner[(1 << l) + (lr >> (D - j))];
-        S |= (unsigned long long)code << (2 * ns);
-        ++ns;
-        if (code == 3) alive = false;
-    }
-    unsigned long long qlo = 0, qhi = 0;
-    int qn = 0;
-    if (alive) {
-        if (D - 2 == Ds) { Q.preDs = ns; Q.aliveAtDs = 1; }      // (Ds <= D-2: the index granularity K is >= 2 here)
-        qlo = (unsigned long long)quadCode;
-        qn = 1;
-        if (quadCode != 3) {
-            unsigned long long H[2];
-            int Hn[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t pc = (pair >> (8 * h)) & 255u;
-                H[h] = pc; Hn[h] = 1;
-                if (pc == 3) continue;
-                uint32_t Lb[2];
-                int Ln[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int k = 2 * h + e;
-                    const uint32_t code = (cl >> (8 * k)) & 255u;
-                    uint32_t bits = code;
-                    int nt = 1;
-                    if (code != 3) {                                         // grown branch, R.cpp:655-704
-                        const int t = (int)((tl >> (8 * k)) & 255u);
-                        int rec = (int)((rl >> (8 * k)) & 255u);
-                        const int m0 = rec > t ? rec - t : t - rec, lim = t < 255 - t ? t : 255 - t;
-                        if (m0 <= lim) {                                     // no clamp can matter: table (see k_chain_lut)
-                            const uint32_t en = lutS[m0];
-                            const uint32_t ch = en >> 16;
-                            bits |= (t > rec ? ch : chain_mirror(ch)) << 2;
-                            nt += (int)((en >> 8) & 7u);
-                        } else {
-                            int depth = D;
-                            while (depth < maxDepth) {
-                                const int err = rec > t ? rec - t : t - rec;
-                                if (err > tol) {
-                                    ++depth;
-                                    const Enc en = encode_node(t, rec, 64 >> (depth - D - 1));   // distanceMap[D+1..] = 64 .. 1
-                                    rec = en.recon;
-                                    if (depth == maxDepth && en.code == 0) Q.zeroRun += 1;
-                                    bits |= (uint32_t)en.code << (2 * nt);
-                                    ++nt;
-                                } else { bits |= 3u << (2 * nt); ++nt; break; }
-                            }
-                        }
-                    }
-                    Lb[e] = bits; Ln[e] = nt;
-                }
-                H[h] = (unsigned long long)pc | ((unsigned long long)Lb[0] << 2) | ((unsigned long long)Lb[1] << (2 + 2 * Ln[0]));
-                Hn[h] = 1 + Ln[0] + Ln[1];
-            }
-            const int sh1 = 2 + 2 * Hn[0];                  // 4 .. 36
-            qlo |= (H[0] << 2) | (H[1] << sh1);
-            qhi = H[1] >> (64 - sh1);
-            qn = 1 + Hn[0] + Hn[1];
-        }
-    }
-    const int shS = 2 * ns;                                 // <= 52
-    Q.s.lo = S | (qlo << shS);
-    Q.s.hi = (qhi << shS) | (shS ? qlo >> (64 - shS) : 0ull);
-    Q.s.n = ns + qn;
-    return Q;
-}
-
-// One flag per 1024-rank emit block: does its depth-(D-10) subtree emit anything at all?
-// No iff a proper ancestor of that subtree's root was pruned and this block does not hold
-// that ancestor's first leaf (the pruned ancestor's own token belongs to the block that does).
-// Lets k_emit4 skip the constant regions of a volume without touching their leaf arrays.
+// One flag per emit block of 2^sub leaves (a 4096-leaf block of k_prune_emit12): does its depth-(D-sub) subtree emit
+// anything at all?  No iff a proper ancestor of that subtree's root was pruned and this block does not hold that
+// ancestor's first leaf (the pruned ancestor's own token belongs to the block that does).  Lets k_index12 and
+// k_concat12 skip the constant regions of a volume.
 __global__ void __launch_bounds__(256)
-k_block_alive(EmitArgs a, int64_t nblk, int sub)     // sub: log2 of the leaves per emit block (10: k_emit4, 12: k_concat12)
+k_block_alive(EmitArgs a, int64_t nblk, int sub)     // sub: log2 of the leaves per emit block (always 12)
 {
     const int brick = blockIdx.y;
     const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2409,7 +2046,7 @@ k_block_alive(EmitArgs a, int64_t nblk, int sub)     // sub: log2 of the leaves 
     const int dl = a.D - sub;
     bool alive = true;
     int val = dmap[0];                       // decoded scalar along the path (root: R.cpp:743)
-    unsigned long long spine = 0, spineR = 0; // tokens above depth D-10 owned by the block's first rank (mid / range stream)
+    unsigned long long spine = 0, spineR = 0; // tokens above depth D-sub owned by the block's first rank (mid / range stream)
     const uint8_t *CbR = a.codesR ? a.codesR + (int64_t)brick * a.codeStride : nullptr;
     int nsp = 0;
     const uint32_t r0 = (uint32_t)blk << sub;
@@ -2430,106 +2067,13 @@ k_block_alive(EmitArgs a, int64_t nblk, int sub)     // sub: log2 of the leaves 
         }
     }
     const int64_t o = (int64_t)brick * a.nEmitBlk + blk;
-    a.blockAlive[o] = (uint8_t)((alive ? 1 : 0) | (pathAlive ? 2 : 0));   // bit1: the depth-(D-10) node itself is live
-    a.blockVal[o] = (uint8_t)val;            // scalar of the depth-(D-11) parent (codes applied down to depth dl-1)
+    a.blockAlive[o] = (uint8_t)((alive ? 1 : 0) | (pathAlive ? 2 : 0));   // bit1: the depth-(D-sub) node itself is live
+    a.blockVal[o] = (uint8_t)val;            // scalar of the depth-(D-sub-1) parent (codes applied down to depth dl-1)
     a.blockSpine[o] = spine | ((unsigned long long)nsp << 56);
     if (CbR) a.blockSpineR[o] = spineR | ((unsigned long long)nsp << 56);
     // tokens this block emits: the upper spine its first rank owns + its own subtree if that is live
-    // (k_prune12 left the subtree's count in blockOff[], which k_emit_scan overwrites afterwards)
+    // (k_prune_emit12 left the subtree's count in blockOff[], which k_emit_scan overwrites afterwards)
     a.blockTot[o] = (uint32_t)nsp + (pathAlive ? a.blockOff[o] : 0u);
-}
-
-template <bool WRITE>
-__global__ void __launch_bounds__(256)
-k_emit4(EmitArgs a)
-{
-    __shared__ uint32_t shw[4];
-    __shared__ uint32_t W[WRITE ? EMIT4_LDS_WORDS : 1];
-    const int brick = blockIdx.y;
-    Ctrl &c = a.ctrls[brick];
-    if (c.constBrick) return;
-    const uint8_t *Cb = a.codes + (int64_t)brick * a.codeStride;
-    const uint8_t *Tb = a.temp + (int64_t)brick * a.heapStride;
-    const uint8_t *Rl = a.rb.b[c.par] + (int64_t)brick * a.leafStride;
-    const uint32_t r0 = blockIdx.x * EMIT4_RANKS + threadIdx.x * 4;
-    __shared__ uint8_t inner[256];
-    __shared__ uint32_t lutS[256];
-    const int64_t bo = (int64_t)brick * a.nEmitBlk + blockIdx.x;
-    const int bflags = a.blockAlive[bo];
-    const int bval = a.blockVal[bo];
-    const unsigned long long upSpine = a.blockSpine[bo];
-    if (!(bflags & 1)) {          // wave-uniform: nothing to emit here
-        if (!WRITE) { if (threadIdx.x == 0) a.blockTot[bo] = 0; return; }
-        if ((r0 & ((1u << a.K) - 1u)) == 0) {     // index entries of a dead region: value of the pruned ancestor
-            a.idxOff[(int64_t)brick * a.nIdx + (r0 >> a.K)] = VR_IDX_DEAD;
-            a.idxVal[(int64_t)brick * a.nIdx + (r0 >> a.K)] = (uint8_t)bval;   // codes below a pruned node are all 3
-        }
-        return;
-    }
-    // every global load of the block is issued here, before any is looked at (one memory round trip
-    // instead of a chain of them): the block's internal nodes of depths D-10 .. D-3 (255 codes, one per
-    // thread, heap index t inside the block), the branch table, the quad's own bytes, the block offset
-    const int t = threadIdx.x ? threadIdx.x : 1, l = 31 - __clz(t);
-    const int64_t innerIdx = ((int64_t)1 << (a.D - 10 + l)) + (((int64_t)blockIdx.x) << l) + (t - (1 << l));
-    const uint32_t innerB = Cb[innerIdx >> 2];
-    const uint32_t lutV = a.chainLut[threadIdx.x];
-    const QuadIn qin = quad_load(Cb, Tb, Rl, a.D, r0);
-    const uint32_t g0 = WRITE ? a.blockOff[bo] : 0u;
-    inner[threadIdx.x] = (uint8_t)((innerB >> ((int)(innerIdx & 3) * 2)) & 3u);
-    lutS[threadIdx.x] = lutV;
-    if (WRITE) for (int i = threadIdx.x; i < EMIT4_LDS_WORDS; i += 256) W[i] = 0;
-    __syncthreads();
-    const Quad Q = quad_tokens(qin, inner, lutS, (bflags & 2) != 0, upSpine, a.D, a.maxDepth, a.tol, a.Ds, r0);
-    uint32_t tot;
-    const uint32_t lo = block_excl_scan_u32((uint32_t)Q.s.n, shw, tot);
-    if (!WRITE) {
-        if (threadIdx.x == 0) a.blockTot[(int64_t)brick * a.nEmitBlk + blockIdx.x] = tot;
-        return;
-    }
-    const uint32_t phase = g0 & 15u;
-    if (Q.zeroRun) atomicAdd(&c.zeroRun, Q.zeroRun);
-    // never write outside the brick's stream buffer, whatever the counts say (a count/emit mismatch
-    // would be a bug; it must surface as a failed parity check, not as a memory fault)
-    if (((unsigned long long)g0 + tot + 32ull) * 2ull > (unsigned long long)a.treeCap * 8ull) {
-        if (threadIdx.x == 0) atomicMax(&c.emitOverflow, 1);
-        return;
-    }
-    if (Q.s.n) {
-        const uint32_t pos = phase + lo;
-        const int sh = (int)(pos & 15u) * 2;
-        uint32_t w = pos >> 4;
-        // 128-bit string shifted into up to five words
-        const unsigned long long v0 = Q.s.lo << sh;
-        const unsigned long long v1 = (Q.s.hi << sh) | (sh ? (Q.s.lo >> (64 - sh)) : 0ull);
-        const uint32_t v2 = sh ? (uint32_t)(Q.s.hi >> (64 - sh)) : 0u;
-        const int nbits = sh + 2 * Q.s.n;
-        atomicOr(&W[w], (uint32_t)v0);
-        if (nbits > 32) atomicOr(&W[w + 1], (uint32_t)(v0 >> 32));
-        if (nbits > 64) atomicOr(&W[w + 2], (uint32_t)v1);
-        if (nbits > 96) atomicOr(&W[w + 3], (uint32_t)(v1 >> 32));
-        if (nbits > 128) atomicOr(&W[w + 4], v2);
-    }
-    if ((r0 & ((1u << a.K) - 1u)) == 0) {     // decode side-car index entry (K >= 2): depth Ds = D-K >= D-10
-        const uint32_t sidx = r0 >> a.K;
-        int val = bval;                        // scalar of the parent of the block's depth-(D-10) node
-        const uint32_t lr = r0 & 1023u;
-        for (int j = a.D - 10; j <= a.Ds; ++j) {
-            const int l = j - (a.D - 10);
-            const int code = j >= a.D - 2 ? cget(Cb, ((int64_t)1 << j) + (r0 >> (a.D - j)))
-                                          : inner[(1 << l) + (lr >> (a.D - j))];
-            val = j == 0 ? val : apply_code(val, code, c.distanceMap[j]);
-        }
-        a.idxOff[(int64_t)brick * a.nIdx + sidx] = Q.aliveAtDs ? g0 + lo + (uint32_t)Q.preDs : VR_IDX_DEAD;
-        a.idxVal[(int64_t)brick * a.nIdx + sidx] = (uint8_t)val;
-    }
-    __syncthreads();
-    if (tot == 0) return;
-    uint32_t *G = (uint32_t *)(a.tree + (int64_t)brick * a.treeCap) + (g0 >> 4);
-    const uint32_t nw = ((phase + tot - 1) >> 4) + 1;
-    for (uint32_t i = threadIdx.x; i < nw; i += 256) {
-        if (i == 0 || i == nw - 1) { if (W[i]) atomicOr(&G[i], W[i]); }
-        else G[i] = W[i];
-    }
 }
 
 // The decode index of a fused build: block-local offsets -> offsets into the gapped stream buffer (slot b starts at
@@ -2613,9 +2157,7 @@ k_index12(EmitArgs a, uint32_t nblk)
 // piece's very first and last word can belong to a neighbouring workgroup too: those were zeroed by k_emit_zero and
 // take atomicOr (two atomics per workgroup instead of two per block: the atomics were a third of this kernel).
 #define CC_BLOCKS 16
-#ifndef CC_BATCH
 #define CC_BATCH 4          // chunks per thread whose loads are in flight together
-#endif
 template <bool RANGE>        // RANGE: MidRangeTree's second stream -- same offsets and shape, its own strings and spine
 __global__ void __launch_bounds__(256)
 k_concat12(EmitArgs a, const uint8_t *__restrict__ gap, int64_t nblk)
@@ -3019,8 +2561,8 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     const bool mr = bs->variant == 2;
     hipEventRecord(bs->ev[0], st);
     const uint8_t *rootMinP = nullptr, *rootMaxP = nullptr;   // where the last pyramid round leaves each brick's root (min,max)
-    const bool fused = D >= 12 && bs->K == 6 && !bs->sw.noFusedEmit;   // prune + block-local emit in one kernel
-    if (bs->leafless != (fused && bs->maxEpochs >= 1)) return -2;      // (the arrays were sized for the other mode: capi alloc_encoder_buffers)
+    const bool fused = D >= 12;      // prune + block-local emit in one kernel (K = 6 for every D >= 6)
+    if (bs->leafless != leafless_build(*bs)) return -2;      // (the arrays were sized for the other mode: capi alloc_encoder_buffers)
     // SkipBlocks needs k_pyramid12's constant bit in front and k_prune_emit12 behind, a prune that makes such blocks
     // one token (tolerance >= 1) and a level loop that runs
     bool skipOn = fused && bs->blockFlag && (!mr || bs->blockFlagR) && bs->tolerance >= 1 && bs->maxEpochs >= 1 && D >= 14 && !bs->sw.noSkipBlocks;
@@ -3055,7 +2597,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         if (use12) {
             const int64_t Bx = bs->g.X >> pg.ax, By = bs->g.Y >> pg.ay, Bz = bs->g.Z >> pg.az;
             const int64_t perLine = (bs->g.X < 128 ? bs->g.X : 128) >> pg.ax;
-            pg.swz = (perLine == 8 && Bx % 8 == 0 && ((Bx / 8) * By * Bz) % 8 == 0 && !bs->sw.noSwz) ? 1 : 0;
+            pg.swz = (perLine == 8 && Bx % 8 == 0 && ((Bx / 8) * By * Bz) % 8 == 0) ? 1 : 0;
             pg.nbx = (int)Bx; pg.nby = (int)By;
             pg.lnbx = 0; while ((1 << pg.lnbx) < pg.nbx) ++pg.lnbx;
             pg.lnby = 0; while ((1 << pg.lnby) < pg.nby) ++pg.lnby;
@@ -3097,7 +2639,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     // MidRangeTree: the two streams' level loops do not depend on each other (M.cpp:399-544 runs them one after the
     // other): the half-range stream's goes to the set's second stream, so its one-wave-per-brick walkers run beside
     // the mid stream's wide kernels and the other way round
-    const bool forkR = mr && bs->blockErrR && bs->estSummR && !bs->sw.mrSerial && ensure_aux(bs, 1) == 1;
+    const bool forkR = mr && bs->blockErrR && bs->estSummR && ensure_aux(bs, 1) == 1;
     if (forkR) {
         hipEventRecord(bs->evFork, st);
         hipStreamWaitEvent(bs->aux, bs->evFork, 0);
@@ -3107,7 +2649,6 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     }
     // VolumeKdtree: the same trick over ranges of the bricks (vr_brickset_set_concurrency; 2 by default)
     int parts = bs->levelLoopStreams;
-    if (bs->sw.forkBricks > 0) parts = bs->sw.forkBricks;
     if (parts > 4) parts = 4;
     if (mr || B < 16 * parts || parts < 2) parts = 1;
     if (parts > 1) parts = 1 + ensure_aux(bs, parts - 1);
@@ -3160,13 +2701,6 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         }
         pruneFrom = D - 13;
         bs->fineHas.assign((size_t)B, 1);
-    } else if (D >= 12) {
-        hipLaunchKernelGGL(k_prune12, dim3((unsigned)((int64_t)1 << (D - 12)), B), dim3(256), 0, st, D, bs->tolerance,
-                           bs->mid.ctrl, bs->mid.temp, bs->mid.codes, mr ? bs->rng.codes : nullptr, bs->heapStride,
-                           bs->codeStride, rb, bs->reconStride, bs->maxDepth, (!mr && bs->K >= 2) ? bs->blockOff : nullptr,
-                           bs->nEmitBlk,    // per-brick stride of the block arrays (same as EmitArgs::nEmitBlk)
-                           bs->blockL1, bs->chainLut);
-        pruneFrom = D - 13;
     } else
         hipLaunchKernelGGL(k_prune_leaf, dim3(cdiv((int64_t)1 << D, 256), B), dim3(256), 0, st, D, bs->tolerance,
                            bs->mid.ctrl, bs->mid.temp, bs->mid.codes, mr ? bs->rng.codes : nullptr, bs->heapStride,
@@ -3181,13 +2715,8 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     // ---- CONVERT
     EmitArgs a;
     fill_emit_args(bs, a);
-    if (bs->idx64 && !fused) {      // the level-synchronous emitters write absolute (32-bit) index entries: zero bases
-        a.blockOff64 = nullptr; a.idxBase = nullptr;
-        hipMemsetAsync(bs->idxBase, 0, (size_t)B * bs->nEmitBlk * sizeof(unsigned long long), st);
-    }
-    const bool quad = (!mr || fused) && D >= 12 && bs->K >= 2;
-    const int64_t nblk = cdiv((int64_t)1 << D, fused ? 4096 : (quad ? EMIT4_RANKS : EMIT_RANKS_PER_BLOCK));
-    if (quad) hipLaunchKernelGGL(k_block_alive, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk, fused ? 12 : 10);   // + token counts
+    const int64_t nblk = cdiv((int64_t)1 << D, fused ? 4096 : EMIT_RANKS_PER_BLOCK);
+    if (fused) hipLaunchKernelGGL(k_block_alive, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk, 12);   // + token counts
     else hipLaunchKernelGGL(k_emit_count, dim3((unsigned)nblk, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
     dbg_sync(st, "block_alive/count");
     hipLaunchKernelGGL(k_emit_scan, dim3(B), dim3(1024), 0, st, a, nblk);
@@ -3199,10 +2728,9 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     if (fused) hipLaunchKernelGGL(k_index12, dim3(cdiv(nblk, 4), B), dim3(256), 0, st, a, (uint32_t)nblk);
     else {
         hipLaunchKernelGGL(k_emit_zero, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk);
-        if (quad) hipLaunchKernelGGL(k_emit4<true>, dim3((unsigned)nblk, B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_emit_write, dim3((unsigned)nblk, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
+        hipLaunchKernelGGL(k_emit_write, dim3((unsigned)nblk, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
     }
-    // statistics records: one per 1024 leaves from k_prune12, one per 256 from k_prune_leaf
+    // statistics records: one per 1024 leaves from k_prune_emit12, one per 256 from k_prune_leaf
     hipLaunchKernelGGL(k_emit_stats, dim3(B), dim3(1024), 0, st, a, (int64_t)(D >= 12 ? cdiv((int64_t)1 << D, 1024) : cdiv((int64_t)1 << D, 256)));
     hipLaunchKernelGGL(k_const_finish, dim3(cdiv(bs->nIdx, 256), B), dim3(256), 0, st, D, bs->mid.ctrl, bs->mid.tree,
                        bs->treeCap, bs->idxOff, bs->idxVal, bs->nIdx);
