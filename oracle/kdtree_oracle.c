@@ -13,15 +13,15 @@
  * Each function cites the lines it follows.  Written from the algorithm, not
  * copied: no Eigen, no PPL, no std::stack; plain C99.
  *
- * PARITY UNPINNED (see DESIGN.md "Oracle"): the reference needs <ppl.h> (MSVC) and
- * Eigen, neither present in this image, and building it with stand-in headers
- * is not permitted, so oracle/_ref does not exist; the reference ships no
- * tests or golden vectors.  The only reference outputs available are the
- * known-answer values the survey session recorded (SURVEY.md section 8c /
- * Appendix B: numActiveNodes, full distanceMap, FNV-1a-64 of tree bytes and of
- * decoded voxels for 16^3/128^3/256^3 sphere_n3, the MidRangeTree 32^3 hashes)
- * -- from a build with stand-in headers, which does not count as a pin.
- * tests/test_oracle_golden.py reproduces all of them all the same.
+ * PINNED TO THE REFERENCE ITSELF (see DESIGN.md "Oracle"): oracle/Makefile's
+ * `ref` target compiles VolumeKdTree_recover.cpp, MidRangeTree.cpp and
+ * DebugTimer.cpp in place from an upstream checkout into oracle/_ref/libvkref.so
+ * (serial stand-ins for <ppl.h> and <Eigen/Core> under oracle/ref/, locals
+ * zero-initialised by the compiler).  tests/test_ref_parity.py compares this
+ * file with it bit for bit -- saved files, both streams, distance maps, the
+ * 4-bit packing, decoded voxels -- over a seeded matrix of shapes, volumes,
+ * tolerances and epochs, and regenerates the known answers of
+ * tests/golden/survey_known_answers.json and the golden tree file from it.
  *
  * Reference defects reproduced on purpose:
  *  C-1 currentError/currentDF/currentStepSize start at 0.0 and carry over

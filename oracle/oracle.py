@@ -37,7 +37,201 @@ def build(force=False):
                 subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
                 with open(stamp, "w") as f:
                     f.write(_source_hash())
+    build_ref()
     return _LIB_PATH
+
+
+# -- oracle/_ref: the reference codec itself, compiled in place (oracle/Makefile, target `ref`)
+
+_REF_LIB_PATH = os.path.join(_HERE, "_ref", "libvkref.so")
+_REF_SOURCES = ("VolumeKdTree_recover.cpp", "VolumeKdtree_recover.h", "MidRangeTree.cpp", "MidRangeTree.h",
+                "DebugTimer.cpp", "DebugTimer.h", "TwoBitArray.h", "point.h")
+_REF_RECIPE = ("Makefile", "ref/ref_capi.cpp", "ref/ppl.h", "ref/Eigen/Core")
+_ref_lib = None
+
+
+def ref_dir():
+    """Upstream VolumeRenderer sources: $REF_DIR, else `reference/volume_renderer` beside the repository, else the
+    location the oracle's citations use (/root/reference/volume_renderer)."""
+    if os.environ.get("REF_DIR"):
+        return os.environ["REF_DIR"]
+    beside = os.path.normpath(os.path.join(_HERE, "..", "..", "reference", "volume_renderer"))
+    return beside if os.path.isdir(beside) else "/root/reference/volume_renderer"
+
+
+def _ref_source_hash(d):
+    import hashlib
+    h = hashlib.sha256()
+    for s in _REF_RECIPE:
+        h.update(open(os.path.join(_HERE, s), "rb").read())
+    for s in _REF_SOURCES:
+        h.update(open(os.path.join(d, s), "rb").read())
+    return h.hexdigest()
+
+
+def build_ref(force=False):
+    """Build oracle/_ref/libvkref.so when the reference sources are present and _ref is missing or stale.
+    Without the sources an existing _ref is used as it is.  Never raises: a failed build leaves
+    ref_available() False and says why on stderr."""
+    import sys
+    d = ref_dir()
+    if not all(os.path.isfile(os.path.join(d, s)) for s in _REF_SOURCES):
+        return _REF_LIB_PATH if os.path.exists(_REF_LIB_PATH) else None
+    try:
+        want = _ref_source_hash(d)
+        stamp = _REF_LIB_PATH + ".srchash"
+        fresh = lambda: os.path.exists(_REF_LIB_PATH) and os.path.exists(stamp) and open(stamp).read().strip() == want
+        if force or not fresh():
+            import fcntl
+            os.makedirs(os.path.dirname(_REF_LIB_PATH), exist_ok=True)
+            with open(_REF_LIB_PATH + ".lock", "w") as lk:
+                fcntl.flock(lk, fcntl.LOCK_EX)
+                if force or not fresh():
+                    subprocess.check_call(["make", "-C", _HERE, "-B", "ref", "REF_DIR=" + d], stdout=subprocess.DEVNULL)
+                    with open(stamp, "w") as f:
+                        f.write(want)
+    except (OSError, subprocess.CalledProcessError) as e:
+        print("oracle: reference build skipped: %s" % e, file=sys.stderr)
+    return _REF_LIB_PATH if os.path.exists(_REF_LIB_PATH) else None
+
+
+def ref_available():
+    return os.path.exists(_REF_LIB_PATH)
+
+
+def ref_lib():
+    global _ref_lib
+    if _ref_lib is not None:
+        return _ref_lib
+    if not ref_available():
+        raise FileNotFoundError("oracle/_ref/libvkref.so is not built (no reference sources at %s)" % ref_dir())
+    L = C.CDLL(_REF_LIB_PATH)
+    p, u8p, i64, i32 = C.c_void_p, C.POINTER(C.c_uint8), C.c_int64, C.c_int32
+    for k in ("kd", "mid"):
+        f = lambda n: getattr(L, "vkref_%s_%s" % (k, n))
+        f("create").restype = p
+        f("create").argtypes = [p, i64, i64, i64]
+        f("destroy").argtypes = [p]
+        f("set_error_tolerance").argtypes = [p, C.c_int]
+        f("set_max_epochs").argtypes = [p, C.c_int]
+        f("build").argtypes = [p]
+        f("build").restype = C.c_int
+        for n in ("max_tree_depth", "orig_tree_depth"):
+            f(n).argtypes = [p]
+            f(n).restype = i32
+        for n in ("num_active_nodes", "tree_bytes", "distance_map_len"):
+            f(n).argtypes = [p]
+            f(n).restype = i64
+        for n in ("tree_ptr", "distance_map_ptr"):
+            f(n).argtypes = [p]
+            f(n).restype = u8p
+        f("dims").argtypes = [p, C.POINTER(i64)]
+        f("save").argtypes = [p, C.c_char_p]
+        f("save").restype = C.c_int
+        f("open").argtypes = [C.c_char_p]
+        f("open").restype = p
+        f("level_cut").argtypes = [p, C.c_int, p]
+        f("level_cut").restype = C.c_int
+    for n in ("tree_range_bytes", "distance_map_range_len"):
+        getattr(L, "vkref_mid_" + n).argtypes = [p]
+        getattr(L, "vkref_mid_" + n).restype = i64
+    for n in ("tree_range_ptr", "distance_map_range_ptr"):
+        getattr(L, "vkref_mid_" + n).argtypes = [p]
+        getattr(L, "vkref_mid_" + n).restype = u8p
+    L.vkref_mid_convert_to_byte_array.argtypes = [p, p, i64]
+    L.vkref_mid_convert_to_byte_array.restype = i64
+    _ref_lib = L
+    return L
+
+
+class RefTree:
+    """The reference's own VolumeKdtree (or MidRangeTree with midrange=True), serial build(false),
+    through oracle/_ref/libvkref.so.  Accessors mirror OracleTree's.  The reference empties its input
+    on build(), so the handle owns a copy of `voxels`; its measureMaxError/measureMeanError read that
+    emptied copy and are not exposed (compute errors from levelCut())."""
+
+    def __init__(self, voxels=None, dims=None, tolerance=6, max_epochs=5, midrange=False, _handle=None):
+        self._L = ref_lib()
+        self._k = "mid" if midrange else "kd"
+        self.midrange = midrange
+        self._h = None
+        if _handle is not None:
+            self._h = _handle
+            return
+        v = np.ascontiguousarray(voxels, dtype=np.uint8)
+        if dims is None:
+            z, y, x = v.shape
+            dims = (x, y, z)
+        assert v.size == dims[0] * dims[1] * dims[2]
+        self._h = self._f("create")(v.reshape(-1).ctypes.data, dims[0], dims[1], dims[2])
+        assert self._h, "vkref create failed"
+        self._f("set_error_tolerance")(self._h, tolerance)
+        self._f("set_max_epochs")(self._h, max_epochs)
+
+    def _f(self, name):
+        return getattr(self._L, "vkref_%s_%s" % (self._k, name))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._f("destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @classmethod
+    def open(cls, path, midrange=False):
+        h = getattr(ref_lib(), "vkref_%s_open" % ("mid" if midrange else "kd"))(os.fsencode(path))
+        if not h:
+            raise FileNotFoundError(path)
+        return cls(midrange=midrange, _handle=h)
+
+    def build(self):
+        rc = self._f("build")(self._h)
+        if rc != 0:
+            raise RuntimeError("reference build failed: %d" % rc)
+        return self
+
+    def save(self, path):
+        rc = self._f("save")(self._h, os.fsencode(path))
+        if rc != 0:
+            raise RuntimeError("reference save failed: %d" % rc)
+
+    @property
+    def origTreeDepth(self): return self._f("orig_tree_depth")(self._h)
+    @property
+    def maxTreeDepth(self): return self._f("max_tree_depth")(self._h)
+    @property
+    def numActiveNodes(self): return self._f("num_active_nodes")(self._h)
+    @property
+    def dims(self):
+        d = (C.c_int64 * 3)()
+        self._f("dims")(self._h, d)
+        return tuple(d)
+    @property
+    def tree(self): return _u8(self._f("tree_ptr")(self._h), self._f("tree_bytes")(self._h))
+    @property
+    def distanceMap(self): return _u8(self._f("distance_map_ptr")(self._h), self._f("distance_map_len")(self._h))
+    @property
+    def tree_range(self):
+        return _u8(self._L.vkref_mid_tree_range_ptr(self._h), self._L.vkref_mid_tree_range_bytes(self._h))
+    @property
+    def distanceMap_range(self):
+        return _u8(self._L.vkref_mid_distance_map_range_ptr(self._h), self._L.vkref_mid_distance_map_range_len(self._h))
+
+    def convertToByteArray(self):
+        n = self._L.vkref_mid_convert_to_byte_array(self._h, None, 0)
+        out = np.zeros(n, np.uint8)
+        self._L.vkref_mid_convert_to_byte_array(self._h, out.ctypes.data, n)
+        return out
+
+    def levelCut(self, cutDepth=None):
+        X, Y, Z = self.dims
+        out = np.zeros(X * Y * Z, np.uint8)
+        rc = self._f("level_cut")(self._h, int(self.maxTreeDepth if cutDepth is None else cutDepth), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("reference levelCut failed: %d" % rc)
+        return out.reshape(Z, Y, X)
 
 
 class TraceRec(C.Structure):

@@ -86,13 +86,15 @@ def test_argument_validation_and_no_cpu_fallback(L):
 
 
 def test_product_never_imports_oracle():
-    """The oracle is test infrastructure: nothing under volumerenderer_amd/ or include/ may reference it."""
+    """The oracle and the reference build beside it (oracle/_ref/libvkref.so) are test infrastructure: nothing under
+    volumerenderer_amd/ or include/ may reference either."""
     for base in ("volumerenderer_amd", "include"):
         for dp, _, fs in os.walk(os.path.join(ROOT, base)):
             for f in fs:
                 if f.endswith((".py", ".h", ".hpp", ".hip", ".cpp")):
                     txt = open(os.path.join(dp, f), errors="ignore").read()
-                    for needle in ("import oracle", "from oracle", "liboracle", "oracle/"):
+                    for needle in ("import oracle", "from oracle", "liboracle", "oracle/", "_ref/", "libvkref", "vkref_",
+                                   "RefTree", "ref_lib"):
                         assert needle not in txt, "%s references the oracle (%s)" % (f, needle)
 
 

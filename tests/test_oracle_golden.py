@@ -1,9 +1,10 @@
 """Pins the CPU oracle (oracle/kdtree_oracle.c) to outputs of the reference itself.
 
-The only reference outputs that exist for this path are the known-answer values
-the survey recorded and the tree file the
-reference's own save() wrote for the 16^3 case; see tests/golden/
-survey_known_answers.json for provenance.  Bit-exact."""
+The known-answer values the survey recorded
+and the tree file the reference's own save() wrote for the 16^3 case; see
+tests/golden/survey_known_answers.json for provenance.  Bit-exact.
+tests/test_ref_parity.py regenerates them from the reference compiled in place
+and compares the oracle with it far more widely."""
 import json
 import os
 
