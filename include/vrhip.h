@@ -149,6 +149,49 @@ vr_status vr_brickset_decode(vr_brickset *bs, int32_t cut_depth, uint8_t *out_de
  * the host (as vr_brickset_decode does).  vr_brickset_last_timings reports the call's whole time as `decode`. */
 vr_status vr_brickset_decode_lod(vr_brickset *bs, const int32_t *cuts_host, uint8_t *out_dev, void *stream);
 
+/* Level-of-detail pool: each brick of a frame stored at the resolution its cut actually has.  For power-of-two brick
+ * extents a progressive cut c is piecewise constant on the boxes of the depth-min(c, orig_tree_depth) nodes, so a
+ * brick cut at c is kept as one byte per box with nothing lost.  One 16-byte entry per grid cell (x fastest): */
+typedef struct vr_pool_entry {
+    int64_t offset;      /* byte offset of the cell's brick in the pool; -1 = absent (culled, or no brick at the cell) */
+    uint8_t shift[3];    /* log2 of the box one stored voxel stands for, per axis (0 = full resolution) */
+    uint8_t pad[5];      /* 0 */
+} vr_pool_entry;
+
+/* Host-only: the pool layout of vr_brickset_decode_lod_pool.  Bricks as in vr_assemble_bricks (brick b of brick_dims
+ * voxels at cell brick_ijk[3b..3b+2] of `grid`), cuts as in vr_brickset_decode_lod.  The rule:
+ *  - split axes: depth d = 0, 1, ... splits axis sd = d % 3, or, while the box still has more than one voxel and
+ *    extent 1 on sd, the next axis (d + 1) % 3, (d + 2) % 3 ...; the split halves that extent (the reference's
+ *    buildRecursive).  n_k = the splits on axis k among depths 0 .. min(cut, orig_tree_depth) - 1.
+ *  - shift_k = log2(brick_dims_k) - n_k; a cut >= orig_tree_depth gives shift 0 on every axis.
+ *  - bricks are placed in index order b = 0 .. num_bricks-1: brick b with cuts[b] >= 0 gets offset = the running
+ *    total rounded up to a multiple of 256, and adds prod_k(brick_dims_k >> shift_k) bytes to it.  The stored voxel
+ *    (x, y, z) of a brick, x fastest, is brick voxel (x << shift_x, y << shift_y, z << shift_z): voxel (x, y, z) of the
+ *    brick reads stored voxel (x >> shift_x, y >> shift_y, z >> shift_z).
+ *  - cells with no brick, or whose brick has cut -1, get offset -1 and shift 0.  *pool_bytes = the final total (not
+ *    rounded; 0 if every brick is culled).
+ * VR_ERR_INVALID: a null pointer (table_out aside), num_bricks <= 0, a brick_dims extent that is not a power of two,
+ * a grid extent <= 0, a brick outside the grid, two bricks on one cell, a cut outside -1 .. max_tree_depth, orig_tree_depth not the depth of
+ * brick_dims (log2 X + log2 Y + log2 Z), or max_tree_depth < orig_tree_depth.  table_out may be NULL. */
+vr_status vr_lod_pool_layout(const int64_t brick_dims[3], int32_t num_bricks, const int64_t *brick_ijk,
+                             const int64_t grid[3], const int32_t *cuts, int32_t orig_tree_depth,
+                             int32_t max_tree_depth, vr_pool_entry *table_out, int64_t *pool_bytes);
+
+/* Per-brick progressive decode into a pool laid out by vr_lod_pool_layout (the set's dims, the same brick_ijk, grid
+ * and cuts): brick b's stored voxel (x, y, z) = voxel (x << shift_x, y << shift_y, z << shift_z) of brick b in
+ * vr_brickset_decode_lod's output for the same cuts, i.e. the box's min-corner voxel, which every voxel of the box
+ * equals.  pool_bytes must be at least the layout's.  Pool bytes outside the slots of decoded bricks are not written.
+ * table_dev (may be NULL): receives the layout's grid[0]*grid[1]*grid[2] entries, uploaded on `stream`.
+ * Full-resolution bricks are decoded straight into their slots; coarse ones at most VR_POOL_STAGE_BRICKS at a time into
+ * a staging buffer of the set, then packed.  The staging buffer's use is ordered across streams by an event; the
+ * lists come from vr_brickset_decode_lod's ring (same concurrency contract, no host synchronisation).
+ * VR_ERR_UNSUPPORTED (nothing launched) unless every brick extent is a power of two; VR_ERR_INVALID as for the layout
+ * and for a pool smaller than the layout's.  vr_brickset_last_timings reports the call's whole time as `decode`. */
+#define VR_POOL_STAGE_BRICKS 32
+vr_status vr_brickset_decode_lod_pool(vr_brickset *bs, const int32_t *cuts_host, const int64_t *brick_ijk_host,
+                                      const int64_t grid[3], uint8_t *pool_dev, int64_t pool_bytes,
+                                      vr_pool_entry *table_dev, void *stream);
+
 /* MidRangeTree only (new: the reference builds the half-range stream, MidRangeTree.cpp:399-544, 871-982, but
  * never decodes it -- its levelCut, :984-1093, reads the mid stream alone): the same progressive
  * decode applied to the range stream, i.e. per voxel the half range of its terminal node's box as the
@@ -273,6 +316,20 @@ vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *params, in
  * bracket (vr_brickset_decode_range remains available for previews).  Both buffers may start at any byte. */
 vr_status vr_skip_grid_build(const uint8_t *volume_dev, const int64_t dims[3], int32_t skip_cell, uint8_t *grid_dev,
                              void *stream);
+
+/* vr_raycast and vr_skip_grid_build over a pool (vr_brickset_decode_lod_pool) in place of a dense volume.  The volume
+ * is the virtual grid * brick_dims voxels whose voxel (x, y, z) is pool[e.offset + (lx >> sx) + (X >> sx) * ((ly >> sy)
+ * + (Y >> sy) * (lz >> sz))], e = table_dev[cell], cell = (x / X, y / Y, z / Z), (lx, ly, lz) = the position in the
+ * brick, and 0 where e.offset = -1.  Bit-identical to vr_raycast / vr_skip_grid_build on that volume assembled densely,
+ * in every mode, with or without a skip grid (one built by vr_skip_grid_build_pool from the same pool and table, or by
+ * vr_skip_grid_build from the dense volume: they are byte-identical).  brick_dims must be powers of two and the
+ * virtual extents below 2^31; params->vol_origin must be 0 and params->global_dims 0 or the virtual extents, else
+ * VR_ERR_INVALID. */
+vr_status vr_raycast_pool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                          const int64_t grid[3], const vr_camera *cam, const vr_render_params *params, float *rgba_dev,
+                          void *stream);
+vr_status vr_skip_grid_build_pool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                                  const int64_t grid[3], int32_t skip_cell, uint8_t *grid_dev, void *stream);
 
 /* Sort-last compositing of VR_RENDER_PARTIAL images: front = front OVER back, per pixel
  * (c1 + t1*c2, t1*t2); and the final colour transfer of raycaster.frag:82-85. */

@@ -86,6 +86,15 @@ public:
         const vr_camera c = camera();
         return vr_raycast(vol, dims, &c, &P, rgba_dev, stream);
     }
+    // one frame of a level-of-detail pool (vr_brickset_decode_lod_pool's pool and table for this frame's cuts, e.g. from
+    // vr_lod_select with camera()): vr_raycast_pool, the frame draw() gives for the pool's volume assembled densely
+    vr_status drawPool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3], const int64_t grid[3],
+                       vr_render_params P, float *rgba_dev, void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f;
+        const vr_camera c = camera();
+        return vr_raycast_pool(pool_dev, table_dev, brick_dims, grid, &c, &P, rgba_dev, stream);
+    }
     // binary PPM of a host float RGBA frame (what glReadPixels of the 8-bit framebuffer would hold)
     static bool dumpPPM(const std::string &path, const std::vector<float> &rgba, int w, int h)
     {

@@ -1,0 +1,355 @@
+"""The level-of-detail pool on the GPU: vr_brickset_decode_lod_pool stores each brick at the resolution of its cut
+(checked against vr_brickset_decode_lod over whole bricks), and vr_raycast_pool / vr_skip_grid_build_pool render and
+bound the pool's virtual volume bit-identically to vr_raycast / vr_skip_grid_build of the dense LOD volume."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+
+
+@pytest.fixture(scope="module")
+def vr():
+    import torch
+    assert torch.cuda.is_available()
+    import __graft_entry__ as g
+    g.build()
+    import volumerenderer_amd as vr
+    return vr
+
+
+def rm_like(shape, seed=3):
+    rng = np.random.default_rng(seed)
+    z, y, x = np.meshgrid(*[np.arange(s) for s in shape], indexing="ij")
+    h = shape[0] / 2 + 3 * np.sin(x * 0.4) + 2 * np.cos(y * 0.23)
+    v = 128 + 120 * np.tanh((z - h) / 3.0) + rng.integers(0, 3, shape)
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def cut_pool(D, M):
+    """The LOD tests' cuts: skipped, above the index level, the fine / tile kernels, the region / quad kernels, the
+    grown-branch levels."""
+    Ds = D - min(D, 6)
+    pool = [-1, 0, 3, Ds - 1, Ds, D - 3, D - 1, D, M - 1, M]
+    return sorted({c for c in pool if c == -1 or 0 <= c <= M})
+
+
+def line_ijk(B):
+    return np.array([(b, 0, 0) for b in range(B)], np.int64), (B, 1, 1)
+
+
+def dense_lod(bs, cuts):
+    import torch
+    out = torch.full((bs.num_bricks * bs.voxels_per_brick,), FILL, dtype=torch.uint8, device="cuda")
+    bs.decode_lod(cuts, out=out)
+    return out
+
+
+def check_pool(vr, bs, cuts, ijk, grid, pool, table):
+    """Every decoded brick's slot holds the min corner of every box of the dense decode, and the dense decode is
+    constant on the boxes; bytes outside the slots keep FILL; the uploaded table is the layout's."""
+    from volumerenderer_amd.render import POOL_ENTRY
+    info = bs.info(0)
+    want_t, nbytes = vr.lod_pool_layout(bs.dims, ijk, grid, cuts, info["orig_tree_depth"], info["max_tree_depth"])
+    got_t = np.frombuffer(table.cpu().numpy().tobytes(), POOL_ENTRY)
+    assert np.array_equal(got_t, want_t)
+    X, Y, Z = bs.dims
+    dense = dense_lod(bs, cuts).cpu().numpy().reshape(bs.num_bricks, Z, Y, X)
+    p = pool.cpu().numpy()
+    used = np.zeros(p.size, bool)
+    for b, c in enumerate(cuts):
+        i, j, k = ijk[b]
+        e = want_t[i + grid[0] * (j + grid[1] * k)]
+        if c < 0:
+            assert e["offset"] == -1
+            continue
+        sx, sy, sz = (int(v) for v in e["shift"])
+        n = (X >> sx) * (Y >> sy) * (Z >> sz)
+        o = int(e["offset"])
+        assert o % 256 == 0 and o + n <= nbytes
+        used[o:o + n] = True
+        stored = p[o:o + n].reshape(Z >> sz, Y >> sy, X >> sx)
+        up = np.repeat(np.repeat(np.repeat(stored, 1 << sz, 0), 1 << sy, 1), 1 << sx, 2)
+        assert np.array_equal(up, dense[b]), (b, c, (sx, sy, sz))
+    assert np.all(p[~used] == FILL)
+
+
+def run_pool(vr, bs, cuts, ijk, grid, extra=4096, stream=None):
+    import torch
+    info = bs.info(0)
+    _, nbytes = vr.lod_pool_layout(bs.dims, ijk, grid, cuts, info["orig_tree_depth"], info["max_tree_depth"])
+    pool = torch.full((nbytes + extra,), FILL, dtype=torch.uint8, device="cuda")
+    table = torch.full((int(np.prod(grid)) * 16,), 0x5A, dtype=torch.uint8, device="cuda")
+    bs.decode_lod_pool(cuts, ijk, grid, pool=pool, table=table, stream=stream)
+    return pool, table
+
+
+def check_all_cuts(vr, bs, rounds=None, seed=0):
+    info = bs.info(0)
+    pool = cut_pool(info["orig_tree_depth"], info["max_tree_depth"])
+    B = bs.num_bricks
+    ijk, grid = line_ijk(B)
+    rng = np.random.default_rng(seed)
+    plans = [[pool[(r + b) % len(pool)] for b in range(B)] for r in range(rounds or len(pool))]
+    plans.append(list(rng.choice(pool, B)))
+    for cuts in plans:
+        cuts = np.array(cuts, np.int32)
+        p, t = run_pool(vr, bs, cuts, ijk, grid)
+        check_pool(vr, bs, cuts, ijk, grid, p, t)
+
+
+def test_pool_64cubed(vr):
+    rng = np.random.default_rng(21)
+    vols = [rm_like((64, 64, 64), s) for s in range(4)] + [rng.integers(0, 256, (64, 64, 64), dtype=np.uint8)]
+    vols += [np.full((64, 64, 64), 9, np.uint8), rm_like((64, 64, 64), 9)[::-1].copy(), rm_like((64, 64, 64), 11).transpose(2, 1, 0).copy()]
+    bs = vr.BrickSet(8, (64, 64, 64), 1, 2)
+    bs.build(np.stack(vols))
+    check_all_cuts(vr, bs)
+
+
+@pytest.fixture(scope="module")
+def bench_set(vr):
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    bd = (256, 256, 128)
+    vox = bench.make_volume_gpu(torch, (256, 256, 512), bd, seed=12345, kind="rm_volume")
+    bs = vr.BrickSet(4, bd, 1, 2)
+    bs.build(vox.reshape(-1))
+    return bs
+
+
+def test_pool_bench_bricks(vr, bench_set):
+    check_all_cuts(vr, bench_set)
+
+
+def test_pool_midrange(vr):
+    shape = (16, 32, 128)
+    vols = [rm_like(shape, 4), rm_like(shape, 5)[::-1].copy(), np.full(shape, 200, np.uint8)]
+    bs = vr.BrickSet(3, (128, 32, 16), 2, 2, vr.VARIANT_MIDRANGE)
+    bs.build(np.stack(vols))
+    check_all_cuts(vr, bs)
+
+
+def test_pool_opened_golden_file(vr):
+    bs = vr.BrickSet.open(os.path.join(GOLD, "ref_sphere_n3_16_tol1_ep2.tree.bin"))
+    check_all_cuts(vr, bs)
+
+
+def test_pool_general_extents_unsupported(vr):
+    import torch
+    shape = (40, 80, 96)
+    bs = vr.BrickSet(2, (96, 80, 40), 1, 2)
+    bs.build(np.stack([rm_like(shape, 2), rm_like(shape, 7)]))
+    pool = torch.full((1 << 20,), FILL, dtype=torch.uint8, device="cuda")
+    table = torch.zeros(2 * 16, dtype=torch.uint8, device="cuda")
+    with pytest.raises(vr.VrError) as e:
+        bs.decode_lod_pool(np.array([3, 5], np.int32), np.array([(0, 0, 0), (1, 0, 0)]), (2, 1, 1), pool=pool, table=table)
+    assert e.value.status == -7
+    torch.cuda.synchronize()
+    assert torch.all(pool == FILL) and torch.all(table == 0)
+
+
+# ---- rendering
+
+GRID, BD, DIMS = (4, 4, 4), (32, 32, 32), (128, 128, 128)
+
+
+@pytest.fixture(scope="module")
+def render_set(vr):
+    """A 128^3 volume as 64 bricks of 32^3 in a 4 x 4 x 4 grid (more coarse bricks than the staging buffer holds)."""
+    full = rm_like((128, 128, 128), 6)
+    ijk = np.array([(i, j, k) for k in range(4) for j in range(4) for i in range(4)], np.int64)
+    bricks = np.stack([full[k * 32:(k + 1) * 32, j * 32:(j + 1) * 32, i * 32:(i + 1) * 32] for i, j, k in ijk])
+    bs = vr.BrickSet(64, BD, 1, 2)
+    bs.build(bricks.copy())
+    return bs, ijk
+
+
+def test_pool_staging_batches(vr, render_set):
+    """33, 32 and 64 coarse bricks: one and two staging batches, exactly full and one over."""
+    bs, ijk = render_set
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    pool = [c for c in cut_pool(D, M) if 0 <= c < D]
+    for ncoarse in (32, 33, 64):
+        cuts = np.full(64, M, np.int32)
+        cuts[:ncoarse] = [pool[b % len(pool)] for b in range(ncoarse)]
+        cuts[ncoarse::7] = -1
+        p, t = run_pool(vr, bs, cuts, ijk, GRID)
+        check_pool(vr, bs, cuts, ijk, GRID, p, t)
+
+
+def _cam(vr, pos, front, fov):
+    cam = vr.default_camera()
+    f = np.array(front) / np.linalg.norm(front)
+    cam.pos[:], cam.front[:], cam.fov_deg = pos, tuple(float(v) for v in f), fov
+    if abs(f[1]) > 0.99:
+        cam.up[:] = (0.0, 0.0, 1.0)
+    return cam
+
+
+CAMERAS = [  # (pos, front, fov)
+    ((0.25, 0.2, -0.6), (0.0, 0.0, 1.0), 20.0),          # outside
+    ((-0.3, 0.0, -0.7), (0.5, 0.0, 1.0), 15.0),
+    ((0.0, 0.0, 0.2), (0.0, 0.0, 1.0), 50.0),            # inside the volume
+    ((0.0, 0.1, 0.0), (0.3, -0.2, 1.0), 60.0),
+    ((-0.8, 0.0, 0.0), (1.0, 0.0001, 0.0), 30.0),        # grazing a brick face (x = 0 is a face of bricks)
+    ((-1.2, 0.0, 0.0), (1.0, 0.0, 0.0), 40.0),           # down each axis
+    ((0.05, -1.2, 0.05), (0.0, 1.0, 0.0), 40.0),
+    ((0.07, 0.03, 1.3), (0.0, 0.0, -1.0), 40.0),
+]
+
+
+def _dense(vr, bs, cuts, ijk):
+    import torch
+    buf = torch.zeros(bs.num_bricks * bs.voxels_per_brick, dtype=torch.uint8, device="cuda")
+    bs.decode_lod(cuts, out=buf)
+    return vr.assemble_bricks(buf, BD, ijk, GRID)
+
+
+def test_pool_frames_equal_dense_frames(vr, render_set):
+    """Arbitrary per-brick cuts (culled bricks read as 0): composite, iso-surface and PARTIAL, with and without the skip
+    grid; the pool's skip grid equals the dense one byte for byte."""
+    import torch
+    bs, ijk = render_set
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    rng = np.random.default_rng(5)
+    choices = [-1] + list(range(max(0, D - 6), M + 1))
+    shown = 0
+    for plan in range(3):
+        cuts = rng.choice(choices, 64).astype(np.int32)
+        if plan == 0:
+            cuts[:] = np.where(cuts < 0, M, cuts)
+        vol = _dense(vr, bs, cuts, ijk)
+        pool, table = bs.decode_lod_pool(cuts, ijk, GRID)
+        for cell in (8, 5):
+            g_d = vr.build_skip_grid(vol, DIMS, cell)
+            g_p = vr.build_skip_grid_pool(pool, table, BD, GRID, cell)
+            assert torch.equal(g_d, g_p), (plan, cell)
+        for pos, front, fov in CAMERAS:
+            cam = _cam(vr, pos, front, fov)
+            for mode in (0, 1, 2):
+                P = vr.default_params(96, 72, BD, mode, 100.0 / 255.0)
+                if mode == 2:
+                    P.box_min[:] = (0.25, 0.0, 0.125)
+                    P.box_max[:] = (0.75, 0.8, 1.0)
+                for skip in (False, True):
+                    if skip:
+                        vr.use_skip_grid(P, vr.build_skip_grid(vol, DIMS, 8), 8)
+                        Pp = vr.default_params(96, 72, BD, mode, 100.0 / 255.0)
+                        Pp.box_min[:], Pp.box_max[:] = P.box_min[:], P.box_max[:]
+                        vr.use_skip_grid(Pp, vr.build_skip_grid_pool(pool, table, BD, GRID, 8), 8)
+                    else:
+                        vr.use_skip_grid(P, None)
+                        Pp = P
+                    want = vr.raycast(vol, DIMS, cam, P).cpu().numpy()
+                    got = vr.raycast_pool(pool, table, BD, GRID, cam, Pp).cpu().numpy()
+                    assert np.array_equal(got, want), (plan, pos, mode, skip, np.abs(got - want).max())
+                    shown += int(np.any(want != want[0, 0]))
+    assert shown > 20, shown
+
+
+def test_raycast_pool_rejects_bad_params(vr, render_set):
+    bs, ijk = render_set
+    cuts = np.full(64, bs.info(0)["max_tree_depth"], np.int32)
+    pool, table = bs.decode_lod_pool(cuts, ijk, GRID)
+    cam = vr.default_camera()
+    P = vr.default_params(32, 32, BD)
+    P.vol_origin[:] = (1, 0, 0)
+    with pytest.raises(vr.VrError):
+        vr.raycast_pool(pool, table, BD, GRID, cam, P)
+    P = vr.default_params(32, 32, BD)
+    P.global_dims[:] = (128, 128, 64)
+    with pytest.raises(vr.VrError):
+        vr.raycast_pool(pool, table, BD, GRID, cam, P)
+    P.global_dims[:] = DIMS
+    vr.raycast_pool(pool, table, BD, GRID, cam, P)
+
+
+@pytest.mark.parametrize("mode,skip", [(0, 0), (0, 8), (1, 0), (1, 8)])
+def test_draw_lod_pool_equals_draw_lod(vr, render_set, mode, skip):
+    from volumerenderer_amd.viewer import HeadlessViewer
+    bs, ijk = render_set
+    a, b = HeadlessViewer(128, 96), HeadlessViewer(128, 96)
+    for pos in ((0.0, 0.0, -2.5), (0.1, 0.05, -0.75), (0.0, 0.0, 0.2)):
+        for v in (a, b):
+            v.cameraPos = np.array(pos, np.float32)
+        fa, ca = a.draw_lod(bs, ijk, GRID, pixel_tolerance=2.0, mode=mode)
+        fb, cb = b.draw_lod_pool(bs, ijk, GRID, pixel_tolerance=2.0, mode=mode, skip_cell=skip)
+        assert np.array_equal(ca, cb)
+        # draw_lod keeps culled bricks' earlier contents; those bricks are read by no ray (the culling contract)
+        assert np.array_equal(fa.cpu().numpy(), fb.cpu().numpy()), pos
+
+
+def test_draw_lod_pool_keeps_its_pool(vr, render_set):
+    from volumerenderer_amd.viewer import HeadlessViewer
+    bs, ijk = render_set
+    v = HeadlessViewer(64, 48)
+    v.cameraPos = np.array([0.0, 0.0, -0.75], np.float32)
+    v.draw_lod_pool(bs, ijk, GRID, pixel_tolerance=1e-6)
+    p1 = v._pool
+    v.cameraPos = np.array([0.0, 0.0, -3.0], np.float32)         # far: coarser cuts, a smaller pool suffices
+    v.draw_lod_pool(bs, ijk, GRID, pixel_tolerance=4.0)
+    assert v._pool is p1
+
+
+def test_pool_back_to_back_one_stream_and_two_streams(vr, render_set):
+    import torch
+    bs, ijk = render_set
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    rng = np.random.default_rng(9)
+    choices = [-1, 0, 3] + list(range(D - 6, M + 1))
+    plans = [rng.choice(choices, 64).astype(np.int32) for _ in range(3)]
+    serial = []
+    for cuts in plans:
+        p, t = run_pool(vr, bs, cuts, ijk, GRID)
+        torch.cuda.synchronize()
+        serial.append((p.cpu().numpy(), t.cpu().numpy()))
+    for streams in ([torch.cuda.current_stream()] * 2, [torch.cuda.Stream(), torch.cuda.Stream()]):
+        torch.cuda.synchronize()
+        outs = []
+        for i in range(6):
+            outs.append(run_pool(vr, bs, plans[i % 3], ijk, GRID, stream=streams[i % 2]))
+        torch.cuda.synchronize()
+        for i, (p, t) in enumerate(outs):
+            assert np.array_equal(p.cpu().numpy(), serial[i % 3][0]), i
+            assert np.array_equal(t.cpu().numpy(), serial[i % 3][1]), i
+
+
+def test_full_size_start_camera(vr):
+    """The bench volume at the start camera, 1920 x 1080: the pool frame is the dense LOD frame, the pool is the
+    layout's size."""
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    bd, gd, grid = (256, 256, 128), (2048, 2048, 1920), (8, 8, 15)
+    vox4 = bench.make_volume_gpu(torch, gd, bd, seed=12345)
+    B = vox4.shape[0]
+    ijk = np.array([(b % 8, (b // 8) % 8, b // 64) for b in range(B)], np.int64)
+    bs = vr.BrickSet(B, bd, 1, 2)
+    bs.build(vox4.reshape(-1))
+    del vox4
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    cam, P = vr.default_camera(), vr.default_params(1920, 1080, bd)
+    cuts = vr.select_lod(cam, P, bd, ijk, grid, D, M, 1.0)
+    _, nbytes = vr.lod_pool_layout(bd, ijk, grid, cuts, D, M)
+    pool, table = bs.decode_lod_pool(cuts, ijk, grid)
+    assert pool.numel() == nbytes and nbytes <= 0.25 * 2 * B * bd[0] * bd[1] * bd[2]
+    got = vr.raycast_pool(pool, table, bd, grid, cam, P).cpu().numpy()
+    del pool, table
+    buf = torch.zeros(B * bd[0] * bd[1] * bd[2], dtype=torch.uint8, device="cuda")
+    bs.decode_lod(cuts, out=buf)
+    vol = vr.assemble_bricks(buf, bd, ijk, grid)
+    del buf
+    want = vr.raycast(vol, gd, cam, P).cpu().numpy()
+    assert np.array_equal(got, want), np.abs(got - want).max()

@@ -43,6 +43,10 @@ class RenderParams(C.Structure):
                 ("no_early_exit", C.c_int32), ("skip_cell", C.c_int32), ("skip_grid_dev", C.c_void_p)]
 
 
+class PoolEntry(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("shift", C.c_uint8 * 3), ("pad", C.c_uint8 * 5)]
+
+
 # every symbol include/vrhip.h declares, with its signature
 _P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -70,6 +74,11 @@ SIGNATURES = {
     "vr_brickset_decode_lod": (_I32, [_P, C.POINTER(_I32), _P, _P]),
     "vr_lod_select": (_I32, [C.POINTER(Camera), C.POINTER(RenderParams), _I32, C.POINTER(_I64), C.POINTER(_I64),
                              C.POINTER(_I64), _I32, _I32, C.c_float, C.POINTER(_I32)]),
+    "vr_lod_pool_layout": (_I32, [C.POINTER(_I64), _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), _I32, _I32,
+                                  _P, C.POINTER(_I64)]),
+    "vr_brickset_decode_lod_pool": (_I32, [_P, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I64), _P, _I64, _P, _P]),
+    "vr_raycast_pool": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
+    "vr_skip_grid_build_pool": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), _I32, _P, _P]),
     "vr_brickset_set_tree": (_I32, [_P, _I32, _P, _I64, _I64, _P, _I32]),
     "vr_brickset_save": (_I32, [_P, _I32, C.c_char_p]),
     "vr_brickset_open": (_I32, [C.POINTER(_P), C.c_char_p]),

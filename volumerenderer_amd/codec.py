@@ -143,6 +143,37 @@ class BrickSet:
                                              _stream_ptr(stream)), "vr_brickset_decode_lod")
         return out
 
+    def decode_lod_pool(self, cuts, brick_ijk, grid, pool=None, table=None, stream=None):
+        """decode_lod into a pool that stores each brick at the resolution of its cut (vr_brickset_decode_lod_pool;
+        layout: render.lod_pool_layout).  pool: a CUDA uint8 tensor of at least the layout's bytes (None: allocated);
+        table: a CUDA uint8 tensor of 16 bytes per grid cell that receives the layout (None: allocated).  Power-of-two
+        brick extents only.  Returns (pool, table)."""
+        from .render import POOL_ENTRY, _check_buf, lod_pool_layout
+        c = np.ascontiguousarray(np.asarray(cuts).reshape(-1), dtype=np.int32)
+        if c.size != self.num_bricks:
+            raise ValueError("decode_lod_pool: %d cuts for %d bricks" % (c.size, self.num_bricks))
+        ijk = np.ascontiguousarray(brick_ijk, np.int64).reshape(-1, 3)
+        if ijk.shape[0] != self.num_bricks:
+            raise ValueError("decode_lod_pool: %d brick cells for %d bricks" % (ijk.shape[0], self.num_bricks))
+        g = (C.c_int64 * 3)(*[int(q) for q in grid])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if pool is None or table is None:
+            info = self.info(0)
+            _, need = lod_pool_layout(self.dims, ijk, grid, c, info["orig_tree_depth"], info["max_tree_depth"])
+            if pool is None:
+                pool = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            if table is None:
+                table = torch.empty(g[0] * g[1] * g[2] * POOL_ENTRY.itemsize, dtype=torch.uint8, device=dev)
+        if not isinstance(pool, torch.Tensor) or pool.numel() == 0:
+            raise ValueError("pool must be a non-empty torch tensor")
+        _check_buf(pool, "pool", torch.uint8, pool.numel(), pool.device)
+        _check_buf(table, "table", torch.uint8, g[0] * g[1] * g[2] * POOL_ENTRY.itemsize, pool.device)
+        check(self._L.vr_brickset_decode_lod_pool(self._h, c.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  ijk.ctypes.data_as(C.POINTER(C.c_int64)), g, C.c_void_p(pool.data_ptr()),
+                                                  pool.numel(), C.c_void_p(table.data_ptr()), _stream_ptr(stream)),
+              "vr_brickset_decode_lod_pool")
+        return pool, table
+
     def decode_range(self, out=None, cut_depth=-1, stream=None):
         """MidRangeTree sets: the half-range stream decoded like the mid stream (vr_brickset_decode_range)."""
         if out is None:

@@ -1,6 +1,7 @@
 // brickset.h -- host-side state behind the opaque vr_brickset handle.
 #pragma once
 #include "kd_common.h"
+#include "../../include/vrhip.h"
 #include <string>
 #include <vector>
 
@@ -37,6 +38,10 @@ struct LodSlot {
     uint8_t *idxValCut = nullptr;  // B * nIdx: cut values of the bricks cut above depth Ds (first needed: allocated)
     uint32_t *decTables = nullptr; // B * FD_TABLE_WORDS: k_decode_fine's tables at each brick's cut (first needed)
     uint8_t *rankVals = nullptr;   // B * 2^D * 2: general-extent decode scratch (first needed)
+    int64_t *obDev = nullptr;      // 3B, pool decodes only: each list entry's output offset (B), then the pack
+    int64_t *obHost = nullptr;     //   descriptors of the coarse bricks (2 per brick); 3B pinned: the same, staged
+    vr_pool_entry *tabHost = nullptr;  // pool decodes with a table: its pinned host image (tabCap entries)
+    int64_t tabCap = 0;
     hipEvent_t done = nullptr;     // recorded after the call's last launch
     bool pending = false;
 };
@@ -127,6 +132,22 @@ struct BrickSet {
     void *lastStream = nullptr;
     LodSlot lodSlot[VR_LOD_SLOTS];
     int lodNext = 0;
+    // vr_brickset_decode_lod_pool: VR_POOL_STAGE_BRICKS decoded coarse bricks (first needed), shared by the calls of
+    // every stream; stageDone is recorded after a call's last read of it and waited for by the next call's stream
+    uint8_t *poolStage = nullptr;
+    hipEvent_t stageDone = nullptr;
+    bool stagePending = false;
+};
+
+// vr_brickset_decode_lod_pool's destinations (vr_lod_pool_layout, computed by the caller): brick b with cut >= 0 goes
+// to pool + off[b], shift[3b .. 3b+2] as in vr_pool_entry; the table (if tabDev) is uploaded from tab
+struct PoolDest {
+    uint8_t *pool = nullptr;
+    const int64_t *off = nullptr;
+    const uint8_t *shift = nullptr;
+    const vr_pool_entry *tab = nullptr;
+    vr_pool_entry *tabDev = nullptr;
+    int64_t cells = 0;
 };
 
 // Every D >= 12 brick is built by k_prune_emit12; with a level loop that runs, such a build keeps nothing of the leaf
@@ -139,7 +160,7 @@ int compact_launch(BrickSet *bs, hipStream_t st);   // fused builds: contiguous 
 // kd_decode.hip
 int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false);
 // per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
-int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st);
+int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st, const PoolDest *pool = nullptr);
 void free_lod_slots(BrickSet *bs);
 int cut_values_from_stream(BrickSet *bs, const uint8_t *treeHost, int64_t numActive, const uint8_t *dmapHost, int cut,
                            std::vector<uint8_t> &vals);

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -19,6 +20,10 @@ namespace vr {
 int raycast_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, float *, hipStream_t);
 int composite_over_launch(float *, const float *, int64_t, hipStream_t);
 int skip_grid_launch(const uint8_t *, const int64_t dims[3], int, uint8_t *, hipStream_t);
+int raycast_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
+                        const vr_render_params *, float *, hipStream_t);
+int skip_grid_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], int, uint8_t *,
+                          hipStream_t);
 int composite_finish_launch(const float *, float *, int64_t, hipStream_t);
 int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
 int assemble_launch(bool, const uint8_t *, uint8_t *, int, const int64_t bd[3], const int64_t *, const int64_t grid[3], hipStream_t);
@@ -594,6 +599,120 @@ vr_status vr_brickset_decode_lod(vr_brickset *h, const int32_t *cuts, uint8_t *o
     return VR_OK;
 }
 
+// vr_lod_pool_layout's rule (vrhip.h).  off / shift: per brick (shift 3 bytes each); table: per grid cell, may be null.
+static vr_status pool_layout(const int64_t bd[3], int32_t nb, const int64_t *ijk, const int64_t grid[3], const int32_t *cuts,
+                             int32_t origDepth, int32_t maxDepth, int64_t *off, uint8_t *shift, vr_pool_entry *table,
+                             int64_t *total)
+{
+    if (!bd || !ijk || !grid || !cuts || !total || nb <= 0) return VR_ERR_INVALID;
+    int lg[3];
+    for (int k = 0; k < 3; ++k) {
+        if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || bd[k] >= (1ll << 31) || grid[k] <= 0) return VR_ERR_INVALID;
+        lg[k] = 0;
+        while (((int64_t)1 << lg[k]) < bd[k]) ++lg[k];
+    }
+    if (origDepth != lg[0] + lg[1] + lg[2] || maxDepth < origDepth) return VR_ERR_INVALID;
+    const int64_t cells = grid[0] * grid[1] * grid[2];
+    std::vector<int32_t> at;
+    if (table) at.assign((size_t)cells, -1);
+    // splits[c][k]: splits on axis k among depths 0 .. c-1 (the split-axis rule of buildRecursive)
+    std::vector<std::array<int, 3>> splits((size_t)origDepth + 1);
+    {
+        int64_t ext[3] = {bd[0], bd[1], bd[2]};
+        std::array<int, 3> n = {0, 0, 0};
+        splits[0] = n;
+        for (int d = 0; d < origDepth; ++d) {
+            int sd = d % 3, i = 0;
+            while (ext[0] * ext[1] * ext[2] > 1 && ext[sd] == 1) sd = (d + ++i) % 3;
+            ext[sd] /= 2;
+            ++n[(size_t)sd];
+            splits[(size_t)d + 1] = n;
+        }
+    }
+    int64_t run = 0;
+    for (int32_t b = 0; b < nb; ++b) {
+        const int64_t *q = ijk + 3 * (int64_t)b;
+        for (int k = 0; k < 3; ++k) if (q[k] < 0 || q[k] >= grid[k]) return VR_ERR_INVALID;
+        const int c = cuts[b];
+        if (c < -1 || c > maxDepth) return VR_ERR_INVALID;
+        const int64_t cell = q[0] + grid[0] * (q[1] + grid[1] * q[2]);
+        if (table) {
+            if (at[(size_t)cell] >= 0) return VR_ERR_INVALID;
+            at[(size_t)cell] = b;
+        }
+        uint8_t sh[3] = {0, 0, 0};
+        if (c >= 0 && c < origDepth)
+            for (int k = 0; k < 3; ++k) sh[k] = (uint8_t)(lg[k] - splits[(size_t)c][(size_t)k]);
+        if (shift) for (int k = 0; k < 3; ++k) shift[3 * b + k] = sh[k];
+        int64_t o = -1;
+        if (c >= 0) {
+            o = (run + 255) & ~(int64_t)255;
+            run = o + ((bd[0] >> sh[0]) * (bd[1] >> sh[1]) * (bd[2] >> sh[2]));
+        }
+        if (off) off[b] = o;
+    }
+    if (table) {
+        for (int64_t cell = 0; cell < cells; ++cell) { table[cell] = vr_pool_entry(); table[cell].offset = -1; }
+        for (int64_t cell = 0; cell < cells; ++cell) {
+            const int32_t b = at[(size_t)cell];
+            if (b < 0 || cuts[b] < 0) continue;
+            table[cell].offset = off[b];
+            for (int k = 0; k < 3; ++k) table[cell].shift[k] = shift[3 * b + k];
+        }
+    } else {
+        // two bricks on one cell: sort the cells
+        std::vector<int64_t> cs((size_t)nb);
+        for (int32_t b = 0; b < nb; ++b) cs[(size_t)b] = ijk[3 * b] + grid[0] * (ijk[3 * b + 1] + grid[1] * ijk[3 * b + 2]);
+        std::sort(cs.begin(), cs.end());
+        if (std::adjacent_find(cs.begin(), cs.end()) != cs.end()) return VR_ERR_INVALID;
+    }
+    *total = run;
+    return VR_OK;
+}
+
+vr_status vr_lod_pool_layout(const int64_t brick_dims[3], int32_t num_bricks, const int64_t *brick_ijk, const int64_t grid[3],
+                             const int32_t *cuts, int32_t orig_tree_depth, int32_t max_tree_depth, vr_pool_entry *table_out,
+                             int64_t *pool_bytes)
+{
+    if (!brick_dims || !brick_ijk || !grid || !cuts || !pool_bytes || num_bricks <= 0) return VR_ERR_INVALID;
+    std::vector<int64_t> off((size_t)num_bricks);
+    std::vector<uint8_t> sh((size_t)num_bricks * 3);
+    return pool_layout(brick_dims, num_bricks, brick_ijk, grid, cuts, orig_tree_depth, max_tree_depth, off.data(), sh.data(),
+                       table_out, pool_bytes);
+}
+
+vr_status vr_brickset_decode_lod_pool(vr_brickset *h, const int32_t *cuts, const int64_t *ijk, const int64_t grid[3],
+                                      uint8_t *pool, int64_t pool_bytes, vr_pool_entry *table_dev, void *stream)
+{
+    if (!h || !cuts || !ijk || !grid || !pool) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    if (!b.built) return VR_ERR_STATE;
+    const int64_t bd[3] = {b.g.X, b.g.Y, b.g.Z};
+    for (int k = 0; k < 3; ++k) if ((bd[k] & (bd[k] - 1)) != 0) return VR_ERR_UNSUPPORTED;
+    for (int k = 0; k < 3; ++k) if (grid[k] <= 0) return VR_ERR_INVALID;
+    const int64_t cells = grid[0] * grid[1] * grid[2];
+    std::vector<int64_t> off((size_t)b.B);
+    std::vector<uint8_t> sh((size_t)b.B * 3);
+    std::vector<vr_pool_entry> tab((size_t)cells);
+    int64_t total = 0;
+    vr_status st = pool_layout(bd, b.B, ijk, grid, cuts, b.D, b.maxDepth, off.data(), sh.data(), tab.data(), &total);
+    if (st != VR_OK) return st;
+    if (pool_bytes < total) return VR_ERR_INVALID;
+    bool above = false;
+    for (int br = 0; br < b.B; ++br) above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
+    if (above && b.foreign) {
+        vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
+        if (rc != VR_OK) return rc;
+    }
+    PoolDest d;
+    d.pool = pool; d.off = off.data(); d.shift = sh.data(); d.tab = tab.data(); d.tabDev = table_dev; d.cells = cells;
+    const int rc = decode_lod_launch(&b, cuts, nullptr, (hipStream_t)stream, &d);
+    if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
+    b.decodeTimingPending = true;
+    b.lastStream = stream;
+    return VR_OK;
+}
+
 // The frame of vr_raycast (raymarch.hip raycast_launch): glm::lookAt basis and glm::perspectiveFov half-angle tangents,
 // the same float operations.  Every ray of the frame is dir = f + nx tanX s + ny tanY u, |nx|, |ny| < 1; its ray
 // parameter is the view depth d . f (d = point - pos), and its march starts at depth >= z_near.
@@ -984,6 +1103,39 @@ vr_status vr_skip_grid_build(const uint8_t *vol, const int64_t dims[3], int32_t 
     for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return skip_grid_launch(vol, dims, cell, grid, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// the virtual volume of a pool: power-of-two bricks, extents below 2^31 (tex3d's int indices)
+static bool pool_dims_ok(const int64_t bd[3], const int64_t grid[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || grid[k] <= 0) return false;
+        if (grid[k] >= (1ll << 31) / bd[k]) return false;
+    }
+    return true;
+}
+
+vr_status vr_raycast_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                          const vr_camera *cam, const vr_render_params *P, float *rgba, void *stream)
+{
+    if (!pool || !table || !bd || !grid || !cam || !P || !rgba) return VR_ERR_INVALID;
+    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
+    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) {
+        if (P->vol_origin[k] != 0) return VR_ERR_INVALID;
+        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return VR_ERR_INVALID;
+    }
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_pool_launch(pool, table, bd, grid, cam, P, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_skip_grid_build_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                                  int32_t cell, uint8_t *out, void *stream)
+{
+    if (!pool || !table || !bd || !grid || !out || cell <= 0 || cell > 64) return VR_ERR_INVALID;
+    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return skip_grid_pool_launch(pool, table, bd, grid, cell, out, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }
 
 vr_status vr_composite_over(float *front, const float *back, int64_t n, void *stream)

@@ -136,18 +136,27 @@ __device__ __forceinline__ int lod_cut(const int32_t *cuts, int brick, int cut)
 {
     return cuts ? __builtin_amdgcn_readfirstlane(cuts[brick]) : cut;
 }
+// Byte offset in `out` of the voxels grid row `row` writes (brick `brick`): obase[row] where the caller places the rows
+// itself (vr_brickset_decode_lod_pool: pool slots and staging), else brick * voxels.  Workgroup-uniform: one scalar load.
+__device__ __forceinline__ int64_t lod_obase(const int64_t *obase, unsigned row, int brick, int64_t voxels)
+{
+    return obase ? (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)obase[row]) |
+                             ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)obase[row] >> 32)) << 32))
+                 : (int64_t)brick * voxels;
+}
 
 // out[voxel] = value of the leaf rank that owns it, if the box its terminal node writes still holds the voxel
 // (rankVals: value | branch nodes below the leaf << 8; 0 branch nodes = the leaf or an ancestor is pruned: whole box)
 __global__ void __launch_bounds__(256)
 k_owner_gather(const uint16_t *__restrict__ rankVals, int64_t leafStride, const uint32_t *__restrict__ owner,
-               const uint8_t *__restrict__ surv, int64_t voxels, uint8_t *__restrict__ out, const int32_t *list)
+               const uint8_t *__restrict__ surv, int64_t voxels, uint8_t *__restrict__ out, const int32_t *list,
+               const int64_t *obase)
 {
     const int brick = lod_brick(list, blockIdx.y);
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= voxels) return;
     const uint32_t e = rankVals[(int64_t)brick * leafStride + owner[v]];
-    out[(int64_t)brick * voxels + v] = (e >> 8) <= (uint32_t)surv[v] ? (uint8_t)e : (uint8_t)0;
+    out[lod_obase(obase, blockIdx.y, brick, voxels) + v] = (e >> 8) <= (uint32_t)surv[v] ? (uint8_t)e : (uint8_t)0;
 }
 
 // local rank inside a depth-(D-K) subtree -> packed voxel offset (dx | dy<<10 | dz<<20)
@@ -181,6 +190,7 @@ struct DecodeArgs {
     int cut;                    // progressive cut depth (maxTreeDepth = the reference's levelCut)
     const uint8_t *idxValCut;   // cut < Ds: scalar of every subtree's ancestor at depth `cut`
     const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
+    const int64_t *obase;       // per-row output offsets (lod_obase); null: brick * voxels
 };
 
 // v1: one lane per subtree, direct byte stores.  RANK_OUT: the value of every leaf RANK goes to a.out (B * 2^D bytes,
@@ -201,7 +211,7 @@ k_decode_lane(DecodeArgs a)
     int ox = 0, oy = 0, oz = 0;
     if (!RANK_OUT) rank_to_xyz(a.g, (uint32_t)(s << a.K), ox, oy, oz);
     uint8_t *O = RANK_OUT ? a.out + 2 * ((int64_t)brick * ((int64_t)1 << a.D) + (s << a.K))
-                          : a.out + (int64_t)brick * a.g.voxels + ox + (int64_t)a.g.X * (oy + (int64_t)a.g.Y * oz);
+                          : a.out + lod_obase(a.obase, blockIdx.y, brick, a.g.voxels) + ox + (int64_t)a.g.X * (oy + (int64_t)a.g.Y * oz);
     const int64_t sy = a.g.X, sz = (int64_t)a.g.X * a.g.Y;
     const int K = a.K;
     int branchNodes = 0;      // RANK_OUT: nodes of the grown branch below the leaf being written (0: pruned at or above it)
@@ -285,6 +295,7 @@ struct TileArgs {
     const uint8_t *val3;        // BrickSet::idxVal3 (k_decode_quad only)
     uint8_t kqBit[8];           // k_decode_quad: bit i of a workgroup's ticket number = this bit of the tile's number
     const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
+    const int64_t *obase;       // per-row output offsets (lod_obase); null: brick * voxels
 };
 
 #define DEC_WAVES 4
@@ -347,7 +358,7 @@ __device__ __forceinline__ void tile_gather(const TileArgs &a, const uint32_t *t
 {
     const int jx = a.jx, jy = a.jy, jz = a.jz;
     const int c = lane & 7;
-    uint8_t *O = a.out + (int64_t)brick * a.g.voxels + (int64_t)tx * 128 + c * 16;
+    uint8_t *O = a.out + lod_obase(a.obase, blockIdx.y, brick, a.g.voxels) + (int64_t)tx * 128 + c * 16;
     const auto tile_at = [stride](int rank) { return (rank >> 2) * (4 * stride) + (rank & 3); };   // byte of a leaf within a column
     const int r1 = live * tile_at(1 << jx), r2 = live * tile_at(8 << jx);             // steps of dx bit 0 / bit 1
 #pragma unroll
@@ -386,7 +397,7 @@ __device__ __forceinline__ void tile_gather_wide(const TileArgs &a, const uint32
 {
     const int jx = a.jx, jy = a.jy, jz = a.jz;
     const int c = lane & 7, y = lane >> 3, dy = y & 3;
-    uint8_t *O = a.out + (int64_t)brick * a.g.voxels + (int64_t)tx * 128 + c * 16 +
+    uint8_t *O = a.out + lod_obase(a.obase, blockIdx.y, brick, a.g.voxels) + (int64_t)tx * 128 + c * 16 +
                  (int64_t)a.g.X * ((int64_t)ty * 8 + y + (int64_t)a.g.Y * ((int64_t)tz * 4));
     const int64_t zs = (int64_t)a.g.X * a.g.Y;
     const uint32_t rby = ((uint32_t)(dy & 1) << jy) | ((uint32_t)(dy >> 1) << (3 + jy));
@@ -423,7 +434,7 @@ __device__ __forceinline__ void tile_gather_wide(const TileArgs &a, const uint32
 __device__ __forceinline__ void tile_fill_dead(const TileArgs &a, const uint32_t *tile, int brick, int tx, int ty, int tz, int lane)
 {
     const int c = lane & 7, y = lane >> 3;
-    uint8_t *O = a.out + (int64_t)brick * a.g.voxels + (int64_t)tx * 128 + c * 16 +
+    uint8_t *O = a.out + lod_obase(a.obase, blockIdx.y, brick, a.g.voxels) + (int64_t)tx * 128 + c * 16 +
                  (int64_t)a.g.X * ((int64_t)ty * 8 + y + (int64_t)a.g.Y * ((int64_t)tz * 4));
     const int64_t zs = (int64_t)a.g.X * a.g.Y;
     const uint4 v = *(const uint4 *)(tile + 4 * c + 32 * (y >> 2));
@@ -1225,6 +1236,7 @@ struct RegionArgs {
     uint32_t blkX, blkY, blkZ;  // 6 x 5 bits each: bit k of x >> 4 (y >> 4, z >> 4) is this bit of the emit block's number (= leaf rank >> 12)
     int nreg;                   // regions of a brick
     const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
+    const int64_t *obase;       // per-row output offsets (lod_obase); null: brick * voxels
 };
 
 __device__ __forceinline__ uint32_t wave_incl_scan_max_dpp(uint32_t v)
@@ -1580,7 +1592,7 @@ k_decode_region(RegionArgs a)
         }
         // ---- where this region's voxels go
         const uint32_t rxC = (uint32_t)rid & ((1u << a.lrx) - 1u), ryC = ((uint32_t)rid >> a.lrx) & ((1u << a.lry) - 1u), rzC = (uint32_t)rid >> (a.lrx + a.lry);
-        uint8_t *O = a.out + (int64_t)brick * a.voxels + ((int64_t)rzC * 16 * a.Y + (int64_t)ryC * 16) * a.X + (int64_t)rxC * RG_REGX + (lane & (RG_WAVES - 1)) * 16;
+        uint8_t *O = a.out + lod_obase(a.obase, blockIdx.y, brick, a.voxels) + ((int64_t)rzC * 16 * a.Y + (int64_t)ryC * 16) * a.X + (int64_t)rxC * RG_REGX + (lane & (RG_WAVES - 1)) * 16;
         // ---- the pipeline: the next region staged (the ring is free now; a stale piece of this region still in flight
         // lands before the next region's piece for the same slot: loads return in issue order)
         slot = slot + 1 == RG_IDXD ? 0 : slot + 1;
@@ -1851,6 +1863,7 @@ struct LodClass {
     uint8_t *idxValCut = nullptr;
     uint32_t *decTables = nullptr;
     uint8_t *rankVals = nullptr;
+    const int64_t *obase = nullptr; // device: each row's output offset (pool decode); null: brick * voxels
 };
 
 // One launch of kernel k.  lod: one class of a per-brick decode (decode_lod_launch): grid rows = the class's bricks,
@@ -1862,6 +1875,7 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
     if (!lod) hipEventRecord(bs->ev[5], st);
     const unsigned rows = lod ? (unsigned)lod->n : (unsigned)bs->B;
     const int32_t *list = lod ? lod->list : nullptr, *cuts = lod ? lod->cuts : nullptr;
+    const int64_t *obase = lod ? lod->obase : nullptr;
     // MidRangeTree's second stream is emitted in lock step with the first (M.cpp:871-982): same token positions,
     // so the same side-car offsets serve it; only the scalars (its own codes, its own distanceMap) differ
     const Stream2 &sm = rangeStream ? bs->rng : bs->mid;
@@ -1883,7 +1897,7 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
         t.idxOff = bs->idxOff; t.idxVal = idxVals; t.nIdx = bs->nIdx;
         t.ctrls = sm.ctrl; t.out = out; t.g = bs->g; t.D = bs->D; t.Ds = bs->Ds;
         t.cut = cut; t.idxValCut = cutVals; t.spread = bs->spread;
-        t.list = list; t.cuts = cuts;
+        t.list = list; t.cuts = cuts; t.obase = obase;
         t.fine = bs->fineIdx;
         t.val3 = bs->idxVal3;
         return t;
@@ -1899,10 +1913,10 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
         a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
         a.ctrls = sm.ctrl; a.lut = nullptr; a.out = rankVals; a.g = bs->g;
         a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
-        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts;
+        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts; a.obase = nullptr;
         hipLaunchKernelGGL(k_decode_lane<true>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_owner_gather, dim3((unsigned)((bs->g.voxels + 255) / 256), rows), dim3(256), 0, st,
-                           (const uint16_t *)rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list);
+                           (const uint16_t *)rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list, obase);
         break;
     }
     case DecodeKernel::REGION: {
@@ -1910,7 +1924,7 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
         r.tree = sm.tree; r.treeCap = bs->treeCap;
         r.idxOff = bs->idxOff; r.idxVal = idxVals; r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.nIdx = bs->nIdx;
         r.ctrls = sm.ctrl; r.out = out; r.spread = bs->spread; r.D = bs->D; r.cut = cut;
-        r.list = list; r.cuts = cuts;
+        r.list = list; r.cuts = cuts; r.obase = obase;
         // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
         // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
         unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);
@@ -1961,7 +1975,7 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
         a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
         a.ctrls = sm.ctrl; a.lut = bs->lut; a.out = out; a.g = bs->g;
         a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
-        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts;
+        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts; a.obase = obase;
         hipLaunchKernelGGL(k_decode_lane<false>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
         break;
     }
@@ -1980,13 +1994,56 @@ void free_lod_slots(BrickSet *bs)
 {
     for (LodSlot &s : bs->lodSlot) {
         if (s.done) { if (s.pending) hipEventSynchronize(s.done); hipEventDestroy(s.done); }
-        hipFree(s.dev); hipFree(s.idxValCut); hipFree(s.decTables); hipFree(s.rankVals);
+        hipFree(s.dev); hipFree(s.idxValCut); hipFree(s.decTables); hipFree(s.rankVals); hipFree(s.obDev);
         if (s.host) hipHostFree(s.host);
+        if (s.obHost) hipHostFree(s.obHost);
+        if (s.tabHost) hipHostFree(s.tabHost);
         s = LodSlot();
+    }
+    if (bs->stageDone) { hipEventSynchronize(bs->stageDone); hipEventDestroy(bs->stageDone); bs->stageDone = nullptr; }
+    hipFree(bs->poolStage);
+    bs->poolStage = nullptr;
+    bs->stagePending = false;
+}
+
+// vr_brickset_decode_lod_pool: staged brick `row` (decoded at full size, X x Y x Z, powers of two) -> its pool slot,
+// one byte per box of 2^sx x 2^sy x 2^sz voxels, the box's min-corner voxel.  desc[2 row] = the slot's byte offset,
+// desc[2 row + 1] = sx | sy << 8 | sz << 16.  A lane writes four consecutive stored voxels of a row (one 32-bit store;
+// slots start 256-byte aligned, stored rows are X >> sx >= 4 bytes) or, for narrower rows, one; it reads only the
+// staged rows and columns it keeps.
+__global__ void __launch_bounds__(256)
+k_pool_pack(const uint8_t *__restrict__ stage, int64_t voxels, int lx, int ly, const int64_t *__restrict__ desc,
+            uint8_t *__restrict__ pool)
+{
+    const int row = blockIdx.y;
+    const int64_t off = desc[2 * row];
+    const uint32_t sh = (uint32_t)desc[2 * row + 1];
+    const int sx = sh & 255u, sy = (sh >> 8) & 255u, sz = (sh >> 16) & 255u;
+    const int rlx = lx - sx, rly = ly - sy;                 // log2 of the stored row / column lengths
+    const int64_t n = voxels >> (sx + sy + sz);
+    const uint8_t *src = stage + (int64_t)row * voxels;
+    uint8_t *dst = pool + off;
+    const int64_t X = (int64_t)1 << lx, XY = (int64_t)1 << (lx + ly);
+    if (rlx >= 2) {
+        for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; 4 * q < n; q += (int64_t)gridDim.x * 256) {
+            const int64_t i = 4 * q;
+            const int64_t x = i & (((int64_t)1 << rlx) - 1), y = (i >> rlx) & (((int64_t)1 << rly) - 1), z = i >> (rlx + rly);
+            const uint8_t *r = src + (x << sx) + X * (y << sy) + XY * (z << sz);
+            const uint32_t v = (uint32_t)r[0] | ((uint32_t)r[1 << sx] << 8) | ((uint32_t)r[2 << sx] << 16) | ((uint32_t)r[3 << sx] << 24);
+            *(uint32_t *)(dst + i) = v;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+            const int64_t x = i & (((int64_t)1 << rlx) - 1), y = (i >> rlx) & (((int64_t)1 << rly) - 1), z = i >> (rlx + rly);
+            dst[i] = src[(x << sx) + X * (y << sy) + XY * (z << sz)];
+        }
     }
 }
 
-int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipStream_t st)
+// pool: vr_brickset_decode_lod_pool.  The bricks then go in passes: the full-resolution ones straight to their pool
+// slots, the coarse ones VR_POOL_STAGE_BRICKS at a time (index order) to the set's staging buffer, each such pass
+// followed by k_pool_pack.  All passes of a call share its slot: its lists hold every brick at most once.
+int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipStream_t st, const PoolDest *pool)
 {
     const int B = bs->B;
     LodSlot &s = bs->lodSlot[bs->lodNext];
@@ -1996,31 +2053,70 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
     if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return -1;
     if (!s.dev && hipMalloc(&s.dev, (size_t)3 * B * sizeof(int32_t)) != hipSuccess) return -3;
     if (!s.host && hipHostMalloc(&s.host, (size_t)3 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return -3;
+    if (pool) {
+        if (!s.obDev && hipMalloc(&s.obDev, (size_t)3 * B * sizeof(int64_t)) != hipSuccess) return -3;
+        if (!s.obHost && hipHostMalloc(&s.obHost, (size_t)3 * B * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) return -3;
+        if (pool->tabDev && s.tabCap < pool->cells) {
+            if (s.tabHost) hipHostFree(s.tabHost);
+            s.tabHost = nullptr; s.tabCap = 0;
+            if (hipHostMalloc(&s.tabHost, (size_t)pool->cells * sizeof(vr_pool_entry), hipHostMallocDefault) != hipSuccess) return -3;
+            s.tabCap = pool->cells;
+        }
+    }
     bs->lodNext = (bs->lodNext + 1) % VR_LOD_SLOTS;
-    // host image: cuts [0, B), bricks cut above Ds, then the classes' lists
+    // host image: cuts [0, B), bricks cut above Ds, then the passes' classes' lists
     int32_t *H = s.host;
     const DecodePlan plan(bs, false);
-    int nAbove = 0, nCls[DECODE_KERNELS] = {}, cutOf[DECODE_KERNELS] = {};
-    std::vector<int> cls((size_t)B, -1);
+    int nAbove = 0;
     for (int b = 0; b < B; ++b) {
         H[b] = cutsHost[b];
+        if (cutsHost[b] >= 0 && cutsHost[b] < bs->Ds) H[B + nAbove++] = b;
+    }
+    // the passes: [0] full resolution (every decoded brick without a pool), then the staged batches
+    const auto coarse = [&](int b) { return pool && (pool->shift[3 * b] | pool->shift[3 * b + 1] | pool->shift[3 * b + 2]) != 0; };
+    std::vector<std::vector<int>> passes(1);
+    for (int b = 0; b < B; ++b) {
         if (cutsHost[b] < 0) continue;
-        if (cutsHost[b] < bs->Ds) H[B + nAbove++] = b;
-        cls[(size_t)b] = (int)plan.kernel(cutsHost[b]);
-        ++nCls[cls[(size_t)b]];
-        cutOf[cls[(size_t)b]] = cutsHost[b];
+        if (!coarse(b)) { passes[0].push_back(b); continue; }
+        if (passes.size() == 1 || passes.back().size() == VR_POOL_STAGE_BRICKS) passes.emplace_back();
+        passes.back().push_back(b);
     }
-    int first[DECODE_KERNELS], at = B + nAbove;
-    for (int c = 0; c < DECODE_KERNELS; ++c) { first[c] = at; at += nCls[c]; }
-    {
-        int fill[DECODE_KERNELS];
-        for (int c = 0; c < DECODE_KERNELS; ++c) fill[c] = first[c];
-        for (int b = 0; b < B; ++b) if (cls[(size_t)b] >= 0) H[fill[cls[(size_t)b]]++] = b;
+    struct Launch { int pass, cls, first, n, cut; };
+    std::vector<Launch> launches;
+    int at = B + nAbove;
+    for (int p = 0; p < (int)passes.size(); ++p) {
+        int nCls[DECODE_KERNELS] = {}, cutOf[DECODE_KERNELS] = {};
+        for (int b : passes[(size_t)p]) { const int c = (int)plan.kernel(cutsHost[b]); ++nCls[c]; cutOf[c] = cutsHost[b]; }
+        for (int c = 0; c < DECODE_KERNELS; ++c) {
+            if (!nCls[c]) continue;
+            launches.push_back({p, c, at, nCls[c], cutOf[c]});
+            for (int i = 0; i < (int)passes[(size_t)p].size(); ++i) {
+                const int b = passes[(size_t)p][(size_t)i];
+                if ((int)plan.kernel(cutsHost[b]) != c) continue;
+                if (pool) s.obHost[at - B - nAbove] = p == 0 ? pool->off[b] : (int64_t)i * bs->g.voxels;
+                H[at++] = b;
+            }
+        }
     }
-    if (at == B) return 0;              // every brick skipped: nothing to launch
+    const int nRows = at - B - nAbove;
+    int nDesc = 0;                      // pack descriptors, batch by batch
+    for (int p = 1; p < (int)passes.size(); ++p)
+        for (int b : passes[(size_t)p]) {
+            s.obHost[B + 2 * nDesc] = pool->off[b];
+            s.obHost[B + 2 * nDesc + 1] = pool->shift[3 * b] | (pool->shift[3 * b + 1] << 8) | (pool->shift[3 * b + 2] << 16);
+            ++nDesc;
+        }
+    const bool table = pool && pool->tabDev;
+    if (at == B && !table) return 0;    // every brick skipped: nothing to launch
+    int nc[DECODE_KERNELS] = {};
+    for (const Launch &l : launches) nc[l.cls] += l.n;
     if (nAbove && !s.idxValCut && hipMalloc(&s.idxValCut, (size_t)B * bs->nIdx) != hipSuccess) return -3;
-    if ((nCls[(int)DecodeKernel::REGION] || nCls[(int)DecodeKernel::QUAD] || nCls[(int)DecodeKernel::FINE]) && !s.decTables && hipMalloc(&s.decTables, (size_t)B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
-    if (nCls[(int)DecodeKernel::GENERAL] && !s.rankVals && hipMalloc(&s.rankVals, (size_t)B * bs->leafStride * 2) != hipSuccess) return -3;
+    if ((nc[(int)DecodeKernel::REGION] || nc[(int)DecodeKernel::QUAD] || nc[(int)DecodeKernel::FINE]) && !s.decTables && hipMalloc(&s.decTables, (size_t)B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
+    if (nc[(int)DecodeKernel::GENERAL] && !s.rankVals && hipMalloc(&s.rankVals, (size_t)B * bs->leafStride * 2) != hipSuccess) return -3;
+    if (passes.size() > 1) {
+        if (!bs->poolStage && hipMalloc(&bs->poolStage, (size_t)VR_POOL_STAGE_BRICKS * bs->g.voxels) != hipSuccess) return -3;
+        if (!bs->stageDone && hipEventCreateWithFlags(&bs->stageDone, hipEventDisableTiming) != hipSuccess) return -1;
+    }
     if (nAbove && bs->foreign) {
         // ancestor scalars at each brick's cut, from the stream bytes kept at set_tree/open time (as vr_brickset_decode)
         std::vector<uint8_t> vals;
@@ -2035,18 +2131,37 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
         }
     }
     hipEventRecord(bs->ev[5], st);
-    if (hipMemcpyAsync(s.dev, H, (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (table) {
+        memcpy(s.tabHost, pool->tab, (size_t)pool->cells * sizeof(vr_pool_entry));
+        if (hipMemcpyAsync(pool->tabDev, s.tabHost, (size_t)pool->cells * sizeof(vr_pool_entry), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    }
+    if (at > B && hipMemcpyAsync(s.dev, H, (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (pool && (nRows || nDesc) &&
+        hipMemcpyAsync(s.obDev, s.obHost, (size_t)(B + 2 * nDesc) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     if (nAbove && !bs->foreign)
         hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), nAbove), dim3(256), 0, st,
                            bs->mid.codes, bs->codeStride, bs->mid.ctrl, bs->Ds, 0, bs->nIdx, s.idxValCut, s.dev + B, s.dev);
-    int rc = 0;
-    for (int c = 0; c < DECODE_KERNELS && rc == 0; ++c) {
-        if (!nCls[c]) continue;
+    int rc = 0, desc = 0;
+    for (size_t li = 0; li < launches.size() && rc == 0; ++li) {
+        const Launch &l = launches[li];
+        if (l.pass == 1 && (li == 0 || launches[li - 1].pass == 0) && bs->stagePending)
+            hipStreamWaitEvent(st, bs->stageDone, 0);     // an earlier call, on any stream, may still pack from staging
         LodClass L;
-        L.list = s.dev + first[c]; L.n = nCls[c]; L.cuts = s.dev;
+        L.list = s.dev + l.first; L.n = l.n; L.cuts = s.dev;
         L.idxValCut = s.idxValCut; L.decTables = s.decTables; L.rankVals = s.rankVals;
-        rc = launch_decode(bs, plan, (DecodeKernel)c, out, cutOf[c], st, false, &L);
+        L.obase = pool ? s.obDev + (l.first - B - nAbove) : nullptr;
+        rc = launch_decode(bs, plan, (DecodeKernel)l.cls, l.pass == 0 ? (pool ? pool->pool : out) : bs->poolStage, l.cut, st,
+                           false, &L);
+        if (rc == 0 && l.pass > 0 && (li + 1 == launches.size() || launches[li + 1].pass != l.pass)) {
+            const int n = (int)passes[(size_t)l.pass].size();
+            const unsigned gx = (unsigned)std::min<int64_t>(1024, (bs->g.voxels / 4 + 255) / 256);
+            hipLaunchKernelGGL(k_pool_pack, dim3(gx, n), dim3(256), 0, st, bs->poolStage, bs->g.voxels, bs->g.nb[0], bs->g.nb[1],
+                               s.obDev + B + 2 * desc, pool->pool);
+            desc += n;
+            rc = launch_status("pool_pack");
+        }
     }
+    if (passes.size() > 1) { hipEventRecord(bs->stageDone, st); bs->stagePending = true; }
     hipEventRecord(bs->ev[6], st);
     hipEventRecord(s.done, st);
     s.pending = true;

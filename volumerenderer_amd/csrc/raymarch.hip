@@ -58,6 +58,81 @@ __device__ __forceinline__ float tex3d(const Tex &t, float px, float py, float p
     return c0 + fz * (c1 - c0);
 }
 
+// ---- the level-of-detail pool (vr_raycast_pool): a virtual volume of grid * brick_dims voxels, brick cell c stored at
+// pool + tab[c].offset with one byte per 2^shift box (vrhip.h).  Brick extents are powers of two.
+struct PoolTex {
+    const uint8_t *pool;
+    const vr_pool_entry *tab;
+    int lx, ly, lz;        // log2 of the brick extents
+    int gx, gy;            // grid cells along x, y
+};
+
+struct PoolCell { int64_t off; int sx, sy, sz; };
+
+// the table entry of brick cell (cx, cy, cz): one 16-byte load
+__device__ __forceinline__ PoolCell pool_cell(const PoolTex &p, int cx, int cy, int cz)
+{
+    const uint4 e = *(const uint4 *)(p.tab + (cx + (int64_t)p.gx * (cy + (int64_t)p.gy * cz)));
+    PoolCell c;
+    c.off = (int64_t)((uint64_t)e.x | ((uint64_t)e.y << 32));
+    c.sx = e.z & 255u; c.sy = (e.z >> 8) & 255u; c.sz = (e.z >> 16) & 255u;
+    return c;
+}
+// byte offset in the pool of the stored voxel that virtual voxel (x, y, z) of cell c reads
+__device__ __forceinline__ int64_t pool_at(const PoolTex &p, const PoolCell &c, int x, int y, int z)
+{
+    const int lx = (x & ((1 << p.lx) - 1)) >> c.sx, ly = (y & ((1 << p.ly) - 1)) >> c.sy, lz = (z & ((1 << p.lz) - 1)) >> c.sz;
+    return c.off + lx + ((int64_t)1 << (p.lx - c.sx)) * (ly + ((int64_t)1 << (p.ly - c.sy)) * lz);
+}
+__device__ __forceinline__ uint32_t pool_voxel(const PoolTex &p, int x, int y, int z)
+{
+    const PoolCell c = pool_cell(p, x >> p.lx, y >> p.ly, z >> p.lz);
+    return c.off < 0 ? 0u : (uint32_t)p.pool[pool_at(p, c, x, y, z)];
+}
+
+// tex3d of the virtual volume (GX, GY, GZ its extents): the same tap indices, weights and interpolation, only the
+// byte fetch differs.  Taps in one brick (the common case): one table load; the two x taps of a row as one 16-bit load
+// where the brick is stored at full x resolution.  Taps across a brick face: a table load per tap.
+__device__ __forceinline__ float tex3d_pool(const PoolTex &t, int GX, int GY, int GZ, float px, float py, float pz)
+{
+    float x = px * (float)GX - 0.5f, y = py * (float)GY - 0.5f, z = pz * (float)GZ - 0.5f;
+    float fx0 = floorf(x), fy0 = floorf(y), fz0 = floorf(z);
+    float fx = x - fx0, fy = y - fy0, fz = z - fz0;
+    int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
+    int xa = clampi(x0, 0, GX - 1), xb = clampi(x0 + 1, 0, GX - 1);
+    int ya = clampi(y0, 0, GY - 1), yb = clampi(y0 + 1, 0, GY - 1);
+    int za = clampi(z0, 0, GZ - 1), zb = clampi(z0 + 1, 0, GZ - 1);
+    const float k = 1.0f / 255.0f;
+    uint32_t q0, q1, q2, q3;
+    const int cx = xa >> t.lx, cy = ya >> t.ly, cz = za >> t.lz;
+    if (cx == (xb >> t.lx) && cy == (yb >> t.ly) && cz == (zb >> t.lz)) {
+        const PoolCell c = pool_cell(t, cx, cy, cz);
+        if (c.off < 0) { q0 = q1 = q2 = q3 = 0u; }
+        else {
+            const int64_t sy = (int64_t)1 << (t.lx - c.sx), sz = sy << (t.ly - c.sy);
+            const int mx = (1 << t.lx) - 1, my = (1 << t.ly) - 1, mz = (1 << t.lz) - 1;
+            const int la = (xa & mx) >> c.sx, lb = (xb & mx) >> c.sx;
+            const int64_t ra = sy * ((ya & my) >> c.sy), rb = sy * ((yb & my) >> c.sy);
+            const int64_t pa = sz * ((za & mz) >> c.sz), pb = sz * ((zb & mz) >> c.sz);
+            const uint8_t *r0 = t.pool + c.off + ra + pa, *r1 = t.pool + c.off + rb + pa;
+            const uint8_t *r2 = t.pool + c.off + ra + pb, *r3 = t.pool + c.off + rb + pb;
+            if (lb == la + 1) { q0 = *(const u16u *)(r0 + la); q1 = *(const u16u *)(r1 + la); q2 = *(const u16u *)(r2 + la); q3 = *(const u16u *)(r3 + la); }
+            else { q0 = r0[la] | (r0[lb] << 8); q1 = r1[la] | (r1[lb] << 8); q2 = r2[la] | (r2[lb] << 8); q3 = r3[la] | (r3[lb] << 8); }
+        }
+    } else {
+        q0 = pool_voxel(t, xa, ya, za) | (pool_voxel(t, xb, ya, za) << 8);
+        q1 = pool_voxel(t, xa, yb, za) | (pool_voxel(t, xb, yb, za) << 8);
+        q2 = pool_voxel(t, xa, ya, zb) | (pool_voxel(t, xb, ya, zb) << 8);
+        q3 = pool_voxel(t, xa, yb, zb) | (pool_voxel(t, xb, yb, zb) << 8);
+    }
+    float c000 = (float)(q0 & 255u) * k, c100 = (float)(q0 >> 8) * k, c010 = (float)(q1 & 255u) * k, c110 = (float)(q1 >> 8) * k;
+    float c001 = (float)(q2 & 255u) * k, c101 = (float)(q2 >> 8) * k, c011 = (float)(q3 & 255u) * k, c111 = (float)(q3 >> 8) * k;
+    float c00 = c000 + fx * (c100 - c000), c10 = c010 + fx * (c110 - c010);
+    float c01 = c001 + fx * (c101 - c001), c11 = c011 + fx * (c111 - c011);
+    float c0 = c00 + fy * (c10 - c00), c1 = c01 + fy * (c11 - c01);
+    return c0 + fz * (c1 - c0);
+}
+
 __device__ __forceinline__ void norm3(float &a, float &b, float &c)
 {
     float l = sqrtf(a * a + b * b + c * c);
@@ -180,8 +255,17 @@ struct RayArgs {
     float *out;
 };
 
+// k_raycast's fetch: the dense volume a.t (vr_raycast) or a pool (vr_raycast_pool) whose virtual extents are a.t's
+struct DenseSampler {};
+__device__ __forceinline__ float sample3d(const DenseSampler &, const RayArgs &a, float x, float y, float z) { return tex3d(a.t, x, y, z); }
+__device__ __forceinline__ float sample3d(const PoolTex &p, const RayArgs &a, float x, float y, float z)
+{
+    return tex3d_pool(p, a.t.GX, a.t.GY, a.t.GZ, x, y, z);
+}
+
+template <class SAMPLER>
 __global__ void __launch_bounds__(64)
-k_raycast(RayArgs a)
+k_raycast(RayArgs a, SAMPLER tex)
 {
     // 8x8 pixel tile per wave
     const int px = blockIdx.x * 8 + (threadIdx.x & 7), py = blockIdx.y * 8 + (threadIdx.x >> 3);
@@ -228,7 +312,7 @@ k_raycast(RayArgs a)
             if (!inside(pos[0], pos[1], pos[2])) break;
             // all eight taps zero: the sample is exactly 0 and the three updates below are exact no-ops
             if (a.sg.g && probe && (skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]) >> 8) == 0u) continue;
-            float smp = tex3d(a.t, pos[0], pos[1], pos[2]);
+            float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
             probe = smp == 0.0f;
             float pa = smp - (smp * A);          // raycaster.frag:69
             rgb = pa * smp + rgb;                // :70
@@ -245,7 +329,7 @@ k_raycast(RayArgs a)
 #pragma unroll
             for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.P.box_min[k] && pos[k] < a.P.box_max[k]);
             if (!own) continue;
-            float smp = tex3d(a.t, pos[0], pos[1], pos[2]);
+            float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
             c = c + tau * (smp * smp);
             tau = tau * (1.0f - 0.6f * smp);
         }
@@ -272,21 +356,21 @@ k_raycast(RayArgs a)
                 carriedBounds = b2; haveBounds = true;
                 if ((float)((int)(b2 >> 8) + 1) * (1.0f / 255.0f) < iso) { haveCarried = false; continue; }
             }
-            float s1 = haveCarried ? carried : tex3d(a.t, pos[0], pos[1], pos[2]);
-            float s2 = tex3d(a.t, pos[0] + st[0], pos[1] + st[1], pos[2] + st[2]);
+            float s1 = haveCarried ? carried : sample3d(tex, a, pos[0], pos[1], pos[2]);
+            float s2 = sample3d(tex, a, pos[0] + st[0], pos[1] + st[1], pos[2] + st[2]);
             carried = s2; haveCarried = true;
             if ((s1 - iso) < 0.0f && (s2 - iso) >= 0.0f) {                     // :126
                 float l[3] = {pos[0], pos[1], pos[2]}, r[3] = {pos[0] + st[0], pos[1] + st[1], pos[2] + st[2]};
                 for (int b = 0; b < 4; ++b) {                                  // Bisection :23-42
                     float m0 = (r[0] + l[0]) * 0.5f, m1 = (r[1] + l[1]) * 0.5f, m2 = (r[2] + l[2]) * 0.5f;
-                    float cm = tex3d(a.t, m0, m1, m2);
+                    float cm = sample3d(tex, a, m0, m1, m2);
                     if (cm < iso) { l[0] = m0; l[1] = m1; l[2] = m2; } else { r[0] = m0; r[1] = m1; r[2] = m2; }
                 }
                 float tc0 = (r[0] + l[0]) * 0.5f, tc1 = (r[1] + l[1]) * 0.5f, tc2 = (r[2] + l[2]) * 0.5f;
                 const float DELTA = 0.01f;                                     // GetGradient :47-62
-                float N0 = (tex3d(a.t, tc0 - DELTA, tc1, tc2) - tex3d(a.t, tc0 + DELTA, tc1, tc2)) / 2.0f;
-                float N1 = (tex3d(a.t, tc0, tc1 - DELTA, tc2) - tex3d(a.t, tc0, tc1 + DELTA, tc2)) / 2.0f;
-                float N2 = (tex3d(a.t, tc0, tc1, tc2 - DELTA) - tex3d(a.t, tc0, tc1, tc2 + DELTA)) / 2.0f;
+                float N0 = (sample3d(tex, a, tc0 - DELTA, tc1, tc2) - sample3d(tex, a, tc0 + DELTA, tc1, tc2)) / 2.0f;
+                float N1 = (sample3d(tex, a, tc0, tc1 - DELTA, tc2) - sample3d(tex, a, tc0, tc1 + DELTA, tc2)) / 2.0f;
+                float N2 = (sample3d(tex, a, tc0, tc1, tc2 - DELTA) - sample3d(tex, a, tc0, tc1, tc2 + DELTA)) / 2.0f;
                 norm3(N0, N1, N2);
                 float V0 = -gd[0], V1 = -gd[1], V2 = -gd[2];                   // head light: L = V (:142-146)
                 float diffuse = fmaxf(V0 * N0 + V1 * N1 + V2 * N2, 0.0f);
@@ -449,8 +533,87 @@ int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *c
     a.tanX = a.tanY * (float)P->width / (float)P->height;
     a.out = rgba;
     dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast, grid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_raycast<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler());
     return launch_status("raymarch");
+}
+
+static int ilog2(int64_t v) { int n = 0; while (((int64_t)1 << n) < v) ++n; return n; }
+
+int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                        const vr_camera *cam, const vr_render_params *P, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    a.t.v = nullptr;
+    a.t.X = a.t.GX = (int)(grid[0] * bd[0]); a.t.Y = a.t.GY = (int)(grid[1] * bd[1]); a.t.Z = a.t.GZ = (int)(grid[2] * bd[2]);
+    a.t.ox = a.t.oy = a.t.oz = 0;
+    a.cam = *cam;
+    a.P = *P;
+    a.sg.g = nullptr; a.sg.S = 1; a.sg.nx = a.sg.ny = a.sg.nz = 0;
+    if (P->skip_grid_dev && P->skip_cell > 0) {     // a grid of the whole virtual volume
+        a.sg.g = P->skip_grid_dev; a.sg.S = P->skip_cell;
+        a.sg.nx = (a.t.X + a.sg.S - 1) / a.sg.S; a.sg.ny = (a.t.Y + a.sg.S - 1) / a.sg.S; a.sg.nz = (a.t.Z + a.sg.S - 1) / a.sg.S;
+    }
+    for (int k = 0; k < 3; ++k) a.f[k] = cam->front[k];
+    hnorm3(a.f);
+    cross3(a.f, cam->up, a.s);
+    hnorm3(a.s);
+    cross3(a.s, a.f, a.u);
+    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
+    a.tanY = tanf(0.5f * rad);
+    a.tanX = a.tanY * (float)P->width / (float)P->height;
+    a.out = rgba;
+    PoolTex pt;
+    pt.pool = pool; pt.tab = tab;
+    pt.lx = ilog2(bd[0]); pt.ly = ilog2(bd[1]); pt.lz = ilog2(bd[2]);
+    pt.gx = (int)grid[0]; pt.gy = (int)grid[1];
+    dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
+    hipLaunchKernelGGL(k_raycast<PoolTex>, g, dim3(64), 0, st, a, pt);
+    return launch_status("raymarch_pool");
+}
+
+// k_skip_grid over a pool's virtual volume: the same cells, rows and bounds; a row's voxels come from the stored voxels of
+// the bricks it crosses (a table load where it enters one)
+__global__ void __launch_bounds__(256)
+k_skip_grid_pool(PoolTex p, int X, int Y, int Z, int S, int nx, int ny, int nz, uint8_t *__restrict__ grid)
+{
+    const int64_t cell = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (cell >= (int64_t)nx * ny * nz) return;
+    const int cx = (int)(cell % nx), cy = (int)((cell / nx) % ny), cz = (int)(cell / ((int64_t)nx * ny));
+    const int x0 = cx * S, y0 = cy * S, z0 = cz * S;
+    const int ex = min(S + 1, X - x0), ey = min(S + 1, Y - y0), ez = min(S + 1, Z - z0);
+    uint32_t mn = 255, mx = 0;
+    for (int r = lane; r < ey * ez; r += 64) {
+        const int y = y0 + r % ey, z = z0 + r / ey;
+        int i = 0;
+        while (i < ex) {
+            const int x = x0 + i, bx = x >> p.lx;
+            const int end = min(ex, ((bx + 1) << p.lx) - x0);       // the row's voxels in this brick
+            const PoolCell c = pool_cell(p, bx, y >> p.ly, z >> p.lz);
+            if (c.off < 0) { mn = 0; i = end; continue; }
+            const uint8_t *row = p.pool + pool_at(p, c, x, y, z) - ((x & ((1 << p.lx) - 1)) >> c.sx);
+            for (; i < end; ++i) {
+                const uint32_t v = row[((x0 + i) & ((1 << p.lx) - 1)) >> c.sx];
+                mn = min(mn, v); mx = max(mx, v);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, o)); mx = max(mx, (uint32_t)__shfl_xor((int)mx, o)); }
+    if (lane == 0) { grid[2 * cell] = (uint8_t)mn; grid[2 * cell + 1] = (uint8_t)mx; }
+}
+
+int skip_grid_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3], int S,
+                          uint8_t *out, hipStream_t st)
+{
+    PoolTex pt;
+    pt.pool = pool; pt.tab = tab;
+    pt.lx = ilog2(bd[0]); pt.ly = ilog2(bd[1]); pt.lz = ilog2(bd[2]);
+    pt.gx = (int)grid[0]; pt.gy = (int)grid[1];
+    const int X = (int)(grid[0] * bd[0]), Y = (int)(grid[1] * bd[1]), Z = (int)(grid[2] * bd[2]);
+    const int nx = (X + S - 1) / S, ny = (Y + S - 1) / S, nz = (Z + S - 1) / S;
+    const int64_t cells = (int64_t)nx * ny * nz;
+    hipLaunchKernelGGL(k_skip_grid_pool, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, pt, X, Y, Z, S, nx, ny, nz, out);
+    return launch_status("skip_grid_pool");
 }
 
 // process-wide debugging switch (vr_debug_set("skip_grid_v1", 1), or VRHIP_SKIP_GRID_V1 in the environment when the

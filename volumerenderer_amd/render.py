@@ -195,6 +195,80 @@ def select_lod(cam, params, brick_dims, brick_ijk, grid, orig_tree_depth, max_tr
     return cuts
 
 
+# vr_pool_entry as numpy: one row per grid cell, x fastest
+POOL_ENTRY = np.dtype([("offset", "<i8"), ("shift", "u1", (3,)), ("pad", "u1", (5,))])
+
+
+def lod_pool_layout(brick_dims, brick_ijk, grid, cuts, orig_tree_depth, max_tree_depth):
+    """The pool layout of BrickSet.decode_lod_pool (vr_lod_pool_layout, host only; the rule is in vrhip.h).
+    Returns (table, pool_bytes): table a POOL_ENTRY numpy array of grid[0]*grid[1]*grid[2] cells, x fastest."""
+    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
+    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    ijk = np.ascontiguousarray(brick_ijk, np.int64).reshape(-1, 3)
+    c = np.ascontiguousarray(np.asarray(cuts).reshape(-1), dtype=np.int32)
+    if c.size != ijk.shape[0]:
+        raise ValueError("lod_pool_layout: %d cuts for %d bricks" % (c.size, ijk.shape[0]))
+    table = np.zeros(g[0] * g[1] * g[2], POOL_ENTRY)
+    nbytes = C.c_int64(0)
+    check(_lib.lib().vr_lod_pool_layout(bd, int(ijk.shape[0]), ijk.ctypes.data_as(C.POINTER(C.c_int64)), g,
+                                        c.ctypes.data_as(C.POINTER(C.c_int32)), int(orig_tree_depth), int(max_tree_depth),
+                                        C.c_void_p(table.ctypes.data), C.byref(nbytes)), "vr_lod_pool_layout")
+    return table, int(nbytes.value)
+
+
+def _check_pool(pool, table, grid, device):
+    cells = int(grid[0]) * int(grid[1]) * int(grid[2])
+    _check_buf(table, "table", torch.uint8, cells * POOL_ENTRY.itemsize, device)
+    if not isinstance(pool, torch.Tensor) or pool.numel() == 0:
+        raise ValueError("pool must be a non-empty torch tensor")
+    _check_buf(pool, "pool", torch.uint8, pool.numel(), device)
+
+
+def build_skip_grid_pool(pool, table, brick_dims, grid, cell=8, out=None, stream=None):
+    """build_skip_grid of the virtual volume of a pool (vr_skip_grid_build_pool): the same bytes as build_skip_grid of
+    that volume assembled densely.  pool, table: as BrickSet.decode_lod_pool returns them."""
+    if not isinstance(pool, torch.Tensor):
+        raise ValueError("pool must be a torch tensor")
+    _check_pool(pool, table, grid, pool.device)
+    if not 1 <= int(cell) <= 64:
+        raise ValueError("cell must be 1..64, not %d" % int(cell))
+    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
+    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    dims = [g[k] * bd[k] for k in range(3)]
+    nbytes = _skip_grid_bytes(dims, cell)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=pool.device)
+    else:
+        _check_buf(out, "out", torch.uint8, nbytes, pool.device)
+    check(_lib.lib().vr_skip_grid_build_pool(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, int(cell),
+                                             C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_skip_grid_build_pool")
+    return out
+
+
+def raycast_pool(pool, table, brick_dims, grid, cam, params, out=None, stream=None):
+    """raycast of the virtual volume of a pool (vr_raycast_pool): bit-identical to raycast of that volume assembled
+    densely (absent bricks 0).  A skip grid attached with use_skip_grid must come from build_skip_grid_pool (or
+    build_skip_grid of the dense volume).  Returns float32 CUDA [H][W][4]."""
+    if not isinstance(pool, torch.Tensor):
+        raise ValueError("pool must be a torch tensor")
+    _check_pool(pool, table, grid, pool.device)
+    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
+    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    dims = [g[k] * bd[k] for k in range(3)]
+    if params.skip_grid_dev and params.skip_cell > 0:
+        kg = getattr(params, "_keep_grid", None)
+        if kg is None or kg.data_ptr() != params.skip_grid_dev:
+            raise ValueError("attach skip grids with use_skip_grid()")
+        _check_buf(kg, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), pool.device)
+    if out is None:
+        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=pool.device)
+    else:
+        _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
+    check(_lib.lib().vr_raycast_pool(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
+                                     C.byref(params), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_pool")
+    return out
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}

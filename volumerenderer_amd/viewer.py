@@ -7,7 +7,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .render import assemble_bricks, default_camera, default_params, raycast, select_lod
+from .render import (POOL_ENTRY, assemble_bricks, build_skip_grid_pool, default_camera, default_params, lod_pool_layout,
+                     raycast, raycast_pool, select_lod, use_skip_grid)
 
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
@@ -101,6 +102,31 @@ class HeadlessViewer:
         vol = self._lodVol
         dims = (g[0] * bd[0], g[1] * bd[1], g[2] * bd[2])
         return raycast(vol, dims, cam, P, out), cuts
+
+    def draw_lod_pool(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, skip_cell=0, out=None):
+        """draw_lod's frame (bit for bit) from a pool: select_lod, decode_lod_pool, raycast_pool -- no brick buffer and no
+        assembled volume; each brick is stored at the resolution of its cut.  The pool is kept across frames and grows
+        only when a frame needs more.  skip_cell > 0: a skip grid of that cell size is built from the pool for the frame.
+        Power-of-two brick extents only.  Returns (frame, cuts)."""
+        import torch
+        bd = tuple(int(q) for q in bset.dims)
+        g = tuple(int(q) for q in grid)
+        info = bset.info(0)
+        P = default_params(self.width, self.height, bd, mode, float(self.currIsoVal) / 255.0)
+        cam = self.camera()
+        cuts = select_lod(cam, P, bd, brick_ijk, g, info["orig_tree_depth"], info["max_tree_depth"], pixel_tolerance)
+        _, need = lod_pool_layout(bd, brick_ijk, g, cuts, info["orig_tree_depth"], info["max_tree_depth"])
+        cells = g[0] * g[1] * g[2]
+        if getattr(self, "_pool", None) is None or self._pool.numel() < max(need, 1):
+            self._pool = None
+            self._pool = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
+        if getattr(self, "_poolTable", None) is None or self._poolTable.numel() != cells * POOL_ENTRY.itemsize:
+            self._poolTable = torch.empty(cells * POOL_ENTRY.itemsize, dtype=torch.uint8, device="cuda")
+        bset.decode_lod_pool(cuts, brick_ijk, g, pool=self._pool, table=self._poolTable)
+        if skip_cell > 0:
+            sg = build_skip_grid_pool(self._pool, self._poolTable, bd, g, skip_cell)
+            use_skip_grid(P, sg, skip_cell)
+        return raycast_pool(self._pool, self._poolTable, bd, g, cam, P, out), cuts
 
     @staticmethod
     def dump_ppm(path, rgba):
