@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
-"""bench.py -- kd-tree compress+decode throughput (Mvoxels/s) of the HIP hot path, with
+"""bench.py -- kd-tree compress+decode throughput (Mvoxels/s) of the HIP hot path; with --full, also
 the decode kernel's HBM roofline, the 1080p ray-cast rate and the CPU oracle beside it.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            # the headline figure only
+  python bench.py --gpus N --steps K --warmup W --full     # and every further leg (below)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  --full adds,
+after the timed steps: the same steps without compaction (value_no_compact), the serial per-kernel pass with the
+decode / encode rooflines, the 1080p frame rates, the RCCL-composited frames (N > 1), the config-5 streaming, disk
+and general-extent legs and the CPU oracle baseline.
 
 Workload (BASELINE.json metric): one 2048x2048x1920 uint8 volume = the reference's 8x8x15
 grid of 256x256x128 bricks (main.cpp:78-79), one kd-tree per brick, all 960 trees built and
 decoded by one batched launch sequence.  A "step" = build() + levelCut() of the whole
-volume (+ one 1080p ray-cast frame of the decoded volume, timed separately).
+volume (+ with --full, 1080p ray-cast frames of the decoded volume, timed separately).
 N > 1: one rank per GPU over RCCL; the codec shards with no data-path collective.  Default = BASELINE config 4
 (--scaling strong): ONE volume, its 960 bricks dealt to the ranks by slabs of the brick grid, value = the volume's
-voxels / the slowest rank's time; then every rank ray-marches its slab and the frame is composited sort-last over RCCL
-(vr_compositor_composite) and compared with the one-GPU frame.  --scaling weak: one volume (timestep) per rank.  Launched either by
+voxels / the slowest rank's time; with --full every rank then ray-marches its slab and the frame is composited sort-last
+over RCCL (vr_compositor_composite) and compared with the one-GPU frame.  --scaling weak: one volume (timestep) per rank.  Launched either by
 torch.distributed.run (RANK / WORLD_SIZE in the environment) or plainly as `python bench.py
 --gpus N`: the parent then starts the N ranks itself, before it touches the GPU, and relays
 rank 0's JSON line.
@@ -422,6 +428,72 @@ def disk_stage_leg(torch, vr, vox4, gdims, bdims, grid, args, timesteps=2):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def serial_leg(torch, bs, vox, out, B, V, args, strong):
+    """--full: per-kernel timing outside the timed region, strictly serial: hipEvents on the launch stream
+    (vr_brickset_last_timings); the decode kernel's and the whole encoder's HBM rooflines and the compression figures
+    of the trees `bs` built."""
+    gdims, bdims = tuple(args.volume), tuple(args.dims)
+    bs.set_concurrency(args.level_loop_streams)      # default 4: the fastest single build() (vr_brickset_set_concurrency)
+    enc_ms, dec_ms = [], []
+    for i in range(4):
+        bs.build(vox)
+        bs.decode(out)
+        torch.cuda.synchronize()
+        tm = bs.last_timings()
+        if i == 0:
+            continue        # the first serial pass after the pipelined region still pays for its cold caches
+        enc_ms.append(tm["BUILD"] + tm["COMPRESS"] + tm["PRUNE"] + tm["CONVERT"])
+        dec_ms.append(tm["DECODE"])
+        phases = tm
+    # decode kernel roofline: algorithmic bytes = V + ceil(numActiveNodes/4) + (maxTreeDepth+1) per brick (SURVEY 8d)
+    alg = 0
+    tokens = 0
+    n_const = 0                       # bricks of a single value: encoded in closed form (k_const_finish)
+    for b in range(B):
+        inf = bs.info(b)
+        alg += V + inf["tree_bytes"] + inf["max_tree_depth"] + 1
+        tokens += inf["num_active_nodes"]
+        n_const += inf["num_active_nodes"] <= 3
+    dec_avg_s = sum(dec_ms) / len(dec_ms) / 1e3
+    achieved = alg / dec_avg_s / 1e9
+    # HBM traffic of the decode launch from the committed PMC passes (separate rocprofv3 --pmc FETCH_SIZE /
+    # --pmc WRITE_SIZE runs of this same command, profiles/): only quoted when the workload is the profiled one
+    traffic = None
+    try:
+        pm = json.load(open(os.path.join(ROOT, PMC_TRAFFIC)))
+        if args.kind == "rm_volume" and not args.bricks and gdims == (2048, 2048, 1920) and bdims == (256, 256, 128) \
+                and args.tolerance == 1 and args.max_epochs == 2 and not strong:
+            traffic = pm["decode_traffic_bytes_per_launch"]
+    except Exception:
+        pass
+    roofline = {"bound": "hbm", "kernel": "k_decode_region", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                "traffic_source": PMC_TRAFFIC + " (bytes per launch)" if traffic else None,
+                "alg_bytes_per_launch": alg, "avg_launch_ms": round(dec_avg_s * 1e3, 4)}
+
+    # the encoder as a whole against the same roof: algorithmic bytes of a build = the voxels read + the stream written
+    enc_avg_s = sum(enc_ms) / len(enc_ms) / 1e3
+    enc_alg = alg                       # V + tree bytes (+ distanceMap) per brick: the same sum, read and written the other way round
+    enc_traffic = None
+    try:
+        if traffic is not None:
+            enc_traffic = pm.get("encode_traffic_bytes_per_build")
+    except Exception:
+        pass
+    roofline_encode = {"bound": "hbm", "kernels": "one build() = pyramid + level loop + prune/emit + index + compaction",
+                       "achieved": round(enc_alg / enc_avg_s / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(enc_alg / enc_avg_s / 1e9 / HBM_PEAK_GBS, 5), "traffic": enc_traffic,
+                       "alg_bytes_per_build": enc_alg, "avg_build_ms": round(enc_avg_s * 1e3, 3)}
+
+    return {"config": {"constant_bricks": int(n_const),
+                       "tokens_per_voxel": round(tokens / float(V * B), 3),
+                       "compression_ratio": round(float(V * B) / (tokens / 4.0), 2)},
+            "serial_ms_per_step": round(sum(enc_ms) / len(enc_ms) + dec_avg_s * 1e3, 3),
+            "encode_ms": round(sum(enc_ms) / len(enc_ms), 3), "decode_ms": round(dec_avg_s * 1e3, 3),
+            "phases_ms": {k: round(v, 3) for k, v in phases.items()},
+            "roofline": roofline, "roofline_encode": roofline_encode}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,11 +526,15 @@ def main():
                     help="N > 1: strong (default, BASELINE config 4) = ONE volume, its bricks dealt to the ranks by slabs of the "
                          "brick grid along y, value = the volume's voxels / the slowest rank's time; weak = one volume per rank")
     ap.add_argument("--no-composite", action="store_true",
-                    help="N > 1: skip the sort-last composited 1080p frames over RCCL (they run by default, after the timed "
+                    help="N > 1: skip the sort-last composited 1080p frames over RCCL (they run with --full, after the timed "
                          "region, under the process group's timeout: a collective that fails ends the run non-zero)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (rank 0's decoded volume and "
                          "compressed trees, sampled from a fixed seed beyond 64 MB in all) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every further leg: value_no_compact, the serial per-kernel "
+                         "pass and rooflines, frame rates, composited frames (N > 1), config 5, general extents and the "
+                         "CPU baseline (the --no-* options above pick among them).  Off: the headline figure alone")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -608,7 +684,7 @@ def main():
     # the same steps without the contiguous copy of the compressed stream at the end of build() (vr_brickset_set_compaction:
     # a pipeline that only decodes on the device may leave it to the first get_tree / save): reported beside `value`, never as it
     value_nc = None
-    if not args.no_extra_timing:
+    if args.full and not args.no_extra_timing:
         for s_ in sets:
             s_.set_compaction(False)
         run_steps(min(args.warmup, NS))
@@ -631,60 +707,6 @@ def main():
     outs = None                        # the extra output volumes are not needed any more
     torch.cuda.empty_cache()
 
-    # per-kernel timing outside the timed region, strictly serial: hipEvents on the launch stream
-    # (vr_brickset_last_timings)
-    bs.set_concurrency(args.level_loop_streams)      # default 4: the fastest single build() (vr_brickset_set_concurrency)
-    enc_ms, dec_ms = [], []
-    for i in range(4):
-        bs.build(vox)
-        bs.decode(out)
-        torch.cuda.synchronize()
-        tm = bs.last_timings()
-        if i == 0:
-            continue        # the first serial pass after the pipelined region still pays for its cold caches
-        enc_ms.append(tm["BUILD"] + tm["COMPRESS"] + tm["PRUNE"] + tm["CONVERT"])
-        dec_ms.append(tm["DECODE"])
-        phases = tm
-    # decode kernel roofline: algorithmic bytes = V + ceil(numActiveNodes/4) + (maxTreeDepth+1) per brick
-    alg = 0
-    tokens = 0
-    n_const = 0                       # bricks of a single value: encoded in closed form (k_const_finish)
-    for b in range(B):
-        inf = bs.info(b)
-        alg += V + inf["tree_bytes"] + inf["max_tree_depth"] + 1
-        tokens += inf["num_active_nodes"]
-        n_const += inf["num_active_nodes"] <= 3
-    dec_avg_s = sum(dec_ms) / len(dec_ms) / 1e3
-    achieved = alg / dec_avg_s / 1e9
-    # HBM traffic of the decode launch from the committed PMC passes (separate rocprofv3 --pmc FETCH_SIZE /
-    # --pmc WRITE_SIZE runs of this same command, profiles/): only quoted when the workload is the profiled one
-    traffic = None
-    try:
-        pm = json.load(open(os.path.join(ROOT, PMC_TRAFFIC)))
-        if args.kind == "rm_volume" and not args.bricks and gdims == (2048, 2048, 1920) and bdims == (256, 256, 128) \
-                and args.tolerance == 1 and args.max_epochs == 2 and not strong:
-            traffic = pm["decode_traffic_bytes_per_launch"]
-    except Exception:
-        pass
-    roofline = {"bound": "hbm", "kernel": "k_decode_region", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                "traffic_source": PMC_TRAFFIC + " (bytes per launch)" if traffic else None,
-                "alg_bytes_per_launch": alg, "avg_launch_ms": round(dec_avg_s * 1e3, 4)}
-
-    # the encoder as a whole against the same roof: algorithmic bytes of a build = the voxels read + the stream written
-    enc_avg_s = sum(enc_ms) / len(enc_ms) / 1e3
-    enc_alg = alg                       # V + tree bytes (+ distanceMap) per brick: the same sum, read and written the other way round
-    enc_traffic = None
-    try:
-        if traffic is not None:
-            enc_traffic = pm.get("encode_traffic_bytes_per_build")
-    except Exception:
-        pass
-    roofline_encode = {"bound": "hbm", "kernels": "one build() = pyramid + level loop + prune/emit + index + compaction",
-                       "achieved": round(enc_alg / enc_avg_s / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": round(enc_alg / enc_avg_s / 1e9 / HBM_PEAK_GBS, 5), "traffic": enc_traffic,
-                       "alg_bytes_per_build": enc_alg, "avg_build_ms": round(enc_avg_s * 1e3, 3)}
-
     res = {"metric": "Mvoxels/s kd-tree compress+decode", "value": round(value, 2), "unit": "Mvoxels/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
@@ -695,20 +717,18 @@ def main():
                                   + "%s, tolerance %d, maxEpochs %d, VolumeKdtree build + levelCut" % (args.kind, args.tolerance, args.max_epochs),
                       "pipeline": ("%d bricksets in flight, each on its own stream: build + levelCut of step k run "
                                    "beside those of the following steps" % NS if NS >= 2 else "serial"),
-                      "level_loop_streams": {"pipelined": lls_pipe if NS >= 2 else args.level_loop_streams, "serial": args.level_loop_streams},
-                      "constant_bricks": int(n_const),
-                      "tokens_per_voxel": round(tokens / float(V * B), 3),
-                      "compression_ratio": round(float(V * B) / (tokens / 4.0), 2)},
+                      "level_loop_streams": {"pipelined": lls_pipe if NS >= 2 else args.level_loop_streams, "serial": args.level_loop_streams}},
            "device_bytes_per_set": int(device_bytes_per_set), "device_bytes_per_set_over_input": round(device_bytes_per_set / float(V * B), 3),
            "device_bytes_pipeline": int(device_bytes_per_set * NS + vox.numel() * (1 + NS)),
-           "serial_ms_per_step": round(sum(enc_ms) / len(enc_ms) + dec_avg_s * 1e3, 3),
-           "encode_ms": round(sum(enc_ms) / len(enc_ms), 3), "decode_ms": round(dec_avg_s * 1e3, 3),
-           "phases_ms": {k: round(v, 3) for k, v in phases.items()},
-           "value_no_compact": round(value_nc, 2) if value_nc else None,
            "backend": (dist.get_backend() if world > 1 else None), "rccl_ranks": (dist.get_world_size() if world > 1 else 1),
-           "roofline": roofline, "roofline_encode": roofline_encode}
+           "full": args.full}
+    if args.full:
+        serial = serial_leg(torch, bs, vox, out, B, V, args, strong)
+        res["config"].update(serial.pop("config"))
+        res.update(serial)
+        res["value_no_compact"] = round(value_nc, 2) if value_nc else None
 
-    if not args.no_render and not args.bricks and rank == 0:
+    if args.full and not args.no_render and not args.bricks and rank == 0:
         # 1080p frames of the decoded volume on a camera orbit: raycaster.frag and isosurface.frag, each also with the
         # empty-space skip grid (bit-identical frames, tests/test_gpu_render_pins.py)
         ijk_all = np.array([[b % grid[0], (b // grid[0]) % grid[1], b // (grid[0] * grid[1])] for b in range(B)], np.int64)
@@ -745,7 +765,7 @@ def main():
             vr.default_params(1920, 1080, (256, 256, 128), vr.RENDER_ISOSURFACE, 40.0 / 255.0), sgrid, 8))
         del vol, sgrid
 
-    if world > 1 and not args.no_composite and not args.bricks and args.kind == "rm_volume":
+    if args.full and world > 1 and not args.no_composite and not args.bricks and args.kind == "rm_volume":
         # sort-last frames over RCCL (the path's one real exchange): rank r ray-marches ITS slab of the decoded volume
         # (strong: the y-slab of the bricks it decoded, plus one halo plane from each neighbour; weak: z-slab r of its own
         # volume) into a partial (c, tau) image; vr_compositor_composite: direct-send exchange (grouped ncclSend / ncclRecv),
@@ -890,7 +910,7 @@ def main():
                 res["composite_max_abs_diff"] = None
                 res["composite_reference_error"] = repr(ex)[:200]
 
-    if rank == 0 and world == 1 and not args.no_stream and not args.bricks and args.kind == "rm_volume":
+    if args.full and rank == 0 and world == 1 and not args.no_stream and not args.bricks and args.kind == "rm_volume":
         del sets, bs
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -912,7 +932,7 @@ def main():
             res["general_extents"] = {"error": repr(ex)[:300]}
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline(vox4, B, V, args.tolerance, args.max_epochs, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(res))

@@ -39,7 +39,7 @@ for k, e in kern.items():
     enc += b
 enc = int(enc)
 out = {
- "command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu --no-render --no-stream",
+ "command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-render --no-stream",
  "units": "counter values are KiB (rocprofv3 FETCH_SIZE / WRITE_SIZE); bytes = value * 1024",
  "note": "gfx950: WRITE_SIZE is exact for 16-byte-per-lane streaming stores; FETCH_SIZE under-reports wide coalesced reads by 2x and is uncalibrated for other widths (MI355X_MICROARCH.md, HBM section). k_decode_region reads its stream words, the per-4-leaf counts and the depth-(D-3) scalars as 16-byte-per-lane LDS-DMA loads (the 4-byte offsets and 1-byte scalars of the index are the smaller part), so decode_traffic_bytes_per_launch = 2 * FETCH_SIZE + WRITE_SIZE (the guide's correction); the per-kernel FETCH figures below are raw.",
  "kernels": kern,

@@ -1,4 +1,5 @@
-"""bench.py keeps the driver's contract: one JSON line with the required fields (a reduced workload here)."""
+"""bench.py keeps the driver's contract: one JSON line with the required fields (a reduced workload here); a plain run
+prints the headline figure alone, --full every further leg."""
 import json
 import os
 import subprocess
@@ -11,17 +12,48 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline")
 
 
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "config")
+FULL_ONLY = ("roofline", "roofline_encode", "cpu_baseline", "value_no_compact", "serial_ms_per_step", "phases_ms",
+             "raycast_1080p_fps", "config5", "general_extents")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", [1, 3])
+def test_plain_bench_prints_the_headline_alone(pipeline):
+    """Without --full the run times its steps and prints the headline line, with none of the further legs."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bricks", "6", "--steps", "2", "--warmup", "1",
+                        "--pipeline", str(pipeline)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in HEADLINE:
+        assert k in j, k
+    for k in FULL_ONLY:
+        assert k not in j, k
+    assert j["full"] is False and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["metric"] == "Mvoxels/s kd-tree compress+decode" and j["unit"] == "Mvoxels/s" and j["dtype"] == "u8"
+    assert j["higher_is_better"] is True and j["vs_baseline"] is None and j["scaling"] == "weak"
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and "workload" in j["config"]
+    # value = voxels x steps / the timed wall time = voxels per step / ms_per_step, up to the rounding of both
+    vox_per_step, ms = 6 * 256 * 256 * 128, j["ms_per_step"]
+    assert vox_per_step / ((ms + 5e-4) * 1e3) - 0.01 <= j["value"] <= vox_per_step / ((ms - 5e-4) * 1e3) + 0.01
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("pipeline", [1, 3])
 def test_bench_prints_one_contract_line(pipeline):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bricks", "6", "--steps", "2", "--warmup", "1",
-                        "--cpu-seconds", "1", "--pipeline", str(pipeline)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+                        "--cpu-seconds", "1", "--pipeline", str(pipeline), "--full"], capture_output=True, text=True, cwd=ROOT,
+                       timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     j = json.loads(lines[0])
     for k in REQUIRED:
         assert k in j, k
+    assert j["full"] is True
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["higher_is_better"] is True
     assert j["unit"] == "Mvoxels/s" and j["dtype"] == "u8" and j["vs_baseline"] is None and j["scaling"] == "weak"
     assert j["value_no_compact"] is None or j["value_no_compact"] > 0
