@@ -331,6 +331,43 @@ vr_status vr_raycast_pool(const uint8_t *pool_dev, const vr_pool_entry *table_de
 vr_status vr_skip_grid_build_pool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
                                   const int64_t grid[3], int32_t skip_cell, uint8_t *grid_dev, void *stream);
 
+/* ---- direct volume rendering with a user transfer function (new; the reference's compositor is hard-wired) --------
+ * A transfer function is 256 entries of (r, g, b, a) float32, each in [0, 1]; entry k belongs to the scalar k / 255.
+ * Ray set-up is vr_raycast's, unchanged: the pixel ray, the cube entry, vUV, gd, st = gd * step_size, pos += st, the
+ * inside() stop and max_samples.  Each sample, in order:
+ *  1. clip box: a pos outside [box_min, box_max) on any axis contributes nothing (the partial mode's ownership test;
+ *     the single-GPU default {0,0,0}-{1,1,1} clips nothing);
+ *  2. fetch: s = vr_raycast's trilinear sample, bit for bit (dense volume or pool);
+ *  3. lookup: x = clamp(s * 255, 0, 255), i = min((int)x, 254), f = x - i; per channel e = lut[i] + f (lut[i+1] - lut[i]);
+ *     e.a is clamped to [0, 1] against rounding;
+ *  4. opacity correction: opacity_unit > 0: a = 1 - (1 - e.a)^(L / opacity_unit), L = |st| in texture space (fixed per
+ *     ray); opacity_unit == 0: a = e.a.  e.a == 0 gives exactly 0; e.a == 1 with L > 0 gives exactly 1; L == 0 gives 0;
+ *  5. over: C += (T a) e.rgb, then T *= 1 - a, from C = 0, T = 1;
+ *  6. early exit once T < 0.01, unless no_early_exit (the mirror of raycaster.frag's A > 0.99).
+ * The pixel is (C + T * background, 1 - T); a pixel the cube does not cover is (background, 0), the same value a
+ * covered ray that gathers nothing produces.
+ * From vr_render_params: width, height, step_size, max_samples, no_early_exit, box_min / box_max, global_dims,
+ * vol_origin, skip_cell, skip_grid_dev (iso_value is ignored); mode must be VR_RENDER_COMPOSITE.  The skip grid has
+ * vr_raycast's limit (used only where volume_dev is the whole volume).  A sample whose grid bounds are (mn, mx) is not
+ * fetched when every entry in [max(mn - 1, 0), min(mx + 1, 255)] has alpha exactly 0 (the one-entry margin covers the
+ * rounding of s * 255 past a tap's value): its a would be 0 and both updates of step 5 exact no-ops, so frames are
+ * bit-identical with and without the grid. */
+typedef struct vr_transfer_function {
+    const float *lut_dev;     /* 256 x (r,g,b,a) float32 on the device, 16-byte aligned, values in [0,1] */
+    float opacity_unit;       /* texture-space distance the alphas are defined for; 0 = no correction */
+    float background[3];      /* colour behind the volume; (1,1,1) = the clear colour of main.cpp:392 */
+} vr_transfer_function;       /* 24 bytes */
+
+/* vr_raycast's checks, plus VR_ERR_INVALID (nothing launched) for a null tf or lut_dev, a lut_dev that is not 16-byte
+ * aligned, an opacity_unit that is negative or not finite, a background that is not finite, or a mode other than
+ * VR_RENDER_COMPOSITE.  The pool variant also takes vr_raycast_pool's restrictions and is bit-identical to
+ * vr_raycast_tf of the pool's volume assembled densely. */
+vr_status vr_raycast_tf(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                        const vr_render_params *params, const vr_transfer_function *tf, float *rgba_dev, void *stream);
+vr_status vr_raycast_pool_tf(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                             const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
+                             const vr_transfer_function *tf, float *rgba_dev, void *stream);
+
 /* Sort-last compositing of VR_RENDER_PARTIAL images: front = front OVER back, per pixel
  * (c1 + t1*c2, t1*t2); and the final colour transfer of raycaster.frag:82-85. */
 vr_status vr_composite_over(float *front_dev, const float *back_dev, int64_t num_pixels, void *stream);

@@ -1,9 +1,10 @@
 // vrhip/Viewer.hpp -- the reference viewer's camera / key / mouse state machine without a window
 // (volume_renderer/main.cpp:30-57 start values, :462-578 do_movement, key_callback, scroll_callback,
-// mouse_callback, reset), driving vr_raycast and dumping frames.  No GL, no GLFW: events are fed by
+// mouse_callback, reset), driving vr_raycast (or vr_raycast_tf) and dumping frames.  No GL, no GLFW: events are fed by
 // the caller (a script, a test, a remote session).  Plain C++14 over include/vrhip.h.
 #pragma once
 #include "../vrhip.h"
+#include "TransferFunction.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -94,6 +95,21 @@ public:
         P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f;
         const vr_camera c = camera();
         return vr_raycast_pool(pool_dev, table_dev, brick_dims, grid, &c, &P, rgba_dev, stream);
+    }
+    // the same frames through a transfer function (vr_raycast_tf / vr_raycast_pool_tf; P.mode must be VR_RENDER_COMPOSITE)
+    vr_status draw(const uint8_t *vol, const int64_t dims[3], vr_render_params P, const vr_transfer_function *tf, float *rgba_dev,
+                   void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f;
+        const vr_camera c = camera();
+        return vr_raycast_tf(vol, dims, &c, &P, tf, rgba_dev, stream);
+    }
+    vr_status drawPool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3], const int64_t grid[3],
+                       vr_render_params P, const vr_transfer_function *tf, float *rgba_dev, void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f;
+        const vr_camera c = camera();
+        return vr_raycast_pool_tf(pool_dev, table_dev, brick_dims, grid, &c, &P, tf, rgba_dev, stream);
     }
     // binary PPM of a host float RGBA frame (what glReadPixels of the 8-bit framebuffer would hold)
     static bool dumpPPM(const std::string &path, const std::vector<float> &rgba, int w, int h)

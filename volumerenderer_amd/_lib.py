@@ -43,6 +43,11 @@ class RenderParams(C.Structure):
                 ("no_early_exit", C.c_int32), ("skip_cell", C.c_int32), ("skip_grid_dev", C.c_void_p)]
 
 
+class TransferFunctionDesc(C.Structure):
+    """vr_transfer_function (24 bytes)."""
+    _fields_ = [("lut_dev", C.c_void_p), ("opacity_unit", C.c_float), ("background", C.c_float * 3)]
+
+
 class PoolEntry(C.Structure):
     _fields_ = [("offset", C.c_int64), ("shift", C.c_uint8 * 3), ("pad", C.c_uint8 * 5)]
 
@@ -89,6 +94,10 @@ SIGNATURES = {
     "vr_disassemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_raycast": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
     "vr_skip_grid_build": (_I32, [_P, C.POINTER(_I64), _I32, _P, _P]),
+    "vr_raycast_tf": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(TransferFunctionDesc),
+                             _P, _P]),
+    "vr_raycast_pool_tf": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                  C.POINTER(TransferFunctionDesc), _P, _P]),
     "vr_composite_over": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_finish": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_slabs": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),

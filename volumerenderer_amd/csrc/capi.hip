@@ -24,6 +24,10 @@ int raycast_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd
                         const vr_render_params *, float *, hipStream_t);
 int skip_grid_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], int, uint8_t *,
                           hipStream_t);
+int raycast_tf_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *,
+                      const vr_transfer_function *, float *, hipStream_t);
+int raycast_pool_tf_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
+                           const vr_render_params *, const vr_transfer_function *, float *, hipStream_t);
 int composite_finish_launch(const float *, float *, int64_t, hipStream_t);
 int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
 int assemble_launch(bool, const uint8_t *, uint8_t *, int, const int64_t bd[3], const int64_t *, const int64_t grid[3], hipStream_t);
@@ -1127,6 +1131,42 @@ vr_status vr_raycast_pool(const uint8_t *pool, const vr_pool_entry *table, const
     }
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return raycast_pool_launch(pool, table, bd, grid, cam, P, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// what vr_raycast_tf / vr_raycast_pool_tf check beyond vr_raycast / vr_raycast_pool (vrhip.h)
+static bool tf_ok(const vr_transfer_function *tf, const vr_render_params *P)
+{
+    if (!tf || !tf->lut_dev || ((uintptr_t)tf->lut_dev & 15u) != 0u) return false;
+    if (!(tf->opacity_unit >= 0.0f) || !isfinite(tf->opacity_unit)) return false;
+    for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return false;
+    return P->mode == VR_RENDER_COMPOSITE;
+}
+
+vr_status vr_raycast_tf(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                        const vr_transfer_function *tf, float *rgba, void *stream)
+{
+    if (!vol || !dims || !cam || !P || !rgba) return VR_ERR_INVALID;
+    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
+    if (!tf_ok(tf, P)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_tf_launch(vol, dims, cam, P, tf, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_raycast_pool_tf(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                             const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
+                             void *stream)
+{
+    if (!pool || !table || !bd || !grid || !cam || !P || !rgba) return VR_ERR_INVALID;
+    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
+    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) {
+        if (P->vol_origin[k] != 0) return VR_ERR_INVALID;
+        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return VR_ERR_INVALID;
+    }
+    if (!tf_ok(tf, P)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_pool_tf_launch(pool, table, bd, grid, cam, P, tf, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }
 
 vr_status vr_skip_grid_build_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],

@@ -388,6 +388,120 @@ k_raycast(RayArgs a, SAMPLER tex)
     }
 }
 
+// ---- direct volume rendering through a user transfer function (vr_raycast_tf; the rule is in vrhip.h) --------------
+struct TfArgs {
+    const float4 *lut;      // 256 (r, g, b, a), 16-byte aligned
+    float unit;             // opacity_unit (0: no correction)
+    float bg[3];
+};
+
+// k_raycast's ray set-up and fetch, a table lookup per sample and "over" into (C, T).  The workgroup is one wave: it
+// stages the table in LDS (four float4 per lane) with next_opaque[k] = the first j >= k whose alpha is not 0 (256:
+// none), found by one wave-wide suffix min.  A sample the skip grid bounds by (mn, mx) is skippable when
+// next_opaque[max(mn - 1, 0)] > min(mx + 1, 255).
+template <class SAMPLER>
+__global__ void __launch_bounds__(64)
+k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf)
+{
+    __shared__ float4 lut[256];
+    __shared__ uint16_t nextOpaque[256];
+    const int lane = threadIdx.x;
+    {
+        float4 e[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { e[j] = tf.lut[4 * lane + j]; lut[4 * lane + j] = e[j]; }
+        int first = 256;                                    // my four entries' first non-zero alpha
+#pragma unroll
+        for (int j = 3; j >= 0; --j) if (e[j].w != 0.0f) first = 4 * lane + j;
+        int suffix = first;                                 // min over lanes >= mine
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_down(suffix, o);
+            if (lane + o < 64) suffix = min(suffix, u);
+        }
+        const int after = __shfl_down(suffix, 1);           // min over lanes > mine
+        int carry = lane == 63 ? 256 : after;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+            if (e[j].w != 0.0f) carry = 4 * lane + j;
+            nextOpaque[4 * lane + j] = (uint16_t)carry;
+        }
+    }
+    __syncthreads();
+    // 8x8 pixel tile per wave
+    const int px = blockIdx.x * 8 + (lane & 7), py = blockIdx.y * 8 + (lane >> 3);
+    const int W = a.P.width, H = a.P.height;
+    if (px >= W || py >= H) return;
+    float *o = a.out + 4 * ((size_t)py * W + px);
+    const float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
+    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
+    float dir[3], cp[3] = {a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dir[k] = a.f[k] + nx * a.tanX * a.s[k] + ny * a.tanY * a.u[k];
+    float t0 = -INFINITY, t1 = INFINITY;
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (dir[k] != 0.0f) {
+            float lo = (-0.5f - cp[k]) / dir[k], hi = (0.5f - cp[k]) / dir[k];
+            if (lo > hi) { float q = lo; lo = hi; hi = q; }
+            if (lo > t0) t0 = lo;
+            if (hi < t1) t1 = hi;
+        } else if (cp[k] < -0.5f || cp[k] > 0.5f) miss = true;
+    }
+    const float th = t0 >= a.cam.z_near ? t0 : t1;
+    float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, T = 1.0f;
+    if (!(miss || t0 > t1 || th < a.cam.z_near || th > a.cam.z_far)) {
+        float vuv[3], gd[3], st[3], pos[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) vuv[k] = (cp[k] + th * dir[k]) + 0.5f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cp[k];
+        norm3(gd[0], gd[1], gd[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { st[k] = gd[k] * a.P.step_size[k]; pos[k] = vuv[k]; }
+        // opacity correction exponent L / opacity_unit (0 = none, or L = 0: a = 1 - t^0 = 0)
+        const float L = sqrtf(st[0] * st[0] + st[1] * st[1] + st[2] * st[2]);
+        const bool correct = tf.unit > 0.0f;
+        const float ex = correct ? L / tf.unit : 0.0f;
+        const int ns = a.P.max_samples;
+        bool probe = true;      // ask the grid only while the ray is in empty space (the last sample's a was 0)
+        for (int i = 0; i < ns; ++i) {
+            pos[0] = pos[0] + st[0]; pos[1] = pos[1] + st[1]; pos[2] = pos[2] + st[2];
+            if (!inside(pos[0], pos[1], pos[2])) break;
+            bool own = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.P.box_min[k] && pos[k] < a.P.box_max[k]);
+            if (!own) continue;
+            if (a.sg.g && probe) {
+                const uint32_t b = skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]);
+                const int lo = max((int)(b & 255u) - 1, 0), hi = min((int)(b >> 8) + 1, 255);
+                if ((int)nextOpaque[lo] > hi) continue;        // every entry the lookup can touch is transparent
+            }
+            const float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
+            const float x = fminf(fmaxf(smp * 255.0f, 0.0f), 255.0f);
+            const int li = min((int)x, 254);
+            const float f = x - (float)li;
+            const float4 e0 = lut[li], e1 = lut[li + 1];
+            float ea = e0.w + f * (e1.w - e0.w);
+            ea = fminf(fmaxf(ea, 0.0f), 1.0f);
+            float al = ea;
+            if (correct) {
+                // 1 - (1 - ea)^ex: ea = 0 -> log2(1) = 0 -> exactly 0; ea = 1 -> log2(0) = -inf -> exp2(-inf) = 0 -> 1
+                const float p = ex == 0.0f ? 1.0f : exp2f(ex * log2f(1.0f - ea));
+                al = 1.0f - p;
+            }
+            probe = al == 0.0f;
+            const float w = T * al;
+            C0 = C0 + w * (e0.x + f * (e1.x - e0.x));
+            C1 = C1 + w * (e0.y + f * (e1.y - e0.y));
+            C2 = C2 + w * (e0.z + f * (e1.z - e0.z));
+            T = T * (1.0f - al);
+            if (!a.P.no_early_exit && T < 0.01f) break;
+        }
+    }
+    o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T;
+}
+
 __global__ void k_composite_over(float4 *front, const float4 *back, int64_t n)
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -504,68 +618,109 @@ static void hnorm3(float *v)
     if (l > 0.0f) { v[0] /= l; v[1] /= l; v[2] /= l; } else { v[0] = v[1] = v[2] = 0.0f; }
 }
 
-int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                   float *rgba, hipStream_t st)
+// the frame (glm::lookAt basis and glm::perspectiveFov half-angle tangents, main.cpp:396-397) and the output
+static void ray_frame(RayArgs &a, const vr_camera *cam, const vr_render_params *P, float *rgba)
 {
-    RayArgs a;
+    a.cam = *cam;
+    a.P = *P;
+    for (int k = 0; k < 3; ++k) a.f[k] = cam->front[k];
+    hnorm3(a.f);
+    cross3(a.f, cam->up, a.s);
+    hnorm3(a.s);
+    cross3(a.s, a.f, a.u);
+    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
+    a.tanY = tanf(0.5f * rad);
+    a.tanX = a.tanY * (float)P->width / (float)P->height;
+    a.out = rgba;
+}
+
+// the dense volume's texture and skip grid
+static void dense_args(RayArgs &a, const uint8_t *vol, const int64_t dims[3], const vr_render_params *P)
+{
     a.t.v = vol;
     a.t.X = (int)dims[0]; a.t.Y = (int)dims[1]; a.t.Z = (int)dims[2];
     a.t.GX = P->global_dims[0] > 0 ? (int)P->global_dims[0] : a.t.X;
     a.t.GY = P->global_dims[1] > 0 ? (int)P->global_dims[1] : a.t.Y;
     a.t.GZ = P->global_dims[2] > 0 ? (int)P->global_dims[2] : a.t.Z;
     a.t.ox = (int)P->vol_origin[0]; a.t.oy = (int)P->vol_origin[1]; a.t.oz = (int)P->vol_origin[2];
-    a.cam = *cam;
-    a.P = *P;
     a.sg.g = nullptr; a.sg.S = 1; a.sg.nx = a.sg.ny = a.sg.nz = 0;
     // the grid describes volume_dev as a whole: only used where the local volume IS the texture (single-GPU path)
     if (P->skip_grid_dev && P->skip_cell > 0 && a.t.GX == a.t.X && a.t.GY == a.t.Y && a.t.GZ == a.t.Z && a.t.ox == 0 && a.t.oy == 0 && a.t.oz == 0) {
         a.sg.g = P->skip_grid_dev; a.sg.S = P->skip_cell;
         a.sg.nx = (a.t.X + a.sg.S - 1) / a.sg.S; a.sg.ny = (a.t.Y + a.sg.S - 1) / a.sg.S; a.sg.nz = (a.t.Z + a.sg.S - 1) / a.sg.S;
     }
-    // glm::lookAt basis and glm::perspectiveFov half-angle tangents (main.cpp:396-397)
-    for (int k = 0; k < 3; ++k) a.f[k] = cam->front[k];
-    hnorm3(a.f);
-    cross3(a.f, cam->up, a.s);
-    hnorm3(a.s);
-    cross3(a.s, a.f, a.u);
-    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
-    a.tanY = tanf(0.5f * rad);
-    a.tanX = a.tanY * (float)P->width / (float)P->height;
-    a.out = rgba;
-    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler());
-    return launch_status("raymarch");
 }
 
 static int ilog2(int64_t v) { int n = 0; while (((int64_t)1 << n) < v) ++n; return n; }
 
-int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
-                        const vr_camera *cam, const vr_render_params *P, float *rgba, hipStream_t st)
+// a pool's virtual volume (its extents in a.t), sampler and skip grid
+static PoolTex pool_args(RayArgs &a, const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                         const vr_render_params *P)
 {
-    RayArgs a;
     a.t.v = nullptr;
     a.t.X = a.t.GX = (int)(grid[0] * bd[0]); a.t.Y = a.t.GY = (int)(grid[1] * bd[1]); a.t.Z = a.t.GZ = (int)(grid[2] * bd[2]);
     a.t.ox = a.t.oy = a.t.oz = 0;
-    a.cam = *cam;
-    a.P = *P;
     a.sg.g = nullptr; a.sg.S = 1; a.sg.nx = a.sg.ny = a.sg.nz = 0;
     if (P->skip_grid_dev && P->skip_cell > 0) {     // a grid of the whole virtual volume
         a.sg.g = P->skip_grid_dev; a.sg.S = P->skip_cell;
         a.sg.nx = (a.t.X + a.sg.S - 1) / a.sg.S; a.sg.ny = (a.t.Y + a.sg.S - 1) / a.sg.S; a.sg.nz = (a.t.Z + a.sg.S - 1) / a.sg.S;
     }
-    for (int k = 0; k < 3; ++k) a.f[k] = cam->front[k];
-    hnorm3(a.f);
-    cross3(a.f, cam->up, a.s);
-    hnorm3(a.s);
-    cross3(a.s, a.f, a.u);
-    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
-    a.tanY = tanf(0.5f * rad);
-    a.tanX = a.tanY * (float)P->width / (float)P->height;
-    a.out = rgba;
     PoolTex pt;
     pt.pool = pool; pt.tab = tab;
     pt.lx = ilog2(bd[0]); pt.ly = ilog2(bd[1]); pt.lz = ilog2(bd[2]);
     pt.gx = (int)grid[0]; pt.gy = (int)grid[1];
+    return pt;
+}
+
+static TfArgs tf_args(const vr_transfer_function *tf)
+{
+    TfArgs t;
+    t.lut = (const float4 *)tf->lut_dev;
+    t.unit = tf->opacity_unit;
+    for (int k = 0; k < 3; ++k) t.bg[k] = tf->background[k];
+    return t;
+}
+
+int raycast_tf_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                      const vr_transfer_function *tf, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    dense_args(a, vol, dims, P);
+    ray_frame(a, cam, P, rgba);
+    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
+    hipLaunchKernelGGL(k_raycast_tf<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler(), tf_args(tf));
+    return launch_status("raymarch_tf");
+}
+
+int raycast_pool_tf_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                           const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
+                           hipStream_t st)
+{
+    RayArgs a;
+    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
+    ray_frame(a, cam, P, rgba);
+    dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
+    hipLaunchKernelGGL(k_raycast_tf<PoolTex>, g, dim3(64), 0, st, a, pt, tf_args(tf));
+    return launch_status("raymarch_pool_tf");
+}
+
+int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                   float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    dense_args(a, vol, dims, P);
+    ray_frame(a, cam, P, rgba);
+    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
+    hipLaunchKernelGGL(k_raycast<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler());
+    return launch_status("raymarch");
+}
+
+int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                        const vr_camera *cam, const vr_render_params *P, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
+    ray_frame(a, cam, P, rgba);
     dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
     hipLaunchKernelGGL(k_raycast<PoolTex>, g, dim3(64), 0, st, a, pt);
     return launch_status("raymarch_pool");

@@ -6,6 +6,7 @@
                  Draw() launches the ray-march kernel on the cube's pixel footprint)
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -266,6 +267,131 @@ def raycast_pool(pool, table, brick_dims, grid, cam, params, out=None, stream=No
         _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
     check(_lib.lib().vr_raycast_pool(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
                                      C.byref(params), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_pool")
+    return out
+
+
+# ---- direct volume rendering with a user transfer function (vr_raycast_tf; the rule is in vrhip.h) -------------------
+def transfer_function_table(points):
+    """The (256, 4) float32 table of control points (value, r, g, b, a): value in [0, 255], non-decreasing from point to
+    point, colours in [0, 1].  Entry k is linear between the last point at or below k and the point after it, the first
+    point's colour below the first value and the last point's from the last value on; computed in float64 and rounded
+    to float32 (vrhip::transfer_function_from_points in include/vrhip/TransferFunction.hpp is the same rule)."""
+    pts = [tuple(float(q) for q in p) for p in points]
+    if not pts or any(len(p) != 5 for p in pts):
+        raise ValueError("points must be a non-empty list of (value, r, g, b, a)")
+    for i, p in enumerate(pts):
+        if not all(math.isfinite(q) for q in p) or not 0.0 <= p[0] <= 255.0:
+            raise ValueError("point %d: value must lie in [0, 255]" % i)
+        if not all(0.0 <= q <= 1.0 for q in p[1:]):
+            raise ValueError("point %d: r, g, b, a must lie in [0, 1]" % i)
+        if i and p[0] < pts[i - 1][0]:
+            raise ValueError("points must be sorted by value")
+    out = np.empty((256, 4), np.float32)
+    j = -1                                  # the last point at or below k
+    for k in range(256):
+        while j + 1 < len(pts) and pts[j + 1][0] <= k:
+            j += 1
+        if j < 0:
+            row = pts[0][1:]
+        elif j + 1 == len(pts):
+            row = pts[-1][1:]
+        else:
+            (v0, *c0), (v1, *c1) = pts[j], pts[j + 1]
+            t = (k - v0) / (v1 - v0)
+            row = [a + t * (b - a) for a, b in zip(c0, c1)]
+        out[k] = row
+    return out
+
+
+class TransferFunction:
+    """A transfer function for raycast_tf / raycast_pool_tf (vr_transfer_function): `lut` the (256, 4) float32 CUDA
+    tensor of (r, g, b, a) in [0, 1], entry k for the scalar k / 255; `opacity_unit` the texture-space distance the
+    alphas are defined for (0: no correction); `background` the colour behind the volume."""
+
+    def __init__(self, lut, opacity_unit=0.0, background=(1.0, 1.0, 1.0), device="cuda"):
+        if isinstance(lut, torch.Tensor):
+            device = lut.device if lut.is_cuda else device
+            host = lut.detach().to("cpu", torch.float32).numpy()
+        else:
+            host = np.asarray(lut, np.float32)
+        if host.shape != (256, 4):
+            raise ValueError("lut must be 256 x (r, g, b, a), not %s" % (tuple(host.shape),))
+        if not np.all(np.isfinite(host)) or host.min() < 0.0 or host.max() > 1.0:
+            raise ValueError("lut values must lie in [0, 1]")
+        self.opacity_unit = float(opacity_unit)
+        if not math.isfinite(self.opacity_unit) or self.opacity_unit < 0.0:
+            raise ValueError("opacity_unit must be finite and >= 0, not %r" % opacity_unit)
+        self.background = tuple(float(v) for v in background)
+        if len(self.background) != 3 or not all(math.isfinite(v) for v in self.background):
+            raise ValueError("background must be three finite values")
+        self.lut = torch.from_numpy(np.ascontiguousarray(host)).to(device)
+
+    @classmethod
+    def from_points(cls, points, opacity_unit=0.0, background=(1.0, 1.0, 1.0), device="cuda"):
+        """The table transfer_function_table(points) builds: (value 0..255, r, g, b, a) control points."""
+        return cls(transfer_function_table(points), opacity_unit, background, device)
+
+    def desc(self):
+        d = _lib.TransferFunctionDesc()
+        d.lut_dev = self.lut.data_ptr()
+        d.opacity_unit = self.opacity_unit
+        d.background[:] = self.background
+        return d
+
+
+def _check_tf(tf, device):
+    if not isinstance(tf, TransferFunction):
+        raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
+    _check_buf(tf.lut, "tf.lut", torch.float32, 256 * 4, device)
+
+
+def _check_attached_grid(params, dims, device):
+    if params.skip_grid_dev and params.skip_cell > 0:
+        # the grid must describe THIS volume at THIS cell size, or skip_bounds reads past it
+        g = getattr(params, "_keep_grid", None)
+        if g is None or g.data_ptr() != params.skip_grid_dev:
+            raise ValueError("attach skip grids with use_skip_grid()")
+        _check_buf(g, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), device)
+
+
+def raycast_tf(volume, dims, cam, params, tf, out=None, stream=None):
+    """raycast's frame set-up with the transfer function `tf` (vr_raycast_tf): each sample is looked up in tf's table
+    and composited front to back.  params.mode must be RENDER_COMPOSITE.  Returns float32 CUDA [H][W][4] =
+    (C + T * background, 1 - T), row 0 = top."""
+    v = _as_dev_u8(volume)
+    d = (C.c_int64 * 3)(*[int(q) for q in dims])
+    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
+        raise ValueError("volume size does not match dims")
+    _check_attached_grid(params, dims, v.device)
+    _check_tf(tf, v.device)
+    if out is None:
+        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=v.device)
+    else:
+        _check_buf(out, "out", torch.float32, params.height * params.width * 4, v.device)
+    desc = tf.desc()
+    check(_lib.lib().vr_raycast_tf(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
+                                   C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_tf")
+    return out
+
+
+def raycast_pool_tf(pool, table, brick_dims, grid, cam, params, tf, out=None, stream=None):
+    """raycast_tf of the virtual volume of a pool (vr_raycast_pool_tf): bit-identical to raycast_tf of that volume
+    assembled densely.  Restrictions and skip grids as raycast_pool."""
+    if not isinstance(pool, torch.Tensor):
+        raise ValueError("pool must be a torch tensor")
+    _check_pool(pool, table, grid, pool.device)
+    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
+    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
+    _check_tf(tf, pool.device)
+    if out is None:
+        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=pool.device)
+    else:
+        _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
+    desc = tf.desc()
+    check(_lib.lib().vr_raycast_pool_tf(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
+                                        C.byref(params), C.byref(desc), C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
+          "vr_raycast_pool_tf")
     return out
 
 

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from .render import (POOL_ENTRY, assemble_bricks, build_skip_grid_pool, default_camera, default_params, lod_pool_layout,
-                     raycast, raycast_pool, select_lod, use_skip_grid)
+                     raycast, raycast_pool, raycast_pool_tf, raycast_tf, select_lod, use_skip_grid)
 
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
@@ -78,8 +78,11 @@ class HeadlessViewer:
         cam.fov_deg = float(self.fov)
         return cam
 
-    def draw(self, volume, dims, brick_dims=(256, 256, 128), mode=_lib.RENDER_COMPOSITE, out=None):
+    def draw(self, volume, dims, brick_dims=(256, 256, 128), mode=_lib.RENDER_COMPOSITE, out=None, tf=None):
+        """One frame of `volume`: raycast, or raycast_tf through the TransferFunction `tf` (composite mode only)."""
         P = default_params(self.width, self.height, brick_dims, mode, float(self.currIsoVal) / 255.0)
+        if tf is not None:
+            return raycast_tf(volume, dims, self.camera(), P, tf, out)
         return raycast(volume, dims, self.camera(), P, out)
 
     def draw_lod(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, out=None):
@@ -103,11 +106,12 @@ class HeadlessViewer:
         dims = (g[0] * bd[0], g[1] * bd[1], g[2] * bd[2])
         return raycast(vol, dims, cam, P, out), cuts
 
-    def draw_lod_pool(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, skip_cell=0, out=None):
+    def draw_lod_pool(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, skip_cell=0, out=None,
+                      tf=None):
         """draw_lod's frame (bit for bit) from a pool: select_lod, decode_lod_pool, raycast_pool -- no brick buffer and no
         assembled volume; each brick is stored at the resolution of its cut.  The pool is kept across frames and grows
         only when a frame needs more.  skip_cell > 0: a skip grid of that cell size is built from the pool for the frame.
-        Power-of-two brick extents only.  Returns (frame, cuts)."""
+        Power-of-two brick extents only.  tf: a TransferFunction, drawn with raycast_pool_tf.  Returns (frame, cuts)."""
         import torch
         bd = tuple(int(q) for q in bset.dims)
         g = tuple(int(q) for q in grid)
@@ -126,6 +130,8 @@ class HeadlessViewer:
         if skip_cell > 0:
             sg = build_skip_grid_pool(self._pool, self._poolTable, bd, g, skip_cell)
             use_skip_grid(P, sg, skip_cell)
+        if tf is not None:
+            return raycast_pool_tf(self._pool, self._poolTable, bd, g, cam, P, tf, out), cuts
         return raycast_pool(self._pool, self._poolTable, bd, g, cam, P, out), cuts
 
     @staticmethod
