@@ -252,7 +252,8 @@ typedef struct vr_camera {
 } vr_camera;
 
 enum { VR_RENDER_COMPOSITE = 0 /* raycaster.frag */, VR_RENDER_ISOSURFACE = 1 /* isosurface.frag */,
-       VR_RENDER_PARTIAL = 2 /* raycaster.frag accumulation as an (rgb-premultiplied c, transmittance) pair for sort-last compositing */ };
+       VR_RENDER_PARTIAL = 2 /* raycaster.frag accumulation as an (rgb-premultiplied c, transmittance) pair for sort-last compositing */,
+       VR_RENDER_SHADED = 3 /* transfer function with gradient lighting: vr_raycast_tf_shaded only */ };
 
 typedef struct vr_render_params {
     int32_t width, height;   /* 1600x1200 in the reference (main.cpp:27); bench uses 1920x1080 */
@@ -291,7 +292,8 @@ vr_status vr_raycast(const uint8_t *volume_dev, const int64_t dims[3], const vr_
  *    G = grid * brick_dims (params->global_dims where non-zero).  Brick b covers [ijk*brick_dims, (ijk+1)*brick_dims)/G.
  *  - its box is grown on every side by one voxel (the reach of a trilinear tap); in VR_RENDER_ISOSURFACE mode also by
  *    0.01 + max|step_size| (the gradient's offset, and the second fetch / bisection points that may leave the cube
- *    and read its clamped edge).
+ *    and read its clamped edge); in VR_RENDER_SHADED mode by two voxels instead of one (a lattice gradient's tap
+ *    reaches one voxel beyond the trilinear taps).
  *  - culled (-1): the grown box lies wholly outside [box_min, box_max) on some axis, or all eight of its corners lie
  *    outside one plane of the frame's frustum.  The frustum is vr_raycast's: f = normalize(front),
  *    s = normalize(f x up), u = s x f, tanY = tan(fov/2), tanX = tanY * width / height (float, as vr_raycast); for a
@@ -367,6 +369,45 @@ vr_status vr_raycast_tf(const uint8_t *volume_dev, const int64_t dims[3], const 
 vr_status vr_raycast_pool_tf(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
                              const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
                              const vr_transfer_function *tf, float *rgba_dev, void *stream);
+
+/* ---- gradient-shaded direct volume rendering (new) -----------------------------------------------------------------
+ * vr_raycast_tf's rule, steps 1-6 unchanged, except that step 5 adds (T a) c, a lit colour c in place of e.rgb, for
+ * every sample whose a > 0 (a sample with a == 0 changes nothing, lit or not):
+ *  - gradient on the lattice: (x0, y0, z0) = the sample's base voxel floor(pos * G - 0.5) and (fx, fy, fz) its weights,
+ *    exactly as the trilinear fetch forms them; v(x, y, z) = the voxel at (x, y, z) with every index clamped to
+ *    [0, G - 1] of the global volume (clamp-to-edge, as the fetch).  For each of the eight corners (x0+i, y0+j, z0+k),
+ *    i, j, k in {0, 1}: d_x = v(x0+i+1, y0+j, z0+k) - v(x0+i-1, y0+j, z0+k), d_y and d_z likewise (integers).  The
+ *    gradient g = the trilinear interpolation of d with the sample's weights, in the fetch's order, times 1 / (2 * 255);
+ *  - m = |g| (grey levels per voxel / 255).  m <= grad_min: c = e.rgb (unlit).  Otherwise:
+ *    N = normalize(G_x g_x, G_y g_y, G_z g_z) (the world-space normal of the unit cube, G the global extents);
+ *    V = -gd (gd the normalized ray direction); L = normalize(light_dir), or V when light_dir is {0,0,0} (head light);
+ *    H = normalize(L + V), and the specular term is 0 when L + V = 0;  two-sided: cd = |N.L|, ch = clamp(|N.H|, 1e-5, 1)
+ *    (the iso-surface shader's 1e-5; the upper clamp only catches rounding);
+ *    c = min(1, e.rgb (ambient + diffuse cd) + specular ch^shininess) per channel.
+ * Alpha, opacity correction, the early exit, the skip grid and the pixel formula are vr_raycast_tf's.  Invariants:
+ *  - ambient = 1, diffuse = specular = 0 gives frames bit-identical to vr_raycast_tf in VR_RENDER_COMPOSITE mode with
+ *    the same params: e.rgb is formed by the same expression, e.rgb * 1 + 0 is exact, and the min(1, .) is a no-op
+ *    because e = lut[i] + f (lut[i+1] - lut[i]) never rounds above 1 for table values in [0, 1];
+ *  - frames are bit-identical with and without the skip grid: the grid's decision depends on alpha alone;
+ *  - the pool frame is bit-identical to the dense frame of the pool's volume assembled densely;
+ *  - a slab under vol_origin / global_dims must hold TWO halo layers (the gradient reaches one voxel beyond the taps)
+ *    to equal the full volume inside its box. */
+typedef struct vr_shading {
+    float ambient, diffuse, specular, shininess;  /* ka, kd, ks >= 0; shininess >= 0; all finite */
+    float light_dir[3];   /* world direction towards the light; {0,0,0} = head light (L = V) */
+    float grad_min;       /* >= 0: samples whose gradient magnitude is <= grad_min are not lit */
+} vr_shading;             /* 32 bytes */
+
+/* vr_raycast_tf's / vr_raycast_pool_tf's checks, except that params->mode must be VR_RENDER_SHADED, plus VR_ERR_INVALID
+ * (nothing launched) for a null shading or any of its fields negative (light_dir excepted) or not finite.  The pool
+ * variant is bit-identical to vr_raycast_tf_shaded of the pool's volume assembled densely. */
+vr_status vr_raycast_tf_shaded(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                               const vr_render_params *params, const vr_transfer_function *tf, const vr_shading *shading,
+                               float *rgba_dev, void *stream);
+vr_status vr_raycast_pool_tf_shaded(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                                    const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
+                                    const vr_transfer_function *tf, const vr_shading *shading, float *rgba_dev,
+                                    void *stream);
 
 /* Sort-last compositing of VR_RENDER_PARTIAL images: front = front OVER back, per pixel
  * (c1 + t1*c2, t1*t2); and the final colour transfer of raycaster.frag:82-85. */

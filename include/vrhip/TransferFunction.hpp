@@ -1,6 +1,7 @@
 // vrhip/TransferFunction.hpp -- a transfer-function table for vr_raycast_tf / vr_raycast_pool_tf from control points,
 // without Python: the rule of volumerenderer_amd.render.transfer_function_table.  Plain C++14, host only.
 #pragma once
+#include "../vrhip.h"
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -44,6 +45,17 @@ inline std::vector<float> transfer_function_from_points(const std::vector<TfPoin
         for (int c = 0; c < 4; ++c) lut[4 * k + c] = (float)(c0[c] + t * (c1[c] - c0[c]));
     }
     return lut;
+}
+
+// the lighting volumerenderer_amd.render.Shading() defaults to: ka 0.3, kd 0.7, ks 0.2, shininess 32, head light,
+// grad_min 1/255
+inline vr_shading default_shading()
+{
+    vr_shading s;
+    s.ambient = 0.3f; s.diffuse = 0.7f; s.specular = 0.2f; s.shininess = 32.0f;
+    s.light_dir[0] = s.light_dir[1] = s.light_dir[2] = 0.0f;
+    s.grad_min = (float)(1.0 / 255.0);
+    return s;
 }
 
 } // namespace vrhip

@@ -111,6 +111,23 @@ public:
         const vr_camera c = camera();
         return vr_raycast_pool_tf(pool_dev, table_dev, brick_dims, grid, &c, &P, tf, rgba_dev, stream);
     }
+    // the same frames lit through the gradient (vr_raycast_tf_shaded / vr_raycast_pool_tf_shaded): P.mode is set to
+    // VR_RENDER_SHADED
+    vr_status draw(const uint8_t *vol, const int64_t dims[3], vr_render_params P, const vr_transfer_function *tf,
+                   const vr_shading *shading, float *rgba_dev, void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f; P.mode = VR_RENDER_SHADED;
+        const vr_camera c = camera();
+        return vr_raycast_tf_shaded(vol, dims, &c, &P, tf, shading, rgba_dev, stream);
+    }
+    vr_status drawPool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3], const int64_t grid[3],
+                       vr_render_params P, const vr_transfer_function *tf, const vr_shading *shading, float *rgba_dev,
+                       void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f; P.mode = VR_RENDER_SHADED;
+        const vr_camera c = camera();
+        return vr_raycast_pool_tf_shaded(pool_dev, table_dev, brick_dims, grid, &c, &P, tf, shading, rgba_dev, stream);
+    }
     // binary PPM of a host float RGBA frame (what glReadPixels of the 8-bit framebuffer would hold)
     static bool dumpPPM(const std::string &path, const std::vector<float> &rgba, int w, int h)
     {

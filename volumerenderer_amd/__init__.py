@@ -17,7 +17,8 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
     if name in ("VolumeReader", "UnitBrick", "raycast", "default_camera", "default_params", "composite_over",
                 "composite_finish", "assemble_bricks", "disassemble_bricks", "fill_volume_brick_map", "build_skip_grid",
                 "use_skip_grid", "select_lod", "lod_pool_layout", "raycast_pool", "build_skip_grid_pool", "TransferFunction",
-                "raycast_tf", "raycast_pool_tf", "transfer_function_table"):
+                "raycast_tf", "raycast_pool_tf", "transfer_function_table", "Shading", "raycast_tf_shaded",
+                "raycast_pool_tf_shaded"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

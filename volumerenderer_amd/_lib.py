@@ -12,7 +12,7 @@ VR_OK = 0
 STATUS = {0: "VR_OK", -1: "VR_ERR_INVALID", -2: "VR_ERR_NO_DEVICE", -3: "VR_ERR_OOM", -4: "VR_ERR_IO",
           -5: "VR_ERR_STATE", -6: "VR_ERR_FORMAT", -7: "VR_ERR_UNSUPPORTED"}
 VARIANT_RECOVER, VARIANT_GUARDED, VARIANT_MIDRANGE = 0, 1, 2
-RENDER_COMPOSITE, RENDER_ISOSURFACE, RENDER_PARTIAL = 0, 1, 2
+RENDER_COMPOSITE, RENDER_ISOSURFACE, RENDER_PARTIAL, RENDER_SHADED = 0, 1, 2, 3
 
 
 class VrError(RuntimeError):
@@ -46,6 +46,12 @@ class RenderParams(C.Structure):
 class TransferFunctionDesc(C.Structure):
     """vr_transfer_function (24 bytes)."""
     _fields_ = [("lut_dev", C.c_void_p), ("opacity_unit", C.c_float), ("background", C.c_float * 3)]
+
+
+class ShadingDesc(C.Structure):
+    """vr_shading (32 bytes)."""
+    _fields_ = [("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float), ("shininess", C.c_float),
+                ("light_dir", C.c_float * 3), ("grad_min", C.c_float)]
 
 
 class PoolEntry(C.Structure):
@@ -98,6 +104,10 @@ SIGNATURES = {
                              _P, _P]),
     "vr_raycast_pool_tf": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
                                   C.POINTER(TransferFunctionDesc), _P, _P]),
+    "vr_raycast_tf_shaded": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                    C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_raycast_pool_tf_shaded": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                         C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
     "vr_composite_over": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_finish": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_slabs": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),

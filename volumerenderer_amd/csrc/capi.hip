@@ -28,6 +28,11 @@ int raycast_tf_launch(const uint8_t *, const int64_t dims[3], const vr_camera *,
                       const vr_transfer_function *, float *, hipStream_t);
 int raycast_pool_tf_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
                            const vr_render_params *, const vr_transfer_function *, float *, hipStream_t);
+int raycast_tf_shaded_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *,
+                             const vr_transfer_function *, const vr_shading *, float *, hipStream_t);
+int raycast_pool_tf_shaded_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3],
+                                  const vr_camera *, const vr_render_params *, const vr_transfer_function *, const vr_shading *,
+                                  float *, hipStream_t);
 int composite_finish_launch(const float *, float *, int64_t, hipStream_t);
 int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
 int assemble_launch(bool, const uint8_t *, uint8_t *, int, const int64_t bd[3], const int64_t *, const int64_t grid[3], hipStream_t);
@@ -744,12 +749,14 @@ vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *P, int32_t
         vs[k] = 1.0 / G[k];
         vmax = std::max(vmax, vs[k]);
     }
-    // the reach beyond a brick's voxels of the samples and taps that read them: one voxel (a trilinear tap); in
-    // iso-surface mode also the gradient's 0.01 offset and one step (the second fetch and the bisection, whose points
+    // the reach beyond a brick's voxels of the samples and taps that read them: one voxel (a trilinear tap), two in
+    // shaded mode; in iso-surface mode also the gradient's 0.01 offset and one step (the second fetch and the bisection, whose points
     // may lie outside the cube and read its clamped edge)
     double grow[3], stepMax = 0.0;
     for (int k = 0; k < 3; ++k) stepMax = std::max(stepMax, (double)fabsf(P->step_size[k]));
     for (int k = 0; k < 3; ++k) grow[k] = vs[k] + (P->mode == VR_RENDER_ISOSURFACE ? 0.01 + stepMax : 0.0);
+    if (P->mode == VR_RENDER_SHADED)    // the lattice gradient's taps reach one voxel beyond the trilinear taps
+        for (int k = 0; k < 3; ++k) grow[k] = 2.0 * vs[k];
     float f[3] = {cam->front[0], cam->front[1], cam->front[2]}, sv[3], u[3];
     lod_norm3(f);
     lod_cross3(f, cam->up, sv);
@@ -1167,6 +1174,47 @@ vr_status vr_raycast_pool_tf(const uint8_t *pool, const vr_pool_entry *table, co
     if (!tf_ok(tf, P)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return raycast_pool_tf_launch(pool, table, bd, grid, cam, P, tf, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// vr_raycast_tf_shaded / vr_raycast_pool_tf_shaded: tf_ok's table checks with mode VR_RENDER_SHADED, and the lighting
+static bool shading_ok(const vr_transfer_function *tf, const vr_shading *sh, const vr_render_params *P)
+{
+    if (P->mode != VR_RENDER_SHADED || !sh) return false;
+    vr_render_params Q = *P;
+    Q.mode = VR_RENDER_COMPOSITE;
+    if (!tf_ok(tf, &Q)) return false;
+    const float nonneg[5] = {sh->ambient, sh->diffuse, sh->specular, sh->shininess, sh->grad_min};
+    for (int k = 0; k < 5; ++k) if (!(nonneg[k] >= 0.0f) || !isfinite(nonneg[k])) return false;
+    for (int k = 0; k < 3; ++k) if (!isfinite(sh->light_dir[k])) return false;
+    return true;
+}
+
+vr_status vr_raycast_tf_shaded(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                               const vr_transfer_function *tf, const vr_shading *sh, float *rgba, void *stream)
+{
+    if (!vol || !dims || !cam || !P || !rgba) return VR_ERR_INVALID;
+    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
+    if (!shading_ok(tf, sh, P)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_tf_shaded_launch(vol, dims, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_raycast_pool_tf_shaded(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                                    const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf,
+                                    const vr_shading *sh, float *rgba, void *stream)
+{
+    if (!pool || !table || !bd || !grid || !cam || !P || !rgba) return VR_ERR_INVALID;
+    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0) return VR_ERR_INVALID;
+    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) {
+        if (P->vol_origin[k] != 0) return VR_ERR_INVALID;
+        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return VR_ERR_INVALID;
+    }
+    if (!shading_ok(tf, sh, P)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_pool_tf_shaded_launch(pool, table, bd, grid, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK
+                                                                                                                : VR_ERR_NO_DEVICE;
 }
 
 vr_status vr_skip_grid_build_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],

@@ -395,10 +395,67 @@ struct TfArgs {
     float bg[3];
 };
 
-// k_raycast's ray set-up and fetch, a table lookup per sample and "over" into (C, T).  The workgroup is one wave: it
-// stages the table in LDS (four float4 per lane) with next_opaque[k] = the first j >= k whose alpha is not 0 (256:
-// none), found by one wave-wide suffix min.  A sample the skip grid bounds by (mn, mx) is skippable when
-// next_opaque[max(mn - 1, 0)] > min(mx + 1, 255).
+// The workgroup's table in LDS (four float4 per lane) with next_opaque[k] = the first j >= k whose alpha is not 0 (256:
+// none), found by one wave-wide suffix min.  The workgroup is one wave.
+__device__ __forceinline__ void tf_stage(const TfArgs &tf, float4 *lut, uint16_t *nextOpaque, int lane)
+{
+    float4 e[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { e[j] = tf.lut[4 * lane + j]; lut[4 * lane + j] = e[j]; }
+    int first = 256;                                    // my four entries' first non-zero alpha
+#pragma unroll
+    for (int j = 3; j >= 0; --j) if (e[j].w != 0.0f) first = 4 * lane + j;
+    int suffix = first;                                 // min over lanes >= mine
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_down(suffix, o);
+        if (lane + o < 64) suffix = min(suffix, u);
+    }
+    const int after = __shfl_down(suffix, 1);           // min over lanes > mine
+    int carry = lane == 63 ? 256 : after;
+#pragma unroll
+    for (int j = 3; j >= 0; --j) {
+        if (e[j].w != 0.0f) carry = 4 * lane + j;
+        nextOpaque[4 * lane + j] = (uint16_t)carry;
+    }
+}
+
+// k_raycast's pixel ray: false where it misses the cube (or enters outside [z_near, z_far]); else the normalized
+// direction gd, the step st = gd * step_size and the entry point pos = vUV.  (k_raycast and k_raycast_tf keep their
+// inline copy of the same statements: through this function their code would be scheduled differently.)
+__device__ __forceinline__ bool ray_enter(const RayArgs &a, int px, int py, float gd[3], float st[3], float pos[3])
+{
+    const int W = a.P.width, H = a.P.height;
+    const float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
+    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
+    float dir[3], cp[3] = {a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dir[k] = a.f[k] + nx * a.tanX * a.s[k] + ny * a.tanY * a.u[k];
+    float t0 = -INFINITY, t1 = INFINITY;
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (dir[k] != 0.0f) {
+            float lo = (-0.5f - cp[k]) / dir[k], hi = (0.5f - cp[k]) / dir[k];
+            if (lo > hi) { float q = lo; lo = hi; hi = q; }
+            if (lo > t0) t0 = lo;
+            if (hi < t1) t1 = hi;
+        } else if (cp[k] < -0.5f || cp[k] > 0.5f) miss = true;
+    }
+    const float th = t0 >= a.cam.z_near ? t0 : t1;
+    if (miss || t0 > t1 || th < a.cam.z_near || th > a.cam.z_far) return false;
+    float vuv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vuv[k] = (cp[k] + th * dir[k]) + 0.5f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cp[k];
+    norm3(gd[0], gd[1], gd[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { st[k] = gd[k] * a.P.step_size[k]; pos[k] = vuv[k]; }
+    return true;
+}
+
+// k_raycast's ray set-up and fetch, a table lookup per sample and "over" into (C, T).  The workgroup stages the table
+// (tf_stage).  A sample the skip grid bounds by (mn, mx) is skippable when next_opaque[max(mn - 1, 0)] > min(mx + 1, 255).
 template <class SAMPLER>
 __global__ void __launch_bounds__(64)
 k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf)
@@ -406,26 +463,7 @@ k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf)
     __shared__ float4 lut[256];
     __shared__ uint16_t nextOpaque[256];
     const int lane = threadIdx.x;
-    {
-        float4 e[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { e[j] = tf.lut[4 * lane + j]; lut[4 * lane + j] = e[j]; }
-        int first = 256;                                    // my four entries' first non-zero alpha
-#pragma unroll
-        for (int j = 3; j >= 0; --j) if (e[j].w != 0.0f) first = 4 * lane + j;
-        int suffix = first;                                 // min over lanes >= mine
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_down(suffix, o);
-            if (lane + o < 64) suffix = min(suffix, u);
-        }
-        const int after = __shfl_down(suffix, 1);           // min over lanes > mine
-        int carry = lane == 63 ? 256 : after;
-#pragma unroll
-        for (int j = 3; j >= 0; --j) {
-            if (e[j].w != 0.0f) carry = 4 * lane + j;
-            nextOpaque[4 * lane + j] = (uint16_t)carry;
-        }
-    }
+    tf_stage(tf, lut, nextOpaque, lane);
     __syncthreads();
     // 8x8 pixel tile per wave
     const int px = blockIdx.x * 8 + (lane & 7), py = blockIdx.y * 8 + (lane >> 3);
@@ -495,6 +533,229 @@ k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf)
             C0 = C0 + w * (e0.x + f * (e1.x - e0.x));
             C1 = C1 + w * (e0.y + f * (e1.y - e0.y));
             C2 = C2 + w * (e0.z + f * (e1.z - e0.z));
+            T = T * (1.0f - al);
+            if (!a.P.no_early_exit && T < 0.01f) break;
+        }
+    }
+    o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T;
+}
+
+// ---- gradient-shaded DVR (vr_raycast_tf_shaded; the rule is in vrhip.h) ---------------------------------------------
+// a 32-bit word at any byte address (one global_load_dword: gfx950 takes unaligned global loads)
+typedef uint32_t __attribute__((aligned(1))) u32u;
+
+// the base voxel and weights of a trilinear fetch at texture position p of a volume of extents G (tex3d's arithmetic)
+struct Lattice { int x0, y0, z0; float fx, fy, fz; };
+__device__ __forceinline__ Lattice lattice(int GX, int GY, int GZ, float px, float py, float pz)
+{
+    float x = px * (float)GX - 0.5f, y = py * (float)GY - 0.5f, z = pz * (float)GZ - 0.5f;
+    float fx0 = floorf(x), fy0 = floorf(y), fz0 = floorf(z);
+    Lattice l;
+    l.fx = x - fx0; l.fy = y - fy0; l.fz = z - fz0;
+    l.x0 = (int)fx0; l.y0 = (int)fy0; l.z0 = (int)fz0;
+    return l;
+}
+
+// The 32 voxels a lattice gradient reads, a plus-shaped set around the eight taps (indices clamped as the fetch's):
+// r[j + 2k] = v(x0-1 .. x0+2, y0+j, z0+k) in bytes 0..3; ym[k] / yp[k] = v(x0 .. x0+1, y0-1 / y0+2, z0+k) and
+// zm[j] / zp[j] = v(x0 .. x0+1, y0+j, z0-1 / z0+2) in bytes 0..1.
+struct Nbhd { uint32_t r[4], ym[2], yp[2], zm[2], zp[2]; };
+
+// the same 32 voxels through an accessor V(a, b, c) = the voxel at x slot a, y slot b, z slot c (slot q = offset q - 1)
+template <class F>
+__device__ __forceinline__ void nbhd_fill(Nbhd &n, F V)
+{
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            n.r[j + 2 * k] = V(0, 1 + j, 1 + k) | (V(1, 1 + j, 1 + k) << 8) | (V(2, 1 + j, 1 + k) << 16) | (V(3, 1 + j, 1 + k) << 24);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { n.ym[k] = V(1, 0, 1 + k) | (V(2, 0, 1 + k) << 8); n.yp[k] = V(1, 3, 1 + k) | (V(2, 3, 1 + k) << 8); }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { n.zm[j] = V(1, 1 + j, 0) | (V(2, 1 + j, 0) << 8); n.zp[j] = V(1, 1 + j, 3) | (V(2, 1 + j, 3) << 8); }
+}
+
+// dense: whole rows where the indices are consecutive -- one dword per x-row, one 16-bit word per y- or z-row pair --
+// and byte loads at a clamped edge
+__device__ __forceinline__ Nbhd gather(const DenseSampler &, const RayArgs &a, const Lattice &l)
+{
+    const Tex &t = a.t;
+    int xi[4], yi[4], zi[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        xi[q] = clampi(clampi(l.x0 + q - 1, 0, t.GX - 1) - t.ox, 0, t.X - 1);
+        yi[q] = clampi(clampi(l.y0 + q - 1, 0, t.GY - 1) - t.oy, 0, t.Y - 1);
+        zi[q] = clampi(clampi(l.z0 + q - 1, 0, t.GZ - 1) - t.oz, 0, t.Z - 1);
+    }
+    const int64_t sy = t.X, sz = (int64_t)t.X * t.Y;
+    const bool row4 = xi[3] == xi[0] + 3, pair = xi[2] == xi[1] + 1;     // clamped indices step by 0 or 1
+    auto row = [&](int b, int c) -> uint32_t {
+        const uint8_t *r = t.v + sy * yi[b] + sz * zi[c];
+        return row4 ? *(const u32u *)(r + xi[0]) : (r[xi[0]] | (r[xi[1]] << 8) | (r[xi[2]] << 16) | ((uint32_t)r[xi[3]] << 24));
+    };
+    auto two = [&](int b, int c) -> uint32_t {
+        const uint8_t *r = t.v + sy * yi[b] + sz * zi[c];
+        return pair ? (uint32_t)*(const u16u *)(r + xi[1]) : (r[xi[1]] | (r[xi[2]] << 8));
+    };
+    Nbhd n;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) n.r[j + 2 * k] = row(1 + j, 1 + k);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { n.ym[k] = two(0, 1 + k); n.yp[k] = two(3, 1 + k); }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { n.zm[j] = two(1 + j, 0); n.zp[j] = two(1 + j, 3); }
+    return n;
+}
+
+// pool: the brick cell resolved once where the 4 x 4 x 4 box of the indices lies in one cell, per voxel otherwise
+__device__ __forceinline__ Nbhd gather(const PoolTex &p, const RayArgs &a, const Lattice &l)
+{
+    int xi[4], yi[4], zi[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        xi[q] = clampi(l.x0 + q - 1, 0, a.t.GX - 1);
+        yi[q] = clampi(l.y0 + q - 1, 0, a.t.GY - 1);
+        zi[q] = clampi(l.z0 + q - 1, 0, a.t.GZ - 1);
+    }
+    Nbhd n;
+    const int cx = xi[0] >> p.lx, cy = yi[0] >> p.ly, cz = zi[0] >> p.lz;
+    if (cx == (xi[3] >> p.lx) && cy == (yi[3] >> p.ly) && cz == (zi[3] >> p.lz)) {
+        const PoolCell c = pool_cell(p, cx, cy, cz);
+        if (c.off < 0) {
+            nbhd_fill(n, [](int, int, int) -> uint32_t { return 0u; });
+        } else {
+            const int64_t sy = (int64_t)1 << (p.lx - c.sx), sz = sy << (p.ly - c.sy);
+            const int mx = (1 << p.lx) - 1, my = (1 << p.ly) - 1, mz = (1 << p.lz) - 1;
+            int64_t ox[4], oy[4], oz[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                ox[q] = (xi[q] & mx) >> c.sx; oy[q] = sy * ((yi[q] & my) >> c.sy); oz[q] = sz * ((zi[q] & mz) >> c.sz);
+            }
+            const uint8_t *b = p.pool + c.off;
+            nbhd_fill(n, [&](int u, int v, int w) -> uint32_t { return b[ox[u] + oy[v] + oz[w]]; });
+        }
+    } else {
+        nbhd_fill(n, [&](int u, int v, int w) -> uint32_t { return pool_voxel(p, xi[u], yi[v], zi[w]); });
+    }
+    return n;
+}
+
+// tex3d's interpolation of eight corner values c[i + 2j + 4k]
+__device__ __forceinline__ float trilerp(const float c[8], float fx, float fy, float fz)
+{
+    float c00 = c[0] + fx * (c[1] - c[0]), c10 = c[2] + fx * (c[3] - c[2]);
+    float c01 = c[4] + fx * (c[5] - c[4]), c11 = c[6] + fx * (c[7] - c[6]);
+    float c0 = c00 + fy * (c10 - c00), c1 = c01 + fy * (c11 - c01);
+    return c0 + fz * (c1 - c0);
+}
+
+// the lattice gradient (vrhip.h): integer central differences at the eight corners, interpolated, scaled once
+__device__ __forceinline__ void lattice_gradient(const Nbhd &n, const Lattice &l, float g[3])
+{
+    auto B = [](uint32_t w, int q) -> int { return (int)((w >> (8 * q)) & 255u); };
+    float dx[8], dy[8], dz[8];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int c = i + 2 * j + 4 * k;
+                dx[c] = (float)(B(n.r[j + 2 * k], 2 + i) - B(n.r[j + 2 * k], i));
+                dy[c] = (float)(j == 0 ? B(n.r[1 + 2 * k], 1 + i) - B(n.ym[k], i) : B(n.yp[k], i) - B(n.r[2 * k], 1 + i));
+                dz[c] = (float)(k == 0 ? B(n.r[j + 2], 1 + i) - B(n.zm[j], i) : B(n.zp[j], i) - B(n.r[j], 1 + i));
+            }
+    const float k = 1.0f / 510.0f;
+    g[0] = trilerp(dx, l.fx, l.fy, l.fz) * k;
+    g[1] = trilerp(dy, l.fx, l.fy, l.fz) * k;
+    g[2] = trilerp(dz, l.fx, l.fy, l.fz) * k;
+}
+
+struct ShadeArgs {
+    float ka, kd, ks, shininess, gmin;
+    float L[3];             // normalized light direction; head: L = V per ray
+    int head;
+};
+
+// k_raycast_tf's rule with a lit colour (vrhip.h): the sample and its alpha as there; for a sample with a > 0 the
+// 32 voxels of its lattice gradient are gathered (gather), then the head-light / directional Blinn-Phong of the
+// iso-surface shader, two-sided.  Transparent samples and empty stretches cost what they cost in k_raycast_tf.
+template <class SAMPLER>
+__global__ void __launch_bounds__(64)
+k_raycast_tf_shaded(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
+{
+    __shared__ float4 lut[256];
+    __shared__ uint16_t nextOpaque[256];
+    const int lane = threadIdx.x;
+    tf_stage(tf, lut, nextOpaque, lane);
+    __syncthreads();
+    const int px = blockIdx.x * 8 + (lane & 7), py = blockIdx.y * 8 + (lane >> 3);
+    const int W = a.P.width, H = a.P.height;
+    if (px >= W || py >= H) return;
+    float *o = a.out + 4 * ((size_t)py * W + px);
+    float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, T = 1.0f;
+    float gd[3], st[3], pos[3];
+    if (ray_enter(a, px, py, gd, st, pos)) {
+        const float L = sqrtf(st[0] * st[0] + st[1] * st[1] + st[2] * st[2]);
+        const bool correct = tf.unit > 0.0f;
+        const float ex = correct ? L / tf.unit : 0.0f;
+        // per ray: V, the light and the half vector; no specular term where L + V = 0
+        const float V0 = -gd[0], V1 = -gd[1], V2 = -gd[2];
+        const float L0 = sh.head ? V0 : sh.L[0], L1 = sh.head ? V1 : sh.L[1], L2 = sh.head ? V2 : sh.L[2];
+        float H0 = L0 + V0, H1 = L1 + V1, H2 = L2 + V2;
+        const float ks = (H0 != 0.0f || H1 != 0.0f || H2 != 0.0f) ? sh.ks : 0.0f;
+        norm3(H0, H1, H2);
+        const float GX = (float)a.t.GX, GY = (float)a.t.GY, GZ = (float)a.t.GZ;
+        const int ns = a.P.max_samples;
+        bool probe = true;
+        for (int i = 0; i < ns; ++i) {
+            pos[0] = pos[0] + st[0]; pos[1] = pos[1] + st[1]; pos[2] = pos[2] + st[2];
+            if (!inside(pos[0], pos[1], pos[2])) break;
+            bool own = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.P.box_min[k] && pos[k] < a.P.box_max[k]);
+            if (!own) continue;
+            if (a.sg.g && probe) {
+                const uint32_t b = skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]);
+                const int lo = max((int)(b & 255u) - 1, 0), hi = min((int)(b >> 8) + 1, 255);
+                if ((int)nextOpaque[lo] > hi) continue;
+            }
+            const float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
+            const float x = fminf(fmaxf(smp * 255.0f, 0.0f), 255.0f);
+            const int li = min((int)x, 254);
+            const float f = x - (float)li;
+            const float4 e0 = lut[li], e1 = lut[li + 1];
+            float ea = e0.w + f * (e1.w - e0.w);
+            ea = fminf(fmaxf(ea, 0.0f), 1.0f);
+            float al = ea;
+            if (correct) {
+                const float p = ex == 0.0f ? 1.0f : exp2f(ex * log2f(1.0f - ea));
+                al = 1.0f - p;
+            }
+            probe = al == 0.0f;
+            if (probe) continue;        // a = 0: both updates would be exact no-ops
+            float c0 = e0.x + f * (e1.x - e0.x), c1 = e0.y + f * (e1.y - e0.y), c2 = e0.z + f * (e1.z - e0.z);
+            {
+                const Lattice l = lattice(a.t.GX, a.t.GY, a.t.GZ, pos[0], pos[1], pos[2]);
+                float g[3];
+                lattice_gradient(gather(tex, a, l), l, g);
+                const float m = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+                if (m > sh.gmin) {
+                    float N0 = GX * g[0], N1 = GY * g[1], N2 = GZ * g[2];
+                    norm3(N0, N1, N2);
+                    const float cd = fabsf(N0 * L0 + N1 * L1 + N2 * L2);
+                    const float ch = fminf(fmaxf(fabsf(N0 * H0 + N1 * H1 + N2 * H2), 0.00001f), 1.0f);
+                    const float kl = sh.ka + sh.kd * cd, sp = ks * powf(ch, sh.shininess);
+                    c0 = fminf(1.0f, c0 * kl + sp); c1 = fminf(1.0f, c1 * kl + sp); c2 = fminf(1.0f, c2 * kl + sp);
+                }
+            }
+            const float w = T * al;
+            C0 = C0 + w * c0;
+            C1 = C1 + w * c1;
+            C2 = C2 + w * c2;
             T = T * (1.0f - al);
             if (!a.P.no_early_exit && T < 0.01f) break;
         }
@@ -702,6 +963,41 @@ int raycast_pool_tf_launch(const uint8_t *pool, const vr_pool_entry *tab, const 
     dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
     hipLaunchKernelGGL(k_raycast_tf<PoolTex>, g, dim3(64), 0, st, a, pt, tf_args(tf));
     return launch_status("raymarch_pool_tf");
+}
+
+// the lighting constants; a non-zero light_dir is normalized in double (a tiny one stays a direction)
+static ShadeArgs shade_args(const vr_shading *sh)
+{
+    ShadeArgs s;
+    s.ka = sh->ambient; s.kd = sh->diffuse; s.ks = sh->specular; s.shininess = sh->shininess; s.gmin = sh->grad_min;
+    const double l[3] = {sh->light_dir[0], sh->light_dir[1], sh->light_dir[2]};
+    const double n = sqrt(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+    s.head = n > 0.0 ? 0 : 1;
+    for (int k = 0; k < 3; ++k) s.L[k] = n > 0.0 ? (float)(l[k] / n) : 0.0f;
+    return s;
+}
+
+int raycast_tf_shaded_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                             const vr_transfer_function *tf, const vr_shading *sh, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    dense_args(a, vol, dims, P);
+    ray_frame(a, cam, P, rgba);
+    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
+    hipLaunchKernelGGL(k_raycast_tf_shaded<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler(), tf_args(tf), shade_args(sh));
+    return launch_status("raymarch_tf_shaded");
+}
+
+int raycast_pool_tf_shaded_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                                  const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf,
+                                  const vr_shading *sh, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
+    ray_frame(a, cam, P, rgba);
+    dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
+    hipLaunchKernelGGL(k_raycast_tf_shaded<PoolTex>, g, dim3(64), 0, st, a, pt, tf_args(tf), shade_args(sh));
+    return launch_status("raymarch_pool_tf_shaded");
 }
 
 int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,

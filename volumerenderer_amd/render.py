@@ -395,6 +395,78 @@ def raycast_pool_tf(pool, table, brick_dims, grid, cam, params, tf, out=None, st
     return out
 
 
+# ---- gradient-shaded direct volume rendering (vr_raycast_tf_shaded; the rule is in vrhip.h) ---------------------------
+class Shading:
+    """Lighting for raycast_tf_shaded / raycast_pool_tf_shaded (vr_shading): c = min(1, e.rgb (ambient + diffuse |N.L|)
+    + specular |N.H|^shininess) for samples whose gradient magnitude exceeds grad_min.  light_dir is the world direction
+    towards the light; (0, 0, 0) is the head light (L = V).  Raises ValueError for negative or non-finite values."""
+
+    def __init__(self, ambient=0.3, diffuse=0.7, specular=0.2, shininess=32.0, light_dir=(0.0, 0.0, 0.0), grad_min=1.0 / 255.0):
+        vals = {"ambient": ambient, "diffuse": diffuse, "specular": specular, "shininess": shininess, "grad_min": grad_min}
+        for name, v in vals.items():
+            v = float(v)
+            if not math.isfinite(v) or v < 0.0:
+                raise ValueError("%s must be finite and >= 0, not %r" % (name, vals[name]))
+            setattr(self, name, v)
+        self.light_dir = tuple(float(v) for v in light_dir)
+        if len(self.light_dir) != 3 or not all(math.isfinite(v) for v in self.light_dir):
+            raise ValueError("light_dir must be three finite values")
+
+    def desc(self):
+        d = _lib.ShadingDesc()
+        d.ambient, d.diffuse, d.specular, d.shininess = self.ambient, self.diffuse, self.specular, self.shininess
+        d.light_dir[:] = self.light_dir
+        d.grad_min = self.grad_min
+        return d
+
+
+def _check_shading(shading):
+    if not isinstance(shading, Shading):
+        raise ValueError("shading must be a Shading, not %s" % type(shading).__name__)
+
+
+def raycast_tf_shaded(volume, dims, cam, params, tf, shading, out=None, stream=None):
+    """raycast_tf with gradient lighting (vr_raycast_tf_shaded): each sample that contributes is lit by `shading`
+    through its lattice gradient.  params.mode must be RENDER_SHADED.  Returns float32 CUDA [H][W][4]."""
+    v = _as_dev_u8(volume)
+    d = (C.c_int64 * 3)(*[int(q) for q in dims])
+    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
+        raise ValueError("volume size does not match dims")
+    _check_attached_grid(params, dims, v.device)
+    _check_tf(tf, v.device)
+    _check_shading(shading)
+    if out is None:
+        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=v.device)
+    else:
+        _check_buf(out, "out", torch.float32, params.height * params.width * 4, v.device)
+    desc, sh = tf.desc(), shading.desc()
+    check(_lib.lib().vr_raycast_tf_shaded(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
+                                          C.byref(sh), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_tf_shaded")
+    return out
+
+
+def raycast_pool_tf_shaded(pool, table, brick_dims, grid, cam, params, tf, shading, out=None, stream=None):
+    """raycast_tf_shaded of the virtual volume of a pool (vr_raycast_pool_tf_shaded): bit-identical to
+    raycast_tf_shaded of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
+    if not isinstance(pool, torch.Tensor):
+        raise ValueError("pool must be a torch tensor")
+    _check_pool(pool, table, grid, pool.device)
+    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
+    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
+    _check_tf(tf, pool.device)
+    _check_shading(shading)
+    if out is None:
+        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=pool.device)
+    else:
+        _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
+    desc, sh = tf.desc(), shading.desc()
+    check(_lib.lib().vr_raycast_pool_tf_shaded(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g,
+                                               C.byref(cam), C.byref(params), C.byref(desc), C.byref(sh),
+                                               C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_pool_tf_shaded")
+    return out
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}
