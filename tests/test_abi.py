@@ -85,6 +85,123 @@ def test_argument_validation_and_no_cpu_fallback(L):
         assert L.vr_compositor_create_with_transport(C.byref(h), table, None, 0, 1, 64, 1) == -2
 
 
+# the six ray-casting entry points: (source, style)
+RAYCAST_ENTRIES = {"vr_raycast": ("dense", "grey"), "vr_raycast_pool": ("pool", "grey"),
+                   "vr_raycast_tf": ("dense", "table"), "vr_raycast_pool_tf": ("pool", "table"),
+                   "vr_raycast_tf_shaded": ("dense", "lit"), "vr_raycast_pool_tf_shaded": ("pool", "lit")}
+
+
+@pytest.mark.parametrize("entry", sorted(RAYCAST_ENTRIES))
+def test_raycast_entries_reject_bad_arguments_before_the_device(L, entry):
+    """Every ray-casting entry point faces the bad inputs of its source kind (dense volume or pool) and its style
+    (greyscale, table, lit): each pointer null in turn, the frame, the extents, the mode, the table and the lighting."""
+    import math
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_transfer_function_cpu import _Bufs
+    from volumerenderer_amd import _lib
+    from volumerenderer_amd import render as R
+    source, style = RAYCAST_ENTRIES[entry]
+    n = C.c_int32(-1)
+    assert L.vr_device_count(C.byref(n)) == 0
+    B = _Bufs(L, n.value)
+    I64 = C.c_int64 * 3
+    fn = getattr(L, entry)
+    valid_mode = _lib.RENDER_SHADED if style == "lit" else _lib.RENDER_COMPOSITE
+
+    def params(**kw):
+        P = R.default_params(8, 8, (4, 4, 4), valid_mode)
+        for k, v in kw.items():
+            if isinstance(v, tuple):
+                getattr(P, k)[:] = v
+            else:
+                setattr(P, k, v)
+        return P
+
+    def tf(lut=B.lut, unit=0.0, bg=(1.0, 1.0, 1.0)):
+        t = _lib.TransferFunctionDesc()
+        t.lut_dev, t.opacity_unit = lut, unit
+        t.background[:] = bg
+        return t
+
+    def sh(**kw):
+        s = R.Shading().desc()
+        for k, v in kw.items():
+            if k == "light_dir":
+                s.light_dir[:] = v
+            else:
+                setattr(s, k, v)
+        return s
+
+    def call(**kw):
+        a = dict(vol=B.vol, dims=I64(4, 4, 4), pool=B.vol, table=B.table, bd=I64(4, 4, 4), grid=I64(1, 1, 1),
+                 cam=R.default_camera(), P=params(), tf=tf(), sh=sh(), rgba=B.img)
+        a.update(kw)
+        ref = [None if a[k] is None else C.byref(a[k]) for k in ("cam", "P", "tf", "sh")]
+        cam, P, t, s = ref
+        if source == "dense":
+            head = [a["vol"], a["dims"]]
+        else:
+            head = [a["pool"], a["table"], a["bd"], a["grid"]]
+        tail = {"grey": [], "table": [t], "lit": [t, s]}[style]
+        return fn(*head, cam, P, *tail, a["rgba"], None)
+
+    try:
+        bad = []
+        # every pointer argument null in turn
+        ptrs = ["vol", "dims"] if source == "dense" else ["pool", "table", "bd", "grid"]
+        ptrs += ["cam", "P", "rgba"] + {"grey": [], "table": ["tf"], "lit": ["tf", "sh"]}[style]
+        bad += [{p: None} for p in ptrs]
+        # the frame
+        bad += [{"P": params(width=0)}, {"P": params(width=-8)}, {"P": params(height=0)}, {"P": params(height=-1)},
+                {"P": params(max_samples=-1)}]
+        if source == "dense":
+            for d in ((0, 16, 16), (16, -1, 16), (16, 16, -(1 << 40)), (1 << 31, 1, 1), (1, 1 << 31, 1), (1, 1, 1 << 40),
+                      (-1, -1, 1)):
+                bad.append({"dims": I64(*d)})
+        else:
+            for b in ((4, 6, 4), (0, 4, 4), (4, -4, 4), (4, 4, 3), (-(1 << 40), 4, 4)):     # not positive powers of two
+                bad.append({"bd": I64(*b)})
+            for g in ((0, 1, 1), (1, -1, 1), (1, 1, 0)):
+                bad.append({"grid": I64(*g)})
+            # a virtual extent of 2^31 voxels or more
+            bad += [{"grid": I64(1 << 29, 1, 1)}, {"grid": I64(1, 1 << 40, 1)}, {"bd": I64(1 << 31, 4, 4)},
+                    {"bd": I64(4, 4, 1 << 20), "grid": I64(1, 1, 1 << 11)}]
+            for k in range(3):
+                o = [0, 0, 0]
+                o[k] = 1
+                bad.append({"P": params(vol_origin=tuple(o))})
+                o[k] = -1
+                bad.append({"P": params(vol_origin=tuple(o))})
+                gd = [4, 4, 4]
+                gd[k] = 8
+                bad.append({"P": params(global_dims=tuple(gd))})
+                gd[k] = -4
+                bad.append({"P": params(global_dims=tuple(gd))})
+        # the mode of the style
+        modes = {"grey": (-1, 3, 4), "table": (-1, 1, 2, 3, 4), "lit": (-1, 0, 1, 2, 4)}[style]
+        bad += [{"P": params(mode=m)} for m in modes]
+        if style != "grey":
+            bad += [{"tf": t} for t in (tf(lut=None), tf(lut=B.lut + 4), tf(lut=B.lut + 8), tf(unit=-1e-6),
+                                        tf(unit=math.inf), tf(unit=math.nan), tf(bg=(1.0, math.nan, 1.0)),
+                                        tf(bg=(math.inf, 0.0, 0.0)), tf(bg=(0.0, 0.0, -math.inf)))]
+        if style == "lit":
+            for f in ("ambient", "diffuse", "specular", "shininess", "grad_min"):
+                bad += [{"sh": sh(**{f: v})} for v in (-1e-6, math.nan, math.inf)]
+            bad += [{"sh": sh(light_dir=(0.0, math.nan, 1.0))}, {"sh": sh(light_dir=(math.inf, 0.0, 0.0))}]
+        for k, kw in enumerate(bad):
+            assert call(**kw) == -1, (entry, k, sorted(kw))
+        if n.value == 0:
+            # valid arguments reach the device check: no CPU fallback
+            assert call() == -2
+            if source == "pool":
+                assert call(P=params(global_dims=(4, 4, 4))) == -2
+            if style == "lit":
+                assert call(sh=sh(light_dir=(-1.0, -2.0, 0.5), ambient=0.0, shininess=0.0, grad_min=0.0)) == -2
+    finally:
+        B.free()
+
+
 def test_product_never_imports_oracle():
     """The oracle and the reference build beside it (oracle/_ref/libvkref.so) are test infrastructure: nothing under
     volumerenderer_amd/ or include/ may reference either."""

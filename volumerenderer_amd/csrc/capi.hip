@@ -17,22 +17,14 @@
 using namespace vr;
 
 namespace vr {
-int raycast_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, float *, hipStream_t);
+int raycast_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, const vr_transfer_function *,
+                   const vr_shading *, float *, hipStream_t);
+int raycast_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
+                        const vr_render_params *, const vr_transfer_function *, const vr_shading *, float *, hipStream_t);
 int composite_over_launch(float *, const float *, int64_t, hipStream_t);
 int skip_grid_launch(const uint8_t *, const int64_t dims[3], int, uint8_t *, hipStream_t);
-int raycast_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
-                        const vr_render_params *, float *, hipStream_t);
 int skip_grid_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], int, uint8_t *,
                           hipStream_t);
-int raycast_tf_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *,
-                      const vr_transfer_function *, float *, hipStream_t);
-int raycast_pool_tf_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
-                           const vr_render_params *, const vr_transfer_function *, float *, hipStream_t);
-int raycast_tf_shaded_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *,
-                             const vr_transfer_function *, const vr_shading *, float *, hipStream_t);
-int raycast_pool_tf_shaded_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3],
-                                  const vr_camera *, const vr_render_params *, const vr_transfer_function *, const vr_shading *,
-                                  float *, hipStream_t);
 int composite_finish_launch(const float *, float *, int64_t, hipStream_t);
 int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
 int assemble_launch(bool, const uint8_t *, uint8_t *, int, const int64_t bd[3], const int64_t *, const int64_t grid[3], hipStream_t);
@@ -1097,28 +1089,25 @@ vr_status vr_disassemble_bricks(const uint8_t *volume, int32_t nb, const int64_t
     return assemble_common(false, volume, nb, bd, ijk, grid, bricks, stream);
 }
 
-vr_status vr_raycast(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                     float *rgba, void *stream)
+// The checks of the ray-casting entry points, each written once.  A frame: the camera, params and output, a positive
+// size and max_samples >= 0.
+static bool frame_ok(const vr_camera *cam, const vr_render_params *P, const float *rgba)
 {
-    if (!vol || !dims || !cam || !P || !rgba) return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
-    // tex3d clamps to [0, X-1] (-1 for X = 0) and the launch narrows the extents to int
-    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_launch(vol, dims, cam, P, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return cam && P && rgba && P->width > 0 && P->height > 0 && P->max_samples >= 0;
 }
 
-vr_status vr_skip_grid_build(const uint8_t *vol, const int64_t dims[3], int32_t cell, uint8_t *grid, void *stream)
+// a dense volume: tex3d clamps to [0, X-1] (-1 for X = 0) and the launch narrows the extents to int
+static bool dense_ok(const uint8_t *vol, const int64_t dims[3])
 {
-    if (!vol || !dims || !grid || cell <= 0 || cell > 64) return VR_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return skip_grid_launch(vol, dims, cell, grid, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    if (!vol || !dims) return false;
+    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return false;
+    return true;
 }
 
 // the virtual volume of a pool: power-of-two bricks, extents below 2^31 (tex3d's int indices)
-static bool pool_dims_ok(const int64_t bd[3], const int64_t grid[3])
+static bool pool_ok(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3])
 {
+    if (!pool || !table || !bd || !grid) return false;
     for (int k = 0; k < 3; ++k) {
         if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || grid[k] <= 0) return false;
         if (grid[k] >= (1ll << 31) / bd[k]) return false;
@@ -1126,102 +1115,112 @@ static bool pool_dims_ok(const int64_t bd[3], const int64_t grid[3])
     return true;
 }
 
-vr_status vr_raycast_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
-                          const vr_camera *cam, const vr_render_params *P, float *rgba, void *stream)
+// a pool is the whole volume: no slab origin, and global_dims (if given) its extents
+static bool pool_frame_ok(const vr_render_params *P, const int64_t bd[3], const int64_t grid[3])
 {
-    if (!pool || !table || !bd || !grid || !cam || !P || !rgba) return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
-    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
     for (int k = 0; k < 3; ++k) {
-        if (P->vol_origin[k] != 0) return VR_ERR_INVALID;
-        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return VR_ERR_INVALID;
+        if (P->vol_origin[k] != 0) return false;
+        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return false;
     }
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_pool_launch(pool, table, bd, grid, cam, P, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return true;
 }
 
-// what vr_raycast_tf / vr_raycast_pool_tf check beyond vr_raycast / vr_raycast_pool (vrhip.h)
-static bool tf_ok(const vr_transfer_function *tf, const vr_render_params *P)
+// the transfer function's table (vrhip.h)
+static bool table_ok(const vr_transfer_function *tf)
 {
     if (!tf || !tf->lut_dev || ((uintptr_t)tf->lut_dev & 15u) != 0u) return false;
     if (!(tf->opacity_unit >= 0.0f) || !isfinite(tf->opacity_unit)) return false;
     for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return false;
-    return P->mode == VR_RENDER_COMPOSITE;
+    return true;
 }
 
-vr_status vr_raycast_tf(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                        const vr_transfer_function *tf, float *rgba, void *stream)
+static bool lighting_ok(const vr_shading *sh)
 {
-    if (!vol || !dims || !cam || !P || !rgba) return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
-    if (!tf_ok(tf, P)) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_tf_launch(vol, dims, cam, P, tf, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
-}
-
-vr_status vr_raycast_pool_tf(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
-                             const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
-                             void *stream)
-{
-    if (!pool || !table || !bd || !grid || !cam || !P || !rgba) return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0 || P->mode < 0 || P->mode > 2) return VR_ERR_INVALID;
-    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) {
-        if (P->vol_origin[k] != 0) return VR_ERR_INVALID;
-        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return VR_ERR_INVALID;
-    }
-    if (!tf_ok(tf, P)) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_pool_tf_launch(pool, table, bd, grid, cam, P, tf, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
-}
-
-// vr_raycast_tf_shaded / vr_raycast_pool_tf_shaded: tf_ok's table checks with mode VR_RENDER_SHADED, and the lighting
-static bool shading_ok(const vr_transfer_function *tf, const vr_shading *sh, const vr_render_params *P)
-{
-    if (P->mode != VR_RENDER_SHADED || !sh) return false;
-    vr_render_params Q = *P;
-    Q.mode = VR_RENDER_COMPOSITE;
-    if (!tf_ok(tf, &Q)) return false;
+    if (!sh) return false;
     const float nonneg[5] = {sh->ambient, sh->diffuse, sh->specular, sh->shininess, sh->grad_min};
     for (int k = 0; k < 5; ++k) if (!(nonneg[k] >= 0.0f) || !isfinite(nonneg[k])) return false;
     for (int k = 0; k < 3; ++k) if (!isfinite(sh->light_dir[k])) return false;
     return true;
 }
 
+// The style is the entry point's, not a consequence of which pointers are null: greyscale (vr_raycast*) takes modes
+// 0..2, a table (vr_raycast*_tf) VR_RENDER_COMPOSITE, lit (vr_raycast*_tf_shaded) VR_RENDER_SHADED and the lighting.
+enum Style { GREY, TABLE, LIT };
+static bool style_ok(Style s, const vr_render_params *P, const vr_transfer_function *tf, const vr_shading *sh)
+{
+    if (s == GREY) return P->mode >= 0 && P->mode <= 2;
+    if (s == TABLE) return table_ok(tf) && P->mode == VR_RENDER_COMPOSITE;
+    return table_ok(tf) && P->mode == VR_RENDER_SHADED && lighting_ok(sh);
+}
+
+static vr_status raycast_dense(Style s, const uint8_t *vol, const int64_t dims[3], const vr_camera *cam,
+                               const vr_render_params *P, const vr_transfer_function *tf, const vr_shading *sh, float *rgba,
+                               void *stream)
+{
+    if (!frame_ok(cam, P, rgba) || !dense_ok(vol, dims) || !style_ok(s, P, tf, sh)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_launch(vol, dims, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+static vr_status raycast_pool(Style s, const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3],
+                              const int64_t grid[3], const vr_camera *cam, const vr_render_params *P,
+                              const vr_transfer_function *tf, const vr_shading *sh, float *rgba, void *stream)
+{
+    if (!frame_ok(cam, P, rgba) || !pool_ok(pool, table, bd, grid) || !pool_frame_ok(P, bd, grid) || !style_ok(s, P, tf, sh))
+        return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_pool_launch(pool, table, bd, grid, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_raycast(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                     float *rgba, void *stream)
+{
+    return raycast_dense(GREY, vol, dims, cam, P, nullptr, nullptr, rgba, stream);
+}
+
+vr_status vr_raycast_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                          const vr_camera *cam, const vr_render_params *P, float *rgba, void *stream)
+{
+    return raycast_pool(GREY, pool, table, bd, grid, cam, P, nullptr, nullptr, rgba, stream);
+}
+
+vr_status vr_raycast_tf(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                        const vr_transfer_function *tf, float *rgba, void *stream)
+{
+    return raycast_dense(TABLE, vol, dims, cam, P, tf, nullptr, rgba, stream);
+}
+
+vr_status vr_raycast_pool_tf(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                             const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
+                             void *stream)
+{
+    return raycast_pool(TABLE, pool, table, bd, grid, cam, P, tf, nullptr, rgba, stream);
+}
+
 vr_status vr_raycast_tf_shaded(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
                                const vr_transfer_function *tf, const vr_shading *sh, float *rgba, void *stream)
 {
-    if (!vol || !dims || !cam || !P || !rgba) return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0) return VR_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] >= (1ll << 31)) return VR_ERR_INVALID;
-    if (!shading_ok(tf, sh, P)) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_tf_shaded_launch(vol, dims, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return raycast_dense(LIT, vol, dims, cam, P, tf, sh, rgba, stream);
 }
 
 vr_status vr_raycast_pool_tf_shaded(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
                                     const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf,
                                     const vr_shading *sh, float *rgba, void *stream)
 {
-    if (!pool || !table || !bd || !grid || !cam || !P || !rgba) return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || P->max_samples < 0) return VR_ERR_INVALID;
-    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) {
-        if (P->vol_origin[k] != 0) return VR_ERR_INVALID;
-        if (P->global_dims[k] != 0 && P->global_dims[k] != grid[k] * bd[k]) return VR_ERR_INVALID;
-    }
-    if (!shading_ok(tf, sh, P)) return VR_ERR_INVALID;
+    return raycast_pool(LIT, pool, table, bd, grid, cam, P, tf, sh, rgba, stream);
+}
+
+vr_status vr_skip_grid_build(const uint8_t *vol, const int64_t dims[3], int32_t cell, uint8_t *grid, void *stream)
+{
+    if (!dense_ok(vol, dims) || !grid || cell <= 0 || cell > 64) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_pool_tf_shaded_launch(pool, table, bd, grid, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK
-                                                                                                                : VR_ERR_NO_DEVICE;
+    return skip_grid_launch(vol, dims, cell, grid, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }
 
 vr_status vr_skip_grid_build_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
                                   int32_t cell, uint8_t *out, void *stream)
 {
-    if (!pool || !table || !bd || !grid || !out || cell <= 0 || cell > 64) return VR_ERR_INVALID;
-    if (!pool_dims_ok(bd, grid)) return VR_ERR_INVALID;
+    if (!pool_ok(pool, table, bd, grid) || !out || cell <= 0 || cell > 64) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return skip_grid_pool_launch(pool, table, bd, grid, cell, out, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }

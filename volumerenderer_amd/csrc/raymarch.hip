@@ -419,127 +419,6 @@ __device__ __forceinline__ void tf_stage(const TfArgs &tf, float4 *lut, uint16_t
     }
 }
 
-// k_raycast's pixel ray: false where it misses the cube (or enters outside [z_near, z_far]); else the normalized
-// direction gd, the step st = gd * step_size and the entry point pos = vUV.  (k_raycast and k_raycast_tf keep their
-// inline copy of the same statements: through this function their code would be scheduled differently.)
-__device__ __forceinline__ bool ray_enter(const RayArgs &a, int px, int py, float gd[3], float st[3], float pos[3])
-{
-    const int W = a.P.width, H = a.P.height;
-    const float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
-    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
-    float dir[3], cp[3] = {a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dir[k] = a.f[k] + nx * a.tanX * a.s[k] + ny * a.tanY * a.u[k];
-    float t0 = -INFINITY, t1 = INFINITY;
-    bool miss = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (dir[k] != 0.0f) {
-            float lo = (-0.5f - cp[k]) / dir[k], hi = (0.5f - cp[k]) / dir[k];
-            if (lo > hi) { float q = lo; lo = hi; hi = q; }
-            if (lo > t0) t0 = lo;
-            if (hi < t1) t1 = hi;
-        } else if (cp[k] < -0.5f || cp[k] > 0.5f) miss = true;
-    }
-    const float th = t0 >= a.cam.z_near ? t0 : t1;
-    if (miss || t0 > t1 || th < a.cam.z_near || th > a.cam.z_far) return false;
-    float vuv[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vuv[k] = (cp[k] + th * dir[k]) + 0.5f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cp[k];
-    norm3(gd[0], gd[1], gd[2]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { st[k] = gd[k] * a.P.step_size[k]; pos[k] = vuv[k]; }
-    return true;
-}
-
-// k_raycast's ray set-up and fetch, a table lookup per sample and "over" into (C, T).  The workgroup stages the table
-// (tf_stage).  A sample the skip grid bounds by (mn, mx) is skippable when next_opaque[max(mn - 1, 0)] > min(mx + 1, 255).
-template <class SAMPLER>
-__global__ void __launch_bounds__(64)
-k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf)
-{
-    __shared__ float4 lut[256];
-    __shared__ uint16_t nextOpaque[256];
-    const int lane = threadIdx.x;
-    tf_stage(tf, lut, nextOpaque, lane);
-    __syncthreads();
-    // 8x8 pixel tile per wave
-    const int px = blockIdx.x * 8 + (lane & 7), py = blockIdx.y * 8 + (lane >> 3);
-    const int W = a.P.width, H = a.P.height;
-    if (px >= W || py >= H) return;
-    float *o = a.out + 4 * ((size_t)py * W + px);
-    const float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
-    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
-    float dir[3], cp[3] = {a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dir[k] = a.f[k] + nx * a.tanX * a.s[k] + ny * a.tanY * a.u[k];
-    float t0 = -INFINITY, t1 = INFINITY;
-    bool miss = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (dir[k] != 0.0f) {
-            float lo = (-0.5f - cp[k]) / dir[k], hi = (0.5f - cp[k]) / dir[k];
-            if (lo > hi) { float q = lo; lo = hi; hi = q; }
-            if (lo > t0) t0 = lo;
-            if (hi < t1) t1 = hi;
-        } else if (cp[k] < -0.5f || cp[k] > 0.5f) miss = true;
-    }
-    const float th = t0 >= a.cam.z_near ? t0 : t1;
-    float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, T = 1.0f;
-    if (!(miss || t0 > t1 || th < a.cam.z_near || th > a.cam.z_far)) {
-        float vuv[3], gd[3], st[3], pos[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) vuv[k] = (cp[k] + th * dir[k]) + 0.5f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cp[k];
-        norm3(gd[0], gd[1], gd[2]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { st[k] = gd[k] * a.P.step_size[k]; pos[k] = vuv[k]; }
-        // opacity correction exponent L / opacity_unit (0 = none, or L = 0: a = 1 - t^0 = 0)
-        const float L = sqrtf(st[0] * st[0] + st[1] * st[1] + st[2] * st[2]);
-        const bool correct = tf.unit > 0.0f;
-        const float ex = correct ? L / tf.unit : 0.0f;
-        const int ns = a.P.max_samples;
-        bool probe = true;      // ask the grid only while the ray is in empty space (the last sample's a was 0)
-        for (int i = 0; i < ns; ++i) {
-            pos[0] = pos[0] + st[0]; pos[1] = pos[1] + st[1]; pos[2] = pos[2] + st[2];
-            if (!inside(pos[0], pos[1], pos[2])) break;
-            bool own = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.P.box_min[k] && pos[k] < a.P.box_max[k]);
-            if (!own) continue;
-            if (a.sg.g && probe) {
-                const uint32_t b = skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]);
-                const int lo = max((int)(b & 255u) - 1, 0), hi = min((int)(b >> 8) + 1, 255);
-                if ((int)nextOpaque[lo] > hi) continue;        // every entry the lookup can touch is transparent
-            }
-            const float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
-            const float x = fminf(fmaxf(smp * 255.0f, 0.0f), 255.0f);
-            const int li = min((int)x, 254);
-            const float f = x - (float)li;
-            const float4 e0 = lut[li], e1 = lut[li + 1];
-            float ea = e0.w + f * (e1.w - e0.w);
-            ea = fminf(fmaxf(ea, 0.0f), 1.0f);
-            float al = ea;
-            if (correct) {
-                // 1 - (1 - ea)^ex: ea = 0 -> log2(1) = 0 -> exactly 0; ea = 1 -> log2(0) = -inf -> exp2(-inf) = 0 -> 1
-                const float p = ex == 0.0f ? 1.0f : exp2f(ex * log2f(1.0f - ea));
-                al = 1.0f - p;
-            }
-            probe = al == 0.0f;
-            const float w = T * al;
-            C0 = C0 + w * (e0.x + f * (e1.x - e0.x));
-            C1 = C1 + w * (e0.y + f * (e1.y - e0.y));
-            C2 = C2 + w * (e0.z + f * (e1.z - e0.z));
-            T = T * (1.0f - al);
-            if (!a.P.no_early_exit && T < 0.01f) break;
-        }
-    }
-    o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T;
-}
-
 // ---- gradient-shaded DVR (vr_raycast_tf_shaded; the rule is in vrhip.h) ---------------------------------------------
 // a 32-bit word at any byte address (one global_load_dword: gfx950 takes unaligned global loads)
 typedef uint32_t __attribute__((aligned(1))) u32u;
@@ -680,37 +559,65 @@ struct ShadeArgs {
     int head;
 };
 
-// k_raycast_tf's rule with a lit colour (vrhip.h): the sample and its alpha as there; for a sample with a > 0 the
-// 32 voxels of its lattice gradient are gathered (gather), then the head-light / directional Blinn-Phong of the
-// iso-surface shader, two-sided.  Transparent samples and empty stretches cost what they cost in k_raycast_tf.
-template <class SAMPLER>
+// k_raycast's ray set-up and fetch, a table lookup per sample and "over" into (C, T).  The workgroup stages the table
+// (tf_stage).  A sample the skip grid bounds by (mn, mx) is skippable when next_opaque[max(mn - 1, 0)] > min(mx + 1, 255).
+// LIT (vr_raycast_tf_shaded; the rule is in vrhip.h): a sample with a > 0 gathers the 32 voxels of its lattice gradient
+// (gather) and takes the head-light / directional Blinn-Phong of the iso-surface shader, two-sided, as its colour;
+// transparent samples and empty stretches cost what they cost unlit.  The ray set-up is an inline copy of k_raycast's,
+// and the lit and unlit "over" are written out apart: a shared function or a shared update schedules the code differently.
+template <class SAMPLER, bool LIT>
 __global__ void __launch_bounds__(64)
-k_raycast_tf_shaded(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
+k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
 {
     __shared__ float4 lut[256];
     __shared__ uint16_t nextOpaque[256];
     const int lane = threadIdx.x;
     tf_stage(tf, lut, nextOpaque, lane);
     __syncthreads();
+    // 8x8 pixel tile per wave
     const int px = blockIdx.x * 8 + (lane & 7), py = blockIdx.y * 8 + (lane >> 3);
     const int W = a.P.width, H = a.P.height;
     if (px >= W || py >= H) return;
     float *o = a.out + 4 * ((size_t)py * W + px);
+    const float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
+    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
+    float dir[3], cp[3] = {a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dir[k] = a.f[k] + nx * a.tanX * a.s[k] + ny * a.tanY * a.u[k];
+    float t0 = -INFINITY, t1 = INFINITY;
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (dir[k] != 0.0f) {
+            float lo = (-0.5f - cp[k]) / dir[k], hi = (0.5f - cp[k]) / dir[k];
+            if (lo > hi) { float q = lo; lo = hi; hi = q; }
+            if (lo > t0) t0 = lo;
+            if (hi < t1) t1 = hi;
+        } else if (cp[k] < -0.5f || cp[k] > 0.5f) miss = true;
+    }
+    const float th = t0 >= a.cam.z_near ? t0 : t1;
     float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, T = 1.0f;
-    float gd[3], st[3], pos[3];
-    if (ray_enter(a, px, py, gd, st, pos)) {
+    if (!(miss || t0 > t1 || th < a.cam.z_near || th > a.cam.z_far)) {
+        float vuv[3], gd[3], st[3], pos[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) vuv[k] = (cp[k] + th * dir[k]) + 0.5f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cp[k];
+        norm3(gd[0], gd[1], gd[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { st[k] = gd[k] * a.P.step_size[k]; pos[k] = vuv[k]; }
+        // opacity correction exponent L / opacity_unit (0 = none, or L = 0: a = 1 - t^0 = 0)
         const float L = sqrtf(st[0] * st[0] + st[1] * st[1] + st[2] * st[2]);
         const bool correct = tf.unit > 0.0f;
         const float ex = correct ? L / tf.unit : 0.0f;
-        // per ray: V, the light and the half vector; no specular term where L + V = 0
+        // LIT, per ray: V, the light and the half vector; no specular term where L + V = 0
         const float V0 = -gd[0], V1 = -gd[1], V2 = -gd[2];
         const float L0 = sh.head ? V0 : sh.L[0], L1 = sh.head ? V1 : sh.L[1], L2 = sh.head ? V2 : sh.L[2];
         float H0 = L0 + V0, H1 = L1 + V1, H2 = L2 + V2;
         const float ks = (H0 != 0.0f || H1 != 0.0f || H2 != 0.0f) ? sh.ks : 0.0f;
         norm3(H0, H1, H2);
-        const float GX = (float)a.t.GX, GY = (float)a.t.GY, GZ = (float)a.t.GZ;
         const int ns = a.P.max_samples;
-        bool probe = true;
+        bool probe = true;      // ask the grid only while the ray is in empty space (the last sample's a was 0)
         for (int i = 0; i < ns; ++i) {
             pos[0] = pos[0] + st[0]; pos[1] = pos[1] + st[1]; pos[2] = pos[2] + st[2];
             if (!inside(pos[0], pos[1], pos[2])) break;
@@ -721,7 +628,7 @@ k_raycast_tf_shaded(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
             if (a.sg.g && probe) {
                 const uint32_t b = skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]);
                 const int lo = max((int)(b & 255u) - 1, 0), hi = min((int)(b >> 8) + 1, 255);
-                if ((int)nextOpaque[lo] > hi) continue;
+                if ((int)nextOpaque[lo] > hi) continue;        // every entry the lookup can touch is transparent
             }
             const float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
             const float x = fminf(fmaxf(smp * 255.0f, 0.0f), 255.0f);
@@ -732,30 +639,36 @@ k_raycast_tf_shaded(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
             ea = fminf(fmaxf(ea, 0.0f), 1.0f);
             float al = ea;
             if (correct) {
+                // 1 - (1 - ea)^ex: ea = 0 -> log2(1) = 0 -> exactly 0; ea = 1 -> log2(0) = -inf -> exp2(-inf) = 0 -> 1
                 const float p = ex == 0.0f ? 1.0f : exp2f(ex * log2f(1.0f - ea));
                 al = 1.0f - p;
             }
             probe = al == 0.0f;
-            if (probe) continue;        // a = 0: both updates would be exact no-ops
-            float c0 = e0.x + f * (e1.x - e0.x), c1 = e0.y + f * (e1.y - e0.y), c2 = e0.z + f * (e1.z - e0.z);
-            {
+            if (LIT) {
+                if (probe) continue;        // a = 0: both updates would be exact no-ops
+                float c0 = e0.x + f * (e1.x - e0.x), c1 = e0.y + f * (e1.y - e0.y), c2 = e0.z + f * (e1.z - e0.z);
                 const Lattice l = lattice(a.t.GX, a.t.GY, a.t.GZ, pos[0], pos[1], pos[2]);
                 float g[3];
                 lattice_gradient(gather(tex, a, l), l, g);
                 const float m = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
                 if (m > sh.gmin) {
-                    float N0 = GX * g[0], N1 = GY * g[1], N2 = GZ * g[2];
+                    float N0 = (float)a.t.GX * g[0], N1 = (float)a.t.GY * g[1], N2 = (float)a.t.GZ * g[2];
                     norm3(N0, N1, N2);
                     const float cd = fabsf(N0 * L0 + N1 * L1 + N2 * L2);
                     const float ch = fminf(fmaxf(fabsf(N0 * H0 + N1 * H1 + N2 * H2), 0.00001f), 1.0f);
                     const float kl = sh.ka + sh.kd * cd, sp = ks * powf(ch, sh.shininess);
                     c0 = fminf(1.0f, c0 * kl + sp); c1 = fminf(1.0f, c1 * kl + sp); c2 = fminf(1.0f, c2 * kl + sp);
                 }
+                const float w = T * al;
+                C0 = C0 + w * c0;
+                C1 = C1 + w * c1;
+                C2 = C2 + w * c2;
+            } else {
+                const float w = T * al;
+                C0 = C0 + w * (e0.x + f * (e1.x - e0.x));
+                C1 = C1 + w * (e0.y + f * (e1.y - e0.y));
+                C2 = C2 + w * (e0.z + f * (e1.z - e0.z));
             }
-            const float w = T * al;
-            C0 = C0 + w * c0;
-            C1 = C1 + w * c1;
-            C2 = C2 + w * c2;
             T = T * (1.0f - al);
             if (!a.P.no_early_exit && T < 0.01f) break;
         }
@@ -942,29 +855,6 @@ static TfArgs tf_args(const vr_transfer_function *tf)
     return t;
 }
 
-int raycast_tf_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                      const vr_transfer_function *tf, float *rgba, hipStream_t st)
-{
-    RayArgs a;
-    dense_args(a, vol, dims, P);
-    ray_frame(a, cam, P, rgba);
-    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast_tf<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler(), tf_args(tf));
-    return launch_status("raymarch_tf");
-}
-
-int raycast_pool_tf_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
-                           const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
-                           hipStream_t st)
-{
-    RayArgs a;
-    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
-    ray_frame(a, cam, P, rgba);
-    dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast_tf<PoolTex>, g, dim3(64), 0, st, a, pt, tf_args(tf));
-    return launch_status("raymarch_pool_tf");
-}
-
 // the lighting constants; a non-zero light_dir is normalized in double (a tiny one stays a direction)
 static ShadeArgs shade_args(const vr_shading *sh)
 {
@@ -977,49 +867,38 @@ static ShadeArgs shade_args(const vr_shading *sh)
     return s;
 }
 
-int raycast_tf_shaded_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                             const vr_transfer_function *tf, const vr_shading *sh, float *rgba, hipStream_t st)
+// The frame of a through k_raycast (no table), k_raycast_tf (a table) or its lit instantiation (a table and lighting);
+// label[style] names the launch in errors
+template <class SAMPLER>
+static int march_launch(const RayArgs &a, const SAMPLER &tex, const vr_transfer_function *tf, const vr_shading *sh,
+                        const char *const label[3], hipStream_t st)
 {
-    RayArgs a;
-    dense_args(a, vol, dims, P);
-    ray_frame(a, cam, P, rgba);
-    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast_tf_shaded<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler(), tf_args(tf), shade_args(sh));
-    return launch_status("raymarch_tf_shaded");
-}
-
-int raycast_pool_tf_shaded_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
-                                  const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf,
-                                  const vr_shading *sh, float *rgba, hipStream_t st)
-{
-    RayArgs a;
-    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
-    ray_frame(a, cam, P, rgba);
-    dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast_tf_shaded<PoolTex>, g, dim3(64), 0, st, a, pt, tf_args(tf), shade_args(sh));
-    return launch_status("raymarch_pool_tf_shaded");
+    const dim3 grid((a.P.width + 7) / 8, (a.P.height + 7) / 8);
+    if (!tf) hipLaunchKernelGGL(k_raycast<SAMPLER>, grid, dim3(64), 0, st, a, tex);
+    else if (!sh) hipLaunchKernelGGL((k_raycast_tf<SAMPLER, false>), grid, dim3(64), 0, st, a, tex, tf_args(tf), ShadeArgs());
+    else hipLaunchKernelGGL((k_raycast_tf<SAMPLER, true>), grid, dim3(64), 0, st, a, tex, tf_args(tf), shade_args(sh));
+    return launch_status(label[!tf ? 0 : (!sh ? 1 : 2)]);
 }
 
 int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                   float *rgba, hipStream_t st)
+                   const vr_transfer_function *tf, const vr_shading *sh, float *rgba, hipStream_t st)
 {
+    static const char *const label[3] = {"raymarch", "raymarch_tf", "raymarch_tf_shaded"};
     RayArgs a;
     dense_args(a, vol, dims, P);
     ray_frame(a, cam, P, rgba);
-    dim3 grid((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast<DenseSampler>, grid, dim3(64), 0, st, a, DenseSampler());
-    return launch_status("raymarch");
+    return march_launch(a, DenseSampler(), tf, sh, label, st);
 }
 
 int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
-                        const vr_camera *cam, const vr_render_params *P, float *rgba, hipStream_t st)
+                        const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, const vr_shading *sh,
+                        float *rgba, hipStream_t st)
 {
+    static const char *const label[3] = {"raymarch_pool", "raymarch_pool_tf", "raymarch_pool_tf_shaded"};
     RayArgs a;
     const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
     ray_frame(a, cam, P, rgba);
-    dim3 g((P->width + 7) / 8, (P->height + 7) / 8);
-    hipLaunchKernelGGL(k_raycast<PoolTex>, g, dim3(64), 0, st, a, pt);
-    return launch_status("raymarch_pool");
+    return march_launch(a, pt, tf, sh, label, st);
 }
 
 // k_skip_grid over a pool's virtual volume: the same cells, rows and bounds; a row's voxels come from the stored voxels of

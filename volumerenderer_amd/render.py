@@ -68,6 +68,32 @@ def _skip_grid_bytes(dims, cell):
     return n
 
 
+def _dense_source(volume, dims):
+    """A dense volume and its extents as ctypes int64[3]; ValueError where they do not match."""
+    v = _as_dev_u8(volume)
+    d = (C.c_int64 * 3)(*[int(q) for q in dims])
+    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
+        raise ValueError("volume size does not match dims")
+    return v, d
+
+
+def _check_attached_grid(params, dims, device):
+    if params.skip_grid_dev and params.skip_cell > 0:
+        # the grid must describe THIS volume at THIS cell size, or skip_bounds reads past it
+        g = getattr(params, "_keep_grid", None)
+        if g is None or g.data_ptr() != params.skip_grid_dev:
+            raise ValueError("attach skip grids with use_skip_grid()")
+        _check_buf(g, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), device)
+
+
+def _frame_out(out, params, device):
+    """The [H][W][4] float32 frame: `out` checked, or a new tensor."""
+    if out is None:
+        return torch.empty((params.height, params.width, 4), dtype=torch.float32, device=device)
+    _check_buf(out, "out", torch.float32, params.height * params.width * 4, device)
+    return out
+
+
 def build_skip_grid(volume, dims, cell=8, out=None, stream=None):
     """(min, max) per cell^3 voxels (+1 voxel reach of a trilinear fetch) of a device volume: 2 bytes per cell.
     Attach to render params with use_skip_grid(); the frame stays bit-identical, the marcher just does not fetch
@@ -97,20 +123,9 @@ def use_skip_grid(params, grid, cell=8):
 
 def raycast(volume, dims, cam, params, out=None, stream=None):
     """volume: CUDA uint8 (X*Y*Z, x fastest). Returns float32 CUDA [H][W][4], row 0 = top."""
-    v = _as_dev_u8(volume)
-    d = (C.c_int64 * 3)(*[int(q) for q in dims])
-    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
-        raise ValueError("volume size does not match dims")
-    if params.skip_grid_dev and params.skip_cell > 0:
-        # the grid must describe THIS volume at THIS cell size, or skip_bounds reads past it
-        g = getattr(params, "_keep_grid", None)
-        if g is None or g.data_ptr() != params.skip_grid_dev:
-            raise ValueError("attach skip grids with use_skip_grid()")
-        _check_buf(g, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), v.device)
-    if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=v.device)
-    else:
-        _check_buf(out, "out", torch.float32, params.height * params.width * 4, v.device)
+    v, d = _dense_source(volume, dims)
+    _check_attached_grid(params, dims, v.device)
+    out = _frame_out(out, params, v.device)
     check(_lib.lib().vr_raycast(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params),
                                 C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast")
     return out
@@ -225,6 +240,14 @@ def _check_pool(pool, table, grid, device):
     _check_buf(pool, "pool", torch.uint8, pool.numel(), device)
 
 
+def _pool_source(pool, table, brick_dims, grid):
+    """A pool and its table checked; the brick extents and the grid as ctypes int64[3]."""
+    if not isinstance(pool, torch.Tensor):
+        raise ValueError("pool must be a torch tensor")
+    _check_pool(pool, table, grid, pool.device)
+    return (C.c_int64 * 3)(*[int(q) for q in brick_dims]), (C.c_int64 * 3)(*[int(q) for q in grid])
+
+
 def build_skip_grid_pool(pool, table, brick_dims, grid, cell=8, out=None, stream=None):
     """build_skip_grid of the virtual volume of a pool (vr_skip_grid_build_pool): the same bytes as build_skip_grid of
     that volume assembled densely.  pool, table: as BrickSet.decode_lod_pool returns them."""
@@ -250,21 +273,9 @@ def raycast_pool(pool, table, brick_dims, grid, cam, params, out=None, stream=No
     """raycast of the virtual volume of a pool (vr_raycast_pool): bit-identical to raycast of that volume assembled
     densely (absent bricks 0).  A skip grid attached with use_skip_grid must come from build_skip_grid_pool (or
     build_skip_grid of the dense volume).  Returns float32 CUDA [H][W][4]."""
-    if not isinstance(pool, torch.Tensor):
-        raise ValueError("pool must be a torch tensor")
-    _check_pool(pool, table, grid, pool.device)
-    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
-    g = (C.c_int64 * 3)(*[int(q) for q in grid])
-    dims = [g[k] * bd[k] for k in range(3)]
-    if params.skip_grid_dev and params.skip_cell > 0:
-        kg = getattr(params, "_keep_grid", None)
-        if kg is None or kg.data_ptr() != params.skip_grid_dev:
-            raise ValueError("attach skip grids with use_skip_grid()")
-        _check_buf(kg, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), pool.device)
-    if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=pool.device)
-    else:
-        _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
+    bd, g = _pool_source(pool, table, brick_dims, grid)
+    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
+    out = _frame_out(out, params, pool.device)
     check(_lib.lib().vr_raycast_pool(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
                                      C.byref(params), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_pool")
     return out
@@ -345,29 +356,14 @@ def _check_tf(tf, device):
     _check_buf(tf.lut, "tf.lut", torch.float32, 256 * 4, device)
 
 
-def _check_attached_grid(params, dims, device):
-    if params.skip_grid_dev and params.skip_cell > 0:
-        # the grid must describe THIS volume at THIS cell size, or skip_bounds reads past it
-        g = getattr(params, "_keep_grid", None)
-        if g is None or g.data_ptr() != params.skip_grid_dev:
-            raise ValueError("attach skip grids with use_skip_grid()")
-        _check_buf(g, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), device)
-
-
 def raycast_tf(volume, dims, cam, params, tf, out=None, stream=None):
     """raycast's frame set-up with the transfer function `tf` (vr_raycast_tf): each sample is looked up in tf's table
     and composited front to back.  params.mode must be RENDER_COMPOSITE.  Returns float32 CUDA [H][W][4] =
     (C + T * background, 1 - T), row 0 = top."""
-    v = _as_dev_u8(volume)
-    d = (C.c_int64 * 3)(*[int(q) for q in dims])
-    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
-        raise ValueError("volume size does not match dims")
+    v, d = _dense_source(volume, dims)
     _check_attached_grid(params, dims, v.device)
     _check_tf(tf, v.device)
-    if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=v.device)
-    else:
-        _check_buf(out, "out", torch.float32, params.height * params.width * 4, v.device)
+    out = _frame_out(out, params, v.device)
     desc = tf.desc()
     check(_lib.lib().vr_raycast_tf(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
                                    C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_tf")
@@ -377,17 +373,10 @@ def raycast_tf(volume, dims, cam, params, tf, out=None, stream=None):
 def raycast_pool_tf(pool, table, brick_dims, grid, cam, params, tf, out=None, stream=None):
     """raycast_tf of the virtual volume of a pool (vr_raycast_pool_tf): bit-identical to raycast_tf of that volume
     assembled densely.  Restrictions and skip grids as raycast_pool."""
-    if not isinstance(pool, torch.Tensor):
-        raise ValueError("pool must be a torch tensor")
-    _check_pool(pool, table, grid, pool.device)
-    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
-    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    bd, g = _pool_source(pool, table, brick_dims, grid)
     _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
     _check_tf(tf, pool.device)
-    if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=pool.device)
-    else:
-        _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
+    out = _frame_out(out, params, pool.device)
     desc = tf.desc()
     check(_lib.lib().vr_raycast_pool_tf(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
                                         C.byref(params), C.byref(desc), C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
@@ -428,17 +417,11 @@ def _check_shading(shading):
 def raycast_tf_shaded(volume, dims, cam, params, tf, shading, out=None, stream=None):
     """raycast_tf with gradient lighting (vr_raycast_tf_shaded): each sample that contributes is lit by `shading`
     through its lattice gradient.  params.mode must be RENDER_SHADED.  Returns float32 CUDA [H][W][4]."""
-    v = _as_dev_u8(volume)
-    d = (C.c_int64 * 3)(*[int(q) for q in dims])
-    if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
-        raise ValueError("volume size does not match dims")
+    v, d = _dense_source(volume, dims)
     _check_attached_grid(params, dims, v.device)
     _check_tf(tf, v.device)
     _check_shading(shading)
-    if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=v.device)
-    else:
-        _check_buf(out, "out", torch.float32, params.height * params.width * 4, v.device)
+    out = _frame_out(out, params, v.device)
     desc, sh = tf.desc(), shading.desc()
     check(_lib.lib().vr_raycast_tf_shaded(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
                                           C.byref(sh), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_tf_shaded")
@@ -448,18 +431,11 @@ def raycast_tf_shaded(volume, dims, cam, params, tf, shading, out=None, stream=N
 def raycast_pool_tf_shaded(pool, table, brick_dims, grid, cam, params, tf, shading, out=None, stream=None):
     """raycast_tf_shaded of the virtual volume of a pool (vr_raycast_pool_tf_shaded): bit-identical to
     raycast_tf_shaded of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
-    if not isinstance(pool, torch.Tensor):
-        raise ValueError("pool must be a torch tensor")
-    _check_pool(pool, table, grid, pool.device)
-    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
-    g = (C.c_int64 * 3)(*[int(q) for q in grid])
+    bd, g = _pool_source(pool, table, brick_dims, grid)
     _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
     _check_tf(tf, pool.device)
     _check_shading(shading)
-    if out is None:
-        out = torch.empty((params.height, params.width, 4), dtype=torch.float32, device=pool.device)
-    else:
-        _check_buf(out, "out", torch.float32, params.height * params.width * 4, pool.device)
+    out = _frame_out(out, params, pool.device)
     desc, sh = tf.desc(), shading.desc()
     check(_lib.lib().vr_raycast_pool_tf_shaded(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g,
                                                C.byref(cam), C.byref(params), C.byref(desc), C.byref(sh),
