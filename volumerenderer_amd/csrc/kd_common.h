@@ -147,12 +147,36 @@ __device__ __forceinline__ uint32_t dpp_u32(uint32_t identity, uint32_t v)
 {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, CTRL, ROWMASK, 0xf, false);
 }
-__device__ __forceinline__ uint32_t wave_incl_scan_add_dpp(uint32_t v)
+// Inside each 16-lane row only (row shifts, no broadcasts): four independent scans / reductions per wave.
+__device__ __forceinline__ uint32_t row_incl_scan_add_dpp(uint32_t v)
 {
     v += dpp_u32<0x111, 0xf>(0, v);   // row_shr:1
     v += dpp_u32<0x112, 0xf>(0, v);   // row_shr:2
     v += dpp_u32<0x114, 0xf>(0, v);   // row_shr:4
     v += dpp_u32<0x118, 0xf>(0, v);   // row_shr:8
+    return v;
+}
+__device__ __forceinline__ int row_max_i32_dpp(int v)   // the row's maximum, valid in its lane 15
+{
+    const uint32_t I = 0x80000000u;
+    v = max(v, (int)dpp_u32<0x111, 0xf>(I, (uint32_t)v));
+    v = max(v, (int)dpp_u32<0x112, 0xf>(I, (uint32_t)v));
+    v = max(v, (int)dpp_u32<0x114, 0xf>(I, (uint32_t)v));
+    v = max(v, (int)dpp_u32<0x118, 0xf>(I, (uint32_t)v));
+    return v;
+}
+__device__ __forceinline__ int row_min_i32_dpp(int v)   // the row's minimum, valid in its lane 15
+{
+    const uint32_t I = 0x7FFFFFFFu;
+    v = min(v, (int)dpp_u32<0x111, 0xf>(I, (uint32_t)v));
+    v = min(v, (int)dpp_u32<0x112, 0xf>(I, (uint32_t)v));
+    v = min(v, (int)dpp_u32<0x114, 0xf>(I, (uint32_t)v));
+    v = min(v, (int)dpp_u32<0x118, 0xf>(I, (uint32_t)v));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_incl_scan_add_dpp(uint32_t v)
+{
+    v = row_incl_scan_add_dpp(v);
     v += dpp_u32<0x142, 0xa>(0, v);   // row_bcast:15 into rows 1, 3
     v += dpp_u32<0x143, 0xc>(0, v);   // row_bcast:31 into rows 2, 3
     return v;
@@ -160,10 +184,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan_add_dpp(uint32_t v)
 __device__ __forceinline__ int wave_max_i32_dpp(int v)   // result valid in lane 63 (returned via readlane)
 {
     const uint32_t I = 0x80000000u;
-    v = max(v, (int)dpp_u32<0x111, 0xf>(I, (uint32_t)v));
-    v = max(v, (int)dpp_u32<0x112, 0xf>(I, (uint32_t)v));
-    v = max(v, (int)dpp_u32<0x114, 0xf>(I, (uint32_t)v));
-    v = max(v, (int)dpp_u32<0x118, 0xf>(I, (uint32_t)v));
+    v = row_max_i32_dpp(v);
     v = max(v, (int)dpp_u32<0x142, 0xa>(I, (uint32_t)v));
     v = max(v, (int)dpp_u32<0x143, 0xc>(I, (uint32_t)v));
     return __builtin_amdgcn_readlane(v, 63);
@@ -171,10 +192,7 @@ __device__ __forceinline__ int wave_max_i32_dpp(int v)   // result valid in lane
 __device__ __forceinline__ int wave_min_i32_dpp(int v)   // result valid in lane 63 (returned via readlane)
 {
     const uint32_t I = 0x7FFFFFFFu;
-    v = min(v, (int)dpp_u32<0x111, 0xf>(I, (uint32_t)v));
-    v = min(v, (int)dpp_u32<0x112, 0xf>(I, (uint32_t)v));
-    v = min(v, (int)dpp_u32<0x114, 0xf>(I, (uint32_t)v));
-    v = min(v, (int)dpp_u32<0x118, 0xf>(I, (uint32_t)v));
+    v = row_min_i32_dpp(v);
     v = min(v, (int)dpp_u32<0x142, 0xa>(I, (uint32_t)v));
     v = min(v, (int)dpp_u32<0x143, 0xc>(I, (uint32_t)v));
     return __builtin_amdgcn_readlane(v, 63);

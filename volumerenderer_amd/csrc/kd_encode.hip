@@ -339,7 +339,7 @@ __global__ void k_ctrl_init(Ctrl *ctrls, const uint8_t *rootMin, const uint8_t *
 #define EST_HEAD 4096
 
 // Segment summaries of one brick: one plane per candidate, 16 bytes (sumS, sumC, A, B) per segment in it.
-// k_est_summ writes a candidate's record with one 16-byte transaction (four lanes); the walking wave reads 64
+// k_est_summ writes a candidate's record with one 16-byte store (a segment's last lane); the walking wave reads 64
 // consecutive segments of its candidate as one contiguous kilobyte.
 #define est_at(ci, seg) (((int64_t)(ci) * summStride + (int64_t)(seg)) * 4)
 
@@ -466,67 +466,98 @@ k_est_head(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, 
     }
 }
 
-// One wave per segment, 16 consecutive nodes per lane as two chains of 8 (nodes k and k+8 share a
-// packed 16-bit register pair).  With h = (t>p ? 255-t : t) the reference's "forced" cases are
-// pd > h, so under the hypothesis floor(S/(2C+1)) == Th node k counts  <=>  pd_k > min(Th, h_k).
+// A segment's inclusive scan, maximum and minimum over its 32 lanes of the wave (two DPP rows joined by one
+// row_bcast:15); the maximum and minimum are valid in the segment's last lane.
+__device__ __forceinline__ uint32_t seg_incl_scan_add_dpp(uint32_t v)
+{
+    v = row_incl_scan_add_dpp(v);
+    return v + dpp_u32<0x142, 0xa>(0, v);       // row_bcast:15 into rows 1, 3
+}
+__device__ __forceinline__ int seg_max_i32_dpp(int v)
+{
+    v = row_max_i32_dpp(v);
+    return max(v, (int)dpp_u32<0x142, 0xa>(0x80000000u, (uint32_t)v));
+}
+__device__ __forceinline__ int seg_min_i32_dpp(int v)
+{
+    v = row_min_i32_dpp(v);
+    return min(v, (int)dpp_u32<0x142, 0xa>(0x7FFFFFFFu, (uint32_t)v));
+}
+
+// One wave per two consecutive segments: lanes 32r .. 32r+31 summarise segment g + r, 32 consecutive nodes per lane
+// as two chains of NP = 16 (nodes k and k+16 share a packed 16-bit register pair; |low| <= 16*510 and cc <= 16 per
+// chain fit).  A segment's scan and extremes stay inside its two DPP rows, so the per-lane epilogue of a candidate
+// serves two segments (one segment per wave and 16 nodes per lane spent a third of the candidate loop there).  Four
+// segments per wave (one per row, 64 nodes per lane) need 138 VGPRs, three waves per SIMD, and measured slower.
+// With h = (t>p ? 255-t : t) the reference's "forced" cases are pd > h, so under the hypothesis
+// floor(S/(2C+1)) == Th node k counts  <=>  pd_k > min(Th, h_k).
 __global__ void __launch_bounds__(256)
 k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
            int64_t leafStride, uint32_t *__restrict__ summ, int64_t summStride, SkipBlocks sk)
 {
-    const int brick = blockIdx.y, lane = threadIdx.x & 63;
+    constexpr int L = 32, SPW = 64 / L, NP = EST_SEG / 2 / L, TW = NP / 2, PW = NP / 4;   // lanes and pairs per segment, words per lane
+    const int brick = blockIdx.y, lane = threadIdx.x & 63, row = lane / L, rl = lane % L;
     const Ctrl &c = ctrls[brick];
     const uint32_t n = 1u << d;
     // one scalar round trip for the control-block fields, in front of the first branch
     const int cConst = c.constBrick, cDone = c.estDone, cSeg = c.estSeg, cPar = c.par, cTbase = c.estTbase;
     if (cConst || cDone) return;
-    // segments from where the walk stands; later rounds run on a small grid (most bricks are done by then)
-    const uint8_t *Tl = temp + (int64_t)brick * heapStride + ((int64_t)1 << d) + lane * 16;
-    const uint8_t *Pl = (cPar == 0 ? rb.b[0] : (cPar == 1 ? rb.b[1] : rb.b[2])) + (int64_t)brick * leafStride + lane * 8;
-    const uint32_t nseg = n / EST_SEG, seg0 = (uint32_t)cSeg + blockIdx.x * 4 + (threadIdx.x >> 6);
-    // the next segment's bytes are in flight while this one is summarised (a wave's single load round trip is
-    // what bounds this kernel: twice the bytes in flight per wave)
-    uint4 tvN = make_uint4(0, 0, 0, 0);
-    uint2 pvN = make_uint2(0, 0);
-    bool skipN = seg0 < nseg && skip_block(sk, brick, d, seg0 * EST_SEG);       // a segment inside a skipped block: all zero, unread
-    if (seg0 < nseg && !skipN) { tvN = ld16(Tl + (size_t)seg0 * EST_SEG); pvN = ld8(Pl + (size_t)seg0 * (EST_SEG / 2)); }
-    for (uint32_t seg = seg0; seg < nseg; seg += gridDim.x * 4) {
-    const uint4 tv = tvN;
-    const uint2 pv = pvN;
-    const bool skipped = skipN;
-    {
-        const uint32_t sn = seg + gridDim.x * 4;
-        skipN = sn < nseg && skip_block(sk, brick, d, sn * EST_SEG);
-        if (sn < nseg && !skipN) { tvN = ld16(Tl + (size_t)sn * EST_SEG); pvN = ld8(Pl + (size_t)sn * (EST_SEG / 2)); }
-    }
-    if (skipped) {
-        uint32_t *outz = summ + (int64_t)brick * summStride * (4 * EST_CAND);
-        if (lane < 4 * nc) outz[est_at(lane >> 2, seg) + (lane & 3)] = 0;
-        continue;
-    }
-    const uint32_t tw[4] = {tv.x, tv.y, tv.z, tv.w};
-    vr_s16x2 pd[8], h[8];
+    // segments from where the walk stands (any start, not a multiple of SPW); later rounds run on a small grid
+    const uint8_t *Tl = temp + (int64_t)brick * heapStride + ((int64_t)1 << d) + rl * (4 * TW);
+    const uint8_t *Pl = (cPar == 0 ? rb.b[0] : (cPar == 1 ? rb.b[1] : rb.b[2])) + (int64_t)brick * leafStride + rl * (4 * PW);
+    const uint32_t nseg = n / EST_SEG, step = gridDim.x * (4u * SPW);
+    const uint32_t g0 = (uint32_t)cSeg + (blockIdx.x * 4u + (threadIdx.x >> 6)) * SPW;
+    // the next segments' bytes are in flight while these are summarised (a wave's load round trip is what bounds
+    // this kernel otherwise).  A segment past the level's end or inside a skipped block (SkipBlocks) loads nothing:
+    // its zero bytes are pd = 0 everywhere, which never counts and yields the all-zero record by itself.
+    uint4 tN[TW / 4], pN[PW / 4];
+    auto fetch = [&](uint32_t g) {
+        const uint32_t s = g + (uint32_t)row;
+        const bool live = s < nseg && !skip_block(sk, brick, d, s * EST_SEG);
+#pragma unroll
+        for (int j = 0; j < TW / 4; ++j) tN[j] = make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < PW / 4; ++j) pN[j] = make_uint4(0, 0, 0, 0);
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < TW / 4; ++j) tN[j] = ld16(Tl + (size_t)s * EST_SEG + 16 * j);
+#pragma unroll
+            for (int j = 0; j < PW / 4; ++j) pN[j] = ld16(Pl + (size_t)s * (EST_SEG / 2) + 16 * j);
+        }
+    };
+    fetch(g0);
+    const int Tbase = cTbase;
+    uint32_t *out = summ + (int64_t)brick * summStride * (4 * EST_CAND);
+    for (uint32_t g = g0; g < nseg; g += step) {
+    uint32_t tw[TW], pw[PW];
+#pragma unroll
+    for (int j = 0; j < TW / 4; ++j) { tw[4 * j] = tN[j].x; tw[4 * j + 1] = tN[j].y; tw[4 * j + 2] = tN[j].z; tw[4 * j + 3] = tN[j].w; }
+#pragma unroll
+    for (int j = 0; j < PW / 4; ++j) { pw[4 * j] = pN[j].x; pw[4 * j + 1] = pN[j].y; pw[4 * j + 2] = pN[j].z; pw[4 * j + 3] = pN[j].w; }
+    const uint32_t seg = g + (uint32_t)row;
+    const bool segLive = seg < nseg;         // segments past the level's end store nothing
+    vr_s16x2 pd[NP], h[NP];
     uint32_t anyPd = 0;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        // lanes: (node k, node k+8); their parents are bytes k>>1 of the two parent words
-        const uint32_t bsel = (uint32_t)(k & 3), psel = (uint32_t)(k >> 1);
-        const uint32_t T2 = __builtin_amdgcn_perm(tw[(k >> 2) + 2], tw[k >> 2], 0x0c040c00u | bsel | (bsel << 16));
-        const uint32_t P2 = __builtin_amdgcn_perm(pv.y, pv.x, 0x0c040c00u | psel | (psel << 16));
+    for (int k = 0; k < NP; ++k) {
+        // lanes: (node k, node k+NP); their parents are bytes k>>1 and NP/2 + (k>>1) of the lane's parent bytes
+        const uint32_t bsel = (uint32_t)(k & 3), psel = (uint32_t)((k >> 1) & 3);
+        const uint32_t T2 = __builtin_amdgcn_perm(tw[(k >> 2) + TW / 2], tw[k >> 2], 0x0c040c00u | bsel | (bsel << 16));
+        const uint32_t P2 = __builtin_amdgcn_perm(pw[(k >> 3) + PW / 2], pw[k >> 3], 0x0c040c00u | psel | (psel << 16));
         const vr_s16x2 diff = pk_s(T2) - pk_s(P2), nd = (vr_s16x2)(0) - diff;
         pd[k] = __builtin_elementwise_max(diff, nd);
         h[k] = pk_s(T2 ^ (pk_u(nd >> 15) & 0x00FF00FFu));
         anyPd |= pk_u(pd[k]);
     }
-    const int Tbase = cTbase;
-    uint32_t *out = summ + (int64_t)brick * summStride * (4 * EST_CAND);
-    if (__ballot(anyPd != 0) == 0ull) {      // parents reproduce the truths exactly (constant regions): nothing counts
-        if (lane < 4 * nc) out[est_at(lane >> 2, seg) + (lane & 3)] = 0;
+    fetch(g + step);                         // after the unpacking: these bytes and those loads are not live together
+    if (__ballot(anyPd != 0) == 0ull) {      // parents reproduce the truths exactly in all segments (constant regions)
+        if (segLive && rl < nc) *(uint4 *)(out + est_at(rl, seg)) = make_uint4(0, 0, 0, 0);
         continue;
     }
     // every h of the wave at or above the last candidate (the usual case away from 0 and 255): min(Th, h) = Th
     vr_s16x2 hmin = h[0];
 #pragma unroll
-    for (int k = 1; k < 8; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
+    for (int k = 1; k < NP; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
     const bool hBig = __ballot(min((int)hmin.x, (int)hmin.y) < Tbase + nc - 1) == 0ull;
 #pragma unroll 1
     for (int ci = 0; ci < nc; ++ci) {
@@ -537,42 +568,41 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
         const vr_s16x2 two2 = pk_s(0x00020002u);
         if (hBig) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const vr_s16x2 dm = (Th2 - pd[k]) >> 15;     // -1 where the node counts
-            low = dm * (pd[k] - w2) + low;
-            cc -= dm;
-            if (k < 7) {
+        for (int k = 0; k < NP; ++k) {
+            const vr_s16x2 dm = (Th2 - pd[k]) >> 15, one = pk_s(pk_u(dm) & 0x00010001u);   // -1 / 1 where the node counts
+            low = one * (w2 - pd[k]) + low;         // not the other branch's expression: hoisted above the branch, it
+            cc += one;                              // held NP more registers across it
+            if (k < NP - 1) {
                 amax = __builtin_elementwise_max(amax, low);
                 bmin = __builtin_elementwise_min(bmin, pk_mad(cc, two2, low));
             }
         }
         } else
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < NP; ++k) {
             const vr_s16x2 dm = (__builtin_elementwise_min(Th2, h[k]) - pd[k]) >> 15;     // -1 where the node counts
             low = dm * (pd[k] - w2) + low;          // += 2 Th - pd where it counts (v_pk_mad_i16)
             cc -= dm;
-            if (k < 7) {
+            if (k < NP - 1) {
                 amax = __builtin_elementwise_max(amax, low);
                 bmin = __builtin_elementwise_min(bmin, pk_mad(cc, two2, low));
             }
         }
         const int low1 = low.x, low2 = low.y, cc1 = cc.x, cc2 = cc.y;
         const int lowT = low1 + low2, ccT = cc1 + cc2;
-        int a = max((int)amax.x, max((int)amax.y, 0) + low1);          // chain 2 starts at position 8 (its own 0 included)
+        int a = max((int)amax.x, max((int)amax.y, 0) + low1);          // chain 2 starts at position NP (its own 0 included)
         int b = min((int)bmin.x, min((int)bmin.y, 0) + low1 + 2 * cc1);
         const uint32_t sT = (uint32_t)(2 * Th * ccT - lowT);
-        // one scan for both sums: s < 2^18 per wave, cc <= 1024
+        // one scan for both sums: s < 2^18 per segment, cc <= 1024
         const uint32_t packed = sT | ((uint32_t)ccT << 20);
-        const uint32_t incl = wave_incl_scan_add_dpp(packed), excl = incl - packed;
+        const uint32_t incl = seg_incl_scan_add_dpp(packed), excl = incl - packed;
         const int s0 = (int)(excl & 0xFFFFFu), c0 = (int)(excl >> 20);
         a += 2 * Th * c0 - s0;
         b += 2 * (Th + 1) * c0 - s0;
-        a = wave_max_i32_dpp(a);
-        b = wave_min_i32_dpp(b);
-        const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        if (lane < 4)
-            out[est_at(ci, seg) + lane] = lane == 0 ? (tot & 0xFFFFFu) : (lane == 1 ? (tot >> 20) : (lane == 2 ? (uint32_t)a : (uint32_t)b));
+        a = seg_max_i32_dpp(a);
+        b = seg_min_i32_dpp(b);
+        if (segLive && rl == L - 1)      // the segment's last lane holds its totals and extremes
+            *(uint4 *)(out + est_at(ci, seg)) = make_uint4(incl & 0xFFFFFu, incl >> 20, (uint32_t)a, (uint32_t)b);
     }
     }
 }
@@ -2433,7 +2463,8 @@ static void compress_stream(BrickSet *bs, Stream2 &s0, hipStream_t st, const uin
             const int64_t nseg = n / EST_SEG - EST_HEAD / EST_SEG;
             for (int r = 0; r < EST_ROUNDS; ++r) {
                 const int nc = r < 2 ? 4 : EST_CAND, ncNext = r + 1 < 2 ? 4 : EST_CAND;   // two 4-wide windows, then 8-wide ones
-                const unsigned gx = r == 0 ? cdiv(nseg, 16) : (cdiv(nseg, 4) < 64 ? cdiv(nseg, 4) : 64);   // four segments per wave first
+                // eight segments per workgroup and sweep (two per wave); the first round makes four sweeps
+                const unsigned gx = r == 0 ? cdiv(nseg, 32) : (cdiv(nseg, 8) < 64 ? cdiv(nseg, 8) : 64);
                 hipLaunchKernelGGL(k_est_summ, dim3(gx, B), dim3(256), 0, st, d, nc, s.ctrl, s.temp,
                                    bs->heapStride, rb, bs->reconStride, (uint32_t *)estSumm, bs->estSummStride, sk);
                 hipLaunchKernelGGL(k_est_walk, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, nc, ncNext,
