@@ -409,6 +409,41 @@ vr_status vr_raycast_pool_tf_shaded(const uint8_t *pool_dev, const vr_pool_entry
                                     const vr_transfer_function *tf, const vr_shading *shading, float *rgba_dev,
                                     void *stream);
 
+/* ---- sort-last colour partials (new): frames through a transfer function, lit or not, drawn by several GPUs ----------
+ * A colour partial is one float4 per pixel, (C.r, C.g, C.b, T): the premultiplied colour and the transmittance of
+ * vr_raycast_tf's rule when its loop ends (steps 1-6 unchanged; the early exit of step 6 is local to the rank), stored as
+ * they are instead of (C + T * background, 1 - T).  A pixel the cube does not cover, or whose ray owns no sample in
+ * [box_min, box_max), is (0, 0, 0, 1) exactly; there is no coverage flag, because finishing (0, 0, 0, 1) gives
+ * (background, 0), the pixel vr_raycast_tf writes there.
+ * shading == NULL: the unlit march, params->mode must be VR_RENDER_COMPOSITE and the checks are vr_raycast_tf's; with a
+ * shading: the lit march, mode must be VR_RENDER_SHADED and the checks are vr_raycast_tf_shaded's (the pool variants:
+ * those of vr_raycast_pool_tf / vr_raycast_pool_tf_shaded).  tf->background is validated but not used.  A rank's slab
+ * under vol_origin / global_dims holds ONE halo layer unlit and TWO lit (see vr_shading).  Guarantees: a full-box partial
+ * finished by vr_composite_finish_tf (or vr_composite_slabs_tf with one slab) equals the frame of vr_raycast_tf /
+ * vr_raycast_tf_shaded bit for bit; the partial is bit-identical with and without the skip grid; the pool partial is
+ * bit-identical to the dense partial of the pool's volume assembled densely. */
+vr_status vr_raycast_tf_partial(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                                const vr_render_params *params, const vr_transfer_function *tf,
+                                const vr_shading *shading /* NULL = unlit */, float *partial_dev, void *stream);
+vr_status vr_raycast_pool_tf_partial(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                                     const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
+                                     const vr_transfer_function *tf, const vr_shading *shading /* NULL = unlit */,
+                                     float *partial_dev, void *stream);
+/* Combining colour partials.  over: front = front OVER back on all four floats, (C1 + T1*C2, T1*T2).  finish:
+ * (C + T * background, 1 - T), the marcher's final store.  slabs: vr_composite_slabs for colour -- every pixel walks the
+ * num_slabs partials of its tile in ITS view order (the sign of the pixel ray's component along `axis`, formed exactly
+ * as vr_composite_slabs forms it), accumulates C += T * C_k, T *= T_k from C = 0, T = 1 and finishes.  The three are
+ * written with the same operations in the same order: folding slabs pairwise in view order and finishing equals the
+ * slab call bit for bit.  Of tf only background is read: a null lut_dev is allowed here.  VR_ERR_INVALID for a null
+ * pointer, num_pixels < 1, num_slabs < 1, axis outside 0..2, a tile that leaves the frame or a background that is not
+ * finite. */
+vr_status vr_composite_over_tf(float *front_dev, const float *back_dev, int64_t num_pixels, void *stream);
+vr_status vr_composite_finish_tf(const float *partial_dev, const vr_transfer_function *tf, float *rgba_dev,
+                                 int64_t num_pixels, void *stream);
+vr_status vr_composite_slabs_tf(const float *partials_dev, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel,
+                                int32_t axis, const vr_camera *cam, const vr_render_params *params,
+                                const vr_transfer_function *tf, float *rgba_dev, void *stream);
+
 /* Sort-last compositing of VR_RENDER_PARTIAL images: front = front OVER back, per pixel
  * (c1 + t1*c2, t1*t2); and the final colour transfer of raycaster.frag:82-85. */
 vr_status vr_composite_over(float *front_dev, const float *back_dev, int64_t num_pixels, void *stream);
@@ -441,6 +476,13 @@ vr_status vr_compositor_create_from_comm(vr_compositor **out, void *nccl_comm, i
                                          int32_t width, int32_t height);
 vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
                                   const vr_render_params *params, float *rgba_dev, void *stream);
+/* vr_compositor_composite for the colour partials of vr_raycast_tf_partial: the same handle, buffers and exchange (the
+ * same transport calls in the same order), the tile combined by vr_composite_slabs_tf.  Only tf->background is read.
+ * With every rank's early exit on, the frame differs from the single-GPU one by at most 0.01 per channel (plus
+ * rounding): a rank stops only once the frame's transmittance is below 0.01. */
+vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
+                                     const vr_render_params *params, const vr_transfer_function *tf, float *rgba_dev,
+                                     void *stream);
 vr_status vr_compositor_destroy(vr_compositor *c);
 /* The transport seam: vr_compositor_composite's exchange is four point-to-point calls, made through this table.  RCCL
  * is the built-in table (ctx = the ncclComm_t) that the two constructors above install.  With

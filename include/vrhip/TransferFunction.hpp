@@ -1,5 +1,6 @@
 // vrhip/TransferFunction.hpp -- a transfer-function table for vr_raycast_tf / vr_raycast_pool_tf from control points,
-// without Python: the rule of volumerenderer_amd.render.transfer_function_table.  Plain C++14, host only.
+// without Python: the rule of volumerenderer_amd.render.transfer_function_table; and SortLastTf, the sort-last colour
+// partials of such frames (vr_raycast_tf_partial and its combine calls).  Plain C++14, host only.
 #pragma once
 #include "../vrhip.h"
 #include <cmath>
@@ -57,5 +58,78 @@ inline vr_shading default_shading()
     s.grad_min = (float)(1.0 / 255.0);
     return s;
 }
+
+// Sort-last frames through a transfer function, lit or not: what is the same for every slab of a frame (camera, table,
+// lighting) is set once, the calls take what differs.  Buffers are the caller's device memory: a colour partial and a
+// frame are width * height float4 each.  The rule is in vrhip.h (vr_raycast_tf_partial).
+class SortLastTf {
+public:
+    vr_camera cam;
+    vr_transfer_function tf;
+    bool lit;
+    vr_shading shading;
+
+    SortLastTf(const vr_camera &c, const vr_transfer_function &t) : cam(c), tf(t), lit(false), shading(default_shading()) {}
+    SortLastTf(const vr_camera &c, const vr_transfer_function &t, const vr_shading &s) : cam(c), tf(t), lit(true), shading(s) {}
+
+    // halo layers a slab must hold beyond each cut: the trilinear taps, and the gradient's taps one voxel further
+    int halo() const { return lit ? 2 : 1; }
+
+    // Rank `rank`'s slab of a volume of `dims` voxels cut into `world` slabs along `axis` (volumerenderer_amd.distributed.
+    // slab_params): P with box_min / box_max (the last rank's box_max is 2: it owns the far face), vol_origin and
+    // global_dims set; local = the extents of the voxels [range[0], range[1]) along `axis` the rank holds.
+    vr_render_params slab(vr_render_params P, const int64_t dims[3], int axis, int rank, int world, int64_t local[3],
+                          int64_t range[2]) const
+    {
+        if (axis < 0 || axis > 2 || rank < 0 || rank >= world || world > dims[axis]) throw std::invalid_argument("SortLastTf::slab");
+        const int64_t n = dims[axis], q = n / world, m = n % world;
+        const int64_t lo = rank * q + (rank < m ? rank : m), hi = lo + q + (rank < m ? 1 : 0);
+        range[0] = lo - halo() < 0 ? 0 : lo - halo();
+        range[1] = hi + halo() > n ? n : hi + halo();
+        for (int k = 0; k < 3; ++k) {
+            P.box_min[k] = 0.0f; P.box_max[k] = 1.0f; P.vol_origin[k] = 0; P.global_dims[k] = dims[k]; local[k] = dims[k];
+        }
+        P.box_min[axis] = (float)((double)lo / (double)n);
+        P.box_max[axis] = rank < world - 1 ? (float)((double)hi / (double)n) : 2.0f;
+        P.vol_origin[axis] = range[0];
+        local[axis] = range[1] - range[0];
+        return P;
+    }
+
+    // the colour partial of a slab (or of the whole volume); P.mode is set to what the call needs
+    vr_status partial(const uint8_t *vol_dev, const int64_t dims[3], vr_render_params P, float *partial_dev,
+                      void *stream = nullptr) const
+    {
+        P.mode = lit ? VR_RENDER_SHADED : VR_RENDER_COMPOSITE;
+        return vr_raycast_tf_partial(vol_dev, dims, &cam, &P, &tf, lit ? &shading : nullptr, partial_dev, stream);
+    }
+    vr_status partialPool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                          const int64_t grid[3], vr_render_params P, float *partial_dev, void *stream = nullptr) const
+    {
+        P.mode = lit ? VR_RENDER_SHADED : VR_RENDER_COMPOSITE;
+        return vr_raycast_pool_tf_partial(pool_dev, table_dev, brick_dims, grid, &cam, &P, &tf, lit ? &shading : nullptr,
+                                          partial_dev, stream);
+    }
+    // front = front OVER back; (C + T background, 1 - T); num_slabs partials of a tile combined per pixel in view order
+    vr_status over(float *front_dev, const float *back_dev, int64_t num_pixels, void *stream = nullptr) const
+    {
+        return vr_composite_over_tf(front_dev, back_dev, num_pixels, stream);
+    }
+    vr_status finish(const float *partial_dev, float *rgba_dev, int64_t num_pixels, void *stream = nullptr) const
+    {
+        return vr_composite_finish_tf(partial_dev, &tf, rgba_dev, num_pixels, stream);
+    }
+    vr_status combineSlabs(const float *partials_dev, int num_slabs, int64_t num_pixels, int64_t first_pixel, int axis,
+                           const vr_render_params &P, float *rgba_dev, void *stream = nullptr) const
+    {
+        return vr_composite_slabs_tf(partials_dev, num_slabs, num_pixels, first_pixel, axis, &cam, &P, &tf, rgba_dev, stream);
+    }
+    // across ranks: the exchange of a vr_compositor handle, the tile combined by combineSlabs' kernel
+    vr_status composite(vr_compositor *c, const float *partial_dev, int axis, const vr_render_params &P, float *rgba_dev,
+                        void *stream = nullptr) const
+    {
+        return vr_compositor_composite_tf(c, partial_dev, axis, &cam, &P, &tf, rgba_dev, stream);
+    }
+};
 
 } // namespace vrhip

@@ -18,7 +18,8 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
                 "composite_finish", "assemble_bricks", "disassemble_bricks", "fill_volume_brick_map", "build_skip_grid",
                 "use_skip_grid", "select_lod", "lod_pool_layout", "raycast_pool", "build_skip_grid_pool", "TransferFunction",
                 "raycast_tf", "raycast_pool_tf", "transfer_function_table", "Shading", "raycast_tf_shaded",
-                "raycast_pool_tf_shaded"):
+                "raycast_pool_tf_shaded", "raycast_tf_partial", "raycast_pool_tf_partial", "composite_over_tf",
+                "composite_finish_tf"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

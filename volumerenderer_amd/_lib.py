@@ -108,6 +108,14 @@ SIGNATURES = {
                                     C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
     "vr_raycast_pool_tf_shaded": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
                                          C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_raycast_tf_partial": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                     C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_raycast_pool_tf_partial": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                          C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_composite_over_tf": (_I32, [_P, _P, _I64, _P]),
+    "vr_composite_finish_tf": (_I32, [_P, C.POINTER(TransferFunctionDesc), _P, _I64, _P]),
+    "vr_composite_slabs_tf": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams),
+                                     C.POINTER(TransferFunctionDesc), _P, _P]),
     "vr_composite_over": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_finish": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_slabs": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
@@ -116,6 +124,8 @@ SIGNATURES = {
     "vr_compositor_create_from_comm": (_I32, [C.POINTER(_P), _P, _I32, _I32, _I32, _I32]),
     "vr_compositor_create_with_transport": (_I32, [C.POINTER(_P), _P, _P, _I32, _I32, _I32, _I32]),
     "vr_compositor_composite": (_I32, [_P, _P, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
+    "vr_compositor_composite_tf": (_I32, [_P, _P, _I32, C.POINTER(Camera), C.POINTER(RenderParams),
+                                          C.POINTER(TransferFunctionDesc), _P, _P]),
     "vr_compositor_destroy": (_I32, [_P]),
     "vr_stream_create": (_I32, [C.POINTER(_P)]),
     "vr_stream_destroy": (_I32, [_P]),

@@ -18,9 +18,14 @@ using namespace vr;
 
 namespace vr {
 int raycast_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, const vr_transfer_function *,
-                   const vr_shading *, float *, hipStream_t);
+                   const vr_shading *, bool partial, float *, hipStream_t);
 int raycast_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
-                        const vr_render_params *, const vr_transfer_function *, const vr_shading *, float *, hipStream_t);
+                        const vr_render_params *, const vr_transfer_function *, const vr_shading *, bool partial, float *,
+                        hipStream_t);
+int composite_over_tf_launch(float *, const float *, int64_t, hipStream_t);
+int composite_finish_tf_launch(const float *, const vr_transfer_function *, float *, int64_t, hipStream_t);
+int composite_slabs_tf_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *,
+                              const vr_transfer_function *, float *, hipStream_t);
 int composite_over_launch(float *, const float *, int64_t, hipStream_t);
 int skip_grid_launch(const uint8_t *, const int64_t dims[3], int, uint8_t *, hipStream_t);
 int skip_grid_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], int, uint8_t *,
@@ -1153,23 +1158,26 @@ static bool style_ok(Style s, const vr_render_params *P, const vr_transfer_funct
     return table_ok(tf) && P->mode == VR_RENDER_SHADED && lighting_ok(sh);
 }
 
+// partial (TABLE and LIT only): rgba receives the colour partial of vr_raycast_tf_partial instead of the frame
 static vr_status raycast_dense(Style s, const uint8_t *vol, const int64_t dims[3], const vr_camera *cam,
                                const vr_render_params *P, const vr_transfer_function *tf, const vr_shading *sh, float *rgba,
-                               void *stream)
+                               void *stream, bool partial = false)
 {
     if (!frame_ok(cam, P, rgba) || !dense_ok(vol, dims) || !style_ok(s, P, tf, sh)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_launch(vol, dims, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return raycast_launch(vol, dims, cam, P, tf, sh, partial, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }
 
 static vr_status raycast_pool(Style s, const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3],
                               const int64_t grid[3], const vr_camera *cam, const vr_render_params *P,
-                              const vr_transfer_function *tf, const vr_shading *sh, float *rgba, void *stream)
+                              const vr_transfer_function *tf, const vr_shading *sh, float *rgba, void *stream,
+                              bool partial = false)
 {
     if (!frame_ok(cam, P, rgba) || !pool_ok(pool, table, bd, grid) || !pool_frame_ok(P, bd, grid) || !style_ok(s, P, tf, sh))
         return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return raycast_pool_launch(pool, table, bd, grid, cam, P, tf, sh, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return raycast_pool_launch(pool, table, bd, grid, cam, P, tf, sh, partial, rgba, (hipStream_t)stream) == 0 ? VR_OK
+                                                                                                              : VR_ERR_NO_DEVICE;
 }
 
 vr_status vr_raycast(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
@@ -1210,6 +1218,20 @@ vr_status vr_raycast_pool_tf_shaded(const uint8_t *pool, const vr_pool_entry *ta
     return raycast_pool(LIT, pool, table, bd, grid, cam, P, tf, sh, rgba, stream);
 }
 
+// the colour partial of the unlit (shading == NULL, VR_RENDER_COMPOSITE) or lit (VR_RENDER_SHADED) frame
+vr_status vr_raycast_tf_partial(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                                const vr_transfer_function *tf, const vr_shading *sh, float *partial, void *stream)
+{
+    return raycast_dense(sh ? LIT : TABLE, vol, dims, cam, P, tf, sh, partial, stream, true);
+}
+
+vr_status vr_raycast_pool_tf_partial(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3],
+                                     const int64_t grid[3], const vr_camera *cam, const vr_render_params *P,
+                                     const vr_transfer_function *tf, const vr_shading *sh, float *partial, void *stream)
+{
+    return raycast_pool(sh ? LIT : TABLE, pool, table, bd, grid, cam, P, tf, sh, partial, stream, true);
+}
+
 vr_status vr_skip_grid_build(const uint8_t *vol, const int64_t dims[3], int32_t cell, uint8_t *grid, void *stream)
 {
     if (!dense_ok(vol, dims) || !grid || cell <= 0 || cell > 64) return VR_ERR_INVALID;
@@ -1246,6 +1268,41 @@ vr_status vr_composite_slabs(const float *partials, int32_t num_slabs, int64_t n
     if (P->width <= 0 || P->height <= 0 || first_pixel + num_pixels > (int64_t)P->width * P->height) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return composite_slabs_launch(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, rgba, (hipStream_t)stream) == 0
+               ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// the combine calls read tf->background only: a null lut_dev is allowed
+static bool background_ok(const vr_transfer_function *tf)
+{
+    if (!tf) return false;
+    for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return false;
+    return true;
+}
+
+vr_status vr_composite_over_tf(float *front, const float *back, int64_t n, void *stream)
+{
+    if (!front || !back || n <= 0) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return composite_over_tf_launch(front, back, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_composite_finish_tf(const float *partial, const vr_transfer_function *tf, float *rgba, int64_t n, void *stream)
+{
+    if (!partial || !rgba || n <= 0 || !background_ok(tf)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return composite_finish_tf_launch(partial, tf, rgba, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_composite_slabs_tf(const float *partials, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel, int32_t axis,
+                                const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
+                                void *stream)
+{
+    if (!partials || !cam || !P || !rgba || num_slabs <= 0 || num_pixels <= 0 || first_pixel < 0 || axis < 0 || axis > 2)
+        return VR_ERR_INVALID;
+    if (P->width <= 0 || P->height <= 0 || first_pixel + num_pixels > (int64_t)P->width * P->height) return VR_ERR_INVALID;
+    if (!background_ok(tf)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return composite_slabs_tf_launch(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, tf, rgba, (hipStream_t)stream) == 0
                ? VR_OK : VR_ERR_NO_DEVICE;
 }
 

@@ -2,10 +2,10 @@
 // the one real exchange step of the path.  Rank r holds the partial (c, tau) image of slab r of the
 // volume; the frame is cut into `world` row tiles; ONE grouped RCCL call moves tile t of every rank's partial image
 // to rank t (direct send: ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd over xGMI, 4 MB per peer at 1080p and
-// eight ranks); rank t combines its `world` partials per pixel in that pixel's view order (k_composite_slabs:
-// "over" is associative but not commutative, raycaster.frag:69-72); a second grouped call gathers the finished tiles
-// on rank 0.  The reference is single-GPU: this is new, in the form SURVEY 8b proposed (vr_composite_init(comm) /
-// vr_composite).
+// eight ranks); rank t combines its `world` partials per pixel in that pixel's view order (k_composite_slabs, or
+// k_composite_slabs_tf for the colour partials of vr_raycast_tf_partial: "over" is associative but not commutative,
+// raycaster.frag:69-72); a second grouped call gathers the finished tiles on rank 0.  The reference is single-GPU:
+// this is new, in the form SURVEY 8b proposed (vr_composite_init(comm) / vr_composite).
 //
 // RCCL is bound at run time (dlopen of the copy already in the process -- PyTorch brings its own -- or of
 // librccl.so.1), so libvrhip.so loads and every single-GPU entry point works where RCCL is absent.
@@ -15,6 +15,7 @@
 #include "../../include/vrhip.h"
 #include "kd_common.h"
 #include <dlfcn.h>
+#include <math.h>
 #include <rccl/rccl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,6 +25,8 @@
 
 namespace vr {
 int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
+int composite_slabs_tf_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *,
+                              const vr_transfer_function *, float *, hipStream_t);
 }
 
 namespace {
@@ -195,16 +198,18 @@ vr_status vr_compositor_destroy(vr_compositor *c)
     return VR_OK;
 }
 
-vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
-                                  const vr_render_params *params, float *rgba_dev, void *stream)
+// The exchange of both composite calls: a grey and a colour partial are the same width * height * 4 floats, and only
+// the combine differs -- tf == NULL: k_composite_slabs (c, tau, covered), else k_composite_slabs_tf (C, T).
+static vr_status exchange_and_combine(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
+                                      const vr_render_params *params, const vr_transfer_function *tf, float *rgba_dev,
+                                      hipStream_t st)
 {
-    if (!c || !partial_dev || !cam || !params || axis < 0 || axis > 2) return VR_ERR_INVALID;
-    if (params->width != c->W || params->height != c->H) return VR_ERR_INVALID;
-    if (c->rank == 0 && !rgba_dev) return VR_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
+    auto combine = [&](const float *parts, int n, int64_t npix, int64_t first, float *dst) -> int {
+        return tf ? vr::composite_slabs_tf_launch(parts, n, npix, first, axis, cam, params, tf, dst, st)
+                  : vr::composite_slabs_launch(parts, n, npix, first, axis, cam, params, dst, st);
+    };
     const int64_t frame = (int64_t)c->W * c->H;
-    if (c->world == 1)
-        return vr::composite_slabs_launch(partial_dev, 1, frame, 0, axis, cam, params, rgba_dev, st) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    if (c->world == 1) return combine(partial_dev, 1, frame, 0, rgba_dev) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
     const vr_transport &T = c->t;
     int myLo, myHi;
     rows_of(c->H, c->rank, c->world, myLo, myHi);
@@ -225,7 +230,7 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
                        hipMemcpyDeviceToDevice, st) != hipSuccess) return VR_ERR_NO_DEVICE;
     // ---- my tile: every pixel combines the slabs front to back in ITS view order
     float *dst = c->rank == 0 ? rgba_dev + (size_t)myLo * c->W * 4 : c->tile;
-    if (vr::composite_slabs_launch(c->recv, c->world, (int64_t)npix, (int64_t)myLo * c->W, axis, cam, params, dst, st) != 0) return VR_ERR_NO_DEVICE;
+    if (combine(c->recv, c->world, (int64_t)npix, (int64_t)myLo * c->W, dst) != 0) return VR_ERR_NO_DEVICE;
     // ---- the finished tiles to rank 0
     if (T.group_start(c->ctx) != 0) return VR_ERR_NO_DEVICE;
     if (c->rank != 0) ok = T.send(c->ctx, c->tile, (int64_t)npix * 4, 0, st) == 0;
@@ -237,6 +242,30 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
         }
     ok = T.group_end(c->ctx) == 0 && ok;
     return ok ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+static bool composite_args_ok(const vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
+                              const vr_render_params *params, const float *rgba_dev)
+{
+    if (!c || !partial_dev || !cam || !params || axis < 0 || axis > 2) return false;
+    if (params->width != c->W || params->height != c->H) return false;
+    return c->rank != 0 || rgba_dev;
+}
+
+vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
+                                  const vr_render_params *params, float *rgba_dev, void *stream)
+{
+    if (!composite_args_ok(c, partial_dev, axis, cam, params, rgba_dev)) return VR_ERR_INVALID;
+    return exchange_and_combine(c, partial_dev, axis, cam, params, nullptr, rgba_dev, (hipStream_t)stream);
+}
+
+vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
+                                     const vr_render_params *params, const vr_transfer_function *tf, float *rgba_dev,
+                                     void *stream)
+{
+    if (!composite_args_ok(c, partial_dev, axis, cam, params, rgba_dev) || !tf) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return VR_ERR_INVALID;
+    return exchange_and_combine(c, partial_dev, axis, cam, params, tf, rgba_dev, (hipStream_t)stream);
 }
 
 // ---- streams, events, pinned host memory: what a C++ host needs to overlap the stages of a timestep stream

@@ -565,7 +565,8 @@ struct ShadeArgs {
 // (gather) and takes the head-light / directional Blinn-Phong of the iso-surface shader, two-sided, as its colour;
 // transparent samples and empty stretches cost what they cost unlit.  The ray set-up is an inline copy of k_raycast's,
 // and the lit and unlit "over" are written out apart: a shared function or a shared update schedules the code differently.
-template <class SAMPLER, bool LIT>
+// PARTIAL (vr_raycast_tf_partial): the same march; the pixel is (C, T) as the loop leaves them, for sort-last compositing.
+template <class SAMPLER, bool LIT, bool PARTIAL>
 __global__ void __launch_bounds__(64)
 k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
 {
@@ -673,7 +674,8 @@ k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
             if (!a.P.no_early_exit && T < 0.01f) break;
         }
     }
-    o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T;
+    if (PARTIAL) { o[0] = C0; o[1] = C1; o[2] = C2; o[3] = T; }
+    else { o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T; }
 }
 
 __global__ void k_composite_over(float4 *front, const float4 *back, int64_t n)
@@ -695,6 +697,42 @@ __global__ void k_composite_finish(const float4 *partial, float4 *rgba, int64_t 
     if (p.z > 0.0f) { o.x = 1.0f - p.x; o.y = 1.0f - p.x; o.z = 1.0f; o.w = 1.0f - p.y; }
     else { o.x = o.y = o.z = o.w = 1.0f; }
     rgba[i] = o;
+}
+
+// ---- colour partials (vr_raycast_tf_partial): one float4 (C.r, C.g, C.b, T) per pixel.  "Over" and the finish are
+// written with the marcher's own expressions (C + w c, T t; C + T bg, 1 - T), so a fold of slabs rounds like one march.
+struct Bg { float c[3]; };
+
+__device__ __forceinline__ void over_tf(float4 &f, const float4 &b)
+{
+    f.x = f.x + f.w * b.x;       // (C1 + T1*C2, T1*T2)
+    f.y = f.y + f.w * b.y;
+    f.z = f.z + f.w * b.z;
+    f.w = f.w * b.w;
+}
+__device__ __forceinline__ float4 finish_tf(const float4 &p, const Bg &bg)
+{
+    float4 o;
+    o.x = p.x + p.w * bg.c[0]; o.y = p.y + p.w * bg.c[1]; o.z = p.z + p.w * bg.c[2]; o.w = 1.0f - p.w;
+    return o;
+}
+
+__global__ void __launch_bounds__(256)
+k_composite_over_tf(float4 *front, const float4 *back, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 f = front[i];
+    over_tf(f, back[i]);
+    front[i] = f;
+}
+
+__global__ void __launch_bounds__(256)
+k_composite_finish_tf(const float4 *partial, Bg bg, float4 *rgba, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rgba[i] = finish_tf(partial[i], bg);
 }
 
 static void cross3(const float *a, const float *b, float *o);
@@ -731,6 +769,26 @@ k_composite_slabs(SlabArgs a)
     if (cov > 0.0f) { o.x = 1.0f - c; o.y = 1.0f - c; o.z = 1.0f; o.w = 1.0f - tau; }   // raycaster.frag:82-85
     else { o.x = o.y = o.z = o.w = 1.0f; }
     a.out[i] = o;
+}
+
+// k_composite_slabs for colour partials: the same pixel, the same d and the same slab order; a streaming kernel --
+// num_slabs 16-byte loads and one 16-byte store per lane, consecutive lanes on consecutive pixels
+__global__ void __launch_bounds__(256)
+k_composite_slabs_tf(SlabArgs a, Bg bg)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.npix) return;
+    const int64_t gp = a.first + i;
+    const int px = (int)(gp % a.W), py = (int)(gp / a.W);
+    const float nx = 2.0f * ((float)px + 0.5f) / (float)a.W - 1.0f;
+    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)a.H;
+    const float d = a.f[a.axis] + nx * a.tanX * a.s[a.axis] + ny * a.tanY * a.u[a.axis];
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    for (int k = 0; k < a.num_slabs; ++k) {
+        const int sidx = d >= 0.0f ? k : a.num_slabs - 1 - k;
+        over_tf(acc, a.partials[(int64_t)sidx * a.npix + i]);
+    }
+    a.out[i] = finish_tf(acc, bg);
 }
 
 // Brick <-> global volume placement (VolumeReader.h:172-211), 16-byte rows segments: one vector copy each where both
@@ -868,37 +926,42 @@ static ShadeArgs shade_args(const vr_shading *sh)
 }
 
 // The frame of a through k_raycast (no table), k_raycast_tf (a table) or its lit instantiation (a table and lighting);
-// label[style] names the launch in errors
+// label[style] names the launch in errors.  partial (a table only): the colour partial instead of the frame.
 template <class SAMPLER>
 static int march_launch(const RayArgs &a, const SAMPLER &tex, const vr_transfer_function *tf, const vr_shading *sh,
-                        const char *const label[3], hipStream_t st)
+                        bool partial, const char *const label[3], hipStream_t st)
 {
     const dim3 grid((a.P.width + 7) / 8, (a.P.height + 7) / 8);
     if (!tf) hipLaunchKernelGGL(k_raycast<SAMPLER>, grid, dim3(64), 0, st, a, tex);
-    else if (!sh) hipLaunchKernelGGL((k_raycast_tf<SAMPLER, false>), grid, dim3(64), 0, st, a, tex, tf_args(tf), ShadeArgs());
-    else hipLaunchKernelGGL((k_raycast_tf<SAMPLER, true>), grid, dim3(64), 0, st, a, tex, tf_args(tf), shade_args(sh));
+    else if (!sh) {
+        auto kern = partial ? k_raycast_tf<SAMPLER, false, true> : k_raycast_tf<SAMPLER, false, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a, tex, tf_args(tf), ShadeArgs());
+    } else {
+        auto kern = partial ? k_raycast_tf<SAMPLER, true, true> : k_raycast_tf<SAMPLER, true, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a, tex, tf_args(tf), shade_args(sh));
+    }
     return launch_status(label[!tf ? 0 : (!sh ? 1 : 2)]);
 }
 
 int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
-                   const vr_transfer_function *tf, const vr_shading *sh, float *rgba, hipStream_t st)
+                   const vr_transfer_function *tf, const vr_shading *sh, bool partial, float *rgba, hipStream_t st)
 {
     static const char *const label[3] = {"raymarch", "raymarch_tf", "raymarch_tf_shaded"};
     RayArgs a;
     dense_args(a, vol, dims, P);
     ray_frame(a, cam, P, rgba);
-    return march_launch(a, DenseSampler(), tf, sh, label, st);
+    return march_launch(a, DenseSampler(), tf, sh, partial, label, st);
 }
 
 int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
                         const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, const vr_shading *sh,
-                        float *rgba, hipStream_t st)
+                        bool partial, float *rgba, hipStream_t st)
 {
     static const char *const label[3] = {"raymarch_pool", "raymarch_pool_tf", "raymarch_pool_tf_shaded"};
     RayArgs a;
     const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
     ray_frame(a, cam, P, rgba);
-    return march_launch(a, pt, tf, sh, label, st);
+    return march_launch(a, pt, tf, sh, partial, label, st);
 }
 
 // k_skip_grid over a pool's virtual volume: the same cells, rows and bounds; a row's voxels come from the stored voxels of
@@ -970,8 +1033,9 @@ int skip_grid_launch(const uint8_t *vol, const int64_t dims[3], int S, uint8_t *
     return launch_status("skip_grid");
 }
 
-int composite_slabs_launch(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
-                           const vr_render_params *P, float *rgba, hipStream_t st)
+// the frame and buffers of both slab kernels: one set-up, so that they form d from the same basis
+static SlabArgs slab_args(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
+                          const vr_render_params *P, float *rgba)
 {
     SlabArgs a;
     a.partials = (const float4 *)partials; a.num_slabs = nslabs; a.npix = npix; a.first = first;
@@ -985,8 +1049,43 @@ int composite_slabs_launch(const float *partials, int nslabs, int64_t npix, int6
     a.tanY = tanf(0.5f * rad);
     a.tanX = a.tanY * (float)P->width / (float)P->height;
     a.out = (float4 *)rgba;
+    return a;
+}
+
+int composite_slabs_launch(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
+                           const vr_render_params *P, float *rgba, hipStream_t st)
+{
+    const SlabArgs a = slab_args(partials, nslabs, npix, first, axis, cam, P, rgba);
     hipLaunchKernelGGL(k_composite_slabs, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, a);
     return launch_status("composite_slabs");
+}
+
+static Bg background_of(const vr_transfer_function *tf)
+{
+    Bg b;
+    for (int k = 0; k < 3; ++k) b.c[k] = tf->background[k];
+    return b;
+}
+
+int composite_slabs_tf_launch(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
+                              const vr_render_params *P, const vr_transfer_function *tf, float *rgba, hipStream_t st)
+{
+    const SlabArgs a = slab_args(partials, nslabs, npix, first, axis, cam, P, rgba);
+    hipLaunchKernelGGL(k_composite_slabs_tf, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, a, background_of(tf));
+    return launch_status("composite_slabs_tf");
+}
+
+int composite_over_tf_launch(float *front, const float *back, int64_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_composite_over_tf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float4 *)front,
+                       (const float4 *)back, n);
+    return launch_status("composite_over_tf");
+}
+int composite_finish_tf_launch(const float *partial, const vr_transfer_function *tf, float *rgba, int64_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_composite_finish_tf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)partial,
+                       background_of(tf), (float4 *)rgba, n);
+    return launch_status("composite_finish_tf");
 }
 
 int composite_over_launch(float *front, const float *back, int64_t n, hipStream_t st)

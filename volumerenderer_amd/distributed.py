@@ -57,6 +57,46 @@ def _gpu_combine(parts, first_pixel, axis, cam, params):
     return out
 
 
+def _gpu_combine_tf(parts, first_pixel, axis, cam, params, tf):
+    from . import _lib
+    from .codec import _stream_ptr
+    from ._lib import check
+    out = torch.empty((parts.shape[1], 4), dtype=torch.float32, device=parts.device)
+    desc = tf.desc()
+    check(_lib.lib().vr_composite_slabs_tf(C.c_void_p(parts.data_ptr()), parts.shape[0], parts.shape[1], int(first_pixel),
+                                           int(axis), C.byref(cam), C.byref(params), C.byref(desc),
+                                           C.c_void_p(out.data_ptr()), _stream_ptr()), "vr_composite_slabs_tf")
+    return out
+
+
+def slab_params(params, dims, axis, rank, world, halo):
+    """Rank `rank`'s slab when a volume of `dims` = (X, Y, Z) voxels is cut into `world` slabs along `axis`, stored with
+    `halo` voxel layers beyond each cut (1 for the grey and the unlit marches, 2 for the lit one; vrhip.h).  Returns
+    (P, local_dims, (a0, a1)): P = a copy of `params` with box_min / box_max (the last rank's box_max is 2.0: it owns
+    the far face), vol_origin and global_dims set, local_dims the extents of the voxels [a0, a1) along `axis` that the
+    rank has to hold."""
+    dims = [int(q) for q in dims]
+    if len(dims) != 3 or axis not in (0, 1, 2) or not 0 <= rank < world or halo < 0 or world > dims[axis]:
+        raise ValueError("slab_params: axis %r, rank %r of %r, halo %r, extents %r" % (axis, rank, world, halo, dims))
+    n = dims[axis]
+    lo, hi = shard_range(n, rank, world)
+    a0, a1 = max(0, lo - halo), min(n, hi + halo)
+    P = type(params).from_buffer_copy(params)
+    if hasattr(params, "_keep_grid"):
+        P._keep_grid = params._keep_grid
+    bmin, bmax, org = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0, 0, 0]
+    bmin[axis] = lo / n
+    bmax[axis] = hi / n if rank < world - 1 else 2.0
+    org[axis] = a0
+    P.box_min[:] = bmin
+    P.box_max[:] = bmax
+    P.vol_origin[:] = org
+    P.global_dims[:] = dims
+    local = list(dims)
+    local[axis] = a1 - a0
+    return P, tuple(local), (a0, a1)
+
+
 _compositors = {}
 
 
@@ -100,6 +140,22 @@ def composite_sort_last(partial, cam, params, axis=2, group=None, combine=None, 
     gather -- what a C++ host calls); it reads `partial` (and writes `out`) through raw pointers, so anything but a
     contiguous float32 (H, W, 4) device tensor raises ValueError before any C call.  With an injected `combine` (the
     CPU tests: gloo, the oracle's combine) the same exchange runs over torch.distributed point-to-point operations."""
+    return _sort_last(partial, cam, params, None, axis, group, combine, out)
+
+
+def composite_sort_last_tf(partial, cam, params, tf, axis=2, group=None, combine=None, out=None):
+    """composite_sort_last for colour partials: partial = this rank's (C.r, C.g, C.b, T) image [H][W][4] float32 from
+    raycast_tf_partial (unlit or lit), tf the TransferFunction whose background finishes the frame.  The same exchange;
+    device tensors take vr_compositor_composite_tf, an injected `combine(parts, first_pixel, axis, cam, params)` runs
+    over torch.distributed point-to-point operations."""
+    from .render import TransferFunction
+    if not isinstance(tf, TransferFunction):
+        raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
+    return _sort_last(partial, cam, params, tf, axis, group, combine, out)
+
+
+def _sort_last(partial, cam, params, tf, axis, group, combine, out):
+    """The exchange of both calls; tf = None: grey partials (vr_composite_slabs), else colour (vr_composite_slabs_tf)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     if combine is None and partial.is_cuda:
@@ -117,12 +173,19 @@ def composite_sort_last(partial, cam, params, axis=2, group=None, combine=None, 
         frame = None
         if rank == 0:
             frame = out if out is not None else torch.empty((H, W, 4), dtype=torch.float32, device=partial.device)
-        check(_lib.lib().vr_compositor_composite(h, C.c_void_p(partial.data_ptr()), int(axis), C.byref(cam), C.byref(params),
-                                                 C.c_void_p(frame.data_ptr()) if rank == 0 else None, _stream_ptr()),
-              "vr_compositor_composite")
+        dst = C.c_void_p(frame.data_ptr()) if rank == 0 else None
+        if tf is None:
+            check(_lib.lib().vr_compositor_composite(h, C.c_void_p(partial.data_ptr()), int(axis), C.byref(cam),
+                                                     C.byref(params), dst, _stream_ptr()), "vr_compositor_composite")
+        else:
+            desc = tf.desc()
+            check(_lib.lib().vr_compositor_composite_tf(h, C.c_void_p(partial.data_ptr()), int(axis), C.byref(cam),
+                                                        C.byref(params), C.byref(desc), dst, _stream_ptr()),
+                  "vr_compositor_composite_tf")
         return frame
     H, W = partial.shape[0], partial.shape[1]
-    combine = combine or _gpu_combine
+    if combine is None:
+        combine = _gpu_combine if tf is None else (lambda *a: _gpu_combine_tf(*a, tf))
     rows = tile_rows(H, world)
     if world == 1:
         return combine(partial.reshape(1, H * W, 4), 0, axis, cam, params).reshape(H, W, 4)

@@ -443,6 +443,74 @@ def raycast_pool_tf_shaded(pool, table, brick_dims, grid, cam, params, tf, shadi
     return out
 
 
+# ---- sort-last colour partials (vr_raycast_tf_partial and the combine calls; the rule is in vrhip.h) -------------------
+def raycast_tf_partial(volume, dims, cam, params, tf, shading=None, out=None, stream=None):
+    """The colour partial of raycast_tf (shading=None, params.mode RENDER_COMPOSITE) or raycast_tf_shaded (a Shading,
+    RENDER_SHADED) for sort-last compositing (vr_raycast_tf_partial): float32 CUDA [H][W][4] = (C.r, C.g, C.b, T) of the
+    samples in params' box; (0, 0, 0, 1) where the ray owns none.  tf.background is not used."""
+    v, d = _dense_source(volume, dims)
+    _check_attached_grid(params, dims, v.device)
+    _check_tf(tf, v.device)
+    if shading is not None:
+        _check_shading(shading)
+    out = _frame_out(out, params, v.device)
+    desc, sh = tf.desc(), shading.desc() if shading is not None else None
+    check(_lib.lib().vr_raycast_tf_partial(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
+                                           C.byref(sh) if sh is not None else None, C.c_void_p(out.data_ptr()),
+                                           _stream_ptr(stream)), "vr_raycast_tf_partial")
+    return out
+
+
+def raycast_pool_tf_partial(pool, table, brick_dims, grid, cam, params, tf, shading=None, out=None, stream=None):
+    """raycast_tf_partial of the virtual volume of a pool (vr_raycast_pool_tf_partial): bit-identical to the dense partial
+    of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
+    bd, g = _pool_source(pool, table, brick_dims, grid)
+    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
+    _check_tf(tf, pool.device)
+    if shading is not None:
+        _check_shading(shading)
+    out = _frame_out(out, params, pool.device)
+    desc, sh = tf.desc(), shading.desc() if shading is not None else None
+    check(_lib.lib().vr_raycast_pool_tf_partial(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g,
+                                                C.byref(cam), C.byref(params), C.byref(desc),
+                                                C.byref(sh) if sh is not None else None, C.c_void_p(out.data_ptr()),
+                                                _stream_ptr(stream)), "vr_raycast_pool_tf_partial")
+    return out
+
+
+def _check_partial(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("%s must be a CUDA tensor" % what)
+    if t.numel() == 0 or t.numel() % 4:
+        raise ValueError("%s must hold whole (C.r, C.g, C.b, T) pixels, not %d floats" % (what, t.numel()))
+    _check_buf(t, what, torch.float32, t.numel(), t.device)
+
+
+def composite_over_tf(front, back, stream=None):
+    """front = front OVER back on colour partials, in place: (C1 + T1 C2, T1 T2); both contiguous float32 (C.r, C.g,
+    C.b, T) images of the same size."""
+    _check_partial(front, "front")
+    _check_buf(back, "back", torch.float32, front.numel(), front.device)
+    check(_lib.lib().vr_composite_over_tf(C.c_void_p(front.data_ptr()), C.c_void_p(back.data_ptr()), front.numel() // 4,
+                                          _stream_ptr(stream)), "vr_composite_over_tf")
+    return front
+
+
+def composite_finish_tf(partial, tf, out=None, stream=None):
+    """The frame (C + T background, 1 - T) of a colour partial; of tf only the background is used."""
+    _check_partial(partial, "partial")
+    if not isinstance(tf, TransferFunction):
+        raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
+    if out is None:
+        out = torch.empty_like(partial)
+    else:
+        _check_buf(out, "out", torch.float32, partial.numel(), partial.device)
+    desc = tf.desc()
+    check(_lib.lib().vr_composite_finish_tf(C.c_void_p(partial.data_ptr()), C.byref(desc), C.c_void_p(out.data_ptr()),
+                                            partial.numel() // 4, _stream_ptr(stream)), "vr_composite_finish_tf")
+    return out
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}
