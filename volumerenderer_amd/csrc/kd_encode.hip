@@ -536,10 +536,21 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
     for (int j = 0; j < PW / 4; ++j) { pw[4 * j] = pN[j].x; pw[4 * j + 1] = pN[j].y; pw[4 * j + 2] = pN[j].z; pw[4 * j + 3] = pN[j].w; }
     const uint32_t seg = g + (uint32_t)row;
     const bool segLive = seg < nseg;         // segments past the level's end store nothing
+    // Lane-uniform waves (both segments): every lane's 32 truths are one value and its 16 parents' reconstructions one
+    // value -- constant 4096-leaf blocks below their root, see k_fill16.  All pairs of the lane are pair 0 then, and the
+    // candidate loop below has a closed form.
+    uint32_t mixed = 0;
+    {
+        const uint32_t t0 = __builtin_amdgcn_perm(0, tw[0], 0u), p0 = __builtin_amdgcn_perm(0, pw[0], 0u);   // byte 0 x 4
+#pragma unroll
+        for (int j = 0; j < TW; ++j) mixed |= tw[j] ^ t0;
+#pragma unroll
+        for (int j = 0; j < PW; ++j) mixed |= pw[j] ^ p0;
+    }
+    const bool uniform = __ballot(mixed != 0u) == 0ull;
     vr_s16x2 pd[NP], h[NP];
     uint32_t anyPd = 0;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
+    const auto unpack = [&](const int k) {
         // lanes: (node k, node k+NP); their parents are bytes k>>1 and NP/2 + (k>>1) of the lane's parent bytes
         const uint32_t bsel = (uint32_t)(k & 3), psel = (uint32_t)((k >> 1) & 3);
         const uint32_t T2 = __builtin_amdgcn_perm(tw[(k >> 2) + TW / 2], tw[k >> 2], 0x0c040c00u | bsel | (bsel << 16));
@@ -548,7 +559,11 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
         pd[k] = __builtin_elementwise_max(diff, nd);
         h[k] = pk_s(T2 ^ (pk_u(nd >> 15) & 0x00FF00FFu));
         anyPd |= pk_u(pd[k]);
-    }
+    };
+    if (uniform) unpack(0);
+    else
+#pragma unroll
+        for (int k = 0; k < NP; ++k) unpack(k);
     fetch(g + step);                         // after the unpacking: these bytes and those loads are not live together
     if (__ballot(anyPd != 0) == 0ull) {      // parents reproduce the truths exactly in all segments (constant regions)
         if (segLive && rl < nc) *(uint4 *)(out + est_at(rl, seg)) = make_uint4(0, 0, 0, 0);
@@ -556,9 +571,10 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
     }
     // every h of the wave at or above the last candidate (the usual case away from 0 and 255): min(Th, h) = Th
     vr_s16x2 hmin = h[0];
+    if (!uniform)
 #pragma unroll
-    for (int k = 1; k < NP; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
-    const bool hBig = __ballot(min((int)hmin.x, (int)hmin.y) < Tbase + nc - 1) == 0ull;
+        for (int k = 1; k < NP; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
+    const bool hBig = !uniform && __ballot(min((int)hmin.x, (int)hmin.y) < Tbase + nc - 1) == 0ull;
 #pragma unroll 1
     for (int ci = 0; ci < nc; ++ci) {
         const int Th = Tbase + ci;
@@ -566,7 +582,18 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
         // per chain: low = 2*Th*cc - s, and the extremes of low / low + 2cc over the positions BEFORE each node
         vr_s16x2 low = (vr_s16x2)(0), cc = (vr_s16x2)(0), amax = (vr_s16x2)(0), bmin = (vr_s16x2)(0);
         const vr_s16x2 two2 = pk_s(0x00020002u);
-        if (hBig) {
+        if (uniform) {
+            // All NP nodes of a chain count (pd > min(Th, h)) or none does.  With v = 2 Th - pd where they count and 0
+            // where not, the chain's `low` before node j is j * v and `low + 2 cc` is j * (v + 2 [counts]): linear in
+            // j, so their extremes over j = 0 .. NP-1 (what the loops below track) sit at j = 0 or j = NP - 1, and the
+            // totals are NP * v and NP [counts].  |v| <= 510: NP * 512 fits 16 bits.  Equal to the chain, not a bound.
+            const vr_s16x2 dm = (__builtin_elementwise_min(Th2, h[0]) - pd[0]) >> 15;     // -1 where the nodes count
+            const vr_s16x2 v = pk_s(pk_u(w2 - pd[0]) & pk_u(dm)), v2 = v - dm - dm;
+            low = v * (short)NP;
+            cc = pk_s(pk_u(dm) & ((uint32_t)NP * 0x10001u));
+            amax = __builtin_elementwise_max(amax, low - v);
+            bmin = __builtin_elementwise_min(bmin, v2 * (short)NP - v2);
+        } else if (hBig) {
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const vr_s16x2 dm = (Th2 - pd[k]) >> 15, one = pk_s(pk_u(dm) & 0x00010001u);   // -1 / 1 where the node counts
@@ -854,9 +881,7 @@ k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, ui
         uint8_t *f = sk.flag + (int64_t)brick * sk.nBlk + (size_t)chunk * 4 + w;
         if (*f & 1u) *f = 3u;        // the same answer in every epoch of the level: it depends on truths and parents only
     }
-    if (busy)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {                        // sibling pair j: nodes 2j, 2j+1, parent byte j
+    const auto pair = [&](const int j) {                 // sibling pair j: nodes 2j, 2j+1, parent byte j
         const EncPair c = enc_pair(tw[j >> 1], j & 1, pw[j >> 2], j & 3);
         const vr_s16x2 x = enc_pair_x(c, d2), ax = pk_abs(x);
         e0 = pk_sumsq(__builtin_elementwise_min(c.pd, ax), e0);
@@ -872,7 +897,28 @@ k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, ui
             em = pk_sumsq(enc_pair_err(c, dm2), em);
             ep = pk_sumsq(enc_pair_err(c, dp2), ep);
         }
+    };
+    // Lane-uniform waves: every lane's 16 truths are one value and its 8 parents' reconstructions one value (lanes
+    // differ freely).  Inside a constant 4096-leaf block that is every lane of every level below the block's root, by
+    // induction: equal truths and equal parents give equal reconstructions.  The lane's eight pairs are then the same
+    // computation: pair 0 is evaluated, its reconstruction byte and code replicated, and its err^2 (integers, so the
+    // lane's sum is exactly eight times the pair's) multiplied.  The exact shortcut above stays in front (cheaper still).
+    bool uniform = false;
+    if (busy) {
+        const uint32_t t0 = __builtin_amdgcn_perm(0, tw[0], 0u), p0 = __builtin_amdgcn_perm(0, pw[0], 0u);   // byte 0 x 4
+        const uint32_t mixed = (tw[0] ^ t0) | (tw[1] ^ t0) | (tw[2] ^ t0) | (tw[3] ^ t0) | (pw[0] ^ p0) | (pw[1] ^ p0);
+        uniform = __ballot(mixed != 0u) == 0ull;
     }
+    if (uniform) {
+        pair(0);
+        e0 *= 8u; em *= 8u; ep *= 8u;
+        if (STORE) {
+            wa *= 0x1111u; wb = wa;                      // pair 0's codes (bits 0-1 and 16-17) at every pair slot
+            rw[0] = rw[1] = rw[2] = rw[3] = __builtin_amdgcn_perm(0, rprev, 0u);
+        }
+    } else if (busy)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pair(j);
     // even nodes sit at bits 4j, odd ones at 16+4j: fold to 2 bits per node
     const uint32_t cpk = ((wa | (wa >> 14)) & 0xFFFFu) | ((wb | (wb >> 14)) << 16);
     if (!skipped && STORE) {
