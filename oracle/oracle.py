@@ -41,13 +41,18 @@ def build(force=False):
     return _LIB_PATH
 
 
-# -- oracle/_ref: the reference codec itself, compiled in place (oracle/Makefile, target `ref`)
+# -- oracle/_ref: the reference itself, compiled in place (oracle/Makefile, target `ref`): the codec as libvkref.so,
+# the two fragment shaders as libvkfrag.so.  Two libraries with a stamp each, so one failing never takes the other along.
 
 _REF_LIB_PATH = os.path.join(_HERE, "_ref", "libvkref.so")
 _REF_SOURCES = ("VolumeKdTree_recover.cpp", "VolumeKdtree_recover.h", "MidRangeTree.cpp", "MidRangeTree.h",
                 "DebugTimer.cpp", "DebugTimer.h", "TwoBitArray.h", "point.h")
 _REF_RECIPE = ("Makefile", "ref/ref_capi.cpp", "ref/ppl.h", "ref/Eigen/Core")
+_FRAG_LIB_PATH = os.path.join(_HERE, "_ref", "libvkfrag.so")
+_FRAG_SOURCES = ("raycaster.frag", "isosurface.frag")
+_FRAG_RECIPE = ("Makefile", "ref/frag_capi.cpp", "ref/glsl.h")
 _ref_lib = None
+_frag_lib = None
 
 
 def ref_dir():
@@ -59,40 +64,48 @@ def ref_dir():
     return beside if os.path.isdir(beside) else "/root/reference/volume_renderer"
 
 
-def _ref_source_hash(d):
+def _ref_source_hash(d, recipe=_REF_RECIPE, sources=_REF_SOURCES):
     import hashlib
     h = hashlib.sha256()
-    for s in _REF_RECIPE:
+    for s in recipe:
         h.update(open(os.path.join(_HERE, s), "rb").read())
-    for s in _REF_SOURCES:
+    for s in sources:
         h.update(open(os.path.join(d, s), "rb").read())
     return h.hexdigest()
 
 
-def build_ref(force=False):
-    """Build oracle/_ref/libvkref.so when the reference sources are present and _ref is missing or stale.
-    Without the sources an existing _ref is used as it is.  Never raises: a failed build leaves
-    ref_available() False and says why on stderr."""
+def _build_ref_lib(lib_path, recipe, sources, force):
+    """One library of oracle/_ref: built when its reference sources are present and it is missing or stale; without
+    the sources an existing one is used as it is.  Never raises: a failed build says why on stderr."""
     import sys
     d = ref_dir()
-    if not all(os.path.isfile(os.path.join(d, s)) for s in _REF_SOURCES):
-        return _REF_LIB_PATH if os.path.exists(_REF_LIB_PATH) else None
+    if not all(os.path.isfile(os.path.join(d, s)) for s in sources):
+        return lib_path if os.path.exists(lib_path) else None
     try:
-        want = _ref_source_hash(d)
-        stamp = _REF_LIB_PATH + ".srchash"
-        fresh = lambda: os.path.exists(_REF_LIB_PATH) and os.path.exists(stamp) and open(stamp).read().strip() == want
+        want = _ref_source_hash(d, recipe, sources)
+        stamp = lib_path + ".srchash"
+        fresh = lambda: os.path.exists(lib_path) and os.path.exists(stamp) and open(stamp).read().strip() == want
         if force or not fresh():
             import fcntl
-            os.makedirs(os.path.dirname(_REF_LIB_PATH), exist_ok=True)
-            with open(_REF_LIB_PATH + ".lock", "w") as lk:
+            os.makedirs(os.path.dirname(lib_path), exist_ok=True)
+            with open(lib_path + ".lock", "w") as lk:
                 fcntl.flock(lk, fcntl.LOCK_EX)
                 if force or not fresh():
-                    subprocess.check_call(["make", "-C", _HERE, "-B", "ref", "REF_DIR=" + d], stdout=subprocess.DEVNULL)
+                    subprocess.check_call(["make", "-C", _HERE, "-B", os.path.relpath(lib_path, _HERE), "REF_DIR=" + d],
+                                          stdout=subprocess.DEVNULL)
                     with open(stamp, "w") as f:
                         f.write(want)
     except (OSError, subprocess.CalledProcessError) as e:
-        print("oracle: reference build skipped: %s" % e, file=sys.stderr)
-    return _REF_LIB_PATH if os.path.exists(_REF_LIB_PATH) else None
+        print("oracle: reference build of %s skipped: %s" % (os.path.basename(lib_path), e), file=sys.stderr)
+    return lib_path if os.path.exists(lib_path) else None
+
+
+def build_ref(force=False):
+    """Build oracle/_ref/libvkref.so and oracle/_ref/libvkfrag.so when the reference sources are present and _ref is
+    missing or stale.  Without the sources an existing _ref is used as it is.  Never raises: a failed build leaves
+    ref_available() / frag_available() False and says why on stderr.  Returns the codec library's path or None."""
+    _build_ref_lib(_FRAG_LIB_PATH, _FRAG_RECIPE, _FRAG_SOURCES, force)
+    return _build_ref_lib(_REF_LIB_PATH, _REF_RECIPE, _REF_SOURCES, force)
 
 
 def ref_available():
@@ -234,6 +247,69 @@ class RefTree:
         return out.reshape(Z, Y, X)
 
 
+def frag_available():
+    return os.path.exists(_FRAG_LIB_PATH)
+
+
+def frag_lib():
+    global _frag_lib
+    if _frag_lib is not None:
+        return _frag_lib
+    if not frag_available():
+        raise FileNotFoundError("oracle/_ref/libvkfrag.so is not built (no reference shaders at %s)" % ref_dir())
+    L = C.CDLL(_FRAG_LIB_PATH)
+    p, i64, fp = C.c_void_p, C.c_int64, C.POINTER(C.c_float)
+    for n in ("vkfrag_raycaster", "vkfrag_isosurface"):
+        getattr(L, n).argtypes = [p, i64, i64, i64, fp, fp, C.c_float, i64, p, p]
+        getattr(L, n).restype = C.c_int
+    L.vkfrag_max_samples.argtypes = [C.c_int]
+    L.vkfrag_max_samples.restype = C.c_int
+    L.vkfrag_framebuffer_clamp.argtypes = [p, p, i64]
+    _frag_lib = L
+    return L
+
+
+class RefShader:
+    """The reference's own raycaster.frag (mode 0) or isosurface.frag (mode 1), compiled in place, through
+    oracle/_ref/libvkfrag.so.  The texture filter, normalize() and the zeroed `out` variable are the stand-in's
+    choices (oracle/ref/glsl.h); the camera and the rasteriser are not the reference's: the fragments come from
+    fragments() below."""
+
+    def __init__(self, mode):
+        assert mode in (0, 1)
+        self._L = frag_lib()
+        self.mode = mode
+        self._f = self._L.vkfrag_isosurface if mode else self._L.vkfrag_raycaster
+        self.max_samples = int(self._L.vkfrag_max_samples(mode))
+
+    def shade(self, volume, cam_pos, step_size, iso_value, vuv):
+        """volume: uint8 [Z][Y][X]; vuv: float32 [n][3].  Returns the raw vFragColor, float32 [n][4]: not clamped (blue
+        is 255 in mode 0), NaN where the shader computed NaN."""
+        v = np.ascontiguousarray(volume, np.uint8)
+        z, y, x = v.shape
+        uv = np.ascontiguousarray(vuv, np.float32).reshape(-1, 3)
+        out = np.empty((uv.shape[0], 4), np.float32)
+        rc = self._f(v.ctypes.data, x, y, z, (C.c_float * 3)(*cam_pos), (C.c_float * 3)(*step_size),
+                     float(iso_value), uv.shape[0], uv.ctypes.data, out.ctypes.data)
+        assert rc == 0
+        return out
+
+    def frame(self, volume, cam, params):
+        """The raw frame the shader produces from the oracle's fragments of (cam, params): float32 [H][W][4] and the
+        coverage mask; uncovered pixels hold the clear colour (1, 1, 1, 1)."""
+        vuv, covered = fragments(cam, params)
+        out = np.ones((params.height, params.width, 4), np.float32)
+        out[covered] = self.shade(volume, tuple(cam.pos), tuple(params.step_size), params.iso_value, vuv[covered])
+        return out, covered
+
+    def clamp(self, frag):
+        """The framebuffer's clamp to [0, 1] (NaN stays NaN)."""
+        a = np.ascontiguousarray(frag, np.float32)
+        out = np.empty_like(a)
+        self._L.vkfrag_framebuffer_clamp(a.ctypes.data, out.ctypes.data, a.size)
+        return out
+
+
 class TraceRec(C.Structure):
     _fields_ = [("depth", C.c_int32), ("epoch", C.c_int32), ("kind", C.c_int32),
                 ("distance", C.c_double), ("error", C.c_double), ("df", C.c_double), ("step", C.c_double)]
@@ -309,6 +385,8 @@ def lib():
     if hasattr(L, "vro_render"):
         L.vro_render.argtypes = [p, i64, i64, i64, C.POINTER(Camera), C.POINTER(RenderParams), p]
         L.vro_render.restype = C.c_int
+        L.vro_fragments.argtypes = [C.POINTER(Camera), C.POINTER(RenderParams), p, p]
+        L.vro_fragments.restype = None
         L.vro_composite_over.argtypes = [p, p, i64]
         L.vro_composite_finish.argtypes = [p, p, i64]
         L.vro_composite_slabs.argtypes = [p, C.c_int, i64, i64, C.c_int, C.POINTER(Camera), C.c_int, C.c_int, p]
@@ -535,6 +613,14 @@ def render(volume, cam, params):
     rc = lib().vro_render(v.ctypes.data, x, y, z, C.byref(cam), C.byref(params), out.ctypes.data)
     assert rc == 0
     return out
+
+
+def fragments(cam, params):
+    """The ray set-up vro_render marches from: (vUV float32 [H][W][3], covered bool [H][W])."""
+    vuv = np.empty((params.height, params.width, 3), np.float32)
+    covered = np.empty((params.height, params.width), np.uint8)
+    lib().vro_fragments(C.byref(cam), C.byref(params), vuv.ctypes.data, covered.ctypes.data)
+    return vuv, covered.astype(bool)
 
 
 def composite_over(front, back):

@@ -9,13 +9,23 @@
  *   uniforms        main.cpp:319-341,396-402 ; GL state main.cpp:367-369,392
  *   texture state   VolumeReader.h:114-127 (R8, GL_LINEAR, GL_CLAMP)
  *
- * PARITY UNPINNED against a real OpenGL driver: the GLSL cannot run here (no GL,
- * no GPU), the reference holds no golden images, and the GLM version is not
- * pinned.  Defined choices: clamp-to-edge sampling with
- * float32 weights, accumulator starts at 0, blue = 255 clamps to 1.0, identity
- * TransformationMatrix, RH lookAt / perspectiveFov with -1..1 depth.  What the
- * tests pin is (a) analytic cases and (b) GPU kernel == this restatement within
- * 2e-3 per channel.
+ * PINNED to the reference text: the march of both shaders.  The two .frag
+ * files compile in place as C++ (oracle/ref/frag_capi.cpp over the stand-in
+ * oracle/ref/glsl.h), and tests/test_ref_shader_parity.py feeds them the
+ * fragments of vro_fragments below: vro_render's frame is their raw output
+ * with the upper clamp (min(v, 1)), bit for bit, and so the same frame once a
+ * framebuffer has clamped both to [0, 1].  STILL UNPINNED: the texture
+ * filter (the GLSL cannot run on a GL driver here; tex3d is the defined choice
+ * of SURVEY.md Appendix C-8, clamp-to-edge sampling with float32 weights, and
+ * the stand-in's texture() is written the same way) and the camera /
+ * rasteriser (no GLM here: identity TransformationMatrix, RH lookAt /
+ * perspectiveFov with -1..1 depth are this file's reading).  Other defined
+ * choices: the accumulator starts at 0, a zero gradient gives N = 0 (GLSL:
+ * undefined), and the float frame carries the upper clamp only: blue = 255
+ * and the iso colours clamp to 1.0, while 1 - rgb stays below 0 where the
+ * shader computes it so (bright data); the lower clamp is the consumer's
+ * framebuffer's.  The tests also pin analytic cases and GPU kernel == this
+ * restatement within 2e-3 per channel.
  *
  * The rasteriser is replaced by its per-pixel equivalent: the fragment that
  * survives GL_LESS depth testing without culling is the nearest point of the cube
@@ -24,6 +34,7 @@
  */
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 typedef struct { float pos[3], front[3], up[3]; float fov_deg, z_near, z_far; } vro_camera;
@@ -84,15 +95,11 @@ static inline int inside(const float *p)
     return !(d < 3.0f);
 }
 
-/* out: height*width*4 float, row 0 = top of the image. */
-int vro_render(const uint8_t *vol, int64_t X, int64_t Y, int64_t Z, const vro_camera *cam, const vro_params *P, float *out)
+/* The ray set-up: for every pixel (row 0 = top of the image) whether the cube covers it and, where it does, the
+ * fragment's interpolant vUV.  vro_render marches from exactly these; the tests hand the same fragments to the
+ * reference's shaders compiled in place (ref/frag_capi.cpp).  vuv: height*width*3 float, covered: height*width bytes. */
+void vro_fragments(const vro_camera *cam, const vro_params *P, float *vuv_out, uint8_t *covered_out)
 {
-    vro_tex t;
-    t.v = vol; t.X = X; t.Y = Y; t.Z = Z;
-    t.GX = P->global_dims[0] > 0 ? P->global_dims[0] : X;
-    t.GY = P->global_dims[1] > 0 ? P->global_dims[1] : Y;
-    t.GZ = P->global_dims[2] > 0 ? P->global_dims[2] : Z;
-    t.ox = P->vol_origin[0]; t.oy = P->vol_origin[1]; t.oz = P->vol_origin[2];
     const int W = P->width, H = P->height;
     /* glm::lookAt(pos, pos+front, up) basis (main.cpp:396) */
     float f[3] = { cam->front[0], cam->front[1], cam->front[2] }, s[3], u[3];
@@ -106,7 +113,8 @@ int vro_render(const uint8_t *vol, int64_t X, int64_t Y, int64_t Z, const vro_ca
     const float tanX = tanY * (float)W / (float)H;
     for (int py = 0; py < H; ++py) {
         for (int px = 0; px < W; ++px) {
-            float *o = out + 4 * ((size_t)py * W + px);
+            float *vuv = vuv_out + 3 * ((size_t)py * W + px);
+            uint8_t *cov = covered_out + ((size_t)py * W + px);
             float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
             float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
             float dir[3];
@@ -124,12 +132,42 @@ int vro_render(const uint8_t *vol, int64_t X, int64_t Y, int64_t Z, const vro_ca
             }
             float th = t0 >= cam->z_near ? t0 : t1; /* front face, else (camera inside / clipped) back face */
             if (miss || t0 > t1 || th < cam->z_near || th > cam->z_far) {
+                *cov = 0;
+                vuv[0] = vuv[1] = vuv[2] = 0.0f;
+                continue;
+            }
+            *cov = 1;
+            for (int k = 0; k < 3; ++k) vuv[k] = (cam->pos[k] + th * dir[k]) + 0.5f;
+        }
+    }
+}
+
+/* out: height*width*4 float, row 0 = top of the image. */
+int vro_render(const uint8_t *vol, int64_t X, int64_t Y, int64_t Z, const vro_camera *cam, const vro_params *P, float *out)
+{
+    vro_tex t;
+    t.v = vol; t.X = X; t.Y = Y; t.Z = Z;
+    t.GX = P->global_dims[0] > 0 ? P->global_dims[0] : X;
+    t.GY = P->global_dims[1] > 0 ? P->global_dims[1] : Y;
+    t.GZ = P->global_dims[2] > 0 ? P->global_dims[2] : Z;
+    t.ox = P->vol_origin[0]; t.oy = P->vol_origin[1]; t.oz = P->vol_origin[2];
+    const int W = P->width, H = P->height;
+    const size_t npix = (size_t)(W > 0 ? W : 0) * (size_t)(H > 0 ? H : 0);
+    if (npix == 0) return 0;
+    float *frag = (float *)malloc(npix * 3 * sizeof(float));
+    uint8_t *covered = (uint8_t *)malloc(npix);
+    if (!frag || !covered) { free(frag); free(covered); return -1; }
+    vro_fragments(cam, P, frag, covered);
+    for (int py = 0; py < H; ++py) {
+        for (int px = 0; px < W; ++px) {
+            float *o = out + 4 * ((size_t)py * W + px);
+            const float *vuv = frag + 3 * ((size_t)py * W + px);
+            if (!covered[(size_t)py * W + px]) {
                 if (P->mode == 2) { o[0] = 0.0f; o[1] = 1.0f; o[2] = 0.0f; o[3] = 0.0f; }
                 else { o[0] = o[1] = o[2] = o[3] = 1.0f; } /* glClearColor(255,255,255,1) clamps to white */
                 continue;
             }
-            float vuv[3], gd[3], step[3], pos[3];
-            for (int k = 0; k < 3; ++k) vuv[k] = (cam->pos[k] + th * dir[k]) + 0.5f;
+            float gd[3], step[3], pos[3];
             for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cam->pos[k];
             norm3(gd);
             for (int k = 0; k < 3; ++k) { step[k] = gd[k] * P->step_size[k]; pos[k] = vuv[k]; }
@@ -144,6 +182,8 @@ int vro_render(const uint8_t *vol, int64_t X, int64_t Y, int64_t Z, const vro_ca
                     A += pa * 0.6f;
                     if (!P->no_early_exit && A > 0.99f) break;
                 }
+                /* b = 255 is clamped to 1; 1 - rgb is kept as the shader computes it, below 0 in bright data (rgb passes 1:
+                 * A only takes 0.6 of each sample).  A normalised framebuffer would clamp that to 0; the float frame does not. */
                 o[0] = 1.0f - rgb; o[1] = 1.0f - rgb; o[2] = 1.0f; o[3] = A;
             } else if (P->mode == 2) { /* same accumulation as an associative (c, tau) pair, own sub-box only */
                 float c = 0.0f, tau = 1.0f;
@@ -196,6 +236,8 @@ int vro_render(const uint8_t *vol, int64_t X, int64_t Y, int64_t Z, const vro_ca
             }
         }
     }
+    free(frag);
+    free(covered);
     return 0;
 }
 

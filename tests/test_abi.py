@@ -203,15 +203,15 @@ def test_raycast_entries_reject_bad_arguments_before_the_device(L, entry):
 
 
 def test_product_never_imports_oracle():
-    """The oracle and the reference build beside it (oracle/_ref/libvkref.so) are test infrastructure: nothing under
-    volumerenderer_amd/ or include/ may reference either."""
+    """The oracle and the reference builds beside it (oracle/_ref/libvkref.so, the codec; oracle/_ref/libvkfrag.so, the
+    fragment shaders) are test infrastructure: nothing under volumerenderer_amd/ or include/ may reference any of them."""
     for base in ("volumerenderer_amd", "include"):
         for dp, _, fs in os.walk(os.path.join(ROOT, base)):
             for f in fs:
                 if f.endswith((".py", ".h", ".hpp", ".hip", ".cpp")):
                     txt = open(os.path.join(dp, f), errors="ignore").read()
                     for needle in ("import oracle", "from oracle", "liboracle", "oracle/", "_ref/", "libvkref", "vkref_",
-                                   "RefTree", "ref_lib"):
+                                   "RefTree", "ref_lib", "libvkfrag", "vkfrag_", "RefShader", "frag_lib"):
                         assert needle not in txt, "%s references the oracle (%s)" % (f, needle)
 
 

@@ -2,8 +2,10 @@
 raycaster.frag / isosurface.frag (oracle/raymarch_oracle.c).
 
 Tolerance: |delta| <= 2e-3 per channel on float RGBA in [0,1] (about half an LSB of
-an 8-bit framebuffer; covers sqrt/pow/division rounding differences).  Parity with a
-real OpenGL driver is unpinned (no GL here; the reference holds no golden images)."""
+an 8-bit framebuffer; covers sqrt/pow/division rounding differences).  The restatement's march is
+pinned to the reference's shaders compiled in place, bit for bit (tests/test_ref_shader_parity.py;
+tests/test_gpu_ref_shader_parity.py holds the kernels to the shaders directly).  Still unpinned: the
+texture filter (a defined choice) and the camera / rasteriser (no GL driver and no GLM here)."""
 import math
 
 import numpy as np

@@ -4,7 +4,11 @@ The known-answer values the survey recorded
 and the tree file the reference's own save() wrote for the 16^3 case; see
 tests/golden/survey_known_answers.json for provenance.  Bit-exact.
 tests/test_ref_parity.py regenerates them from the reference compiled in place
-and compares the oracle with it far more widely."""
+and compares the oracle with it far more widely.
+
+The ray-march oracle (oracle/raymarch_oracle.c) has the same pin: tests/golden/ref_frag_frames.npz holds frames the
+reference's fragment shaders produced (tests/test_ref_shader_parity.py regenerates them from the shaders compiled in
+place and compares the oracle with them over a far wider matrix)."""
 import json
 import os
 
@@ -61,6 +65,27 @@ def test_mid_range_tree_known_answers(oracle, case):
     assert len(packed) == case["packed_bytes"]
     assert "%016x" % O.fnv1a64(packed) == case["packed_fnv"]
     assert O.measure_max_error(t.levelCut(), vol) == case["decoded_max_error"]
+
+
+def test_raymarch_oracle_reproduces_the_shaders_golden_frames(oracle):
+    """Raw vFragColor frames of raycaster.frag / isosurface.frag (inputs: fragcases.GOLDEN), recorded from the shaders
+    compiled in place.  The oracle's frame equals each, with the upper clamp min(v, 1), bit for bit (so also after a
+    framebuffer's clamp to [0, 1]); uncovered pixels hold the clear colour on both sides.  Runs without the reference, so every checkout keeps the pin."""
+    import fragcases as F
+    gold = np.load(os.path.join(GOLD, "ref_frag_frames.npz"))
+    assert json.loads(str(gold["inputs"])) == json.loads(json.dumps(F.GOLDEN))
+    modes = set()
+    for i in range(len(F.GOLDEN)):
+        vol, cam, P = F.golden_inputs(oracle, i)
+        raw = gold["frame_%d" % i]
+        assert raw.dtype == np.float32 and raw.shape == (F.GOLDEN_H, F.GOLDEN_W, 4) and np.isfinite(raw).all()
+        _, covered = oracle.fragments(cam, P)
+        assert covered.any() and (raw[~covered] == 1.0).all()
+        got = oracle.render(vol, cam, P)
+        assert got.tobytes() == np.minimum(raw, np.float32(1)).tobytes(), F.GOLDEN[i]
+        modes.add(P.mode)
+    assert modes == {0, 1}
+    assert (gold["frame_4"][..., 0] < 0).any() and (gold["frame_0"][..., 2] == 255).any()    # raw: b = 255 and bright data's negative red
 
 
 def test_guarded_variant_is_output_identical(oracle):
