@@ -29,6 +29,20 @@
  *  - a vr_brickset is a batch of B independent bricks of identical dimensions, one
  *    kd-tree per brick (a single VolumeKdtree is a brickset with B = 1).  All B
  *    trees are built / decoded by the same batched kernel launches.
+ *  - alignment of caller buffers.  Host pointers and the render half's device buffers may start at any byte unless
+ *    their entry says otherwise.  The codec's fastest kernels touch the caller's device buffer with 16-byte (the pool
+ *    packer: 4-byte) vectors, and the library does not rely on the hardware's tolerance of misaligned vector accesses:
+ *    a call that would launch such a kernel on a buffer that is not 16-byte aligned returns VR_ERR_INVALID with nothing
+ *    launched, nothing written and the set unchanged (as for vr_transfer_function::lut_dev); the same call with an
+ *    aligned buffer then works as ever.  Every other call takes its buffers at any byte offset and writes exactly the
+ *    bytes its entry names.  Each codec entry point below states its rule in a line that begins "Alignment:".  Two
+ *    terms, for power-of-two extents up to 1024 per axis (a set created under VRHIP_FORCE_IDX64 has neither):
+ *      x-run geometry: orig_tree_depth >= 12 and at least four of the twelve deepest tree levels split x -- e.g.
+ *        16x16x16, 16x8x32, 128x8x4, every cube from 16 up, the reference's brick sizes; not 8x64x64;
+ *      tiled geometry: X >= 128 and the six deepest tree levels split each axis twice in one repeated order, which is
+ *        (log2 X, log2 Y, log2 Z) = (m, m, m), (m+1, m, m) or (m+1, m+1, m) -- 128x64x64, 128x128x64, 128^3, 256x128x128,
+ *        256x256x128, 256^3 ...; not 128x8x4, 128x32x16 or 64^3.
+ *    Bricks of either geometry hold a multiple of 16 voxels, so every brick of an aligned buffer is aligned.
  */
 #ifndef VRHIP_H
 #define VRHIP_H
@@ -114,7 +128,9 @@ vr_status vr_brickset_set_max_epochs(vr_brickset *bs, int32_t max_epochs);      
 /* ---- encode: VolumeKdtree::build (R.cpp:17-140) --------------------------------
  * voxels_dev: num_bricks * X*Y*Z bytes, brick b at offset b*X*Y*Z, each x-fastest.
  * Unlike the reference (R.cpp:51-52) the input buffer is left untouched.
- * Asynchronous on `stream`; vr_brickset_info()/get_* synchronise. */
+ * Asynchronous on `stream`; vr_brickset_info()/get_* synchronise.
+ * Alignment: x-run geometry: voxels_dev 16-byte aligned, else VR_ERR_INVALID (the set keeps its previous trees); any
+ * other set: any byte offset. */
 vr_status vr_brickset_build(vr_brickset *bs, const uint8_t *voxels_dev, void *stream);
 
 /* Public members after build(): per-brick info, tree bytes (TwoBitArray::bits of
@@ -133,7 +149,9 @@ vr_status vr_brickset_get_packed4(vr_brickset *bs, int32_t brick, uint8_t *dst_h
  * levelCut, bit-exact.  0 <= cut_depth < max_tree_depth is a PROGRESSIVE cut with defined
  * semantics (new: the reference's walk de-synchronises there): the stream is
  * parsed completely, refinement stops below the cut, every voxel gets the decoded scalar of its
- * ancestor at depth min(cut_depth, depth of its terminal node).  Asynchronous on `stream`. */
+ * ancestor at depth min(cut_depth, depth of its terminal node).  Asynchronous on `stream`.
+ * Alignment: tiled geometry: out_dev 16-byte aligned at every cut, else VR_ERR_INVALID; any other set: any byte
+ * offset.  Exactly num_bricks * X*Y*Z bytes are written. */
 vr_status vr_brickset_decode(vr_brickset *bs, int32_t cut_depth, uint8_t *out_dev, void *stream);
 
 /* Per-brick progressive decode (view-dependent level of detail).  cuts_host[b] for every brick b of the set:
@@ -146,7 +164,9 @@ vr_status vr_brickset_decode(vr_brickset *bs, int32_t cut_depth, uint8_t *out_de
  * four calls may be in flight, back to back on one stream or on several streams, without a host synchronisation; a
  * fifth waits on the host until the oldest has finished.  Calls on one set from several host threads at once are
  * not supported (no call on a set is).  A set opened from a file, cut above the index level, fills the cut values on
- * the host (as vr_brickset_decode does).  vr_brickset_last_timings reports the call's whole time as `decode`. */
+ * the host (as vr_brickset_decode does).  vr_brickset_last_timings reports the call's whole time as `decode`.
+ * Alignment: tiled geometry with any cut >= 0: out_dev 16-byte aligned, else VR_ERR_INVALID; any other set, or every
+ * brick skipped: any byte offset.  Only the X*Y*Z bytes of bricks with a cut >= 0 are written. */
 vr_status vr_brickset_decode_lod(vr_brickset *bs, const int32_t *cuts_host, uint8_t *out_dev, void *stream);
 
 /* Level-of-detail pool: each brick of a frame stored at the resolution its cut actually has.  For power-of-two brick
@@ -186,7 +206,11 @@ vr_status vr_lod_pool_layout(const int64_t brick_dims[3], int32_t num_bricks, co
  * a staging buffer of the set, then packed.  The staging buffer's use is ordered across streams by an event; the
  * lists come from vr_brickset_decode_lod's ring (same concurrency contract, no host synchronisation).
  * VR_ERR_UNSUPPORTED (nothing launched) unless every brick extent is a power of two; VR_ERR_INVALID as for the layout
- * and for a pool smaller than the layout's.  vr_brickset_last_timings reports the call's whole time as `decode`. */
+ * and for a pool smaller than the layout's.  vr_brickset_last_timings reports the call's whole time as `decode`.
+ * Alignment: pool_dev 16-byte aligned, else VR_ERR_INVALID (the table is not uploaded either), when the set has tiled
+ * geometry and a brick with cut >= 0 is stored at full resolution (shift 0 on every axis), or when a brick of any set
+ * is stored coarser with rows of four stored voxels or more ((X >> shift_x) >= 4); otherwise any byte offset.  table_dev
+ * is written by a copy: any byte offset. */
 #define VR_POOL_STAGE_BRICKS 32
 vr_status vr_brickset_decode_lod_pool(vr_brickset *bs, const int32_t *cuts_host, const int64_t *brick_ijk_host,
                                       const int64_t grid[3], uint8_t *pool_dev, int64_t pool_bytes,
@@ -197,7 +221,8 @@ vr_status vr_brickset_decode_lod_pool(vr_brickset *bs, const int32_t *cuts_host,
  * decode applied to the range stream, i.e. per voxel the half range of its terminal node's box as the
  * encoder reconstructed it (distanceMap_range, codes of tree_range).  With vr_brickset_decode this gives
  * [mid - range, mid + range] bounds at any cut depth (coarse-to-fine refinement, empty-space tests).
- * VR_ERR_STATE for other variants, VR_ERR_UNSUPPORTED for a set opened from a file. */
+ * VR_ERR_STATE for other variants, VR_ERR_UNSUPPORTED for a set opened from a file.
+ * Alignment: as vr_brickset_decode. */
 vr_status vr_brickset_decode_range(vr_brickset *bs, int32_t cut_depth, uint8_t *out_dev, void *stream);
 
 /* Install a foreign preorder stream (e.g. read from a reference-written file) as
@@ -220,7 +245,9 @@ vr_status vr_brickset_open_variant(vr_brickset **out, const char *path, int32_t 
 
 /* ---- error helpers: measureMaxError / measureMeanError / queryError (R.cpp:386-411)
  * The reference dereferences the input it has already cleared (SURVEY C-7); here the
- * original volume is passed explicitly.  n = number of voxels. */
+ * original volume is passed explicitly.  n = number of voxels.
+ * Alignment: decoded_dev, original_dev and error_dev at any byte offset, each independently; vr_query_error writes
+ * exactly n bytes. */
 vr_status vr_measure_error(const uint8_t *decoded_dev, const uint8_t *original_dev, int64_t n,
                            int32_t *max_error, double *mean_error, void *stream);
 vr_status vr_query_error(const uint8_t *decoded_dev, const uint8_t *original_dev, int64_t n,

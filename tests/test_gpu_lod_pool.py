@@ -84,6 +84,10 @@ def run_pool(vr, bs, cuts, ijk, grid, extra=4096, stream=None):
     _, nbytes = vr.lod_pool_layout(bs.dims, ijk, grid, cuts, info["orig_tree_depth"], info["max_tree_depth"])
     pool = torch.full((nbytes + extra,), FILL, dtype=torch.uint8, device="cuda")
     table = torch.full((int(np.prod(grid)) * 16,), 0x5A, dtype=torch.uint8, device="cuda")
+    if stream is not None:
+        # the fills above run on the current stream, which a side stream does not follow: without this they may land
+        # on top of what the call has already written (a wait on the device, no host synchronisation)
+        stream.wait_stream(torch.cuda.current_stream())
     bs.decode_lod_pool(cuts, ijk, grid, pool=pool, table=table, stream=stream)
     return pool, table
 

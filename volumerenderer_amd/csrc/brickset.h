@@ -157,7 +157,11 @@ inline bool leafless_build(const BrickSet &b) { return b.D >= 12 && b.maxEpochs 
 // kd_encode.hip
 int encode_launch(BrickSet *bs, const uint8_t *voxDev, hipStream_t st);
 int compact_launch(BrickSet *bs, hipStream_t st);   // fused builds: contiguous stream(s) into Stream2::treeCompact
+bool build_loads_vectors(const BrickSet *bs);       // k_pyramid12 serves the set: 16-byte loads from the caller's voxels
 // kd_decode.hip
+// would the call store vectors to the caller's buffer (the tiled kernels, k_pool_pack)?  capi.hip asks before it launches
+bool decode_stores_vectors(const BrickSet *bs, int cutDepth, bool rangeStream);
+bool decode_lod_stores_vectors(const BrickSet *bs, const int32_t *cutsHost, const PoolDest *pool);
 int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false);
 // per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
 int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st, const PoolDest *pool = nullptr);

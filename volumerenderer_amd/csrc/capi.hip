@@ -228,6 +228,10 @@ vr_status vr_brickset_destroy(vr_brickset *h)
 
 static bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// vrhip.h "alignment of caller buffers": a call that would launch a kernel with vector accesses to a caller's buffer
+// is refused, before anything is launched, unless that buffer is 16-byte aligned
+static bool misaligned16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+
 vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_t dims[3], int32_t tolerance,
                              int32_t max_epochs, int32_t variant)
 {
@@ -363,6 +367,7 @@ vr_status vr_brickset_build(vr_brickset *h, const uint8_t *vox, void *stream)
 {
     if (!h || !vox) return VR_ERR_INVALID;
     BrickSet &b = h->s;
+    if (build_loads_vectors(&b) && misaligned16(vox)) return VR_ERR_INVALID;
     // (vr_brickset_set_max_epochs(0) <-> >= 1 between two builds changes what the level loop keeps of the leaf level:
     // the encoder's arrays are made again for the other mode)
     if (b.encoderReady && b.leafless != leafless_build(b)) {
@@ -562,6 +567,7 @@ vr_status vr_brickset_decode(vr_brickset *h, int32_t cut_depth, uint8_t *out, vo
     if (!b.built) return VR_ERR_STATE;
     if (cut_depth > b.maxDepth) return VR_ERR_INVALID;
     const int cut = cut_depth < 0 ? b.maxDepth : cut_depth;
+    if (decode_stores_vectors(&b, cut, false) && misaligned16(out)) return VR_ERR_INVALID;
     if (cut < b.Ds && b.foreign) {
         // ancestor scalars at the cut depth, from the stream bytes kept at set_tree/open time
         vr_status rc = sync_ctrl(b);
@@ -594,6 +600,7 @@ vr_status vr_brickset_decode_lod(vr_brickset *h, const int32_t *cuts, uint8_t *o
         if (cuts[br] < -1 || cuts[br] > b.maxDepth) return VR_ERR_INVALID;
         above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
     }
+    if (decode_lod_stores_vectors(&b, cuts, nullptr) && misaligned16(out)) return VR_ERR_INVALID;
     if (above && b.foreign) {
         vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
         if (rc != VR_OK) return rc;
@@ -704,14 +711,15 @@ vr_status vr_brickset_decode_lod_pool(vr_brickset *h, const int32_t *cuts, const
     vr_status st = pool_layout(bd, b.B, ijk, grid, cuts, b.D, b.maxDepth, off.data(), sh.data(), tab.data(), &total);
     if (st != VR_OK) return st;
     if (pool_bytes < total) return VR_ERR_INVALID;
+    PoolDest d;
+    d.pool = pool; d.off = off.data(); d.shift = sh.data(); d.tab = tab.data(); d.tabDev = table_dev; d.cells = cells;
+    if (decode_lod_stores_vectors(&b, cuts, &d) && misaligned16(pool)) return VR_ERR_INVALID;
     bool above = false;
     for (int br = 0; br < b.B; ++br) above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
     if (above && b.foreign) {
         vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
         if (rc != VR_OK) return rc;
     }
-    PoolDest d;
-    d.pool = pool; d.off = off.data(); d.shift = sh.data(); d.tab = tab.data(); d.tabDev = table_dev; d.cells = cells;
     const int rc = decode_lod_launch(&b, cuts, nullptr, (hipStream_t)stream, &d);
     if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
     b.decodeTimingPending = true;
@@ -816,6 +824,7 @@ vr_status vr_brickset_decode_range(vr_brickset *h, int32_t cut_depth, uint8_t *o
     if (b.foreign) return VR_ERR_UNSUPPORTED;          // an opened file carries no BFS codes to seed the index scalars from
     if (cut_depth > b.maxDepth) return VR_ERR_INVALID;
     const int cut = cut_depth < 0 ? b.maxDepth : cut_depth;
+    if (decode_stores_vectors(&b, cut, true) && misaligned16(out)) return VR_ERR_INVALID;
     if (decode_launch(&b, out, cut, (hipStream_t)stream, true) != 0) return VR_ERR_NO_DEVICE;
     b.decodeTimingPending = true;
     b.lastStream = stream;

@@ -1984,6 +1984,32 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
     return launch_status("decode");
 }
 
+// The rule of vrhip.h ("alignment of caller buffers"): the tiled kernels store 16-byte vectors to the caller's buffer,
+// k_decode_lane and k_owner_gather bytes.  capi.hip refuses a misaligned buffer before anything is launched.
+static bool stores_vectors(DecodeKernel k)
+{
+    return k == DecodeKernel::REGION || k == DecodeKernel::QUAD || k == DecodeKernel::FINE || k == DecodeKernel::TILE;
+}
+
+bool decode_stores_vectors(const BrickSet *bs, int cut, bool rangeStream)
+{
+    const DecodePlan plan(bs, rangeStream);
+    return stores_vectors(plan.kernel(cut));
+}
+
+// per-brick cuts.  Without a pool every decoded brick goes to the caller's buffer; with one, the full-resolution bricks
+// do (the coarse ones go to the set's staging buffer) and k_pool_pack writes 32-bit words for stored rows of 4 bytes or more
+bool decode_lod_stores_vectors(const BrickSet *bs, const int32_t *cutsHost, const PoolDest *pool)
+{
+    const DecodePlan plan(bs, false);
+    for (int b = 0; b < bs->B; ++b) {
+        if (cutsHost[b] < 0) continue;
+        const bool coarse = pool && (pool->shift[3 * b] | pool->shift[3 * b + 1] | pool->shift[3 * b + 2]) != 0;
+        if (coarse ? bs->g.nb[0] - pool->shift[3 * b] >= 2 : stores_vectors(plan.kernel(cutsHost[b]))) return true;
+    }
+    return false;
+}
+
 int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream)
 {
     const DecodePlan plan(bs, rangeStream);

@@ -2632,6 +2632,16 @@ static int ensure_aux(BrickSet *bs, int n)
     return have;
 }
 
+// k_pyramid12 builds the bottom twelve levels where they split x four times or more: every thread then loads one
+// 16-byte x-run of the caller's voxels (vrhip.h "alignment of caller buffers"; capi.hip checks the pointer)
+bool build_loads_vectors(const BrickSet *bs)
+{
+    if (bs->D < 12 || bs->generalGeom) return false;
+    int ax = 0;
+    for (int q = 0; q < 12; ++q) ax += bs->g.axis[bs->D - 12 + q] == 0;
+    return ax >= 4;
+}
+
 int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
 {
     const int D = bs->D, B = bs->B;
@@ -2652,16 +2662,14 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         int64_t inStride = 0;
         const int64_t oStride = (int64_t)1 << (D > 10 ? D - 10 : 0);
         Pyr12Geom pg{};
-        bool use12 = D >= 12 && !bs->generalGeom;
+        const bool use12 = build_loads_vectors(bs);
         skipOn = skipOn && use12;
         if (use12) {
             for (int q = 0; q < 12; ++q) {
                 const int ax = bs->g.axis[D - 12 + q];
                 if (ax == 0) pg.ax++; else if (ax == 1) pg.ay++; else pg.az++;
             }
-            use12 = pg.ax >= 4;
-            skipOn = skipOn && use12;
-            for (int i = 0; i < 16 && use12; ++i) {
+            for (int i = 0; i < 16; ++i) {
                 uint32_t r = 0;
                 for (int q = 0; q < 12; ++q) {
                     const int dd = D - 12 + q;
