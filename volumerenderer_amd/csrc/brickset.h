@@ -55,6 +55,10 @@ struct BrickSet {
     int32_t K = 0;            // decode index granularity: subtrees of 2^K leaves
     int32_t Ds = 0;           // D - K
     int64_t heapStride = 0;   // 2^(D+1)
+    // After a SkipBlocks build (kd_encode.hip) parts of the truth heaps (Stream2::temp) are UNDEFINED -- whatever an
+    // earlier build or the allocator left there: levels D-1 and D of every constant 4096-leaf block (blockFlag bit 0) of
+    // a constant brick, and of every such block the level loop skipped (bit 1).  No kernel uses them (DESIGN.md 3.2,
+    // "who loads levels D-1 and D"); a new reader must check Ctrl::constBrick and the flag first.
     int64_t leafStride = 0;   // 2^D
     int64_t codeStride = 0;   // bytes of packed BFS codes per brick: heapStride / 4, 4-byte aligned (leafless builds: the levels above the leaves only)
     int64_t reconStride = 0;  // bytes per brick of a reconstruction buffer: 2^D, or 2^(D-1) in a leafless build

@@ -177,6 +177,49 @@ k_pyramid12(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__re
     const uint4 v4 = *(const uint4 *)(vox + (int64_t)brick * g.voxels + (bx + xs * 16) +
                                       (int64_t)g.X * ((by + y) + (int64_t)g.Y * (bz + z)));
     const uint32_t vw[4] = {v4.x, v4.y, v4.z, v4.w};
+    // SkipBlocks builds: a box whose 4096 voxels are one value v leaves here.  Every level array of it holds v (half
+    // ranges 0); levels D-2 .. D-12 go out as wide stores of the broadcast byte, levels D-1 and D are NOT written: the
+    // level loop never loads them for a block it skips, and k_fill_const_leaves writes them for the others before
+    // their first reader.  One barrier more than the path below, in front of the LDS transposition.
+    if (blockFlag) {
+        const uint32_t v0 = __builtin_amdgcn_perm(0, v4.x, 0u);                    // byte 0 x 4
+        const bool mine = ((v4.x ^ v0) | (v4.y ^ v0) | (v4.z ^ v0) | (v4.w ^ v0)) == 0u;
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)v0);
+        const bool waveConst = __ballot(!mine || v0 != first) == 0ull;
+        if (lane == 0) waveMM[t >> 6] = waveConst ? first : 0x100u;                // (0x100: no byte x 4 looks like it)
+        __syncthreads();
+        const uint32_t c0 = waveMM[0];
+        if (c0 != 0x100u && waveMM[1] == c0 && waveMM[2] == c0 && waveMM[3] == c0) {
+            const uint4 cv = make_uint4(c0, c0, c0, c0), zv = make_uint4(0, 0, 0, 0);
+            if (t < 127) {
+                // 16 bytes per thread: threads 0 .. 63 level D-2, 64 .. 95 D-3, 96 .. 111 D-4, .. , 126 D-8
+                const int m = t < 64 ? 0 : 5 - (31 - __clz(127 - t));             // threads 64 ..: level D-3-m
+                const int k = t < 64 ? 2 : 3 + m, within = t < 64 ? t : (t - 64) - (64 - (64 >> m));
+                const int64_t o = ((int64_t)1 << (D - k)) + (base >> k) + within * 16;
+                st16(T + o, cv);
+                if (TR) *(uint4 *)(TR + o) = zv;
+            } else if (t == 127) {                      // levels D-9 .. D-12 (8, 4, 2, 1 bytes), the block's root
+                const int64_t o9 = ((int64_t)1 << (D - 9)) + (base >> 9), o10 = ((int64_t)1 << (D - 10)) + (base >> 10);
+                const int64_t o11 = ((int64_t)1 << (D - 11)) + (base >> 11), o12 = ((int64_t)1 << (D - 12)) + (base >> 12);
+                *(uint2 *)(T + o9) = make_uint2(c0, c0);
+                *(uint32_t *)(T + o10) = c0;
+                *(uint16_t *)(T + o11) = (uint16_t)c0;
+                T[o12] = (uint8_t)c0;
+                if (TR) {
+                    *(uint2 *)(TR + o9) = make_uint2(0, 0);
+                    *(uint32_t *)(TR + o10) = 0;
+                    *(uint16_t *)(TR + o11) = 0;
+                    TR[o12] = 0;
+                }
+                outMin[(int64_t)brick * outStride + (base >> 12)] = (uint8_t)c0;
+                outMax[(int64_t)brick * outStride + (base >> 12)] = (uint8_t)c0;
+                blockFlag[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = 1u;
+                if (blockFlagR) blockFlagR[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = 1u;
+            }
+            return;
+        }
+        // (waveMM is written again further down, behind the barrier that follows)
+    }
 #pragma unroll
     for (int i = 0; i < 16; ++i) leaf[r0 | pg.sx[i]] = (uint8_t)(vw[i >> 2] >> ((i & 3) * 8));
     __syncthreads();
@@ -1234,6 +1277,44 @@ __global__ void k_level_end(int d, Ctrl *ctrls)
     c.cur = 0; c.prev = 1; c.pendingEqual = 0;
     c.active = 0; c.fillThisEpoch = 0;
     c.altValid = 0; c.altSel = 0;
+}
+
+// Levels D-1 and D of the constant 4096-leaf blocks that the level loop will visit: k_pyramid12 left them unwritten
+// (SkipBlocks builds).  Between the end of level D-2 and the head of level D-1, when bit 1 of the flags is final: a
+// block with bit 0 set and bit 1 clear, in a brick that is not constant, gets 4096 + 2048 bytes of its own
+// depth-(D-12) truth (the voxel value in the mid stream, 0 in the half-range stream).  A wave takes 64 consecutive
+// blocks at a time, one flag and one root byte per lane, and writes the blocks that need it one after the other
+// (6 KiB each, six 16-byte streaming stores per lane).
+__global__ void __launch_bounds__(256)
+k_fill_const_leaves(int D, const Ctrl *ctrls, uint8_t *__restrict__ temp, int64_t heapStride, SkipBlocks sk)
+{
+    const int brick = blockIdx.y, lane = threadIdx.x & 63;
+    if (ctrls[brick].constBrick) return;
+    uint8_t *T = temp + (int64_t)brick * heapStride;
+    const uint8_t *flag = sk.flag + (int64_t)brick * sk.nBlk;
+    const uint32_t nBlk = (uint32_t)sk.nBlk;
+    for (uint32_t b0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; b0 < nBlk; b0 += gridDim.x * 256u) {
+        const uint32_t blk = b0 + (uint32_t)lane;
+        uint32_t v = 0;
+        bool need = false;
+        if (blk < nBlk) {
+            need = (flag[blk] & 3u) == 1u;
+            v = T[((int64_t)1 << (D - 12)) + blk];
+        }
+        unsigned long long todo = __ballot(need);
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1ull;
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)v, l) * 0x01010101u;
+            const uint4 wv = make_uint4(w, w, w, w);
+            uint8_t *leafL = T + ((int64_t)1 << D) + ((int64_t)(b0 + (uint32_t)l) << 12) + lane * 16;
+            uint8_t *parL = T + ((int64_t)1 << (D - 1)) + ((int64_t)(b0 + (uint32_t)l) << 11) + lane * 16;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) st16(leafL + j * 1024, wv);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) st16(parL + j * 1024, wv);
+        }
+    }
 }
 
 // The range stream's prune follows the mid stream (M.cpp:864-865); see k_prune_*.
@@ -2503,6 +2584,11 @@ static void compress_stream(BrickSet *bs, Stream2 &s0, hipStream_t st, const uin
     }
     for (int d = 0; d <= D; ++d) {
         const int64_t n = (int64_t)1 << d;
+        // the skip bits are final (level D-2 has ended): the constant blocks that are not skipped get the two levels
+        // k_pyramid12 did not write, in front of their first reader
+        if (sk.flag && d == D - 1)
+            hipLaunchKernelGGL(k_fill_const_leaves, dim3(cdiv(sk.nBlk, 256), B), dim3(256), 0, st, D, s.ctrl, s.temp,
+                               bs->heapStride, sk);
         hipLaunchKernelGGL(k_est_head, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, s.ctrl, s.temp, bs->heapStride, rb,
                            bs->reconStride, sk);
         if (n > EST_HEAD) {
