@@ -1,4 +1,4 @@
-"""CPU check of k_decode_region's addressing (host tables of region_geometry + the kernel's index arithmetic)."""
+"""CPU check of k_decode_region's addressing (host tables of region_plan / make_plans in csrc/host_plan.cpp + the kernel's index arithmetic)."""
 import itertools
 
 def geometry(jx, jy, jz, X=256, Y=256):

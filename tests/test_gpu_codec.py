@@ -798,3 +798,55 @@ def test_leafless_builds_across_epoch_settings_on_one_handle(vr, oracle):
             assert np.array_equal(bs.tree(0), ref.tree), (ep, tol)
             assert np.array_equal(bs.decode().cpu().numpy().reshape(z, y, x), ref.levelCut()), (ep, tol)
     assert reverts >= 1
+
+
+def test_stored_plans_follow_state_changed_after_create(vr, oracle):
+    """The launch geometry of a set is planned once, at create; the switches, the per-4-leaf side-cars and the epoch
+    setting change afterwards and every decode must follow them.  One handle of two bricks of the smallest extents that
+    k_decode_region serves (tests/golden/decode_plans.json), decoded at cuts on both sides of every kernel's range under
+    each switch in turn, then rebuilt in the storing mode; then a second handle filled by set_tree from the first one's
+    streams (the side-car flag assigned there) through the same switches.  Every decode equals the oracle's."""
+    import json
+    plans = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "decode_plans.json")))["plans"]
+    x, y, z = min((p[:3] for p in plans if p[4][0]), key=lambda d: d[0] * d[1] * d[2])
+    shape = (z, y, x)
+    half = rm_like(shape, 9)
+    half[:, :, x // 2:] = 200                                       # half of it constant: pruned 16^3 blocks
+    vols = [rm_like(shape, 8), half]
+    refs = [oracle.OracleTree(v.copy(), tolerance=1, max_epochs=2).build() for v in vols]
+    D, M = refs[0].origTreeDepth, refs[0].maxTreeDepth
+    cuts = [None, D, D - 3, D - 4, D - 6 - 1]                       # (Ds = D - 6)
+    want = {c: np.stack([r.levelCut() if c is None else r.levelCutProgressive(c) for r in refs]) for c in cuts}
+
+    def decodes(h):
+        return {c: (h.decode() if c is None else h.decode(cut_depth=c)).cpu().numpy().reshape((2,) + shape) for c in cuts}
+
+    def walk_switches(h, tag):
+        first = decodes(h)
+        for c in cuts:
+            assert np.array_equal(first[c], want[c]), (tag, "default", c)
+        for name in ("decode_quad", "decode_fine_v1", "decode_walk"):
+            h.set_switch(name, 1)
+            got = decodes(h)
+            h.set_switch(name, 0)
+            for c in cuts:
+                assert np.array_equal(got[c], want[c]), (tag, name, c)
+        last = decodes(h)
+        for c in cuts:
+            assert last[c].tobytes() == first[c].tobytes(), (tag, "default again", c)
+
+    bs = vr.BrickSet(2, (x, y, z), 1, 2)
+    bs.build(np.stack(vols))
+    for b in range(2):
+        assert np.array_equal(bs.tree(b), refs[b].tree), b
+    walk_switches(bs, "built")
+    streams = [(bs.tree(b).copy(), bs.info(b)["num_active_nodes"], bs.distance_map(b).copy()) for b in range(2)]
+    bs.set_max_epochs(0)
+    bs.build(np.stack(vols))
+    got = bs.decode().cpu().numpy().reshape((2,) + shape)
+    for b in range(2):
+        assert np.array_equal(got[b], oracle.OracleTree(vols[b].copy(), tolerance=1, max_epochs=0).build().levelCut()), b
+    fs = vr.BrickSet(2, (x, y, z), 1, 2)
+    for b, (tree, n, dmap) in enumerate(streams):
+        fs.set_tree(b, tree, n, dmap)
+    walk_switches(fs, "foreign")

@@ -2,6 +2,7 @@
 #pragma once
 #include "kd_common.h"
 #include "../../include/vrhip.h"
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -50,6 +51,9 @@ struct BrickSet {
     int32_t B = 0;
     Switches sw;
     Geom g{};
+    TilePlan tile{};          // launch geometry (host_plan.h), made once by vr_brickset_create: nothing in it depends on
+    RegionPlan region{};      // the switches or on anything else that can change afterwards
+    Pyr12Plan pyr12{};
     int32_t D = 0, maxDepth = 0;
     int32_t tolerance = 6, maxEpochs = 5, variant = 0;
     int32_t K = 0;            // decode index granularity: subtrees of 2^K leaves
@@ -90,6 +94,7 @@ struct BrickSet {
     uint8_t *idxValCut = nullptr; // B * nIdx  progressive cut above the index level: ancestor scalars
     uint8_t *fineIdx = nullptr;   // B * nIdx * 16  tokens owned by each 4-leaf subtree of a depth-Ds node (fused encoder only)
     std::vector<uint8_t> fineHas; // per brick: fineIdx describes its current stream (all set -> k_decode_fine)
+    bool fineAll = false;         // ... of every brick: kept by fine_has_changed() wherever fineHas is assigned
     uint32_t *decTables = nullptr; // B * FD_TABLE_WORDS: k_decode_fine's tables of every brick for the current cut
     uint8_t *idxVal3 = nullptr;   // B * nIdx * 8   decoded scalar of every depth-(D-3) node (k_decode_quad; with fineIdx)
     uint32_t *chainTab = nullptr; // 8 x 16384 entries: k_decode_quad's grown-branch tables, one per number of refining levels (0..7),
@@ -158,10 +163,12 @@ struct PoolDest {
 // level (BrickSet::leafless).
 inline bool leafless_build(const BrickSet &b) { return b.D >= 12 && b.maxEpochs >= 1; }
 
+inline void fine_has_changed(BrickSet &b) { b.fineAll = (int)b.fineHas.size() == b.B && std::find(b.fineHas.begin(), b.fineHas.end(), 0) == b.fineHas.end(); }
+
 // kd_encode.hip
 int encode_launch(BrickSet *bs, const uint8_t *voxDev, hipStream_t st);
 int compact_launch(BrickSet *bs, hipStream_t st);   // fused builds: contiguous stream(s) into Stream2::treeCompact
-bool build_loads_vectors(const BrickSet *bs);       // k_pyramid12 serves the set: 16-byte loads from the caller's voxels
+inline bool build_loads_vectors(const BrickSet *bs) { return bs->pyr12.use12; }   // k_pyramid12 serves the set: 16-byte loads from the caller's voxels
 // kd_decode.hip
 // would the call store vectors to the caller's buffer (the tiled kernels, k_pool_pack)?  capi.hip asks before it launches
 bool decode_stores_vectors(const BrickSet *bs, int cutDepth, bool rangeStream);
@@ -170,13 +177,6 @@ int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, b
 // per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
 int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st, const PoolDest *pool = nullptr);
 void free_lod_slots(BrickSet *bs);
-int cut_values_from_stream(BrickSet *bs, const uint8_t *treeHost, int64_t numActive, const uint8_t *dmapHost, int cut,
-                           std::vector<uint8_t> &vals);
-int build_index_from_stream(BrickSet *bs, int brick, const uint8_t *treeHost, int64_t numActive,
-                            const uint8_t *dmapHost, std::vector<uint32_t> &offs, std::vector<uint8_t> &vals,
-                            std::vector<uint8_t> &fine, std::vector<uint8_t> &val3);
-void make_geom(Geom &g, const int64_t dims[3]);
 int build_general_geometry(BrickSet *bs);   // srcIdx / ownerRank for general extents (0, -3 out of memory, -1 device error)
-void make_lut(const Geom &g, int K, std::vector<uint32_t> &lut);
 
 } // namespace vr

@@ -124,13 +124,13 @@ static void free_stream2(Stream2 &s)
     s = Stream2();
 }
 
-static vr_status alloc_stream2(BrickSet &b, Stream2 &s, bool encoder)
+// (the encoder's arrays are made by ensure_encoder_buffers at the first build)
+static vr_status alloc_stream2(BrickSet &b, Stream2 &s)
 {
     const size_t B = (size_t)b.B;
     HIPCHK(hipMalloc(&s.ctrl, B * sizeof(Ctrl)));
     HIPCHK(hipMemset(s.ctrl, 0, B * sizeof(Ctrl)));
     HIPCHK(hipMalloc(&s.tree, B * (size_t)b.treeCap));
-    (void)encoder;      // (the encoder's arrays are made by ensure_encoder_buffers at the first build)
     return VR_OK;
 }
 
@@ -280,7 +280,8 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         if (gappedBytes > b.treeCap) b.treeCap = gappedBytes;
     }
     b.nIdx = (int64_t)1 << b.Ds;
-    vr_status rc = alloc_stream2(b, b.mid, false);
+    make_plans(b.g, b.K, b.generalGeom, b.idx64, b.treeCap, b.tile, b.region, b.pyr12);
+    vr_status rc = alloc_stream2(b, b.mid);
     if (rc == VR_OK) {
         hipError_t e = hipMalloc(&b.idxOff, (size_t)b.B * b.nIdx * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(&b.idxVal, (size_t)b.B * b.nIdx);
@@ -289,29 +290,13 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
             const int grc = build_general_geometry(&b);
             if (grc != 0) e = grc == -3 ? hipErrorOutOfMemory : hipErrorUnknown;
         }
+        const auto upload = [](uint32_t *dst, const std::vector<uint32_t> &v) {
+            return hipMemcpy(dst, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        };
         if (e == hipSuccess) e = hipMalloc(&b.lut, ((size_t)1 << b.K) * sizeof(uint32_t));
-        if (e == hipSuccess && !general) {
-            std::vector<uint32_t> lut;
-            make_lut(b.g, b.K, lut);
-            e = hipMemcpy(b.lut, lut.data(), lut.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        }
+        if (e == hipSuccess && !general) e = upload(b.lut, make_lut(b.g, b.K));
         if (e == hipSuccess && !general) e = hipMalloc(&b.spread, (size_t)(b.g.X + b.g.Y + b.g.Z) * sizeof(uint32_t));
-        if (e == hipSuccess && !general) {
-            // kernels never walk Geom::axis/bit (a dependent chain of loads from the kernel-argument
-            // segment): a coordinate's contribution to the Morton rank comes from this table
-            std::vector<uint32_t> sp((size_t)(b.g.X + b.g.Y + b.g.Z), 0u);
-            const int off[3] = {0, b.g.X, b.g.X + b.g.Y}, ext[3] = {b.g.X, b.g.Y, b.g.Z};
-            for (int ax = 0; ax < 3; ++ax)
-                for (int v = 0; v < ext[ax]; ++v) {
-                    uint32_t r = 0;
-                    for (int d = 0; d < b.g.D; ++d) {
-                        r <<= 1;
-                        if (b.g.axis[d] == ax) r |= (uint32_t)(v >> b.g.bit[d]) & 1u;
-                    }
-                    sp[(size_t)off[ax] + v] = r;
-                }
-            e = hipMemcpy(b.spread, sp.data(), sp.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        }
+        if (e == hipSuccess && !general) e = upload(b.spread, make_spread(b.g));
         for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&b.ev[i]);
         // (the internal streams of a build are created when a build first needs them: kd_encode.hip ensure_aux)
         if (e != hipSuccess) rc = e == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_NO_DEVICE;
@@ -550,24 +535,26 @@ vr_status vr_brickset_get_packed4(vr_brickset *h, int32_t brick, uint8_t *dst, i
     HIPCHK(hipMemcpy(m.data(), baseM, (size_t)bytes, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(r.data(), baseR, (size_t)bytes, hipMemcpyDeviceToHost));
     memset(dst, 0, (size_t)v);
-    auto get = [](const std::vector<uint8_t> &a, int64_t i) { return (a[(size_t)(i >> 2)] >> ((i & 3) * 2)) & 3; };
     int64_t o = 0;
     for (int64_t i = 0; i < n; i += 2) {
-        int first = get(m, i), second = get(r, i), third = 0, fourth = 0;
-        if (i + 1 < n) { third = get(m, i + 1); fourth = get(r, i + 1); }
+        int first = cget(m.data(), i), second = cget(r.data(), i), third = 0, fourth = 0;
+        if (i + 1 < n) { third = cget(m.data(), i + 1); fourth = cget(r.data(), i + 1); }
         dst[o++] = (uint8_t)((first << 6) | (second << 4) | (third << 2) | fourth);
     }
     return VR_OK;
 }
 
-vr_status vr_brickset_decode(vr_brickset *h, int32_t cut_depth, uint8_t *out, void *stream)
+// rangeStream: a MidRangeTree's half-range stream (vr_brickset_decode_range)
+static vr_status decode_common(vr_brickset *h, int32_t cut_depth, uint8_t *out, void *stream, bool rangeStream)
 {
     if (!h || !out) return VR_ERR_INVALID;
     BrickSet &b = h->s;
     if (!b.built) return VR_ERR_STATE;
+    if (rangeStream && b.variant != VR_VARIANT_MIDRANGE) return VR_ERR_STATE;
+    if (rangeStream && b.foreign) return VR_ERR_UNSUPPORTED;   // an opened file carries no BFS codes to seed the index scalars from
     if (cut_depth > b.maxDepth) return VR_ERR_INVALID;
     const int cut = cut_depth < 0 ? b.maxDepth : cut_depth;
-    if (decode_stores_vectors(&b, cut, false) && misaligned16(out)) return VR_ERR_INVALID;
+    if (decode_stores_vectors(&b, cut, rangeStream) && misaligned16(out)) return VR_ERR_INVALID;
     if (cut < b.Ds && b.foreign) {
         // ancestor scalars at the cut depth, from the stream bytes kept at set_tree/open time
         vr_status rc = sync_ctrl(b);
@@ -575,16 +562,41 @@ vr_status vr_brickset_decode(vr_brickset *h, int32_t cut_depth, uint8_t *out, vo
         for (int br = 0; br < b.B; ++br) {
             std::vector<uint8_t> vals((size_t)b.nIdx, 0);
             if (br < (int)b.hostTree.size() && !b.hostTree[br].empty() &&
-                cut_values_from_stream(&b, b.hostTree[br].data(), (int64_t)b.hostCtrl[br].numActive,
+                cut_values_from_stream(b.D, b.Ds, b.K, b.nIdx, b.hostTree[br].data(), (int64_t)b.hostCtrl[br].numActive,
                                        b.hostCtrl[br].distanceMap, cut, vals) != 0)
                 return VR_ERR_FORMAT;
             HIPCHK(hipMemcpy(b.idxValCut + (size_t)br * b.nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice));
         }
     }
-    {
-        const int rc = decode_launch(&b, out, cut, (hipStream_t)stream);
-        if (rc != 0) return rc == -3 ? VR_ERR_OOM : VR_ERR_NO_DEVICE;
+    const int rc = decode_launch(&b, out, cut, (hipStream_t)stream, rangeStream);
+    if (rc != 0) return rc == -3 && !rangeStream ? VR_ERR_OOM : VR_ERR_NO_DEVICE;   // (the range decode never named out-of-memory)
+    b.decodeTimingPending = true;
+    b.lastStream = stream;
+    return VR_OK;
+}
+
+vr_status vr_brickset_decode(vr_brickset *h, int32_t cut_depth, uint8_t *out, void *stream)
+{
+    return decode_common(h, cut_depth, out, stream, false);
+}
+
+vr_status vr_brickset_decode_range(vr_brickset *h, int32_t cut_depth, uint8_t *out, void *stream)
+{
+    return decode_common(h, cut_depth, out, stream, true);
+}
+
+// the launch of the two per-brick decodes (cuts checked); the caller's buffer is out or pool->pool
+static vr_status lod_decode(BrickSet &b, const int32_t *cuts, uint8_t *out, const PoolDest *pool, void *stream)
+{
+    bool above = false;
+    for (int br = 0; br < b.B; ++br) above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
+    if (decode_lod_stores_vectors(&b, cuts, pool) && misaligned16(pool ? pool->pool : out)) return VR_ERR_INVALID;
+    if (above && b.foreign) {
+        vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
+        if (rc != VR_OK) return rc;
     }
+    const int rc = decode_lod_launch(&b, cuts, out, (hipStream_t)stream, pool);
+    if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
     b.decodeTimingPending = true;
     b.lastStream = stream;
     return VR_OK;
@@ -595,21 +607,8 @@ vr_status vr_brickset_decode_lod(vr_brickset *h, const int32_t *cuts, uint8_t *o
     if (!h || !cuts || !out) return VR_ERR_INVALID;
     BrickSet &b = h->s;
     if (!b.built) return VR_ERR_STATE;
-    bool above = false;
-    for (int br = 0; br < b.B; ++br) {
-        if (cuts[br] < -1 || cuts[br] > b.maxDepth) return VR_ERR_INVALID;
-        above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
-    }
-    if (decode_lod_stores_vectors(&b, cuts, nullptr) && misaligned16(out)) return VR_ERR_INVALID;
-    if (above && b.foreign) {
-        vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
-        if (rc != VR_OK) return rc;
-    }
-    const int rc = decode_lod_launch(&b, cuts, out, (hipStream_t)stream);
-    if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
-    b.decodeTimingPending = true;
-    b.lastStream = stream;
-    return VR_OK;
+    for (int br = 0; br < b.B; ++br) if (cuts[br] < -1 || cuts[br] > b.maxDepth) return VR_ERR_INVALID;
+    return lod_decode(b, cuts, out, nullptr, stream);
 }
 
 // vr_lod_pool_layout's rule (vrhip.h).  off / shift: per brick (shift 3 bytes each); table: per grid cell, may be null.
@@ -626,33 +625,15 @@ static vr_status pool_layout(const int64_t bd[3], int32_t nb, const int64_t *ijk
     }
     if (origDepth != lg[0] + lg[1] + lg[2] || maxDepth < origDepth) return VR_ERR_INVALID;
     const int64_t cells = grid[0] * grid[1] * grid[2];
-    std::vector<int32_t> at;
-    if (table) at.assign((size_t)cells, -1);
-    // splits[c][k]: splits on axis k among depths 0 .. c-1 (the split-axis rule of buildRecursive)
-    std::vector<std::array<int, 3>> splits((size_t)origDepth + 1);
-    {
-        int64_t ext[3] = {bd[0], bd[1], bd[2]};
-        std::array<int, 3> n = {0, 0, 0};
-        splits[0] = n;
-        for (int d = 0; d < origDepth; ++d) {
-            int sd = d % 3, i = 0;
-            while (ext[0] * ext[1] * ext[2] > 1 && ext[sd] == 1) sd = (d + ++i) % 3;
-            ext[sd] /= 2;
-            ++n[(size_t)sd];
-            splits[(size_t)d + 1] = n;
-        }
-    }
+    std::vector<int64_t> cellOf((size_t)nb);
+    const std::vector<std::array<int, 3>> splits = split_counts(bd, origDepth);
     int64_t run = 0;
     for (int32_t b = 0; b < nb; ++b) {
         const int64_t *q = ijk + 3 * (int64_t)b;
         for (int k = 0; k < 3; ++k) if (q[k] < 0 || q[k] >= grid[k]) return VR_ERR_INVALID;
         const int c = cuts[b];
         if (c < -1 || c > maxDepth) return VR_ERR_INVALID;
-        const int64_t cell = q[0] + grid[0] * (q[1] + grid[1] * q[2]);
-        if (table) {
-            if (at[(size_t)cell] >= 0) return VR_ERR_INVALID;
-            at[(size_t)cell] = b;
-        }
+        cellOf[(size_t)b] = q[0] + grid[0] * (q[1] + grid[1] * q[2]);
         uint8_t sh[3] = {0, 0, 0};
         if (c >= 0 && c < origDepth)
             for (int k = 0; k < 3; ++k) sh[k] = (uint8_t)(lg[k] - splits[(size_t)c][(size_t)k]);
@@ -664,20 +645,15 @@ static vr_status pool_layout(const int64_t bd[3], int32_t nb, const int64_t *ijk
         }
         if (off) off[b] = o;
     }
-    if (table) {
-        for (int64_t cell = 0; cell < cells; ++cell) { table[cell] = vr_pool_entry(); table[cell].offset = -1; }
-        for (int64_t cell = 0; cell < cells; ++cell) {
-            const int32_t b = at[(size_t)cell];
-            if (b < 0 || cuts[b] < 0) continue;
-            table[cell].offset = off[b];
-            for (int k = 0; k < 3; ++k) table[cell].shift[k] = shift[3 * b + k];
-        }
-    } else {
-        // two bricks on one cell: sort the cells
-        std::vector<int64_t> cs((size_t)nb);
-        for (int32_t b = 0; b < nb; ++b) cs[(size_t)b] = ijk[3 * b] + grid[0] * (ijk[3 * b + 1] + grid[1] * ijk[3 * b + 2]);
-        std::sort(cs.begin(), cs.end());
-        if (std::adjacent_find(cs.begin(), cs.end()) != cs.end()) return VR_ERR_INVALID;
+    std::vector<int64_t> cs = cellOf;       // two bricks on one cell: refused
+    std::sort(cs.begin(), cs.end());
+    if (std::adjacent_find(cs.begin(), cs.end()) != cs.end()) return VR_ERR_INVALID;
+    for (int64_t cell = 0; table && cell < cells; ++cell) { table[cell] = vr_pool_entry(); table[cell].offset = -1; }
+    for (int32_t b = 0; table && b < nb; ++b) {
+        if (cuts[b] < 0) continue;
+        vr_pool_entry &e = table[cellOf[(size_t)b]];
+        e.offset = off[b];
+        for (int k = 0; k < 3; ++k) e.shift[k] = shift[3 * b + k];
     }
     *total = run;
     return VR_OK;
@@ -713,18 +689,7 @@ vr_status vr_brickset_decode_lod_pool(vr_brickset *h, const int32_t *cuts, const
     if (pool_bytes < total) return VR_ERR_INVALID;
     PoolDest d;
     d.pool = pool; d.off = off.data(); d.shift = sh.data(); d.tab = tab.data(); d.tabDev = table_dev; d.cells = cells;
-    if (decode_lod_stores_vectors(&b, cuts, &d) && misaligned16(pool)) return VR_ERR_INVALID;
-    bool above = false;
-    for (int br = 0; br < b.B; ++br) above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
-    if (above && b.foreign) {
-        vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
-        if (rc != VR_OK) return rc;
-    }
-    const int rc = decode_lod_launch(&b, cuts, nullptr, (hipStream_t)stream, &d);
-    if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
-    b.decodeTimingPending = true;
-    b.lastStream = stream;
-    return VR_OK;
+    return lod_decode(b, cuts, nullptr, &d, stream);
 }
 
 // The frame of vr_raycast (raymarch.hip raycast_launch): glm::lookAt basis and glm::perspectiveFov half-angle tangents,
@@ -815,22 +780,6 @@ vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *P, int32_t
     return VR_OK;
 }
 
-vr_status vr_brickset_decode_range(vr_brickset *h, int32_t cut_depth, uint8_t *out, void *stream)
-{
-    if (!h || !out) return VR_ERR_INVALID;
-    BrickSet &b = h->s;
-    if (!b.built) return VR_ERR_STATE;
-    if (b.variant != VR_VARIANT_MIDRANGE) return VR_ERR_STATE;
-    if (b.foreign) return VR_ERR_UNSUPPORTED;          // an opened file carries no BFS codes to seed the index scalars from
-    if (cut_depth > b.maxDepth) return VR_ERR_INVALID;
-    const int cut = cut_depth < 0 ? b.maxDepth : cut_depth;
-    if (decode_stores_vectors(&b, cut, true) && misaligned16(out)) return VR_ERR_INVALID;
-    if (decode_launch(&b, out, cut, (hipStream_t)stream, true) != 0) return VR_ERR_NO_DEVICE;
-    b.decodeTimingPending = true;
-    b.lastStream = stream;
-    return VR_OK;
-}
-
 vr_status vr_brickset_set_tree(vr_brickset *h, int32_t brick, const uint8_t *tree, int64_t tree_bytes,
                                int64_t num_active, const uint8_t *dmap, int32_t map_len)
 {
@@ -843,13 +792,14 @@ vr_status vr_brickset_set_tree(vr_brickset *h, int32_t brick, const uint8_t *tre
     if (tree_bytes < need || need > b.treeCap) return VR_ERR_FORMAT;
     std::vector<uint32_t> offs;
     std::vector<uint8_t> vals, fine, val3;
-    if (build_index_from_stream(&b, brick, tree, num_active, dmap, offs, vals, fine, val3) != 0) return VR_ERR_FORMAT;
+    if (build_index_from_stream(b.D, b.Ds, b.K, b.nIdx, tree, num_active, dmap, offs, vals, fine, val3) != 0) return VR_ERR_FORMAT;
     // the fine decoders take the grown-branch distances as the constants the reference writes (R.cpp:94-97); a
     // file that says otherwise is decoded by the walking kernel, which reads them from the map
     for (int i = 0; i < VR_CHAIN_LEVELS; ++i)
         if (dmap[b.D + 1 + i] != (uint8_t)(64 >> i)) { fine.clear(); val3.clear(); }
     if (!b.built) { // first foreign tree: other bricks stay empty until set
         b.fineHas.assign((size_t)b.B, 1);   // (their index is all "pruned": no counts are read)
+        fine_has_changed(b);
         HIPCHK(hipMemset(b.mid.ctrl, 0, (size_t)b.B * sizeof(Ctrl)));
         std::vector<uint32_t> dead((size_t)b.B * b.nIdx, VR_IDX_DEAD);
         HIPCHK(hipMemcpy(b.idxOff, dead.data(), dead.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -878,12 +828,14 @@ vr_status vr_brickset_set_tree(vr_brickset *h, int32_t brick, const uint8_t *tre
     }
     if ((int)b.fineHas.size() != b.B) b.fineHas.assign((size_t)b.B, 0);
     b.fineHas[(size_t)brick] = 0;
+    fine_has_changed(b);
     if (!fine.empty()) {
         if (!b.fineIdx) HIPCHK(hipMalloc(&b.fineIdx, (size_t)b.B * b.nIdx * 16));
         HIPCHK(hipMemcpy(b.fineIdx + (size_t)brick * b.nIdx * 16, fine.data(), fine.size(), hipMemcpyHostToDevice));
         if (!b.idxVal3) HIPCHK(hipMalloc(&b.idxVal3, (size_t)b.B * b.nIdx * 8));
         HIPCHK(hipMemcpy(b.idxVal3 + (size_t)brick * b.nIdx * 8, val3.data(), val3.size(), hipMemcpyHostToDevice));
         b.fineHas[(size_t)brick] = 1;
+        fine_has_changed(b);
     }
     if ((int)b.hostTree.size() != b.B) b.hostTree.assign((size_t)b.B, std::vector<uint8_t>());
     b.hostTree[brick].assign(tree, tree + need);
@@ -920,23 +872,22 @@ vr_status vr_brickset_save(vr_brickset *h, int32_t brick, const char *path)
     }
     FILE *f = fopen(path, "wb");
     if (!f) return VR_ERR_IO;
-    int64_t rootMin[3] = {0, 0, 0}, rootMax[3] = {b.g.X, b.g.Y, b.g.Z};
-    int32_t mtd = b.maxDepth, otd = b.D;
-    int64_t X = b.g.X, Y = b.g.Y, Z = b.g.Z, na = (int64_t)c.numActive;
-    bool ok = fwrite(rootMin, 8, 3, f) == 3 && fwrite(rootMax, 8, 3, f) == 3 && fwrite(&mtd, 4, 1, f) == 1 &&
-              fwrite(&otd, 4, 1, f) == 1 && fwrite(&X, 8, 1, f) == 1 && fwrite(&Y, 8, 1, f) == 1 &&
-              fwrite(&Z, 8, 1, f) == 1 && fwrite(&na, 8, 1, f) == 1 &&
-              fwrite(c.distanceMap, 1, (size_t)mtd + 1, f) == (size_t)mtd + 1 &&
-              (!mrFile || fwrite(cr.distanceMap, 1, (size_t)mtd + 1, f) == (size_t)mtd + 1) &&
+    const Header hd = {{0, 0, 0}, {b.g.X, b.g.Y, b.g.Z}, b.maxDepth, b.D, b.g.X, b.g.Y, b.g.Z, (int64_t)c.numActive};
+    const size_t mtd = (size_t)b.maxDepth;
+    bool ok = write_header(f, hd) &&
+              fwrite(c.distanceMap, 1, mtd + 1, f) == mtd + 1 &&
+              (!mrFile || fwrite(cr.distanceMap, 1, mtd + 1, f) == mtd + 1) &&
               fwrite(tree.data(), 1, (size_t)bytes, f) == (size_t)bytes &&
               (!mrFile || fwrite(treeR.data(), 1, (size_t)bytes, f) == (size_t)bytes);
     fclose(f);
     return ok ? VR_OK : VR_ERR_IO;
 }
 
-// VolumeKdtree::open (R.cpp:554-594).  A missing file is an error code here (the
-// reference waits for Enter and calls exit(-1)).
-vr_status vr_brickset_open(vr_brickset **out, const char *path)
+// VolumeKdtree::open (R.cpp:554-594) and, mr, MidRangeTree files (M.cpp:753-785).  A missing file is an error code here
+// (the reference waits for Enter and calls exit(-1)).  The reference's own MidRangeTree reader (M.cpp:787-833) mis-sizes
+// both streams by 4 bytes (it subtracts three of the four int64 header fields before halving), so the range stream it
+// reads back is shifted; there is nothing to match there.  This reader returns exactly what save() wrote.
+static vr_status open_file(vr_brickset **out, const char *path, bool mr)
 {
     if (!out || !path) return VR_ERR_INVALID;
     FILE *f = fopen(path, "rb");
@@ -944,85 +895,55 @@ vr_status vr_brickset_open(vr_brickset **out, const char *path)
     fseek(f, 0, SEEK_END);
     const int64_t fileSize = ftell(f);
     fseek(f, 0, SEEK_SET);
-    int64_t rootMin[3], rootMax[3], X, Y, Z, na;
-    int32_t mtd, otd;
-    bool ok = fread(rootMin, 8, 3, f) == 3 && fread(rootMax, 8, 3, f) == 3 && fread(&mtd, 4, 1, f) == 1 &&
-              fread(&otd, 4, 1, f) == 1 && fread(&X, 8, 1, f) == 1 && fread(&Y, 8, 1, f) == 1 &&
-              fread(&Z, 8, 1, f) == 1 && fread(&na, 8, 1, f) == 1;
-    if (!ok || mtd < VR_CHAIN_LEVELS || mtd >= VR_MAX_DEPTH || na <= 0) { fclose(f); return VR_ERR_FORMAT; }
-    std::vector<uint8_t> dmap((size_t)mtd + 1);
-    // R.cpp:581 subtracts only three of the four int64 fields: tree.bits ends up 8 bytes
-    // longer than what was saved (SURVEY C-6); numActiveNodes is authoritative.
-    const int64_t openBytes = fileSize - (2 * 24 + 2 * 4 + mtd + 1 + 3 * 8);
-    const int64_t have = fileSize - (88 + mtd + 1);
-    if (have < (na + 3) / 4) { fclose(f); return VR_ERR_FORMAT; }
-    std::vector<uint8_t> tree((size_t)have);
-    ok = fread(dmap.data(), 1, dmap.size(), f) == dmap.size() && fread(tree.data(), 1, tree.size(), f) == tree.size();
+    Header hd;
+    if (!read_header(f, hd)) { fclose(f); return VR_ERR_FORMAT; }
+    const int64_t mtd = hd.maxDepth, na = hd.numActive, need = (na + 3) / 4;
+    // VolumeKdtree: whatever follows the map is the stream (numActiveNodes is authoritative); MidRangeTree: two maps,
+    // then two streams of exactly the tokens' bytes
+    const int64_t have = fileSize - (VR_HEADER_BYTES + (mr ? 2 : 1) * (mtd + 1));
+    const int64_t T = mr ? have / 2 : have;
+    if (mr ? (have < 0 || (have & 1) || T != need) : have < need) { fclose(f); return VR_ERR_FORMAT; }
+    std::vector<uint8_t> body((size_t)(fileSize - VR_HEADER_BYTES));
+    const bool ok = fread(body.data(), 1, body.size(), f) == body.size();
+    const uint8_t *dmap = body.data(), *dmapR = dmap + (mtd + 1), *tree = dmap + (mr ? 2 : 1) * (mtd + 1), *treeR = tree + T;
     fclose(f);
     if (!ok) return VR_ERR_IO;
-    int64_t dims[3] = {X, Y, Z};
+    const int64_t dims[3] = {hd.X, hd.Y, hd.Z};
     vr_brickset *h = nullptr;
-    vr_status rc = vr_brickset_create(&h, 1, dims, 6, 5, VR_VARIANT_RECOVER); // ctor defaults R.h:89-94
+    vr_status rc = vr_brickset_create(&h, 1, dims, 6, 5, mr ? VR_VARIANT_MIDRANGE : VR_VARIANT_RECOVER); // ctor defaults R.h:89-94
     if (rc != VR_OK) return rc;
-    if (h->s.D != otd || h->s.maxDepth != mtd) { vr_brickset_destroy(h); return VR_ERR_FORMAT; }
-    rc = vr_brickset_set_tree(h, 0, tree.data(), (int64_t)tree.size(), na, dmap.data(), mtd + 1);
+    BrickSet &b = h->s;
+    if (b.D != hd.origDepth || b.maxDepth != mtd) { vr_brickset_destroy(h); return VR_ERR_FORMAT; }
+    rc = vr_brickset_set_tree(h, 0, tree, T, na, dmap, (int32_t)mtd + 1);
     if (rc != VR_OK) { vr_brickset_destroy(h); return rc; }
-    h->s.openTreeBytes[0] = openBytes;
+    if (!mr) {
+        // R.cpp:581 subtracts only three of the four int64 fields: tree.bits ends up 8 bytes
+        // longer than what was saved (SURVEY C-6); numActiveNodes is authoritative.
+        b.openTreeBytes[0] = fileSize - (2 * 24 + 2 * 4 + mtd + 1 + 3 * 8);
+    } else {
+        Ctrl cr;
+        memset(&cr, 0, sizeof(Ctrl));
+        cr.numActive = (unsigned long long)na;
+        memcpy(cr.distanceMap, dmapR, (size_t)mtd + 1);
+        hipError_t e = hipSuccess;
+        if (!b.rng.ctrl) e = hipMalloc(&b.rng.ctrl, sizeof(Ctrl));
+        if (e == hipSuccess && !b.rng.tree) e = hipMalloc(&b.rng.tree, (size_t)b.treeCap);
+        if (e == hipSuccess) e = hipMemcpy(b.rng.ctrl, &cr, sizeof(Ctrl), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(b.rng.tree, 0, (size_t)b.treeCap);
+        if (e == hipSuccess) e = hipMemcpy(b.rng.tree, treeR, (size_t)T, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { vr_brickset_destroy(h); return VR_ERR_NO_DEVICE; }
+        b.foreignRange = true;
+    }
     *out = h;
     return VR_OK;
 }
 
-// MidRangeTree files (M.cpp:753-785).  The reference's own reader (M.cpp:787-833) mis-sizes both streams by
-// 4 bytes (it subtracts three of the four int64 header fields before halving), so the range stream it reads
-// back is shifted; there is nothing to match there.  This reader returns exactly what save() wrote.
+vr_status vr_brickset_open(vr_brickset **out, const char *path) { return open_file(out, path, false); }
+
 vr_status vr_brickset_open_variant(vr_brickset **out, const char *path, int32_t variant)
 {
-    if (!out || !path) return VR_ERR_INVALID;
-    if (variant != VR_VARIANT_MIDRANGE) {
-        if (variant != VR_VARIANT_RECOVER && variant != VR_VARIANT_GUARDED) return VR_ERR_INVALID;
-        return vr_brickset_open(out, path);
-    }
-    FILE *f = fopen(path, "rb");
-    if (!f) return VR_ERR_IO;
-    fseek(f, 0, SEEK_END);
-    const int64_t fileSize = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    int64_t rootMin[3], rootMax[3], X, Y, Z, na;
-    int32_t mtd, otd;
-    bool ok = fread(rootMin, 8, 3, f) == 3 && fread(rootMax, 8, 3, f) == 3 && fread(&mtd, 4, 1, f) == 1 &&
-              fread(&otd, 4, 1, f) == 1 && fread(&X, 8, 1, f) == 1 && fread(&Y, 8, 1, f) == 1 &&
-              fread(&Z, 8, 1, f) == 1 && fread(&na, 8, 1, f) == 1;
-    if (!ok || mtd < VR_CHAIN_LEVELS || mtd >= VR_MAX_DEPTH || na <= 0) { fclose(f); return VR_ERR_FORMAT; }
-    const int64_t have = fileSize - (88 + 2 * ((int64_t)mtd + 1));
-    const int64_t T = have / 2;
-    if (have < 0 || (have & 1) || T != (na + 3) / 4) { fclose(f); return VR_ERR_FORMAT; }
-    std::vector<uint8_t> dmap((size_t)mtd + 1), dmapR((size_t)mtd + 1), tree((size_t)T), treeR((size_t)T);
-    ok = fread(dmap.data(), 1, dmap.size(), f) == dmap.size() && fread(dmapR.data(), 1, dmapR.size(), f) == dmapR.size() &&
-         fread(tree.data(), 1, tree.size(), f) == tree.size() && fread(treeR.data(), 1, treeR.size(), f) == treeR.size();
-    fclose(f);
-    if (!ok) return VR_ERR_IO;
-    int64_t dims[3] = {X, Y, Z};
-    vr_brickset *h = nullptr;
-    vr_status rc = vr_brickset_create(&h, 1, dims, 6, 5, VR_VARIANT_MIDRANGE);
-    if (rc != VR_OK) return rc;
-    if (h->s.D != otd || h->s.maxDepth != mtd) { vr_brickset_destroy(h); return VR_ERR_FORMAT; }
-    rc = vr_brickset_set_tree(h, 0, tree.data(), (int64_t)tree.size(), na, dmap.data(), mtd + 1);
-    if (rc != VR_OK) { vr_brickset_destroy(h); return rc; }
-    BrickSet &b = h->s;
-    Ctrl cr;
-    memset(&cr, 0, sizeof(Ctrl));
-    cr.numActive = (unsigned long long)na;
-    memcpy(cr.distanceMap, dmapR.data(), (size_t)mtd + 1);
-    hipError_t e = hipSuccess;
-    if (!b.rng.ctrl) e = hipMalloc(&b.rng.ctrl, sizeof(Ctrl));
-    if (e == hipSuccess && !b.rng.tree) e = hipMalloc(&b.rng.tree, (size_t)b.treeCap);
-    if (e == hipSuccess) e = hipMemcpy(b.rng.ctrl, &cr, sizeof(Ctrl), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b.rng.tree, 0, (size_t)b.treeCap);
-    if (e == hipSuccess) e = hipMemcpy(b.rng.tree, treeR.data(), (size_t)T, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { vr_brickset_destroy(h); return VR_ERR_NO_DEVICE; }
-    b.foreignRange = true;
-    *out = h;
-    return VR_OK;
+    if (variant != VR_VARIANT_RECOVER && variant != VR_VARIANT_GUARDED && variant != VR_VARIANT_MIDRANGE) return VR_ERR_INVALID;
+    return open_file(out, path, variant == VR_VARIANT_MIDRANGE);
 }
 
 vr_status vr_measure_error(const uint8_t *dec, const uint8_t *orig, int64_t n, int32_t *max_error, double *mean_error,
@@ -1033,7 +954,8 @@ vr_status vr_measure_error(const uint8_t *dec, const uint8_t *orig, int64_t n, i
     int *dMax = nullptr;
     unsigned long long *dSum = nullptr;
     HIPCHK(hipMalloc(&dMax, sizeof(int)));
-    HIPCHK(hipMalloc(&dSum, sizeof(unsigned long long)));
+    const hipError_t e2 = hipMalloc(&dSum, sizeof(unsigned long long));
+    if (e2 != hipSuccess) { hipFree(dMax); return e2 == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_NO_DEVICE; }
     hipMemsetAsync(dMax, 0, sizeof(int), (hipStream_t)stream);
     hipMemsetAsync(dSum, 0, sizeof(unsigned long long), (hipStream_t)stream);
     int rc = measure_error_launch(dec, orig, n, dMax, dSum, (hipStream_t)stream);

@@ -1,0 +1,275 @@
+// host_plan.cpp -- see host_plan.h.  Plain C++: nothing here touches a device.
+#include "host_plan.h"
+#include <string.h>
+#include <algorithm>
+
+namespace vr {
+
+// The split-axis rule of buildRecursive (R.cpp:151-159), the only copy on the host (the general-extent kernels of
+// kd_decode.hip walk boxes with their own device split_axis): depth d splits axis d % 3, or the next axis that still
+// has more than one voxel.  Halves that extent and returns the axis.
+static int next_split(int64_t ext[3], int d)
+{
+    int sd = d % 3, i = 0;
+    while (ext[0] * ext[1] * ext[2] > 1 && ext[sd] == 1) sd = (d + ++i) % 3;
+    ext[sd] /= 2;
+    return sd;
+}
+
+void make_geom(Geom &g, const int64_t dims[3])
+{
+    memset(&g, 0, sizeof(g));
+    g.X = (int32_t)dims[0]; g.Y = (int32_t)dims[1]; g.Z = (int32_t)dims[2];
+    g.voxels = dims[0] * dims[1] * dims[2];
+    int64_t ext[3] = {dims[0], dims[1], dims[2]};
+    for (int k = 0; k < 3; ++k) { int n = 0; while (((int64_t)1 << (n + 1)) <= dims[k]) ++n; g.nb[k] = n; }
+    g.D = g.nb[0] + g.nb[1] + g.nb[2];         // R.cpp:26-29 (floor of the logarithms)
+    // axis[] / bit[]: the per-depth split axis.  Only meaningful for power-of-two extents, where every node of a
+    // depth splits the same axis; general extents go through BrickSet::srcIdx / ownerRank instead.
+    for (int d = 0; d < g.D && d < 32; ++d) {
+        const int sd = next_split(ext, d);
+        int b = 0; while (((int64_t)1 << (b + 1)) <= ext[sd]) ++b;
+        g.axis[d] = (uint8_t)sd;
+        g.bit[d] = (uint8_t)b;                 // the coordinate bit this split decides
+    }
+}
+
+std::vector<std::array<int, 3>> split_counts(const int64_t dims[3], int depths)
+{
+    std::vector<std::array<int, 3>> splits((size_t)depths + 1, std::array<int, 3>{{0, 0, 0}});
+    int64_t ext[3] = {dims[0], dims[1], dims[2]};
+    for (int d = 0; d < depths; ++d) {
+        splits[(size_t)d + 1] = splits[(size_t)d];
+        ++splits[(size_t)d + 1][(size_t)next_split(ext, d)];
+    }
+    return splits;
+}
+
+std::vector<uint32_t> make_lut(const Geom &g, int K)
+{
+    std::vector<uint32_t> lut((size_t)1 << K);
+    for (uint32_t lr = 0; lr < (1u << K); ++lr) {      // (the low K rank bits are the K deepest levels)
+        int x, y, z;
+        rank_to_xyz(g, lr, x, y, z);
+        lut[lr] = (uint32_t)x | ((uint32_t)y << 10) | ((uint32_t)z << 20);
+    }
+    return lut;
+}
+
+// rank bits of coordinate v of axis ax
+static uint32_t rank_bits(const Geom &g, int ax, int v)
+{
+    uint32_t r = 0;
+    for (int d = 0; d < g.D; ++d) {
+        r <<= 1;
+        if (g.axis[d] == ax) r |= (uint32_t)(v >> g.bit[d]) & 1u;
+    }
+    return r;
+}
+
+std::vector<uint32_t> make_spread(const Geom &g)
+{
+    std::vector<uint32_t> sp;
+    const int ext[3] = {g.X, g.Y, g.Z};
+    for (int ax = 0; ax < 3; ++ax)
+        for (int v = 0; v < ext[ax]; ++v) sp.push_back(rank_bits(g, ax, v));
+    return sp;
+}
+
+// The n deepest triples of split levels repeat one order of the three axes and decide coordinate bits n-1 .. 0 (the
+// 8^n leaves below a depth-(D-3n) node are then a cube).  pos[axis]: the axis's place in a triple, 0 = deepest.
+static bool deep_triples(const Geom &g, int n, int pos[3])
+{
+    pos[0] = pos[1] = pos[2] = -1;
+    for (int q = 0; q < 3; ++q) pos[g.axis[g.D - 3 + q]] = 2 - q;         // deepest level -> rank bit 0
+    if (pos[0] < 0 || pos[1] < 0 || pos[2] < 0) return false;
+    for (int d = g.D - 3 * n; d < g.D; ++d)
+        if (g.axis[d] != g.axis[g.D - 3 + (d - g.D + 3 * n) % 3] || g.bit[d] != (g.D - 1 - d) / 3) return false;
+    return true;
+}
+
+// k_decode_tile and the kernels built on it (their requirements: the comment above TileArgs, kd_decode.hip)
+static bool tile_plan(const Geom &g, int K, TilePlan &a)
+{
+    if (K != 6 || g.D < 6 || g.X < 128 || g.Y < 8 || g.Z < 4) return false;
+    int pos[3];
+    if (!deep_triples(g, 2, pos)) return false;
+    a.jx = pos[0]; a.jy = pos[1]; a.jz = pos[2];
+    a.tilesX = g.X / 128; a.tilesY = g.Y / 8; a.tilesZ = g.Z / 4;
+    a.ltx = g.nb[0] - 7; a.lty = g.nb[1] - 3;       // (power-of-two extents: general ones never get here)
+    // ticket order inside a group of 256 tiles (k_decode_quad): first the bits that stay inside a 16 x 16 (y, z) cell --
+    // z bits 0-1 and y bit 0 of the tile coordinate -- then the others in address order
+    const int first[3] = {a.ltx + a.lty, a.ltx + a.lty + 1, a.ltx};
+    int n = 0;
+    bool used[8] = {};
+    for (int i = 0; i < 3; ++i) {
+        const bool exists = i < 2 ? (1 << (i + 1)) <= a.tilesZ : a.tilesY >= 2;
+        if (exists && first[i] < 8 && !used[first[i]]) { a.kqBit[n++] = (uint8_t)first[i]; used[first[i]] = true; }
+    }
+    for (int b = 0; b < 8; ++b) if (!used[b]) a.kqBit[n++] = (uint8_t)b;
+    return true;
+}
+
+// k_decode_region's geometry: the twelve deepest levels must be four (a, b, c) triples in one axis order, deciding
+// coordinate bits 3, 2, 1, 0 (a 4096-leaf emit block is then a 16 x 16 x 16 box), with whole 128 x 16 x 16 regions
+static bool region_plan(const Geom &g, int K, bool generalGeom, bool idx64, int64_t treeCap, RegionPlan &a)     // a: zeroed
+{
+    const int D = g.D;
+    if (K != 6 || D < 12 || generalGeom || idx64 || (treeCap & 15)) return false;
+    if (g.X < VR_RG_REGX || g.X < 128 || g.Y < 16 || g.Z < 16) return false;
+    if ((g.X & (g.X - 1)) || (g.Y & (g.Y - 1)) || (g.Z & (g.Z - 1))) return false;
+    int pos[3];
+    if (!deep_triples(g, 4, pos)) return false;
+    const int jx = pos[0], jy = pos[1], jz = pos[2];
+    // quad index q = leaf rank >> 2 (10 bits).  Bits 0-5 go to lane / image-word bits: the two lowest x bits first
+    int Pmap[6], nx = 0, nxt = 2;
+    bool isx[6] = {};
+    for (int k = 0; k < 4; ++k) {
+        const int qb = 3 * k + jx - 2;
+        if (qb >= 0 && qb < 6) { isx[qb] = true; Pmap[qb] = nx++; }
+    }
+    if (nx != 2) return false;
+    for (int qb = 0; qb < 6; ++qb) if (!isx[qb]) Pmap[qb] = nxt++;
+    for (int qb = 0; qb < 6; ++qb) a.lanePos |= (uint32_t)qb << (4 * Pmap[qb]);
+    const auto word = [&](int q) { uint32_t w = 0; for (int i = 0; i < 6; ++i) if ((q >> i) & 1) w |= 1u << Pmap[i]; return w; };
+    for (int gg = 0; gg < 16; ++gg) a.parkP[gg >> 2] |= word(gg) << (8 * (gg & 3));
+    for (int sv = 0; sv < 4; ++sv) a.parkS |= word(sv << 4) << (8 * sv);
+    // image-word contribution of quad-index bit qb (XOR-linear: a permutation plus the step swizzle)
+    const auto contrib = [&](int qb) -> uint32_t {
+        if (qb < 6) return 1u << Pmap[qb];
+        const int i = qb - 6;
+        return (1u << (6 + i)) | (i < 3 ? 1u << (2 + i) : 0u);
+    };
+    // the eight (y, z) bits of a region's 16 x 16 plane
+    struct GB { uint32_t addr, byte, out; } bits[8], ord[8];
+    for (int ax = 1; ax <= 2; ++ax)
+        for (int k = 0; k < 4; ++k) {
+            const int rb = 3 * k + (ax == 1 ? jy : jz);
+            GB &b = bits[(ax - 1) * 4 + k];
+            b.addr = rb < 2 ? 0u : contrib(rb - 2);
+            b.byte = rb < 2 ? 1u << rb : 0u;
+            b.out = ax == 1 ? (uint32_t)((1 << k) * g.X) : (uint32_t)((int64_t)(1 << k) * g.X * g.Y);
+        }
+    // gather bits 0 .. 5-RG_LW come from lane >> RG_LW.  Eight emit blocks per region: bit 1 the plane bit at image bit 5
+    // (the 16-byte bank slot's top bit), bits 0 and 2 plane bits that do not move the slot at all (byte index, image bit
+    // 9): the eight rows of a store instruction then read conflict-free (the lanes of one row are the eight emit blocks,
+    // 4 words = one slot apart).  Four blocks per region: the same three first, any fourth (a two-way conflict at worst).
+    bool used[8] = {};
+    int n = 0;
+    const auto take = [&](int i) { ord[n++] = bits[i]; used[i] = true; };
+    int free0 = -1, free1 = -1, top = -1;
+    for (int i = 0; i < 8; ++i) {
+        if (bits[i].addr == 32u && top < 0) top = i;
+        else if ((bits[i].addr & 0x3Cu) == 0u) { if (free0 < 0) free0 = i; else if (free1 < 0) free1 = i; }
+    }
+    if (free0 >= 0) take(free0); else { for (int i = 0; i < 8; ++i) if (!used[i] && i != top && i != free1) { take(i); break; } }
+    if (top >= 0) take(top); else { for (int i = 0; i < 8; ++i) if (!used[i] && i != free1) { take(i); break; } }
+    if (free1 >= 0) take(free1); else { for (int i = 0; i < 8; ++i) if (!used[i]) { take(i); break; } }
+    for (int i = 0; i < 8; ++i) if (!used[i]) take(i);
+    for (int i = 0; i < 8; ++i) {
+        a.gAddr[i >> 1] |= ord[i].addr << (16 * (i & 1));
+        a.gByte |= ord[i].byte << (4 * i);
+        a.gOut[i] = ord[i].out;
+    }
+    // x bits above the two lowest: the gather's reads
+    uint32_t xr[4] = {0, 0, 0, 0};
+    if (jx < 2) xr[1] = contrib(3 * 3 + jx - 2);
+    else { xr[1] = contrib(6); xr[2] = contrib(9); xr[3] = xr[1] ^ xr[2]; }
+    a.xRead[0] = xr[0] | (xr[1] << 16);
+    a.xRead[1] = xr[2] | (xr[3] << 16);
+    a.jx = jx;
+    a.X = g.X; a.Y = g.Y; a.voxels = g.voxels;
+    a.lrx = g.nb[0] - 7; a.lry = g.nb[1] - 4;
+    a.nreg = (g.X / VR_RG_REGX) * (g.Y / 16) * (g.Z / 16);
+    // the emit block of a 16^3 box: the rank bits above the twelve lowest
+    uint32_t bpos[3] = {0, 0, 0};
+    for (int d = 0; d < D - 12; ++d) {
+        const int ax = g.axis[d], kb = g.bit[d] - 4;       // coordinate bit kb + 4 of axis ax sits at rank bit D - 1 - d
+        if (kb < 0 || kb >= 6) return false;
+        bpos[ax] |= (uint32_t)(D - 1 - d - 12) << (5 * kb);
+    }
+    a.blkX = bpos[0]; a.blkY = bpos[1]; a.blkZ = bpos[2];
+    return true;
+}
+
+// k_pyramid12 builds the bottom twelve levels where they split x four times or more (Pyr12Plan::use12)
+static bool pyr12_plan(const Geom &g, bool generalGeom, Pyr12Plan &pg)
+{
+    const int D = g.D;
+    if (D < 12 || generalGeom) return false;
+    int n[3] = {0, 0, 0};
+    for (int q = 0; q < 12; ++q) ++n[g.axis[D - 12 + q]];
+    if (n[0] < 4) return false;
+    pg.ax = n[0]; pg.ay = n[1]; pg.az = n[2];
+    for (int i = 0; i < 16; ++i) pg.sx[i] = (uint16_t)(rank_bits(g, 0, i) & 0xFFFu);   // of x = i, the twelve deepest levels
+    const int64_t Bx = g.X >> pg.ax, By = g.Y >> pg.ay, Bz = g.Z >> pg.az;
+    const int64_t perLine = (g.X < 128 ? g.X : 128) >> pg.ax;
+    pg.swz = (perLine == 8 && Bx % 8 == 0 && ((Bx / 8) * By * Bz) % 8 == 0) ? 1 : 0;
+    pg.nbx = (int)Bx; pg.nby = (int)By;
+    pg.lnbx = g.nb[0] - pg.ax; pg.lnby = g.nb[1] - pg.ay;
+    return true;
+}
+
+void make_plans(const Geom &g, int K, bool generalGeom, bool idx64, int64_t treeCap, TilePlan &tile, RegionPlan &region,
+                Pyr12Plan &pyr12)
+{
+    tile = TilePlan(); region = RegionPlan(); pyr12 = Pyr12Plan();
+    tile.ok = !generalGeom && tile_plan(g, K, tile);
+    region.ok = region_plan(g, K, generalGeom, idx64, treeCap, region);
+    pyr12.use12 = pyr12_plan(g, generalGeom, pyr12);
+}
+
+// a node pruned at depth j stands for every node below it: its value for its descendants at depth L
+static void fill_below(std::vector<uint8_t> &v, int L, int j, uint32_t path, int val)
+{
+    if (j < L) std::fill(v.begin() + ((size_t)path << (L - j)), v.begin() + (((size_t)path + 1) << (L - j)), (uint8_t)val);
+}
+
+int cut_values_from_stream(int D, int Ds, int, int64_t nIdx, const uint8_t *tree, int64_t numActive, const uint8_t *dmap,
+                           int cut, std::vector<uint8_t> &vals)
+{
+    vals.assign((size_t)nIdx, 0);
+    return walk_stream(D, tree, numActive, dmap, cut,
+        [&](int j, uint32_t path, int64_t, int, int val) { if (j == Ds) vals[path] = (uint8_t)val; },
+        [&](int j, uint32_t path, int val) { fill_below(vals, Ds, j, path, val); },
+        [](uint32_t) {});
+}
+
+int build_index_from_stream(int D, int Ds, int K, int64_t nIdx, const uint8_t *tree, int64_t numActive,
+                            const uint8_t *dmap, std::vector<uint32_t> &offs, std::vector<uint8_t> &vals,
+                            std::vector<uint8_t> &fine, std::vector<uint8_t> &val3)
+{
+    offs.assign((size_t)nIdx, VR_IDX_DEAD);
+    vals.assign((size_t)nIdx, 0);
+    // K == 6: tokens owned by each 4-leaf subtree of a depth-Ds node, what k_prune_emit12 leaves for k_decode_fine.
+    // A token at depth >= Ds belongs to the 4-leaf subtree that holds its node's first leaf.
+    const bool wantFine = K == 6 && D >= 6;
+    fine.assign(wantFine ? (size_t)nIdx * 16 : 0, 0);
+    val3.assign(wantFine ? (size_t)nIdx * 8 : 0, 0);      // decoded scalar of every depth-(D-3) node (k_decode_quad)
+    const auto own = [&](uint32_t path, int j) {
+        if (!wantFine || j < Ds) return;
+        const uint32_t first = path << (D - j);     // first leaf (rank) below the node
+        fine[(size_t)(first >> 6) * 16 + ((first >> 2) & 15u)] += 1;
+    };
+    return walk_stream(D, tree, numActive, dmap, D,
+        [&](int j, uint32_t path, int64_t pos, int, int val) {
+            if (j == Ds) { offs[path] = (uint32_t)pos; vals[path] = (uint8_t)val; }
+            if (wantFine && j == D - 3) val3[path] = (uint8_t)val;
+            own(path, j);
+        },
+        [&](int j, uint32_t path, int val) {
+            fill_below(vals, Ds, j, path, val);     // (the offsets below it stay VR_IDX_DEAD)
+            if (wantFine) fill_below(val3, D - 3, j, path, val);
+        },
+        [&](uint32_t path) { own(path, D); });
+}
+
+bool read_header(FILE *f, Header &h)
+{
+    if (fread(&h, VR_HEADER_BYTES, 1, f) != 1) return false;
+    return h.maxDepth >= VR_CHAIN_LEVELS && h.maxDepth < VR_MAX_DEPTH && h.numActive > 0;
+}
+
+bool write_header(FILE *f, const Header &h) { return fwrite(&h, VR_HEADER_BYTES, 1, f) == 1; }
+
+} // namespace vr

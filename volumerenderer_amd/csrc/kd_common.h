@@ -10,34 +10,9 @@
 //                 coordinate bits in the reference's split-axis order (R.cpp:151-159).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#define VR_MAX_DEPTH 40     // origTreeDepth + 7 must stay below this
-#define VR_CHAIN_LEVELS 7   // maxAddLevels (R.cpp:22)
-#define VR_IDX_DEAD 0xFFFFFFFFu
+#include "host_plan.h"     // Geom, rank_to_xyz, apply_code, cget, VR_MAX_DEPTH / VR_CHAIN_LEVELS / VR_IDX_DEAD
 
 namespace vr {
-
-// Split geometry of one brick (power-of-two extents).  Passed to kernels by value.
-struct Geom {
-    int32_t D;                  // origTreeDepth
-    int32_t nb[3];              // log2 of X, Y, Z
-    int32_t X, Y, Z;
-    uint8_t axis[32];           // split axis at depth d (d < D)
-    uint8_t bit[32];            // coordinate bit decided at depth d
-    int64_t voxels;             // X*Y*Z
-};
-
-// rank (D bits, MSB = depth 0) -> voxel coordinates
-__host__ __device__ inline void rank_to_xyz(const Geom &g, uint32_t r, int &x, int &y, int &z)
-{
-    int c[3] = {0, 0, 0};
-    for (int d = 0; d < g.D; ++d) {
-        uint32_t b = (r >> (g.D - 1 - d)) & 1u;
-        c[g.axis[d]] |= (int)(b << g.bit[d]);
-    }
-    x = c[0]; y = c[1]; z = c[2];
-}
 
 // Per-brick gradient-descent state (R.cpp:215-227), lives in device memory.
 struct Ctrl {
@@ -200,17 +175,6 @@ __device__ __forceinline__ int wave_min_i32_dpp(int v)   // result valid in lane
 
 #endif
 
-// decoder step (R.cpp:783-787): child scalar from parent scalar and the child's code
-__host__ __device__ inline int apply_code(int v, int code, int dist)
-{
-    if (code == 1) { v += dist; return v > 255 ? 255 : v; }
-    if (code == 2) { v -= dist; return v < 0 ? 0 : v; }
-    return v;
-}
-
-// The breadth-first 2-bit codes are packed four per byte in heap order (TwoBitArray packing:
-// element i in byte i/4, bits 2*(i&3)).
-__host__ __device__ inline int cget(const uint8_t *C, int64_t i) { return (C[i >> 2] >> ((int)(i & 3) * 2)) & 3; }
 #ifdef __HIPCC__
 // Prune only ever turns a 0 into a 3, so an atomic OR of the two bits is race-free whoever
 // shares the byte (the per-brick code array is 4-byte aligned).

@@ -22,26 +22,6 @@ int launch_status(const char *what)
     return -1;
 }
 
-void make_geom(Geom &g, const int64_t dims[3])
-{
-    memset(&g, 0, sizeof(g));
-    g.X = (int32_t)dims[0]; g.Y = (int32_t)dims[1]; g.Z = (int32_t)dims[2];
-    g.voxels = dims[0] * dims[1] * dims[2];
-    int64_t ext[3] = {dims[0], dims[1], dims[2]};
-    for (int k = 0; k < 3; ++k) { int n = 0; while (((int64_t)1 << (n + 1)) <= dims[k]) ++n; g.nb[k] = n; }
-    g.D = g.nb[0] + g.nb[1] + g.nb[2];         // R.cpp:26-29 (floor of the logarithms)
-    // axis[] / bit[]: the per-depth split axis.  Only meaningful for power-of-two extents, where every node of a
-    // depth splits the same axis; general extents go through BrickSet::srcIdx / ownerRank instead.
-    for (int d = 0; d < g.D && d < 32; ++d) {  // split-axis rule, R.cpp:151-159
-        int sd = d % 3, i = 0;
-        while (ext[0] * ext[1] * ext[2] > 1 && ext[sd] == 1) sd = (d + ++i) % 3;
-        ext[sd] /= 2;
-        int b = 0; while (((int64_t)1 << (b + 1)) <= ext[sd]) ++b;
-        g.axis[d] = (uint8_t)sd;
-        g.bit[d] = (uint8_t)b;                 // the coordinate bit this split decides
-    }
-}
-
 // ---- general extents: the two geometry tables (BrickSet::srcIdx, ownerRank) ------------------------------------
 // Walks of the reference's own box arithmetic, one thread per leaf / per voxel.  Split sizes do not depend on the
 // box position ((2 min + e) / 2 = min + e / 2), but the axis does depend on the node: "while the box has more than
@@ -157,21 +137,6 @@ k_owner_gather(const uint16_t *__restrict__ rankVals, int64_t leafStride, const 
     if (v >= voxels) return;
     const uint32_t e = rankVals[(int64_t)brick * leafStride + owner[v]];
     out[lod_obase(obase, blockIdx.y, brick, voxels) + v] = (e >> 8) <= (uint32_t)surv[v] ? (uint8_t)e : (uint8_t)0;
-}
-
-// local rank inside a depth-(D-K) subtree -> packed voxel offset (dx | dy<<10 | dz<<20)
-void make_lut(const Geom &g, int K, std::vector<uint32_t> &lut)
-{
-    lut.assign((size_t)1 << K, 0);
-    for (uint32_t lr = 0; lr < (1u << K); ++lr) {
-        uint32_t c[3] = {0, 0, 0};
-        for (int q = 0; q < K; ++q) {
-            int d = g.D - K + q;
-            uint32_t b = (lr >> (K - 1 - q)) & 1u;
-            c[g.axis[d]] |= b << g.bit[d];
-        }
-        lut[lr] = c[0] | (c[1] << 10) | (c[2] << 20);
-    }
 }
 
 struct DecodeArgs {
@@ -1208,6 +1173,7 @@ k_decode_quad(TileArgs a)
 #define RG_REGX (16 * RG_WAVES)
 #define RG_BLK_WORDS 1028
 #define RG_RING_MASK (RG_NP * 256 - 1)
+static_assert(RG_REGX == VR_RG_REGX, "region_plan (host_plan.cpp) lays the regions out for this x extent");
 static_assert(RG_NP >= 4 && (RG_NP & (RG_NP - 1)) == 0, "the side-cars of the next region are staged in ring slots 2 and 3: at least four pieces, a power of two");
 
 struct RegionArgs {
@@ -1658,143 +1624,6 @@ k_decode_region(RegionArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (no LDS-DMA may outlive the workgroup's LDS)
 }
 
-static bool tile_geometry(const BrickSet *bs, TileArgs &a)
-{
-    const Geom &g = bs->g;
-    if (bs->K != 6 || g.D < 6 || g.X < 128 || g.Y < 8 || g.Z < 4) return false;
-    const int D = g.D;
-    int seen = 0;
-    for (int q = 0; q < 3; ++q) {
-        if (g.axis[D - 6 + q] != g.axis[D - 3 + q]) return false;
-        if (g.bit[D - 6 + q] != 1 || g.bit[D - 3 + q] != 0) return false;
-        seen |= 1 << g.axis[D - 3 + q];
-    }
-    if (seen != 7) return false;
-    int pos[3];
-    for (int q = 0; q < 3; ++q) pos[g.axis[D - 3 + q]] = 2 - q;   // deepest level -> rank bit 0
-    a.jx = pos[0]; a.jy = pos[1]; a.jz = pos[2];
-    a.tilesX = g.X / 128; a.tilesY = g.Y / 8; a.tilesZ = g.Z / 4;
-    a.ltx = 0; while ((1 << a.ltx) < a.tilesX) ++a.ltx;
-    a.lty = 0; while ((1 << a.lty) < a.tilesY) ++a.lty;
-    if ((1 << a.ltx) != a.tilesX || (1 << a.lty) != a.tilesY) return false;
-    // ticket order inside a group of 256 tiles (k_decode_quad): first the bits that stay inside a 16 x 16 (y, z) cell --
-    // z bits 0-1 and y bit 0 of the tile coordinate -- then the others in address order
-    {
-        const int first[3] = {a.ltx + a.lty, a.ltx + a.lty + 1, a.ltx};
-        int n = 0;
-        bool used[8] = {false, false, false, false, false, false, false, false};
-        for (int i = 0; i < 3; ++i) {
-            const bool exists = i < 2 ? (1 << (i + 1)) <= a.tilesZ : a.tilesY >= 2;
-            if (exists && first[i] < 8 && !used[first[i]]) { a.kqBit[n++] = (uint8_t)first[i]; used[first[i]] = true; }
-        }
-        for (int b = 0; b < 8; ++b) if (!used[b]) a.kqBit[n++] = (uint8_t)b;
-    }
-    return true;
-}
-
-// k_decode_region's geometry: the twelve deepest levels must be four (a, b, c) triples in one axis order, deciding
-// coordinate bits 3, 2, 1, 0 (a 4096-leaf emit block is then a 16 x 16 x 16 box), with whole 128 x 16 x 16 regions
-static bool region_geometry(const BrickSet *bs, RegionArgs &a)
-{
-    const Geom &g = bs->g;
-    const int D = g.D;
-    if (bs->K != 6 || D < 12 || bs->generalGeom || bs->idx64 || (bs->treeCap & 15)) return false;
-    if (g.X < RG_REGX || g.X < 128 || g.Y < 16 || g.Z < 16) return false;
-    if ((g.X & (g.X - 1)) || (g.Y & (g.Y - 1)) || (g.Z & (g.Z - 1))) return false;
-    int pos[3] = {-1, -1, -1};
-    for (int q = 0; q < 3; ++q) pos[g.axis[D - 3 + q]] = 2 - q;           // deepest level -> rank bit 0
-    if (pos[0] < 0 || pos[1] < 0 || pos[2] < 0) return false;
-    for (int k = 0; k < 4; ++k)
-        for (int q = 0; q < 3; ++q) {
-            const int d = D - 3 * (k + 1) + q;
-            if (g.axis[d] != g.axis[D - 3 + q] || g.bit[d] != k) return false;
-        }
-    const int jx = pos[0], jy = pos[1], jz = pos[2];
-    // quad index q = leaf rank >> 2 (10 bits).  Bits 0-5 go to lane / image-word bits: the two lowest x bits first
-    int Pmap[6], nx = 0, nxt = 2;
-    bool isx[6] = {false, false, false, false, false, false};
-    for (int k = 0; k < 4; ++k) {
-        const int qb = 3 * k + jx - 2;
-        if (qb >= 0 && qb < 6) { isx[qb] = true; Pmap[qb] = nx++; }
-    }
-    if (nx != 2) return false;
-    for (int qb = 0; qb < 6; ++qb) if (!isx[qb]) Pmap[qb] = nxt++;
-    a.lanePos = 0;
-    for (int qb = 0; qb < 6; ++qb) a.lanePos |= (uint32_t)qb << (4 * Pmap[qb]);
-    for (int i = 0; i < 4; ++i) a.parkP[i] = 0;
-    for (int gg = 0; gg < 16; ++gg) {
-        uint32_t w = 0;
-        for (int i = 0; i < 4; ++i) if ((gg >> i) & 1) w |= 1u << Pmap[i];
-        a.parkP[gg >> 2] |= w << (8 * (gg & 3));
-    }
-    a.parkS = 0;
-    for (int sv = 0; sv < 4; ++sv) {
-        uint32_t w = 0;
-        if (sv & 1) w |= 1u << Pmap[4];
-        if (sv & 2) w |= 1u << Pmap[5];
-        a.parkS |= w << (8 * sv);
-    }
-    // image-word contribution of quad-index bit qb (XOR-linear: a permutation plus the step swizzle)
-    const auto contrib = [&](int qb) -> uint32_t {
-        if (qb < 6) return 1u << Pmap[qb];
-        const int i = qb - 6;
-        return (1u << (6 + i)) | (i < 3 ? 1u << (2 + i) : 0u);
-    };
-    // the eight (y, z) bits of a region's 16 x 16 plane
-    struct GB { uint32_t addr, byte, out; } bits[8], ord[8];
-    for (int ax = 1; ax <= 2; ++ax)
-        for (int k = 0; k < 4; ++k) {
-            const int rb = 3 * k + (ax == 1 ? jy : jz);
-            GB &b = bits[(ax - 1) * 4 + k];
-            b.addr = rb < 2 ? 0u : contrib(rb - 2);
-            b.byte = rb < 2 ? 1u << rb : 0u;
-            b.out = ax == 1 ? (uint32_t)((1 << k) * g.X) : (uint32_t)((int64_t)(1 << k) * g.X * g.Y);
-        }
-    // gather bits 0 .. 5-RG_LW come from lane >> RG_LW.  Eight emit blocks per region: bit 1 the plane bit at image bit 5
-    // (the 16-byte bank slot's top bit), bits 0 and 2 plane bits that do not move the slot at all (byte index, image bit
-    // 9): the eight rows of a store instruction then read conflict-free (the lanes of one row are the eight emit blocks,
-    // 4 words = one slot apart).  Four blocks per region: the same three first, any fourth (a two-way conflict at worst).
-    bool used[8] = {false, false, false, false, false, false, false, false};
-    int n = 0;
-    const auto take = [&](int i) { ord[n++] = bits[i]; used[i] = true; };
-    int free0 = -1, free1 = -1, top = -1;
-    for (int i = 0; i < 8; ++i) {
-        if (bits[i].addr == 32u && top < 0) top = i;
-        else if ((bits[i].addr & 0x3Cu) == 0u) { if (free0 < 0) free0 = i; else if (free1 < 0) free1 = i; }
-    }
-    if (free0 >= 0) take(free0); else { for (int i = 0; i < 8; ++i) if (!used[i] && i != top && i != free1) { take(i); break; } }
-    if (top >= 0) take(top); else { for (int i = 0; i < 8; ++i) if (!used[i] && i != free1) { take(i); break; } }
-    if (free1 >= 0) take(free1); else { for (int i = 0; i < 8; ++i) if (!used[i]) { take(i); break; } }
-    for (int i = 0; i < 8; ++i) if (!used[i]) take(i);
-    for (int i = 0; i < 4; ++i) a.gAddr[i] = 0;
-    a.gByte = 0;
-    for (int i = 0; i < 8; ++i) {
-        a.gAddr[i >> 1] |= ord[i].addr << (16 * (i & 1));
-        a.gByte |= ord[i].byte << (4 * i);
-        a.gOut[i] = ord[i].out;
-    }
-    // x bits above the two lowest: the gather's reads
-    uint32_t xr[4] = {0, 0, 0, 0};
-    if (jx < 2) xr[1] = contrib(3 * 3 + jx - 2);
-    else { xr[1] = contrib(6); xr[2] = contrib(9); xr[3] = xr[1] ^ xr[2]; }
-    a.xRead[0] = xr[0] | (xr[1] << 16);
-    a.xRead[1] = xr[2] | (xr[3] << 16);
-    a.jx = jx;
-    a.X = g.X; a.Y = g.Y; a.voxels = g.voxels;
-    a.lrx = 0; while ((RG_REGX << a.lrx) < g.X) ++a.lrx;
-    a.lry = 0; while ((16 << a.lry) < g.Y) ++a.lry;
-    a.nreg = (g.X / RG_REGX) * (g.Y / 16) * (g.Z / 16);
-    // the emit block of a 16^3 box: the rank bits above the twelve lowest
-    uint32_t bpos[3] = {0, 0, 0};
-    for (int d = 0; d < D - 12; ++d) {
-        const int ax = g.axis[d], kb = g.bit[d] - 4;       // coordinate bit kb + 4 of axis ax sits at rank bit D - 1 - d
-        if (kb < 0 || kb >= 6) return false;
-        bpos[ax] |= (uint32_t)(D - 1 - d - 12) << (5 * kb);
-    }
-    a.blkX = bpos[0]; a.blkY = bpos[1]; a.blkZ = bpos[2];
-    return true;
-}
-
 // scalar of every depth-Ds subtree's ancestor at depth `cut` (< Ds), from the encoder's BFS codes
 __global__ void __launch_bounds__(256)
 k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *ctrls, int Ds, int cutAll, int64_t nIdx,
@@ -1822,31 +1651,23 @@ k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *
 enum class DecodeKernel { REGION, QUAD, FINE, TILE, GENERAL, LANE };
 constexpr int DECODE_KERNELS = (int)DecodeKernel::LANE + 1;
 
-// What the choice depends on besides the cut: the set's geometry, the per-4-leaf side-cars and the switches.  Worked
+// What the choice depends on besides the cut: the set's geometry (BrickSet::tile / region, planned at create), and what
+// can change from call to call: the stream, the switches and whether every brick has the per-4-leaf side-car.  Worked
 // out once per call (a per-brick decode classifies every brick with one plan); kernel() is the only place a kernel is
 // chosen.
 struct DecodePlan {
     const BrickSet *bs;
-    bool tiled = false;     // tile geometry: k_decode_tile and the kernels built on it
-    bool fine = false;      // every brick has the per-4-leaf side-car (k_decode_fine / quad / region)
-    bool region = false;    // region geometry, and k_decode_quad was not asked for instead
-    TileArgs t;             // (geometry part: tile_geometry)
-    RegionArgs r;           // (geometry part: region_geometry)
+    bool fine;      // every brick has the per-4-leaf side-car (k_decode_fine / quad / region)
+    bool region;    // region geometry, and k_decode_quad was not asked for instead
 
-    DecodePlan(const BrickSet *b, bool rangeStream) : bs(b)
-    {
-        if (bs->generalGeom) return;
-        tiled = tile_geometry(bs, t);
-        if (!tiled) return;
-        fine = bs->fineIdx && (int)bs->fineHas.size() == bs->B && !rangeStream && !bs->sw.decodeWalk;
-        for (int i = 0; fine && i < bs->B; ++i) fine = bs->fineHas[(size_t)i] != 0;
-        region = fine && !bs->sw.decodeQuad && region_geometry(bs, r);
-    }
+    DecodePlan(const BrickSet *b, bool rangeStream)
+        : bs(b), fine(b->tile.ok && b->fineIdx && b->fineAll && !rangeStream && !b->sw.decodeWalk),
+          region(fine && !b->sw.decodeQuad && b->region.ok) {}
 
     DecodeKernel kernel(int cut) const
     {
         if (bs->generalGeom) return DecodeKernel::GENERAL;
-        if (!tiled) return DecodeKernel::LANE;
+        if (!bs->tile.ok) return DecodeKernel::LANE;
         // k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
         // at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
         if (fine && bs->idxVal3 && cut >= bs->D - 3 && !bs->sw.decodeFineV1)
@@ -1869,8 +1690,7 @@ struct LodClass {
 // One launch of kernel k.  lod: one class of a per-brick decode (decode_lod_launch): grid rows = the class's bricks,
 // each at its own cut; `cut` is one of theirs (the kernel is the class's).  The call's cut values, fine tables and rank
 // scratch are its own (LodSlot), and the caller records the timing events around all classes.
-static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, uint8_t *out, int cut, hipStream_t st,
-                         bool rangeStream, const LodClass *lod)
+static int launch_decode(BrickSet *bs, DecodeKernel k, uint8_t *out, int cut, hipStream_t st, bool rangeStream, const LodClass *lod)
 {
     if (!lod) hipEventRecord(bs->ev[5], st);
     const unsigned rows = lod ? (unsigned)lod->n : (unsigned)bs->B;
@@ -1891,40 +1711,48 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
         cutVals = bs->idxValCut;   // foreign streams: filled by the host from the bytes (capi)
         if (rangeStream) idxVals = bs->idxValCut;
     }
+    // the fields that TileArgs, RegionArgs and DecodeArgs share, under one name in all three
+    const auto common = [&](auto &a, uint8_t *dst, const int64_t *dstBase) {
+        a.tree = sm.tree; a.treeCap = bs->treeCap; a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
+        a.ctrls = sm.ctrl; a.out = dst; a.D = bs->D; a.cut = cut; a.list = list; a.cuts = cuts; a.obase = dstBase;
+    };
     const auto tile_args = [&]() {
-        TileArgs t = plan.t;
-        t.tree = sm.tree; t.treeCap = bs->treeCap;
-        t.idxOff = bs->idxOff; t.idxVal = idxVals; t.nIdx = bs->nIdx;
-        t.ctrls = sm.ctrl; t.out = out; t.g = bs->g; t.D = bs->D; t.Ds = bs->Ds;
-        t.cut = cut; t.idxValCut = cutVals; t.spread = bs->spread;
-        t.list = list; t.cuts = cuts; t.obase = obase;
-        t.fine = bs->fineIdx;
-        t.val3 = bs->idxVal3;
+        const TilePlan &p = bs->tile;
+        TileArgs t;
+        common(t, out, obase);
+        t.jx = p.jx; t.jy = p.jy; t.jz = p.jz;
+        t.tilesX = p.tilesX; t.tilesY = p.tilesY; t.tilesZ = p.tilesZ; t.ltx = p.ltx; t.lty = p.lty;
+        memcpy(t.kqBit, p.kqBit, sizeof(t.kqBit));
+        t.g = bs->g; t.Ds = bs->Ds; t.idxValCut = cutVals; t.spread = bs->spread; t.fine = bs->fineIdx; t.val3 = bs->idxVal3;
         return t;
+    };
+    const auto lane_args = [&](const unsigned long long *idxBase, const uint32_t *lut, uint8_t *dst, const int64_t *dstBase) {
+        DecodeArgs a;
+        common(a, dst, dstBase);
+        a.idxBase = idxBase; a.nBase = idxBase ? bs->nEmitBlk : 0; a.lut = lut; a.g = bs->g; a.K = bs->K; a.Ds = bs->Ds; a.idxValCut = cutVals;
+        return a;
     };
     switch (k) {
     case DecodeKernel::GENERAL: {
         // general extents: rank-domain decode, then every voxel takes its owner leaf's value
         if (!lod && !bs->rankVals && hipMalloc(&bs->rankVals, (size_t)bs->B * bs->leafStride * 2) != hipSuccess) return -3;
         uint8_t *rankVals = lod ? lod->rankVals : bs->rankVals;
-        DecodeArgs a;
-        a.tree = sm.tree; a.treeCap = bs->treeCap;
-        a.idxBase = bs->idx64 ? bs->idxBase : nullptr; a.nBase = bs->nEmitBlk;
-        a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
-        a.ctrls = sm.ctrl; a.lut = nullptr; a.out = rankVals; a.g = bs->g;
-        a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
-        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts; a.obase = nullptr;
+        const DecodeArgs a = lane_args(bs->idx64 ? bs->idxBase : nullptr, nullptr, rankVals, nullptr);
         hipLaunchKernelGGL(k_decode_lane<true>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_owner_gather, dim3((unsigned)((bs->g.voxels + 255) / 256), rows), dim3(256), 0, st,
                            (const uint16_t *)rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list, obase);
         break;
     }
     case DecodeKernel::REGION: {
-        RegionArgs r = plan.r;
-        r.tree = sm.tree; r.treeCap = bs->treeCap;
-        r.idxOff = bs->idxOff; r.idxVal = idxVals; r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.nIdx = bs->nIdx;
-        r.ctrls = sm.ctrl; r.out = out; r.spread = bs->spread; r.D = bs->D; r.cut = cut;
-        r.list = list; r.cuts = cuts; r.obase = obase;
+        const RegionPlan &p = bs->region;
+        RegionArgs r;
+        r.X = p.X; r.Y = p.Y; r.voxels = p.voxels; r.lrx = p.lrx; r.lry = p.lry; r.jx = p.jx;
+        r.lanePos = p.lanePos; r.parkS = p.parkS; r.gByte = p.gByte;
+        memcpy(r.parkP, p.parkP, sizeof(r.parkP)); memcpy(r.gAddr, p.gAddr, sizeof(r.gAddr));
+        memcpy(r.gOut, p.gOut, sizeof(r.gOut)); memcpy(r.xRead, p.xRead, sizeof(r.xRead));
+        r.blkX = p.blkX; r.blkY = p.blkY; r.blkZ = p.blkZ; r.nreg = p.nreg;
+        common(r, out, obase);
+        r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.spread = bs->spread;
         // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
         // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
         unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);
@@ -1969,13 +1797,7 @@ static int launch_decode(BrickSet *bs, const DecodePlan &plan, DecodeKernel k, u
         break;
     }
     case DecodeKernel::LANE: {
-        DecodeArgs a;
-        a.tree = sm.tree; a.treeCap = bs->treeCap;
-        a.idxBase = nullptr; a.nBase = 0;
-        a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
-        a.ctrls = sm.ctrl; a.lut = bs->lut; a.out = out; a.g = bs->g;
-        a.D = bs->D; a.K = bs->K; a.Ds = bs->Ds;
-        a.cut = cut; a.idxValCut = cutVals; a.list = list; a.cuts = cuts; a.obase = obase;
+        const DecodeArgs a = lane_args(nullptr, bs->lut, out, obase);
         hipLaunchKernelGGL(k_decode_lane<false>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
         break;
     }
@@ -1993,8 +1815,7 @@ static bool stores_vectors(DecodeKernel k)
 
 bool decode_stores_vectors(const BrickSet *bs, int cut, bool rangeStream)
 {
-    const DecodePlan plan(bs, rangeStream);
-    return stores_vectors(plan.kernel(cut));
+    return stores_vectors(DecodePlan(bs, rangeStream).kernel(cut));
 }
 
 // per-brick cuts.  Without a pool every decoded brick goes to the caller's buffer; with one, the full-resolution bricks
@@ -2012,8 +1833,7 @@ bool decode_lod_stores_vectors(const BrickSet *bs, const int32_t *cutsHost, cons
 
 int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream)
 {
-    const DecodePlan plan(bs, rangeStream);
-    return launch_decode(bs, plan, plan.kernel(cut), out, cut, st, rangeStream, nullptr);
+    return launch_decode(bs, DecodePlan(bs, rangeStream).kernel(cut), out, cut, st, rangeStream, nullptr);
 }
 
 void free_lod_slots(BrickSet *bs)
@@ -2150,8 +1970,8 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
             const int br = H[B + i];
             vals.assign((size_t)bs->nIdx, 0);
             if (br < (int)bs->hostTree.size() && !bs->hostTree[br].empty() &&
-                cut_values_from_stream(bs, bs->hostTree[br].data(), (int64_t)bs->hostCtrl[br].numActive,
-                                       bs->hostCtrl[br].distanceMap, cutsHost[br], vals) != 0)
+                cut_values_from_stream(bs->D, bs->Ds, bs->K, bs->nIdx, bs->hostTree[br].data(),
+                                       (int64_t)bs->hostCtrl[br].numActive, bs->hostCtrl[br].distanceMap, cutsHost[br], vals) != 0)
                 return -4;
             if (hipMemcpy(s.idxValCut + (size_t)br * bs->nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
         }
@@ -2176,7 +1996,7 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
         L.list = s.dev + l.first; L.n = l.n; L.cuts = s.dev;
         L.idxValCut = s.idxValCut; L.decTables = s.decTables; L.rankVals = s.rankVals;
         L.obase = pool ? s.obDev + (l.first - B - nAbove) : nullptr;
-        rc = launch_decode(bs, plan, (DecodeKernel)l.cls, l.pass == 0 ? (pool ? pool->pool : out) : bs->poolStage, l.cut, st,
+        rc = launch_decode(bs, (DecodeKernel)l.cls, l.pass == 0 ? (pool ? pool->pool : out) : bs->poolStage, l.cut, st,
                            false, &L);
         if (rc == 0 && l.pass > 0 && (li + 1 == launches.size() || launches[li + 1].pass != l.pass)) {
             const int n = (int)passes[(size_t)l.pass].size();
@@ -2192,108 +2012,6 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
     hipEventRecord(s.done, st);
     s.pending = true;
     return rc;
-}
-
-// Foreign stream, progressive cut above the index level: scalar of every depth-Ds subtree's ancestor at
-// depth `cut` (< Ds), from the bytes alone.
-int cut_values_from_stream(BrickSet *bs, const uint8_t *tree, int64_t numActive, const uint8_t *dmap, int cut,
-                           std::vector<uint8_t> &vals)
-{
-    const int D = bs->D, Ds = bs->Ds;
-    vals.assign((size_t)bs->nIdx, 0);
-    auto get = [&](int64_t p) { return (tree[p >> 2] >> ((p & 3) * 2)) & 3; };
-    int v[VR_MAX_DEPTH];
-    int64_t pos = 0;
-    int j = 0;
-    uint32_t path = 0;
-    while (true) {
-        if (pos >= numActive) return -1;
-        int tok = get(pos++);
-        int val = j == 0 ? dmap[0] : (j <= cut ? apply_code(v[j - 1], tok, dmap[j]) : v[j - 1]);
-        v[j] = val;
-        if (j == Ds) vals[path] = (uint8_t)val;
-        bool terminal = false;
-        if (tok == 3) {
-            if (j < Ds) {
-                uint32_t lo = path << (Ds - j), hi = (path + 1) << (Ds - j);
-                for (uint32_t q = lo; q < hi; ++q) vals[q] = (uint8_t)val;
-            }
-            terminal = true;
-        } else if (j == D) {
-            for (int c = 1; c <= VR_CHAIN_LEVELS; ++c) {
-                if (pos >= numActive) return -2;
-                if (get(pos++) == 3) break;
-            }
-            terminal = true;
-        }
-        if (terminal) {
-            while (j > 0 && (path & 1u)) { path >>= 1; --j; }
-            if (j == 0) break;
-            path |= 1u;
-        } else { ++j; path <<= 1; }
-    }
-    return pos == numActive ? 0 : -3;
-}
-
-// Serial pass over a foreign stream (host): the side-car index from the bytes alone.
-// Also validates the grammar.  Returns 0 or a negative code.
-int build_index_from_stream(BrickSet *bs, int brick, const uint8_t *tree, int64_t numActive, const uint8_t *dmap,
-                            std::vector<uint32_t> &offs, std::vector<uint8_t> &vals, std::vector<uint8_t> &fine,
-                            std::vector<uint8_t> &val3)
-{
-    const int D = bs->D, Ds = bs->Ds;
-    offs.assign((size_t)bs->nIdx, VR_IDX_DEAD);
-    vals.assign((size_t)bs->nIdx, 0);
-    // K == 6: tokens owned by each 4-leaf subtree of a depth-Ds node, what k_prune_emit12 leaves for k_decode_fine.
-    // A token at depth >= Ds belongs to the 4-leaf subtree that holds its node's first leaf.
-    const bool wantFine = bs->K == 6 && D >= 6;
-    fine.assign(wantFine ? (size_t)bs->nIdx * 16 : 0, 0);
-    val3.assign(wantFine ? (size_t)bs->nIdx * 8 : 0, 0);      // decoded scalar of every depth-(D-3) node (k_decode_quad)
-    auto own = [&](uint32_t path, int j) {
-        if (!wantFine || j < Ds) return;
-        const uint32_t first = path << (D - j);     // first leaf (rank) below the node
-        fine[(size_t)(first >> 6) * 16 + ((first >> 2) & 15u)] += 1;
-    };
-    auto get = [&](int64_t p) { return (tree[p >> 2] >> ((p & 3) * 2)) & 3; };
-    int v[VR_MAX_DEPTH];
-    int64_t pos = 0;
-    int j = 0;
-    uint32_t path = 0;
-    while (true) {
-        if (pos >= numActive) return -1;
-        const int64_t here = pos;
-        int tok = get(pos++);
-        int val = j == 0 ? dmap[0] : apply_code(v[j - 1], tok, dmap[j]);
-        v[j] = val;
-        if (j == Ds) { offs[path] = (uint32_t)here; vals[path] = (uint8_t)val; }
-        if (wantFine && j == D - 3) val3[path] = (uint8_t)val;
-        own(path, j);
-        bool terminal = false;
-        if (tok == 3) {
-            if (j < Ds) {
-                uint32_t lo = path << (Ds - j), hi = (path + 1) << (Ds - j);
-                for (uint32_t q = lo; q < hi; ++q) { offs[q] = VR_IDX_DEAD; vals[q] = (uint8_t)val; }
-            }
-            if (wantFine && j < D - 3) {
-                uint32_t lo = path << (D - 3 - j), hi = (path + 1) << (D - 3 - j);
-                for (uint32_t q = lo; q < hi; ++q) val3[q] = (uint8_t)val;
-            }
-            terminal = true;
-        } else if (j == D) {
-            for (int c = 1; c <= VR_CHAIN_LEVELS; ++c) {
-                if (pos >= numActive) return -2;
-                own(path, j);
-                if (get(pos++) == 3) break;
-            }
-            terminal = true;
-        }
-        if (terminal) {
-            while (j > 0 && (path & 1u)) { path >>= 1; --j; }
-            if (j == 0) break;
-            path |= 1u;
-        } else { ++j; path <<= 1; }
-    }
-    return pos == numActive ? 0 : -3;
 }
 
 } // namespace vr

@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace vr {
 
@@ -2718,16 +2719,6 @@ static int ensure_aux(BrickSet *bs, int n)
     return have;
 }
 
-// k_pyramid12 builds the bottom twelve levels where they split x four times or more: every thread then loads one
-// 16-byte x-run of the caller's voxels (vrhip.h "alignment of caller buffers"; capi.hip checks the pointer)
-bool build_loads_vectors(const BrickSet *bs)
-{
-    if (bs->D < 12 || bs->generalGeom) return false;
-    int ax = 0;
-    for (int q = 0; q < 12; ++q) ax += bs->g.axis[bs->D - 12 + q] == 0;
-    return ax >= 4;
-}
-
 int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
 {
     const int D = bs->D, B = bs->B;
@@ -2747,31 +2738,13 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         const uint8_t *inMin = nullptr, *inMax = nullptr;
         int64_t inStride = 0;
         const int64_t oStride = (int64_t)1 << (D > 10 ? D - 10 : 0);
-        Pyr12Geom pg{};
-        const bool use12 = build_loads_vectors(bs);
-        skipOn = skipOn && use12;
-        if (use12) {
-            for (int q = 0; q < 12; ++q) {
-                const int ax = bs->g.axis[D - 12 + q];
-                if (ax == 0) pg.ax++; else if (ax == 1) pg.ay++; else pg.az++;
-            }
-            for (int i = 0; i < 16; ++i) {
-                uint32_t r = 0;
-                for (int q = 0; q < 12; ++q) {
-                    const int dd = D - 12 + q;
-                    const int cbit = bs->g.axis[dd] == 0 ? (i >> bs->g.bit[dd]) & 1 : 0;
-                    r = (r << 1) | (uint32_t)(bs->g.bit[dd] < 4 ? cbit : 0);
-                }
-                pg.sx[i] = (uint16_t)r;
-            }
-        }
-        if (use12) {
-            const int64_t Bx = bs->g.X >> pg.ax, By = bs->g.Y >> pg.ay, Bz = bs->g.Z >> pg.az;
-            const int64_t perLine = (bs->g.X < 128 ? bs->g.X : 128) >> pg.ax;
-            pg.swz = (perLine == 8 && Bx % 8 == 0 && ((Bx / 8) * By * Bz) % 8 == 0) ? 1 : 0;
-            pg.nbx = (int)Bx; pg.nby = (int)By;
-            pg.lnbx = 0; while ((1 << pg.lnbx) < pg.nbx) ++pg.lnbx;
-            pg.lnby = 0; while ((1 << pg.lnby) < pg.nby) ++pg.lnby;
+        const Pyr12Plan &pp = bs->pyr12;      // (planned at create: host_plan.cpp)
+        skipOn = skipOn && pp.use12;
+        if (pp.use12) {
+            Pyr12Geom pg{};
+            pg.ax = pp.ax; pg.ay = pp.ay; pg.az = pp.az;
+            memcpy(pg.sx, pp.sx, sizeof(pg.sx));
+            pg.swz = pp.swz; pg.nbx = pp.nbx; pg.nby = pp.nby; pg.lnbx = pp.lnbx; pg.lnby = pp.lnby;
             pg.spread = bs->spread;
             hipLaunchKernelGGL(k_pyramid12, dim3((unsigned)((int64_t)1 << (D - 12)), B), dim3(256), 0, st, bs->g, pg, vox,
                                bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr, bs->mmMin[0], bs->mmMax[0],
@@ -2805,6 +2778,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     // ---- COMPRESS
     // constant bricks take the closed form (both streams of a MidRangeTree too; needs the leaf prune and an epoch to exist)
     const bool constOk = bs->maxEpochs >= 1 && bs->tolerance >= 1 && D >= 1;
+    const uint8_t *cMin = constOk ? rootMinP : nullptr, *cMax = constOk ? rootMaxP : nullptr;
     const SkipBlocks sk{skipOn ? bs->blockFlag : nullptr, (int64_t)1 << (D >= 12 ? D - 12 : 0), D - 2};
     const SkipBlocks skR{skipOn && mr ? bs->blockFlagR : nullptr, sk.nBlk, D - 2};
     // MidRangeTree: the two streams' level loops do not depend on each other (M.cpp:399-544 runs them one after the
@@ -2814,8 +2788,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     if (forkR) {
         hipEventRecord(bs->evFork, st);
         hipStreamWaitEvent(bs->aux, bs->evFork, 0);
-        compress_stream(bs, bs->rng, bs->aux, constOk ? rootMinP : nullptr, constOk ? rootMaxP : nullptr, rootStride, skR,
-                        bs->blockErrR, bs->estSummR);
+        compress_stream(bs, bs->rng, bs->aux, cMin, cMax, rootStride, skR, bs->blockErrR, bs->estSummR);
         hipEventRecord(bs->evJoin, bs->aux);
     }
     // VolumeKdtree: the same trick over ranges of the bricks (vr_brickset_set_concurrency; 2 by default)
@@ -2828,18 +2801,15 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         for (int p = 1; p < parts; ++p) {
             const int b0 = (int)((int64_t)B * p / parts), b1 = (int)((int64_t)B * (p + 1) / parts);
             hipStreamWaitEvent(bs->auxN[p - 1], bs->evFork, 0);
-            compress_stream(bs, bs->mid, bs->auxN[p - 1], constOk ? rootMinP : nullptr, constOk ? rootMaxP : nullptr, rootStride, sk,
-                            bs->blockErr, bs->estSumm, b0, b1 - b0);
+            compress_stream(bs, bs->mid, bs->auxN[p - 1], cMin, cMax, rootStride, sk, bs->blockErr, bs->estSumm, b0, b1 - b0);
             hipEventRecord(bs->evJoinN[p - 1], bs->auxN[p - 1]);
         }
-        compress_stream(bs, bs->mid, st, constOk ? rootMinP : nullptr, constOk ? rootMaxP : nullptr, rootStride, sk, bs->blockErr,
-                        bs->estSumm, 0, (int)((int64_t)B / parts));
+        compress_stream(bs, bs->mid, st, cMin, cMax, rootStride, sk, bs->blockErr, bs->estSumm, 0, (int)((int64_t)B / parts));
         for (int p = 1; p < parts; ++p) hipStreamWaitEvent(st, bs->evJoinN[p - 1], 0);
     } else
-    compress_stream(bs, bs->mid, st, constOk ? rootMinP : nullptr, constOk ? rootMaxP : nullptr, rootStride, sk, bs->blockErr, bs->estSumm);
+    compress_stream(bs, bs->mid, st, cMin, cMax, rootStride, sk, bs->blockErr, bs->estSumm);
     if (forkR) hipStreamWaitEvent(st, bs->evJoin, 0);
-    else if (mr) compress_stream(bs, bs->rng, st, constOk ? rootMinP : nullptr, constOk ? rootMaxP : nullptr, rootStride, skR,
-                                 bs->blockErr, bs->estSumm);
+    else if (mr) compress_stream(bs, bs->rng, st, cMin, cMax, rootStride, skR, bs->blockErr, bs->estSumm);
     hipEventRecord(bs->ev[2], st);
     dbg_sync(st, "compress");
     // ---- PRUNE
@@ -2848,6 +2818,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     ReconBufs rbR{{bs->rng.recon[0], bs->rng.recon[1], bs->rng.recon[2]}};
     int pruneFrom = D - 1;
     bs->fineHas.assign((size_t)B, 0);
+    fine_has_changed(*bs);
     if (fused) {
         PruneEmitArgs pa;
         pa.sk = sk; pa.skR = skR;
@@ -2872,6 +2843,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         }
         pruneFrom = D - 13;
         bs->fineHas.assign((size_t)B, 1);
+        fine_has_changed(*bs);
     } else
         hipLaunchKernelGGL(k_prune_leaf, dim3(cdiv((int64_t)1 << D, 256), B), dim3(256), 0, st, D, bs->tolerance,
                            bs->mid.ctrl, bs->mid.temp, bs->mid.codes, mr ? bs->rng.codes : nullptr, bs->heapStride,
