@@ -280,7 +280,8 @@ typedef struct vr_camera {
 
 enum { VR_RENDER_COMPOSITE = 0 /* raycaster.frag */, VR_RENDER_ISOSURFACE = 1 /* isosurface.frag */,
        VR_RENDER_PARTIAL = 2 /* raycaster.frag accumulation as an (rgb-premultiplied c, transmittance) pair for sort-last compositing */,
-       VR_RENDER_SHADED = 3 /* transfer function with gradient lighting: vr_raycast_tf_shaded only */ };
+       VR_RENDER_SHADED = 3 /* transfer function with gradient lighting: vr_raycast_tf_shaded only */,
+       VR_RENDER_PROJECTION = 4 /* intensity projections: vr_raycast_projection & co. only */ };
 
 typedef struct vr_render_params {
     int32_t width, height;   /* 1600x1200 in the reference (main.cpp:27); bench uses 1920x1080 */
@@ -471,6 +472,75 @@ vr_status vr_composite_slabs_tf(const float *partials_dev, int32_t num_slabs, in
                                 int32_t axis, const vr_camera *cam, const vr_render_params *params,
                                 const vr_transfer_function *tf, float *rgba_dev, void *stream);
 
+/* ---- intensity projections (new): MIP, MinIP and the mean along the ray, exact across GPUs ----------------------------
+ * Ray set-up is vr_raycast's, unchanged: positions are formed by the same repeated float additions pos += st, with the
+ * same inside() stop and max_samples.  A sample is OWNED when its position lies in [box_min, box_max) on every axis
+ * (vr_raycast_tf's step 1); an owned sample is fetched exactly as vr_raycast fetches it, bit for bit (dense volume or
+ * pool).  The ray keeps n, the number of owned samples, and v:
+ *   VR_PROJECT_MAX   v = the largest sample (a running maximum that starts at 0: samples are never negative);
+ *   VR_PROJECT_MIN   v = the smallest sample (a running minimum that starts at +inf);
+ *   VR_PROJECT_MEAN  v = the float32 sum of the samples, accumulated in sample order.
+ * There is no early exit: no_early_exit and iso_value are ignored.
+ * The projection PARTIAL is one float4 per pixel, (v, (float)n, 0, 0); a pixel the cube does not cover, or whose ray owns
+ * no sample, is (0, 0, 0, 0) exactly.  max_samples above 2^24 is VR_ERR_INVALID, so that n is exact in a float.
+ * The FINISH (partial to pixel): n == 0: (background, 0).  Otherwise m = v (MAX, MIN) or v / n (MEAN, a float32
+ * division); w = clamp((m - window_lo) / (window_hi - window_lo), 0, 1); lut_dev == NULL: the pixel is (w, w, w, 1); else
+ * e = step 3 of vr_raycast_tf's rule applied to w (the lookup, alpha clamped) and the pixel is
+ * (e.a * e.rgb + (1 - e.a) * background, e.a).  With the window (0, 1), w == m exactly: (m - 0) / 1 is exact and m lies in
+ * [0, 1].
+ * The COMBINE of partials: partials with n == 0 are ignored; n adds; v is the max, the min, or the float32 sum in
+ * ascending slab index.  Max, min and a count are commutative and associative, so the MAX and MIN frames (and partials)
+ * of any number of ranks along any slab axis, combined in any order, equal the single-GPU frame bit for bit; MEAN's n is
+ * exact and its v differs by the rounding of two summation orders.  A rank's slab under vol_origin / global_dims holds
+ * ONE halo layer.
+ * The skip grid (same condition as vr_raycast: volume_dev is the whole volume, or a pool's grid): the ray still advances
+ * sample by sample and n still counts the sample; only the fetch is dropped.  With (mn, mx) the cell's bounds, k = 1/255
+ * and cur the running value:
+ *   MAX   skip iff (mn == mx ? (float)mx * k : (float)(mx + 1) * k) <= cur.  Equal bounds: all eight taps are equal, every
+ *         c + f * (c - c) is exactly c, so the sample is exactly (float)mx * k and max(cur, sample) == cur.  Otherwise
+ *         interpolation can leave the taps' range by rounding only, and a whole grey level covers that (the iso-surface's
+ *         convention);
+ *   MIN   skip iff (mn == mx ? (float)mn * k : (float)(mn - 1) * k) >= cur; never for the first owned sample (cur = +inf);
+ *   MEAN  skip iff mx == 0: the sample is exactly 0 and sum + 0 is a no-op.
+ * Frames and partials are bit-identical with and without the grid, and the pool's to the dense ones of the pool's volume
+ * assembled densely.  finish(partial) equals the frame bit for bit, and pairwise vr_composite_combine_proj folds in
+ * ascending order followed by the finish equal vr_composite_slabs_proj bit for bit (one combine and one finish are shared
+ * by all of them). */
+enum { VR_PROJECT_MAX = 0, VR_PROJECT_MIN = 1, VR_PROJECT_MEAN = 2 };
+
+typedef struct vr_projection {
+    const float *lut_dev;    /* NULL = grey; else 256 x (r,g,b,a) float32 on the device, 16-byte aligned (a colour map) */
+    int32_t op;              /* VR_PROJECT_*  */
+    float window_lo, window_hi;   /* the displayed value is clamp((m - lo) / (hi - lo), 0, 1); 0, 1 = identity */
+    float background[3];
+} vr_projection;             /* 32 bytes */
+
+/* vr_raycast's / vr_raycast_pool's checks, plus VR_ERR_INVALID (nothing launched) for a mode other than
+ * VR_RENDER_PROJECTION, a null proj, an op outside 0..2, a window that is not finite or has hi <= lo, a background that is
+ * not finite, a lut_dev that is neither NULL nor 16-byte aligned, or max_samples > 2^24.  The _partial calls write the
+ * partial instead of the frame: lut_dev, window and background are validated, not used. */
+vr_status vr_raycast_projection(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                                const vr_render_params *params, const vr_projection *proj, float *rgba_dev, void *stream);
+vr_status vr_raycast_pool_projection(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                                     const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
+                                     const vr_projection *proj, float *rgba_dev, void *stream);
+vr_status vr_raycast_projection_partial(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                                        const vr_render_params *params, const vr_projection *proj, float *partial_dev,
+                                        void *stream);
+vr_status vr_raycast_pool_projection_partial(const uint8_t *pool_dev, const vr_pool_entry *table_dev,
+                                             const int64_t brick_dims[3], const int64_t grid[3], const vr_camera *cam,
+                                             const vr_render_params *params, const vr_projection *proj, float *partial_dev,
+                                             void *stream);
+/* combine: front = combine(front, back); finish: the finish; slabs: the num_slabs partials of num_pixels pixels, stacked
+ * back to back, combined in ascending index and finished -- no camera, axis or first_pixel, because order does not
+ * matter.  VR_ERR_INVALID for a null pointer, num_pixels < 1, num_slabs < 1, an op outside 0..2 or a proj that
+ * vr_raycast_projection would refuse. */
+vr_status vr_composite_combine_proj(float *front_dev, const float *back_dev, int64_t num_pixels, int32_t op, void *stream);
+vr_status vr_composite_finish_proj(const float *partial_dev, const vr_projection *proj, float *rgba_dev, int64_t num_pixels,
+                                   void *stream);
+vr_status vr_composite_slabs_proj(const float *partials_dev, int32_t num_slabs, int64_t num_pixels, const vr_projection *proj,
+                                  float *rgba_dev, void *stream);
+
 /* Sort-last compositing of VR_RENDER_PARTIAL images: front = front OVER back, per pixel
  * (c1 + t1*c2, t1*t2); and the final colour transfer of raycaster.frag:82-85. */
 vr_status vr_composite_over(float *front_dev, const float *back_dev, int64_t num_pixels, void *stream);
@@ -510,6 +580,11 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
 vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
                                      const vr_render_params *params, const vr_transfer_function *tf, float *rgba_dev,
                                      void *stream);
+/* vr_compositor_composite for the projection partials of vr_raycast_projection_partial: the same handle, buffers and
+ * exchange (the same transport calls in the same order), the tile combined by vr_composite_slabs_proj.  No camera, axis
+ * or params: the combine has no order.  The MAX and MIN frames equal the single-GPU frame bit for bit. */
+vr_status vr_compositor_composite_proj(vr_compositor *c, const float *partial_dev, const vr_projection *proj, float *rgba_dev,
+                                       void *stream);
 vr_status vr_compositor_destroy(vr_compositor *c);
 /* The transport seam: vr_compositor_composite's exchange is four point-to-point calls, made through this table.  RCCL
  * is the built-in table (ctx = the ncclComm_t) that the two constructors above install.  With

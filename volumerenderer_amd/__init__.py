@@ -19,7 +19,9 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
                 "use_skip_grid", "select_lod", "lod_pool_layout", "raycast_pool", "build_skip_grid_pool", "TransferFunction",
                 "raycast_tf", "raycast_pool_tf", "transfer_function_table", "Shading", "raycast_tf_shaded",
                 "raycast_pool_tf_shaded", "raycast_tf_partial", "raycast_pool_tf_partial", "composite_over_tf",
-                "composite_finish_tf"):
+                "composite_finish_tf", "Projection", "raycast_projection", "raycast_pool_projection",
+                "raycast_projection_partial", "raycast_pool_projection_partial", "composite_combine_proj",
+                "composite_finish_proj"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

@@ -12,7 +12,8 @@ VR_OK = 0
 STATUS = {0: "VR_OK", -1: "VR_ERR_INVALID", -2: "VR_ERR_NO_DEVICE", -3: "VR_ERR_OOM", -4: "VR_ERR_IO",
           -5: "VR_ERR_STATE", -6: "VR_ERR_FORMAT", -7: "VR_ERR_UNSUPPORTED"}
 VARIANT_RECOVER, VARIANT_GUARDED, VARIANT_MIDRANGE = 0, 1, 2
-RENDER_COMPOSITE, RENDER_ISOSURFACE, RENDER_PARTIAL, RENDER_SHADED = 0, 1, 2, 3
+RENDER_COMPOSITE, RENDER_ISOSURFACE, RENDER_PARTIAL, RENDER_SHADED, RENDER_PROJECTION = 0, 1, 2, 3, 4
+PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN = 0, 1, 2
 
 
 class VrError(RuntimeError):
@@ -52,6 +53,12 @@ class ShadingDesc(C.Structure):
     """vr_shading (32 bytes)."""
     _fields_ = [("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float), ("shininess", C.c_float),
                 ("light_dir", C.c_float * 3), ("grad_min", C.c_float)]
+
+
+class Projection(C.Structure):
+    """vr_projection (32 bytes)."""
+    _fields_ = [("lut_dev", C.c_void_p), ("op", C.c_int32), ("window_lo", C.c_float), ("window_hi", C.c_float),
+                ("background", C.c_float * 3)]
 
 
 class PoolEntry(C.Structure):
@@ -116,6 +123,17 @@ SIGNATURES = {
     "vr_composite_finish_tf": (_I32, [_P, C.POINTER(TransferFunctionDesc), _P, _I64, _P]),
     "vr_composite_slabs_tf": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams),
                                      C.POINTER(TransferFunctionDesc), _P, _P]),
+    "vr_raycast_projection": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Projection),
+                                     _P, _P]),
+    "vr_raycast_pool_projection": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                          C.POINTER(Projection), _P, _P]),
+    "vr_raycast_projection_partial": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                             C.POINTER(Projection), _P, _P]),
+    "vr_raycast_pool_projection_partial": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera),
+                                                  C.POINTER(RenderParams), C.POINTER(Projection), _P, _P]),
+    "vr_composite_combine_proj": (_I32, [_P, _P, _I64, _I32, _P]),
+    "vr_composite_finish_proj": (_I32, [_P, C.POINTER(Projection), _P, _I64, _P]),
+    "vr_composite_slabs_proj": (_I32, [_P, _I32, _I64, C.POINTER(Projection), _P, _P]),
     "vr_composite_over": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_finish": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_slabs": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
@@ -126,6 +144,7 @@ SIGNATURES = {
     "vr_compositor_composite": (_I32, [_P, _P, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
     "vr_compositor_composite_tf": (_I32, [_P, _P, _I32, C.POINTER(Camera), C.POINTER(RenderParams),
                                           C.POINTER(TransferFunctionDesc), _P, _P]),
+    "vr_compositor_composite_proj": (_I32, [_P, _P, C.POINTER(Projection), _P, _P]),
     "vr_compositor_destroy": (_I32, [_P]),
     "vr_stream_create": (_I32, [C.POINTER(_P)]),
     "vr_stream_destroy": (_I32, [_P]),

@@ -35,6 +35,13 @@ int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_c
 int assemble_launch(bool, const uint8_t *, uint8_t *, int, const int64_t bd[3], const int64_t *, const int64_t grid[3], hipStream_t);
 int measure_error_launch(const uint8_t *, const uint8_t *, int64_t, int *, unsigned long long *, hipStream_t);
 int query_error_launch(const uint8_t *, const uint8_t *, int64_t, uint8_t *, hipStream_t);
+int raycast_proj_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, const vr_projection *,
+                        bool partial, float *, hipStream_t);
+int raycast_pool_proj_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
+                             const vr_render_params *, const vr_projection *, bool partial, float *, hipStream_t);
+int composite_combine_proj_launch(float *, const float *, int64_t, int, hipStream_t);
+int composite_finish_proj_launch(const float *, const vr_projection *, float *, int64_t, hipStream_t);
+int composite_slabs_proj_launch(const float *, int, int64_t, const vr_projection *, float *, hipStream_t);
 extern std::atomic<int> g_skipGridV1;
 }
 
@@ -49,6 +56,17 @@ static bool device_ok()
     if ((e != hipSuccess || n <= 0) && getenv("VRHIP_DEBUG"))
         fprintf(stderr, "[vrhip] hipGetDeviceCount: %s (n=%d)\n", hipGetErrorString(e), n);
     return e == hipSuccess && n > 0;
+}
+
+// a vr_projection (vrhip.h); vr_compositor_composite_proj (compositor.hip) makes the same check
+namespace vr {
+bool projection_ok(const vr_projection *pj)
+{
+    if (!pj || pj->op < VR_PROJECT_MAX || pj->op > VR_PROJECT_MEAN) return false;
+    if (!isfinite(pj->window_lo) || !isfinite(pj->window_hi) || !(pj->window_hi > pj->window_lo)) return false;
+    for (int k = 0; k < 3; ++k) if (!isfinite(pj->background[k])) return false;
+    return ((uintptr_t)pj->lut_dev & 15u) == 0u;
+}
 }
 
 extern "C" {
@@ -1235,6 +1253,81 @@ vr_status vr_composite_slabs_tf(const float *partials, int32_t num_slabs, int64_
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return composite_slabs_tf_launch(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, tf, rgba, (hipStream_t)stream) == 0
                ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// ---- intensity projections (vrhip.h): the entry points
+
+static bool projection_frame_ok(const vr_render_params *P, const vr_projection *pj)
+{
+    return P->mode == VR_RENDER_PROJECTION && P->max_samples <= (1 << 24) && projection_ok(pj);
+}
+
+static vr_status project_dense(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                               const vr_projection *pj, float *rgba, void *stream, bool partial)
+{
+    if (!frame_ok(cam, P, rgba) || !dense_ok(vol, dims) || !projection_frame_ok(P, pj)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_proj_launch(vol, dims, cam, P, pj, partial, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+static vr_status project_pool(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                              const vr_camera *cam, const vr_render_params *P, const vr_projection *pj, float *rgba,
+                              void *stream, bool partial)
+{
+    if (!frame_ok(cam, P, rgba) || !pool_ok(pool, table, bd, grid) || !pool_frame_ok(P, bd, grid) || !projection_frame_ok(P, pj))
+        return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_pool_proj_launch(pool, table, bd, grid, cam, P, pj, partial, rgba, (hipStream_t)stream) == 0 ? VR_OK
+                                                                                                               : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_raycast_projection(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                                const vr_projection *pj, float *rgba, void *stream)
+{
+    return project_dense(vol, dims, cam, P, pj, rgba, stream, false);
+}
+
+vr_status vr_raycast_pool_projection(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                                     const vr_camera *cam, const vr_render_params *P, const vr_projection *pj, float *rgba,
+                                     void *stream)
+{
+    return project_pool(pool, table, bd, grid, cam, P, pj, rgba, stream, false);
+}
+
+vr_status vr_raycast_projection_partial(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam,
+                                        const vr_render_params *P, const vr_projection *pj, float *partial, void *stream)
+{
+    return project_dense(vol, dims, cam, P, pj, partial, stream, true);
+}
+
+vr_status vr_raycast_pool_projection_partial(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3],
+                                             const int64_t grid[3], const vr_camera *cam, const vr_render_params *P,
+                                             const vr_projection *pj, float *partial, void *stream)
+{
+    return project_pool(pool, table, bd, grid, cam, P, pj, partial, stream, true);
+}
+
+vr_status vr_composite_combine_proj(float *front, const float *back, int64_t n, int32_t op, void *stream)
+{
+    if (!front || !back || n <= 0 || op < VR_PROJECT_MAX || op > VR_PROJECT_MEAN) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return composite_combine_proj_launch(front, back, n, op, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_composite_finish_proj(const float *partial, const vr_projection *pj, float *rgba, int64_t n, void *stream)
+{
+    if (!partial || !rgba || n <= 0 || !projection_ok(pj)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return composite_finish_proj_launch(partial, pj, rgba, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_composite_slabs_proj(const float *partials, int32_t num_slabs, int64_t num_pixels, const vr_projection *pj,
+                                  float *rgba, void *stream)
+{
+    if (!partials || !rgba || num_slabs <= 0 || num_pixels <= 0 || !projection_ok(pj)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return composite_slabs_proj_launch(partials, num_slabs, num_pixels, pj, rgba, (hipStream_t)stream) == 0 ? VR_OK
+                                                                                                            : VR_ERR_NO_DEVICE;
 }
 
 vr_status vr_brickset_set_concurrency(vr_brickset *h, int32_t level_loop_streams)

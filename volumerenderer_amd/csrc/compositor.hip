@@ -27,6 +27,8 @@ namespace vr {
 int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
 int composite_slabs_tf_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *,
                               const vr_transfer_function *, float *, hipStream_t);
+int composite_slabs_proj_launch(const float *, int, int64_t, const vr_projection *, float *, hipStream_t);
+bool projection_ok(const vr_projection *);      // capi.hip
 }
 
 namespace {
@@ -198,13 +200,15 @@ vr_status vr_compositor_destroy(vr_compositor *c)
     return VR_OK;
 }
 
-// The exchange of both composite calls: a grey and a colour partial are the same width * height * 4 floats, and only
-// the combine differs -- tf == NULL: k_composite_slabs (c, tau, covered), else k_composite_slabs_tf (C, T).
+// The exchange of the three composite calls: a grey, a colour and a projection partial are the same width * height * 4
+// floats, and only the combine differs -- proj: k_composite_slabs_proj (v, n), which needs no view order; else tf == NULL:
+// k_composite_slabs (c, tau, covered), else k_composite_slabs_tf (C, T).
 static vr_status exchange_and_combine(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
-                                      const vr_render_params *params, const vr_transfer_function *tf, float *rgba_dev,
-                                      hipStream_t st)
+                                      const vr_render_params *params, const vr_transfer_function *tf,
+                                      const vr_projection *proj, float *rgba_dev, hipStream_t st)
 {
     auto combine = [&](const float *parts, int n, int64_t npix, int64_t first, float *dst) -> int {
+        if (proj) return vr::composite_slabs_proj_launch(parts, n, npix, proj, dst, st);
         return tf ? vr::composite_slabs_tf_launch(parts, n, npix, first, axis, cam, params, tf, dst, st)
                   : vr::composite_slabs_launch(parts, n, npix, first, axis, cam, params, dst, st);
     };
@@ -256,7 +260,7 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
                                   const vr_render_params *params, float *rgba_dev, void *stream)
 {
     if (!composite_args_ok(c, partial_dev, axis, cam, params, rgba_dev)) return VR_ERR_INVALID;
-    return exchange_and_combine(c, partial_dev, axis, cam, params, nullptr, rgba_dev, (hipStream_t)stream);
+    return exchange_and_combine(c, partial_dev, axis, cam, params, nullptr, nullptr, rgba_dev, (hipStream_t)stream);
 }
 
 vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
@@ -265,7 +269,14 @@ vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev,
 {
     if (!composite_args_ok(c, partial_dev, axis, cam, params, rgba_dev) || !tf) return VR_ERR_INVALID;
     for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return VR_ERR_INVALID;
-    return exchange_and_combine(c, partial_dev, axis, cam, params, tf, rgba_dev, (hipStream_t)stream);
+    return exchange_and_combine(c, partial_dev, axis, cam, params, tf, nullptr, rgba_dev, (hipStream_t)stream);
+}
+
+vr_status vr_compositor_composite_proj(vr_compositor *c, const float *partial_dev, const vr_projection *proj, float *rgba_dev,
+                                       void *stream)
+{
+    if (!c || !partial_dev || (c->rank == 0 && !rgba_dev) || !vr::projection_ok(proj)) return VR_ERR_INVALID;
+    return exchange_and_combine(c, partial_dev, 0, nullptr, nullptr, nullptr, proj, rgba_dev, (hipStream_t)stream);
 }
 
 // ---- streams, events, pinned host memory: what a C++ host needs to overlap the stages of a timestep stream

@@ -791,6 +791,155 @@ k_composite_slabs_tf(SlabArgs a, Bg bg)
     a.out[i] = finish_tf(acc, bg);
 }
 
+// ---- intensity projections (vr_raycast_projection; the rule is in vrhip.h) -------------------------------------------
+// A projection partial is (v, n, 0, 0): n owned samples, v their maximum, minimum or float32 sum.  One combine and one
+// finish serve the marcher's final store and the three element-wise kernels, so finish(partial) == frame and pairwise
+// folds == the slab call hold by construction.
+struct ProjArgs {
+    const float4 *lut;      // NULL = grey; else 256 (r, g, b, a), 16-byte aligned
+    int op;                 // VR_PROJECT_*
+    float lo, hi;           // the window
+    float bg[3];
+};
+
+__device__ __forceinline__ void combine_proj(float4 &f, const float4 &b, int op)
+{
+    if (b.y == 0.0f) return;            // a partial that owns no sample
+    if (f.y == 0.0f) { f = b; return; }
+    f.x = op == VR_PROJECT_MAX ? fmaxf(f.x, b.x) : (op == VR_PROJECT_MIN ? fminf(f.x, b.x) : f.x + b.x);
+    f.y = f.y + b.y;
+}
+
+__device__ __forceinline__ float4 finish_proj(const float4 &p, const ProjArgs &A)
+{
+    if (p.y == 0.0f) return make_float4(A.bg[0], A.bg[1], A.bg[2], 0.0f);
+    const float m = A.op == VR_PROJECT_MEAN ? p.x / p.y : p.x;
+    const float w = fminf(fmaxf((m - A.lo) / (A.hi - A.lo), 0.0f), 1.0f);
+    if (!A.lut) return make_float4(w, w, w, 1.0f);
+    // step 3 of vr_raycast_tf's rule, with k_raycast_tf's expressions
+    const float x = fminf(fmaxf(w * 255.0f, 0.0f), 255.0f);
+    const int li = min((int)x, 254);
+    const float f = x - (float)li;
+    const float4 e0 = A.lut[li], e1 = A.lut[li + 1];
+    const float ea = fminf(fmaxf(e0.w + f * (e1.w - e0.w), 0.0f), 1.0f);
+    const float c0 = e0.x + f * (e1.x - e0.x), c1 = e0.y + f * (e1.y - e0.y), c2 = e0.z + f * (e1.z - e0.z);
+    const float tb = 1.0f - ea;
+    return make_float4(ea * c0 + tb * A.bg[0], ea * c1 + tb * A.bg[1], ea * c2 + tb * A.bg[2], ea);
+}
+
+// k_raycast's per-pixel ray set-up (the same expressions in the same order): false where the cube does not cover the
+// pixel, else pos = vUV and st = the step
+__device__ __forceinline__ bool ray_setup(const RayArgs &a, int px, int py, float pos[3], float st[3])
+{
+    const int W = a.P.width, H = a.P.height;
+    const float nx = 2.0f * ((float)px + 0.5f) / (float)W - 1.0f;
+    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)H;
+    float dir[3], cp[3] = {a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dir[k] = a.f[k] + nx * a.tanX * a.s[k] + ny * a.tanY * a.u[k];
+    float t0 = -INFINITY, t1 = INFINITY;
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (dir[k] != 0.0f) {
+            float lo = (-0.5f - cp[k]) / dir[k], hi = (0.5f - cp[k]) / dir[k];
+            if (lo > hi) { float q = lo; lo = hi; hi = q; }
+            if (lo > t0) t0 = lo;
+            if (hi < t1) t1 = hi;
+        } else if (cp[k] < -0.5f || cp[k] > 0.5f) miss = true;
+    }
+    const float th = t0 >= a.cam.z_near ? t0 : t1;
+    if (miss || t0 > t1 || th < a.cam.z_near || th > a.cam.z_far) return false;
+    float vuv[3], gd[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vuv[k] = (cp[k] + th * dir[k]) + 0.5f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gd[k] = (vuv[k] - 0.5f) - cp[k];
+    norm3(gd[0], gd[1], gd[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { st[k] = gd[k] * a.P.step_size[k]; pos[k] = vuv[k]; }
+    return true;
+}
+
+// may the fetch at a position whose taps the grid bounds by b = (mn | mx << 8) be dropped?  (the proof is in vrhip.h)
+template <int OP>
+__device__ __forceinline__ bool proj_skippable(uint32_t b, float cur)
+{
+    const int mn = (int)(b & 255u), mx = (int)(b >> 8);
+    const float k = 1.0f / 255.0f;
+    if (OP == VR_PROJECT_MAX) return (float)(mn == mx ? mx : mx + 1) * k <= cur;
+    if (OP == VR_PROJECT_MIN) return (float)(mn == mx ? mn : mn - 1) * k >= cur;
+    return mx == 0;
+}
+
+// One thread per pixel, 8x8 tile per wave; one fetch per iteration (keeping 2 or 4 in flight was tried and measured: no
+// gain without the grid, fewer skips with it -- DESIGN.md 3.5f).  The grid is asked while the ray's value stands still
+// (after a skip, or a fetch that did not change it; MEAN: a fetch of 0), like k_raycast's probe.
+template <class SAMPLER, int OP, bool PARTIAL>
+__global__ void __launch_bounds__(64)
+k_raycast_proj(RayArgs a, SAMPLER tex, ProjArgs A)
+{
+    const int px = blockIdx.x * 8 + (threadIdx.x & 7), py = blockIdx.y * 8 + (threadIdx.x >> 3);
+    if (px >= a.P.width || py >= a.P.height) return;
+    float *o = a.out + 4 * ((size_t)py * a.P.width + px);
+    float pos[3], st[3];
+    float cur = OP == VR_PROJECT_MIN ? INFINITY : 0.0f;
+    int n = 0;
+    if (ray_setup(a, px, py, pos, st)) {
+        const int ns = a.P.max_samples;
+        bool probe = true;
+        for (int i = 0; i < ns; ++i) {
+            pos[0] = pos[0] + st[0]; pos[1] = pos[1] + st[1]; pos[2] = pos[2] + st[2];
+            if (!inside(pos[0], pos[1], pos[2])) break;
+            bool own = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.P.box_min[k] && pos[k] < a.P.box_max[k]);
+            if (!own) continue;
+            ++n;
+            if (a.sg.g && probe && proj_skippable<OP>(skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]), cur)) continue;
+            const float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
+            if (OP == VR_PROJECT_MEAN) { cur = cur + smp; probe = smp == 0.0f; }
+            else {
+                const float nv = OP == VR_PROJECT_MAX ? fmaxf(cur, smp) : fminf(cur, smp);
+                probe = nv == cur;
+                cur = nv;
+            }
+        }
+    }
+    const float4 part = n > 0 ? make_float4(cur, (float)n, 0.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 r = PARTIAL ? part : finish_proj(part, A);
+    o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
+}
+
+__global__ void __launch_bounds__(256)
+k_composite_combine_proj(float4 *front, const float4 *back, int64_t n, int op)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 f = front[i];
+    combine_proj(f, back[i], op);
+    front[i] = f;
+}
+
+__global__ void __launch_bounds__(256)
+k_composite_finish_proj(const float4 *partial, ProjArgs A, float4 *rgba, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rgba[i] = finish_proj(partial[i], A);
+}
+
+// the slabs in ascending index (the order only matters to MEAN's rounding): num_slabs 16-byte loads, one 16-byte store
+__global__ void __launch_bounds__(256)
+k_composite_slabs_proj(const float4 *partials, int num_slabs, int64_t npix, ProjArgs A, float4 *rgba)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int k = 0; k < num_slabs; ++k) combine_proj(acc, partials[(int64_t)k * npix + i], A.op);
+    rgba[i] = finish_proj(acc, A);
+}
+
 // Brick <-> global volume placement (VolumeReader.h:172-211), 16-byte rows segments: one vector copy each where both
 // buffers start 16-byte aligned, sixteen byte copies otherwise (offset views of a caller's allocation).
 template <bool TO_VOLUME, bool ALIGNED>
@@ -1086,6 +1235,72 @@ int composite_finish_tf_launch(const float *partial, const vr_transfer_function 
     hipLaunchKernelGGL(k_composite_finish_tf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)partial,
                        background_of(tf), (float4 *)rgba, n);
     return launch_status("composite_finish_tf");
+}
+
+static ProjArgs proj_args(const vr_projection *pj)
+{
+    ProjArgs A;
+    A.lut = (const float4 *)pj->lut_dev;
+    A.op = pj->op;
+    A.lo = pj->window_lo; A.hi = pj->window_hi;
+    for (int k = 0; k < 3; ++k) A.bg[k] = pj->background[k];
+    return A;
+}
+
+template <class SAMPLER, int OP>
+static void proj_launch_op(const RayArgs &a, const SAMPLER &tex, const ProjArgs &A, bool partial, hipStream_t st)
+{
+    const dim3 grid((a.P.width + 7) / 8, (a.P.height + 7) / 8);
+    auto kern = partial ? k_raycast_proj<SAMPLER, OP, true> : k_raycast_proj<SAMPLER, OP, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a, tex, A);
+}
+template <class SAMPLER>
+static int proj_launch(const RayArgs &a, const SAMPLER &tex, const vr_projection *pj, bool partial, const char *label, hipStream_t st)
+{
+    const ProjArgs A = proj_args(pj);
+    if (pj->op == VR_PROJECT_MAX) proj_launch_op<SAMPLER, VR_PROJECT_MAX>(a, tex, A, partial, st);
+    else if (pj->op == VR_PROJECT_MIN) proj_launch_op<SAMPLER, VR_PROJECT_MIN>(a, tex, A, partial, st);
+    else proj_launch_op<SAMPLER, VR_PROJECT_MEAN>(a, tex, A, partial, st);
+    return launch_status(label);
+}
+
+int raycast_proj_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                        const vr_projection *pj, bool partial, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    dense_args(a, vol, dims, P);
+    ray_frame(a, cam, P, rgba);
+    return proj_launch(a, DenseSampler(), pj, partial, "raymarch_proj", st);
+}
+
+int raycast_pool_proj_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                             const vr_camera *cam, const vr_render_params *P, const vr_projection *pj, bool partial, float *rgba,
+                             hipStream_t st)
+{
+    RayArgs a;
+    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
+    ray_frame(a, cam, P, rgba);
+    return proj_launch(a, pt, pj, partial, "raymarch_pool_proj", st);
+}
+
+int composite_combine_proj_launch(float *front, const float *back, int64_t n, int op, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_composite_combine_proj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float4 *)front,
+                       (const float4 *)back, n, op);
+    return launch_status("composite_combine_proj");
+}
+int composite_finish_proj_launch(const float *partial, const vr_projection *pj, float *rgba, int64_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_composite_finish_proj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)partial,
+                       proj_args(pj), (float4 *)rgba, n);
+    return launch_status("composite_finish_proj");
+}
+int composite_slabs_proj_launch(const float *partials, int nslabs, int64_t npix, const vr_projection *pj, float *rgba,
+                                hipStream_t st)
+{
+    hipLaunchKernelGGL(k_composite_slabs_proj, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, (const float4 *)partials,
+                       nslabs, npix, proj_args(pj), (float4 *)rgba);
+    return launch_status("composite_slabs_proj");
 }
 
 int composite_over_launch(float *front, const float *back, int64_t n, hipStream_t st)

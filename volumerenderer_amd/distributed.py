@@ -69,9 +69,21 @@ def _gpu_combine_tf(parts, first_pixel, axis, cam, params, tf):
     return out
 
 
+def _gpu_combine_proj(parts, proj):
+    from . import _lib
+    from .codec import _stream_ptr
+    from ._lib import check
+    out = torch.empty((parts.shape[1], 4), dtype=torch.float32, device=parts.device)
+    desc = proj.desc()
+    check(_lib.lib().vr_composite_slabs_proj(C.c_void_p(parts.data_ptr()), parts.shape[0], parts.shape[1], C.byref(desc),
+                                             C.c_void_p(out.data_ptr()), _stream_ptr()), "vr_composite_slabs_proj")
+    return out
+
+
 def slab_params(params, dims, axis, rank, world, halo):
     """Rank `rank`'s slab when a volume of `dims` = (X, Y, Z) voxels is cut into `world` slabs along `axis`, stored with
-    `halo` voxel layers beyond each cut (1 for the grey and the unlit marches, 2 for the lit one; vrhip.h).  Returns
+    `halo` voxel layers beyond each cut (1 for the grey and the unlit marches and the projections, 2 for the lit one;
+    vrhip.h).  Returns
     (P, local_dims, (a0, a1)): P = a copy of `params` with box_min / box_max (the last rank's box_max is 2.0: it owns
     the far face), vol_origin and global_dims set, local_dims the extents of the voxels [a0, a1) along `axis` that the
     rank has to hold."""
@@ -154,8 +166,25 @@ def composite_sort_last_tf(partial, cam, params, tf, axis=2, group=None, combine
     return _sort_last(partial, cam, params, tf, axis, group, combine, out)
 
 
-def _sort_last(partial, cam, params, tf, axis, group, combine, out):
-    """The exchange of both calls; tf = None: grey partials (vr_composite_slabs), else colour (vr_composite_slabs_tf)."""
+def composite_sort_last_proj(partial, proj, group=None, combine=None, out=None):
+    """composite_sort_last for projection partials: partial = this rank's (v, n, 0, 0) image [H][W][4] float32 from
+    raycast_projection_partial (slab_params with halo=1), proj the Projection that finishes the frame.  The same
+    exchange, without camera, axis or params: the combine has no view order.  Device tensors take
+    vr_compositor_composite_proj; an injected `combine(parts, proj)` (parts: [world][pixels][4]) runs over
+    torch.distributed point-to-point operations.  MAX and MIN frames equal the single-GPU frame bit for bit."""
+    from .render import _check_projection
+    _check_projection(proj, partial.device)        # a table goes to C as a raw pointer: it must live where the partial does
+    return _sort_last(partial, None, None, None, 0, group, combine, out, proj)
+
+
+def _sort_last(partial, cam, params, tf, axis, group, combine, out, proj=None):
+    """The exchange of the three calls; proj: projection partials (vr_composite_slabs_proj, no view order); else
+    tf = None: grey partials (vr_composite_slabs), else colour (vr_composite_slabs_tf)."""
+    if proj is not None:
+        inner = combine if combine is not None else _gpu_combine_proj
+        tile_combine = lambda parts, first_pixel, axis, cam, params: inner(parts, proj)     # noqa: E731
+    else:
+        tile_combine = combine
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     if combine is None and partial.is_cuda:
@@ -174,7 +203,11 @@ def _sort_last(partial, cam, params, tf, axis, group, combine, out):
         if rank == 0:
             frame = out if out is not None else torch.empty((H, W, 4), dtype=torch.float32, device=partial.device)
         dst = C.c_void_p(frame.data_ptr()) if rank == 0 else None
-        if tf is None:
+        if proj is not None:
+            desc = proj.desc()
+            check(_lib.lib().vr_compositor_composite_proj(h, C.c_void_p(partial.data_ptr()), C.byref(desc), dst,
+                                                          _stream_ptr()), "vr_compositor_composite_proj")
+        elif tf is None:
             check(_lib.lib().vr_compositor_composite(h, C.c_void_p(partial.data_ptr()), int(axis), C.byref(cam),
                                                      C.byref(params), dst, _stream_ptr()), "vr_compositor_composite")
         else:
@@ -184,6 +217,7 @@ def _sort_last(partial, cam, params, tf, axis, group, combine, out):
                   "vr_compositor_composite_tf")
         return frame
     H, W = partial.shape[0], partial.shape[1]
+    combine = tile_combine
     if combine is None:
         combine = _gpu_combine if tf is None else (lambda *a: _gpu_combine_tf(*a, tf))
     rows = tile_rows(H, world)

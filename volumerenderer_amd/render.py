@@ -511,6 +511,139 @@ def composite_finish_tf(partial, tf, out=None, stream=None):
     return out
 
 
+# ---- intensity projections (vr_raycast_projection and the combine calls; the rule is in vrhip.h) ----------------------
+_PROJECT_OPS = {"max": _lib.PROJECT_MAX, "min": _lib.PROJECT_MIN, "mean": _lib.PROJECT_MEAN}
+
+
+class Projection:
+    """An intensity projection for raycast_projection & co. (vr_projection): `op` "max" (MIP), "min" (MinIP) or "mean"
+    (or PROJECT_MAX / PROJECT_MIN / PROJECT_MEAN); `window` = (lo, hi), the displayed value is clamp((m - lo) / (hi - lo),
+    0, 1); `background` the colour of pixels whose ray owns no sample; `lut` None for a grey frame, else a (256, 4)
+    colour map of (r, g, b, a) in [0, 1] looked up with the displayed value.  Raises ValueError on bad values."""
+
+    def __init__(self, op="max", window=(0.0, 1.0), background=(0.0, 0.0, 0.0), lut=None, device="cuda"):
+        if isinstance(op, str):
+            if op not in _PROJECT_OPS:
+                raise ValueError("op must be 'max', 'min' or 'mean', not %r" % op)
+            self.op = _PROJECT_OPS[op]
+        elif isinstance(op, int) and not isinstance(op, bool) and op in _PROJECT_OPS.values():
+            self.op = op
+        else:
+            raise ValueError("op must be 'max', 'min' or 'mean', not %r" % (op,))
+        try:
+            self.window = tuple(float(v) for v in window)
+        except TypeError:
+            raise ValueError("window must be (lo, hi), not %r" % (window,))
+        if len(self.window) != 2 or not all(math.isfinite(v) for v in self.window) or not self.window[1] > self.window[0]:
+            raise ValueError("window must be finite with hi > lo, not %r" % (window,))
+        # the C ABI holds the window as float32: hi > lo must survive the rounding
+        if not np.float32(self.window[1]) > np.float32(self.window[0]) or not np.isfinite(np.float32(self.window[1]) - np.float32(self.window[0])):
+            raise ValueError("window must be finite with hi > lo in float32, not %r" % (window,))
+        self.background = tuple(float(v) for v in background)
+        if len(self.background) != 3 or not all(math.isfinite(v) for v in self.background):
+            raise ValueError("background must be three finite values")
+        self.lut = None
+        if lut is not None:
+            if isinstance(lut, torch.Tensor):
+                device = lut.device if lut.is_cuda else device
+                host = lut.detach().to("cpu", torch.float32).numpy()
+            else:
+                host = np.asarray(lut, np.float32)
+            if host.shape != (256, 4):
+                raise ValueError("lut must be 256 x (r, g, b, a), not %s" % (tuple(host.shape),))
+            if not np.all(np.isfinite(host)) or host.min() < 0.0 or host.max() > 1.0:
+                raise ValueError("lut values must lie in [0, 1]")
+            self.lut = torch.from_numpy(np.ascontiguousarray(host)).to(device)
+
+    def desc(self):
+        d = _lib.Projection()
+        d.lut_dev = self.lut.data_ptr() if self.lut is not None else None
+        d.op = self.op
+        d.window_lo, d.window_hi = self.window
+        d.background[:] = self.background
+        return d
+
+
+def _check_projection(proj, device):
+    if not isinstance(proj, Projection):
+        raise ValueError("proj must be a Projection, not %s" % type(proj).__name__)
+    if proj.lut is not None:
+        _check_buf(proj.lut, "proj.lut", torch.float32, 256 * 4, device)
+
+
+def _projection_dense(fn, volume, dims, cam, params, proj, out, stream):
+    v, d = _dense_source(volume, dims)
+    _check_attached_grid(params, dims, v.device)
+    _check_projection(proj, v.device)
+    out = _frame_out(out, params, v.device)
+    desc = proj.desc()
+    check(getattr(_lib.lib(), fn)(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
+                                  C.c_void_p(out.data_ptr()), _stream_ptr(stream)), fn)
+    return out
+
+
+def _projection_pool(fn, pool, table, brick_dims, grid, cam, params, proj, out, stream):
+    bd, g = _pool_source(pool, table, brick_dims, grid)
+    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
+    _check_projection(proj, pool.device)
+    out = _frame_out(out, params, pool.device)
+    desc = proj.desc()
+    check(getattr(_lib.lib(), fn)(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
+                                  C.byref(params), C.byref(desc), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), fn)
+    return out
+
+
+def raycast_projection(volume, dims, cam, params, proj, out=None, stream=None):
+    """The intensity projection `proj` of a dense volume (vr_raycast_projection): raycast's rays, no early exit; the
+    maximum, minimum or mean of every ray's samples in params' box, windowed, grey or through proj.lut.  params.mode must
+    be RENDER_PROJECTION.  Returns float32 CUDA [H][W][4], row 0 = top; (background, 0) where the ray owns no sample."""
+    return _projection_dense("vr_raycast_projection", volume, dims, cam, params, proj, out, stream)
+
+
+def raycast_pool_projection(pool, table, brick_dims, grid, cam, params, proj, out=None, stream=None):
+    """raycast_projection of the virtual volume of a pool (vr_raycast_pool_projection): bit-identical to
+    raycast_projection of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
+    return _projection_pool("vr_raycast_pool_projection", pool, table, brick_dims, grid, cam, params, proj, out, stream)
+
+
+def raycast_projection_partial(volume, dims, cam, params, proj, out=None, stream=None):
+    """The projection partial of raycast_projection for sort-last compositing (vr_raycast_projection_partial): float32
+    CUDA [H][W][4] = (v, n, 0, 0), n the owned samples and v their maximum, minimum or sum; zeros where n = 0."""
+    return _projection_dense("vr_raycast_projection_partial", volume, dims, cam, params, proj, out, stream)
+
+
+def raycast_pool_projection_partial(pool, table, brick_dims, grid, cam, params, proj, out=None, stream=None):
+    """raycast_projection_partial of the virtual volume of a pool (vr_raycast_pool_projection_partial)."""
+    return _projection_pool("vr_raycast_pool_projection_partial", pool, table, brick_dims, grid, cam, params, proj, out,
+                            stream)
+
+
+def composite_combine_proj(front, back, proj, stream=None):
+    """front = combine(front, back) on projection partials, in place: n adds, v is the max, the min or the sum by
+    proj.op; a partial with n = 0 is ignored.  Both contiguous float32 (v, n, 0, 0) images of the same size."""
+    _check_partial(front, "front")
+    _check_buf(back, "back", torch.float32, front.numel(), front.device)
+    if not isinstance(proj, Projection):
+        raise ValueError("proj must be a Projection, not %s" % type(proj).__name__)
+    check(_lib.lib().vr_composite_combine_proj(C.c_void_p(front.data_ptr()), C.c_void_p(back.data_ptr()), front.numel() // 4,
+                                               proj.op, _stream_ptr(stream)), "vr_composite_combine_proj")
+    return front
+
+
+def composite_finish_proj(partial, proj, out=None, stream=None):
+    """The frame of a projection partial (vr_composite_finish_proj): the window, then grey or proj.lut."""
+    _check_partial(partial, "partial")
+    _check_projection(proj, partial.device)
+    if out is None:
+        out = torch.empty_like(partial)
+    else:
+        _check_buf(out, "out", torch.float32, partial.numel(), partial.device)
+    desc = proj.desc()
+    check(_lib.lib().vr_composite_finish_proj(C.c_void_p(partial.data_ptr()), C.byref(desc), C.c_void_p(out.data_ptr()),
+                                              partial.numel() // 4, _stream_ptr(stream)), "vr_composite_finish_proj")
+    return out
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}

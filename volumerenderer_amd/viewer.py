@@ -8,8 +8,8 @@ import numpy as np
 
 from . import _lib
 from .render import (POOL_ENTRY, assemble_bricks, build_skip_grid_pool, default_camera, default_params, lod_pool_layout,
-                     raycast, raycast_pool, raycast_pool_tf, raycast_pool_tf_shaded, raycast_tf, raycast_tf_shaded, select_lod,
-                     use_skip_grid)
+                     raycast, raycast_pool, raycast_pool_projection, raycast_pool_tf, raycast_pool_tf_shaded, raycast_projection,
+                     raycast_tf, raycast_tf_shaded, select_lod, use_skip_grid)
 
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
@@ -79,9 +79,18 @@ class HeadlessViewer:
         cam.fov_deg = float(self.fov)
         return cam
 
-    def draw(self, volume, dims, brick_dims=(256, 256, 128), mode=_lib.RENDER_COMPOSITE, out=None, tf=None, shading=None):
+    def draw(self, volume, dims, brick_dims=(256, 256, 128), mode=_lib.RENDER_COMPOSITE, out=None, tf=None, shading=None,
+             projection=None):
         """One frame of `volume`: raycast, or raycast_tf through the TransferFunction `tf` (composite mode only).
-        shading: a Shading (requires tf): the frame is drawn with raycast_tf_shaded in RENDER_SHADED mode."""
+        shading: a Shading (requires tf): the frame is drawn with raycast_tf_shaded in RENDER_SHADED mode.
+        projection: a Projection (neither tf nor shading): drawn with raycast_projection in RENDER_PROJECTION mode."""
+        if projection is not None:
+            if tf is not None or shading is not None:
+                raise ValueError("a projection takes neither a transfer function nor shading")
+            if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_PROJECTION):
+                raise ValueError("a projection is drawn in RENDER_PROJECTION mode, not mode %r" % (mode,))
+            P = default_params(self.width, self.height, brick_dims, _lib.RENDER_PROJECTION, float(self.currIsoVal) / 255.0)
+            return raycast_projection(volume, dims, self.camera(), P, projection, out)
         if shading is not None:
             if tf is None:
                 raise ValueError("shading requires a transfer function (tf=)")
@@ -115,13 +124,20 @@ class HeadlessViewer:
         return raycast(vol, dims, cam, P, out), cuts
 
     def draw_lod_pool(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, skip_cell=0, out=None,
-                      tf=None, shading=None):
+                      tf=None, shading=None, projection=None):
         """draw_lod's frame (bit for bit) from a pool: select_lod, decode_lod_pool, raycast_pool -- no brick buffer and no
         assembled volume; each brick is stored at the resolution of its cut.  The pool is kept across frames and grows
         only when a frame needs more.  skip_cell > 0: a skip grid of that cell size is built from the pool for the frame.
         Power-of-two brick extents only.  tf: a TransferFunction, drawn with raycast_pool_tf; shading (requires tf): a
-        Shading, drawn with raycast_pool_tf_shaded in RENDER_SHADED mode (select_lod included).  Returns (frame, cuts)."""
+        Shading, drawn with raycast_pool_tf_shaded in RENDER_SHADED mode (select_lod included); projection (neither tf nor
+        shading): a Projection, drawn with raycast_pool_projection in RENDER_PROJECTION mode.  Returns (frame, cuts)."""
         import torch
+        if projection is not None:
+            if tf is not None or shading is not None:
+                raise ValueError("a projection takes neither a transfer function nor shading")
+            if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_PROJECTION):
+                raise ValueError("a projection is drawn in RENDER_PROJECTION mode, not mode %r" % (mode,))
+            mode = _lib.RENDER_PROJECTION
         if shading is not None:
             if tf is None:
                 raise ValueError("shading requires a transfer function (tf=)")
@@ -143,6 +159,8 @@ class HeadlessViewer:
         if skip_cell > 0:
             sg = build_skip_grid_pool(self._pool, self._poolTable, bd, g, skip_cell)
             use_skip_grid(P, sg, skip_cell)
+        if projection is not None:
+            return raycast_pool_projection(self._pool, self._poolTable, bd, g, cam, P, projection, out), cuts
         if shading is not None:
             return raycast_pool_tf_shaded(self._pool, self._poolTable, bd, g, cam, P, tf, shading, out), cuts
         if tf is not None:
