@@ -541,6 +541,49 @@ vr_status vr_composite_finish_proj(const float *partial_dev, const vr_projection
 vr_status vr_composite_slabs_proj(const float *partials_dev, int32_t num_slabs, int64_t num_pixels, const vr_projection *proj,
                                   float *rgba_dev, void *stream);
 
+/* ---- slice views (new): oblique planes and thick slabs of a dense volume, exact across GPUs ------------------------------
+ * A slice is a parallelepiped of samples, width x height pixels by `layers` layers, in texture space; it produces a
+ * projection partial and finishes through the projection's finish.  layers == 1 is a thin slice, more layers are a thick
+ * slab reduced by proj->op.  No camera, no render params and no render mode are involved.
+ * Sample (px, py, l) sits at
+ *   pos_k = ((origin_k + (float)px * du_k) + (float)py * dv_k) + (float)l * dw_k        (k = x, y, z)
+ * with every product and sum rounded to float32, in that order.  A position is never accumulated by repeated addition:
+ * a sample depends neither on its neighbours nor on the launch shape.
+ * A sample is TAKEN iff vr_raycast's inside(pos) holds (strictly inside the unit cube) and pos lies in
+ * [box_min, box_max) on every axis.  Its value:
+ *   VR_SLICE_LINEAR   vr_raycast's trilinear fetch at pos, bit for bit;
+ *   VR_SLICE_NEAREST  (float)voxel * (1.0f / 255.0f) of voxel clamp((int)floorf(pos_k * (float)G_k), 0, G_k - 1) of the
+ *                     global volume (G = global_dims, or dims), located in the local volume as the fetch locates its taps
+ *                     (minus vol_origin, clamped to the local extents).
+ * Per pixel, n is the number of taken samples and v their maximum (a running maximum from 0), their minimum (from +inf) or
+ * their float32 sum in ascending l.  The partial is (v, (float)n, 0, 0), or (0, 0, 0, 0) where n == 0; the frame is the
+ * projection FINISH of that partial (the same function, not a copy), so vr_composite_finish_proj(partial) equals the
+ * frame bit for bit, and the partials of slabs combine through vr_composite_combine_proj / _slabs_proj /
+ * vr_compositor_composite_proj unchanged: MAX and MIN at any layer count, and every op at layers == 1 (one sample per
+ * pixel has one owner), equal the single-GPU partial and frame bit for bit; MEAN of a thick slab has an exact n and a v
+ * within two summation orders.  A rank's slab holds ONE halo layer, for both filters (NEAREST reads the voxel a position
+ * falls into, which lies in the owner's slab; the halo only matters to LINEAR's second tap, but the layout is one).
+ * There is no skip grid: at most `layers` fetches per pixel.  Row 0 of the frame is the row of `origin`. */
+enum { VR_SLICE_NEAREST = 0, VR_SLICE_LINEAR = 1 };
+
+typedef struct vr_slice_plane {
+    int32_t width, height;      /* > 0 */
+    int32_t layers;             /* 1 .. 2^24 (n stays exact in a float) */
+    int32_t filter;             /* VR_SLICE_* */
+    float origin[3];            /* texture-space centre of pixel (0,0), layer 0; row 0 = top */
+    float du[3], dv[3], dw[3];  /* texture-space step per column, per row, per layer */
+    float box_min[3], box_max[3];          /* ownership box, {0,0,0}-{1,1,1} on one GPU */
+    int64_t global_dims[3], vol_origin[3]; /* as vr_render_params: 0 / 0 on one GPU */
+} vr_slice_plane;               /* 136 bytes */
+
+/* VR_ERR_INVALID (nothing launched) for a null pointer; width, height < 1; layers outside 1 .. 2^24; a filter that is
+ * neither value; a non-finite origin, du, dv, dw or box; dims as vr_raycast refuses them; a proj that
+ * vr_raycast_projection would refuse.  Then VR_ERR_NO_DEVICE: there is no CPU fallback.  volume_dev may start at any
+ * byte.  The _partial call writes the partial instead of the frame: of proj it uses the op. */
+vr_status vr_reslice(const uint8_t *volume_dev, const int64_t dims[3], const vr_slice_plane *plane, const vr_projection *proj,
+                     float *rgba_dev, void *stream);
+vr_status vr_reslice_partial(const uint8_t *volume_dev, const int64_t dims[3], const vr_slice_plane *plane,
+                             const vr_projection *proj, float *partial_dev, void *stream);
 /* Sort-last compositing of VR_RENDER_PARTIAL images: front = front OVER back, per pixel
  * (c1 + t1*c2, t1*t2); and the final colour transfer of raycaster.frag:82-85. */
 vr_status vr_composite_over(float *front_dev, const float *back_dev, int64_t num_pixels, void *stream);
@@ -650,7 +693,8 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
  * once, when the set is created, and changed afterwards only through this call -- never by the environment at launch
  * time.  Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks"; any other name is VR_ERR_INVALID.
  * Results never depend on a switch; the tests use them to check the kernels against each other.
- * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1". */
+ * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1"; "reslice_tile_w" = 8, 16 or 64, the width of
+ * the 64-pixel tile a wave of vr_reslice covers (16 is the default, chosen by measurement: DESIGN.md 3.5g). */
 vr_status vr_brickset_set_switch(vr_brickset *bs, const char *name, int32_t value);
 vr_status vr_debug_set(const char *name, int32_t value);
 

@@ -128,6 +128,13 @@ public:
         const vr_camera c = camera();
         return vr_raycast_pool_tf_shaded(pool_dev, table_dev, brick_dims, grid, &c, &P, tf, shading, rgba_dev, stream);
     }
+    // a slice view (vr_reslice): the plane brings its own geometry and frame size, rgba_dev holds
+    // plane.width * plane.height float4; the camera plays no part
+    vr_status drawSlice(const uint8_t *vol, const int64_t dims[3], const vr_slice_plane &plane, const vr_projection &proj,
+                        float *rgba_dev, void *stream = nullptr) const
+    {
+        return vr_reslice(vol, dims, &plane, &proj, rgba_dev, stream);
+    }
     // binary PPM of a host float RGBA frame (what glReadPixels of the 8-bit framebuffer would hold)
     static bool dumpPPM(const std::string &path, const std::vector<float> &rgba, int w, int h)
     {

@@ -21,7 +21,7 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
                 "raycast_pool_tf_shaded", "raycast_tf_partial", "raycast_pool_tf_partial", "composite_over_tf",
                 "composite_finish_tf", "Projection", "raycast_projection", "raycast_pool_projection",
                 "raycast_projection_partial", "raycast_pool_projection_partial", "composite_combine_proj",
-                "composite_finish_proj"):
+                "composite_finish_proj", "SlicePlane", "reslice", "reslice_partial"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

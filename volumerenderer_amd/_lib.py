@@ -14,6 +14,7 @@ STATUS = {0: "VR_OK", -1: "VR_ERR_INVALID", -2: "VR_ERR_NO_DEVICE", -3: "VR_ERR_
 VARIANT_RECOVER, VARIANT_GUARDED, VARIANT_MIDRANGE = 0, 1, 2
 RENDER_COMPOSITE, RENDER_ISOSURFACE, RENDER_PARTIAL, RENDER_SHADED, RENDER_PROJECTION = 0, 1, 2, 3, 4
 PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN = 0, 1, 2
+SLICE_NEAREST, SLICE_LINEAR = 0, 1
 
 
 class VrError(RuntimeError):
@@ -59,6 +60,14 @@ class Projection(C.Structure):
     """vr_projection (32 bytes)."""
     _fields_ = [("lut_dev", C.c_void_p), ("op", C.c_int32), ("window_lo", C.c_float), ("window_hi", C.c_float),
                 ("background", C.c_float * 3)]
+
+
+class SlicePlaneDesc(C.Structure):
+    """vr_slice_plane (136 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("layers", C.c_int32), ("filter", C.c_int32),
+                ("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dw", C.c_float * 3),
+                ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("global_dims", C.c_int64 * 3), ("vol_origin", C.c_int64 * 3)]
 
 
 class PoolEntry(C.Structure):
@@ -134,6 +143,8 @@ SIGNATURES = {
     "vr_composite_combine_proj": (_I32, [_P, _P, _I64, _I32, _P]),
     "vr_composite_finish_proj": (_I32, [_P, C.POINTER(Projection), _P, _I64, _P]),
     "vr_composite_slabs_proj": (_I32, [_P, _I32, _I64, C.POINTER(Projection), _P, _P]),
+    "vr_reslice": (_I32, [_P, C.POINTER(_I64), C.POINTER(SlicePlaneDesc), C.POINTER(Projection), _P, _P]),
+    "vr_reslice_partial": (_I32, [_P, C.POINTER(_I64), C.POINTER(SlicePlaneDesc), C.POINTER(Projection), _P, _P]),
     "vr_composite_over": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_finish": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_slabs": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),

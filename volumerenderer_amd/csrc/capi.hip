@@ -42,7 +42,10 @@ int raycast_pool_proj_launch(const uint8_t *, const vr_pool_entry *, const int64
 int composite_combine_proj_launch(float *, const float *, int64_t, int, hipStream_t);
 int composite_finish_proj_launch(const float *, const vr_projection *, float *, int64_t, hipStream_t);
 int composite_slabs_proj_launch(const float *, int, int64_t, const vr_projection *, float *, hipStream_t);
+int reslice_launch(const uint8_t *, const int64_t dims[3], const vr_slice_plane *, const vr_projection *, bool partial, float *,
+                   hipStream_t);
 extern std::atomic<int> g_skipGridV1;
+extern std::atomic<int> g_resliceTileLog2;
 }
 
 struct vr_brickset { BrickSet s; };
@@ -350,6 +353,11 @@ vr_status vr_debug_set(const char *name, int32_t value)
 {
     if (!name) return VR_ERR_INVALID;
     if (!strcmp(name, "skip_grid_v1")) { vr::g_skipGridV1.store(value ? 1 : 0); return VR_OK; }
+    if (!strcmp(name, "reslice_tile_w")) {      // k_reslice's wave footprint: 8 x 8, 16 x 4 or 64 x 1 pixels
+        if (value != 8 && value != 16 && value != 64) return VR_ERR_INVALID;
+        vr::g_resliceTileLog2.store(value == 8 ? 3 : (value == 16 ? 4 : 6));
+        return VR_OK;
+    }
     return VR_ERR_INVALID;
 }
 
@@ -1328,6 +1336,40 @@ vr_status vr_composite_slabs_proj(const float *partials, int32_t num_slabs, int6
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return composite_slabs_proj_launch(partials, num_slabs, num_pixels, pj, rgba, (hipStream_t)stream) == 0 ? VR_OK
                                                                                                             : VR_ERR_NO_DEVICE;
+}
+
+// ---- slice views (vrhip.h): the entry points
+
+// a vr_slice_plane (vrhip.h): the sizes, the filter and finite geometry
+static bool plane_ok(const vr_slice_plane *pl)
+{
+    if (!pl || pl->width <= 0 || pl->height <= 0 || pl->layers < 1 || pl->layers > (1 << 24)) return false;
+    if (pl->filter != VR_SLICE_NEAREST && pl->filter != VR_SLICE_LINEAR) return false;
+    for (int k = 0; k < 3; ++k)
+        if (!isfinite(pl->origin[k]) || !isfinite(pl->du[k]) || !isfinite(pl->dv[k]) || !isfinite(pl->dw[k]) ||
+            !isfinite(pl->box_min[k]) || !isfinite(pl->box_max[k]))
+            return false;
+    return true;
+}
+
+static vr_status slice_dense(const uint8_t *vol, const int64_t dims[3], const vr_slice_plane *pl, const vr_projection *pj,
+                             float *out, void *stream, bool partial)
+{
+    if (!out || !dense_ok(vol, dims) || !plane_ok(pl) || !projection_ok(pj)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return reslice_launch(vol, dims, pl, pj, partial, out, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_reslice(const uint8_t *vol, const int64_t dims[3], const vr_slice_plane *pl, const vr_projection *pj, float *rgba,
+                     void *stream)
+{
+    return slice_dense(vol, dims, pl, pj, rgba, stream, false);
+}
+
+vr_status vr_reslice_partial(const uint8_t *vol, const int64_t dims[3], const vr_slice_plane *pl, const vr_projection *pj,
+                             float *partial, void *stream)
+{
+    return slice_dense(vol, dims, pl, pj, partial, stream, true);
 }
 
 vr_status vr_brickset_set_concurrency(vr_brickset *h, int32_t level_loop_streams)

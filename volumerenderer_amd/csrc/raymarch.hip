@@ -940,6 +940,62 @@ k_composite_slabs_proj(const float4 *partials, int num_slabs, int64_t npix, Proj
     rgba[i] = finish_proj(acc, A);
 }
 
+// ---- slice views (vr_reslice; the rule is in vrhip.h) ------------------------------------------------------------------
+// a pixel at any float address: four floats stored as one 16-byte word (gfx950 takes unaligned global stores)
+struct __attribute__((aligned(4))) Pixel4 { float x, y, z, w; };
+
+#define RESLICE_TILE_LOG2 4    // the wave's tile is 16 x 4 pixels (measured: DESIGN.md 3.5g)
+struct SliceArgs {
+    Tex t;                  // the dense volume
+    int W, H, layers;
+    int ltw;                // log2 of the wave's tile width: lane l is pixel (l & (tw - 1), l >> ltw) of a tw x 64 / tw tile
+    float o[3], du[3], dv[3], dw[3], bmin[3], bmax[3];
+    float *out;
+};
+
+// the voxel a position falls into, as a float: global index clamped, then located like a tap of tex3d
+__device__ __forceinline__ float nearest3d(const DenseSampler &, const Tex &t, float px, float py, float pz)
+{
+    const int gx = clampi((int)floorf(px * (float)t.GX), 0, t.GX - 1), gy = clampi((int)floorf(py * (float)t.GY), 0, t.GY - 1),
+              gz = clampi((int)floorf(pz * (float)t.GZ), 0, t.GZ - 1);
+    const int x = clampi(gx - t.ox, 0, t.X - 1), y = clampi(gy - t.oy, 0, t.Y - 1), z = clampi(gz - t.oz, 0, t.Z - 1);
+    return (float)t.v[x + (int64_t)t.X * (y + (int64_t)t.Y * z)] * (1.0f / 255.0f);
+}
+__device__ __forceinline__ float linear3d(const DenseSampler &, const Tex &t, float x, float y, float z) { return tex3d(t, x, y, z); }
+
+// One thread per pixel, the layers looped inside the thread; every position is formed from the pixel and layer indices
+// alone.  The wave's footprint is a launch parameter (slice_launch picks it; DESIGN.md 3.5g has the measurements).
+template <class SAMPLER, int OP, int FILTER, bool PARTIAL>
+__global__ void __launch_bounds__(64)
+k_reslice(SliceArgs a, SAMPLER tex, ProjArgs A)
+{
+    const int lane = threadIdx.x;
+    const int px = (int)(blockIdx.x << a.ltw) + (lane & ((1 << a.ltw) - 1)), py = (int)(blockIdx.y << (6 - a.ltw)) + (lane >> a.ltw);
+    if (px >= a.W || py >= a.H) return;
+    float base[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) base[k] = (a.o[k] + (float)px * a.du[k]) + (float)py * a.dv[k];
+    float cur = OP == VR_PROJECT_MIN ? INFINITY : 0.0f;
+    int n = 0;
+    for (int l = 0; l < a.layers; ++l) {
+        float pos[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pos[k] = base[k] + (float)l * a.dw[k];
+        if (!inside(pos[0], pos[1], pos[2])) continue;
+        bool own = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.bmin[k] && pos[k] < a.bmax[k]);
+        if (!own) continue;
+        ++n;
+        const float smp = FILTER == VR_SLICE_LINEAR ? linear3d(tex, a.t, pos[0], pos[1], pos[2])
+                                                    : nearest3d(tex, a.t, pos[0], pos[1], pos[2]);
+        cur = OP == VR_PROJECT_MEAN ? cur + smp : (OP == VR_PROJECT_MAX ? fmaxf(cur, smp) : fminf(cur, smp));
+    }
+    const float4 part = n > 0 ? make_float4(cur, (float)n, 0.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 r = PARTIAL ? part : finish_proj(part, A);
+    *(Pixel4 *)(a.out + 4 * ((size_t)py * a.W + px)) = Pixel4{r.x, r.y, r.z, r.w};
+}
+
 // Brick <-> global volume placement (VolumeReader.h:172-211), 16-byte rows segments: one vector copy each where both
 // buffers start 16-byte aligned, sixteen byte copies otherwise (offset views of a caller's allocation).
 template <bool TO_VOLUME, bool ALIGNED>
@@ -1301,6 +1357,66 @@ int composite_slabs_proj_launch(const float *partials, int nslabs, int64_t npix,
     hipLaunchKernelGGL(k_composite_slabs_proj, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, (const float4 *)partials,
                        nslabs, npix, proj_args(pj), (float4 *)rgba);
     return launch_status("composite_slabs_proj");
+}
+
+// process-wide debugging switch (vr_debug_set("reslice_tile_w", 8 | 16 | 64)): the width of the wave's pixel tile in
+// k_reslice, for profiles/tools/slice_bench.py; results do not depend on it
+std::atomic<int> g_resliceTileLog2{RESLICE_TILE_LOG2};
+
+static void slice_args(SliceArgs &a, const vr_slice_plane *pl, float *out)
+{
+    a.W = pl->width; a.H = pl->height; a.layers = pl->layers;
+    a.ltw = g_resliceTileLog2.load(std::memory_order_relaxed);
+    for (int k = 0; k < 3; ++k) {
+        a.o[k] = pl->origin[k]; a.du[k] = pl->du[k]; a.dv[k] = pl->dv[k]; a.dw[k] = pl->dw[k];
+        a.bmin[k] = pl->box_min[k]; a.bmax[k] = pl->box_max[k];
+    }
+    a.out = out;
+}
+
+template <class SAMPLER, int OP, int FILTER>
+static void slice_launch_of(const SliceArgs &a, const SAMPLER &tex, const ProjArgs &A, bool partial, hipStream_t st)
+{
+    const int tw = 1 << a.ltw, th = 64 >> a.ltw;
+    const dim3 grid((a.W + tw - 1) / tw, (a.H + th - 1) / th);
+    auto kern = partial ? k_reslice<SAMPLER, OP, FILTER, true> : k_reslice<SAMPLER, OP, FILTER, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a, tex, A);
+}
+template <class SAMPLER, int OP>
+static void slice_launch_op(const SliceArgs &a, const SAMPLER &tex, const ProjArgs &A, int filter, bool partial, hipStream_t st)
+{
+    if (filter == VR_SLICE_LINEAR) slice_launch_of<SAMPLER, OP, VR_SLICE_LINEAR>(a, tex, A, partial, st);
+    else slice_launch_of<SAMPLER, OP, VR_SLICE_NEAREST>(a, tex, A, partial, st);
+}
+template <class SAMPLER>
+static int slice_launch(const SliceArgs &a, const SAMPLER &tex, const vr_slice_plane *pl, const vr_projection *pj, bool partial,
+                        const char *label, hipStream_t st)
+{
+    const ProjArgs A = proj_args(pj);
+    if (pj->op == VR_PROJECT_MAX) slice_launch_op<SAMPLER, VR_PROJECT_MAX>(a, tex, A, pl->filter, partial, st);
+    else if (pj->op == VR_PROJECT_MIN) slice_launch_op<SAMPLER, VR_PROJECT_MIN>(a, tex, A, pl->filter, partial, st);
+    else slice_launch_op<SAMPLER, VR_PROJECT_MEAN>(a, tex, A, pl->filter, partial, st);
+    return launch_status(label);
+}
+
+// the texture of a slice: dense_args lays it out from render params; a plane carries the same two fields
+static vr_render_params plane_params(const vr_slice_plane *pl)
+{
+    vr_render_params P = {};
+    for (int k = 0; k < 3; ++k) { P.global_dims[k] = pl->global_dims[k]; P.vol_origin[k] = pl->vol_origin[k]; }
+    return P;
+}
+
+int reslice_launch(const uint8_t *vol, const int64_t dims[3], const vr_slice_plane *pl, const vr_projection *pj, bool partial,
+                   float *out, hipStream_t st)
+{
+    RayArgs r;
+    const vr_render_params P = plane_params(pl);
+    dense_args(r, vol, dims, &P);
+    SliceArgs a;
+    a.t = r.t;
+    slice_args(a, pl, out);
+    return slice_launch(a, DenseSampler(), pl, pj, partial, "reslice", st);
 }
 
 int composite_over_launch(float *front, const float *back, int64_t n, hipStream_t st)

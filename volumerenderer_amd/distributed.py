@@ -109,6 +109,29 @@ def slab_params(params, dims, axis, rank, world, halo):
     return P, tuple(local), (a0, a1)
 
 
+def slab_plane(plane, dims, axis, rank, world, halo=1):
+    """slab_params' twin for a slice: rank `rank`'s copy of the SlicePlane `plane` when a volume of `dims` voxels is cut
+    into `world` slabs along `axis`, stored with `halo` voxel layers beyond each cut (1, for both filters; vrhip.h).
+    Returns (plane, local_dims, (a0, a1)) with box_min / box_max (the last rank's box_max is 2.0), vol_origin and
+    global_dims set.  The partials of reslice_partial go through composite_sort_last_proj unchanged."""
+    import copy
+    dims = [int(q) for q in dims]
+    if len(dims) != 3 or axis not in (0, 1, 2) or not 0 <= rank < world or halo < 0 or world > dims[axis]:
+        raise ValueError("slab_plane: axis %r, rank %r of %r, halo %r, extents %r" % (axis, rank, world, halo, dims))
+    n = dims[axis]
+    lo, hi = shard_range(n, rank, world)
+    a0, a1 = max(0, lo - halo), min(n, hi + halo)
+    p = copy.copy(plane)
+    bmin, bmax, org = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0, 0, 0]
+    bmin[axis] = lo / n
+    bmax[axis] = hi / n if rank < world - 1 else 2.0
+    org[axis] = a0
+    p.box_min, p.box_max, p.vol_origin, p.global_dims = tuple(bmin), tuple(bmax), tuple(org), tuple(dims)
+    local = list(dims)
+    local[axis] = a1 - a0
+    return p, tuple(local), (a0, a1)
+
+
 _compositors = {}
 
 

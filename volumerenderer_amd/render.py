@@ -644,6 +644,145 @@ def composite_finish_proj(partial, proj, out=None, stream=None):
     return out
 
 
+# ---- slice views (vr_reslice; the rule is in vrhip.h) -------------------------------------------------------------------
+_SLICE_FILTERS = {"nearest": _lib.SLICE_NEAREST, "linear": _lib.SLICE_LINEAR}
+# the image axes (column, row) of an axis-aligned slice: axial (axis 2) shows x across and y down, coronal (1) x and z,
+# sagittal (0) y and z
+_SLICE_IMAGE_AXES = {0: (1, 2), 1: (0, 2), 2: (0, 1)}
+
+
+def _vec3(v, what):
+    try:
+        t = tuple(float(q) for q in v)
+    except TypeError:
+        raise ValueError("%s must be three numbers, not %r" % (what, v))
+    if len(t) != 3 or not all(abs(q) <= 3.4028234663852886e38 for q in t):      # finite as float32, the ABI's type
+        raise ValueError("%s must be three finite values, not %r" % (what, v))
+    return t
+
+
+class SlicePlane:
+    """A slice for reslice & co. (vr_slice_plane): `width` x `height` pixels by `layers` layers of samples at
+    origin + px du + py dv + l dw in texture space ([0, 1]^3 is the volume; row 0 is the row of `origin`).  filter:
+    "linear" (the marcher's trilinear fetch) or "nearest" (or SLICE_LINEAR / SLICE_NEAREST).  box_min, box_max,
+    global_dims and vol_origin are a rank's slab (distributed.slab_plane sets them); the defaults are one GPU's.
+    Raises ValueError on bad values."""
+
+    def __init__(self, width, height, origin, du, dv, dw=(0.0, 0.0, 0.0), layers=1, filter="linear",
+                 box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0), global_dims=(0, 0, 0), vol_origin=(0, 0, 0)):
+        for name, v in (("width", width), ("height", height), ("layers", layers)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError("%s must be a positive integer, not %r" % (name, v))
+        self.width, self.height, self.layers = int(width), int(height), int(layers)
+        if self.layers > 1 << 24 or self.width >= 1 << 31 or self.height >= 1 << 31:
+            raise ValueError("width, height must fit an int32 and layers 2^24, not %r x %r x %r" % (width, height, layers))
+        if isinstance(filter, str):
+            if filter not in _SLICE_FILTERS:
+                raise ValueError("filter must be 'nearest' or 'linear', not %r" % filter)
+            self.filter = _SLICE_FILTERS[filter]
+        elif isinstance(filter, int) and not isinstance(filter, bool) and filter in _SLICE_FILTERS.values():
+            self.filter = filter
+        else:
+            raise ValueError("filter must be 'nearest' or 'linear', not %r" % (filter,))
+        self.origin, self.du, self.dv, self.dw = _vec3(origin, "origin"), _vec3(du, "du"), _vec3(dv, "dv"), _vec3(dw, "dw")
+        self.box_min, self.box_max = _vec3(box_min, "box_min"), _vec3(box_max, "box_max")
+        self.global_dims = tuple(int(q) for q in global_dims)
+        self.vol_origin = tuple(int(q) for q in vol_origin)
+        if len(self.global_dims) != 3 or len(self.vol_origin) != 3 or min(self.global_dims + self.vol_origin) < 0:
+            raise ValueError("global_dims and vol_origin must be three non-negative integers")
+
+    @classmethod
+    def axis_aligned(cls, dims, axis, index, pixels_per_voxel=1, layers=1, filter="linear"):
+        """The slice of a volume of `dims` = (X, Y, Z) voxels through voxel layer `index` along `axis`: axial (axis 2)
+        shows x across and y down, coronal (1) x and z, sagittal (0) y and z.  With pixels_per_voxel = 1 the frame has
+        one pixel per voxel and the pixel centres ARE the voxel centres; otherwise the frame covers the same extent
+        with round(n * pixels_per_voxel) pixels per axis.  layers > 1: a slab of the voxel layers index, index + 1, ..."""
+        dims = [int(q) for q in dims]
+        if len(dims) != 3 or min(dims) < 1 or axis not in (0, 1, 2) or not 0 <= int(index) < dims[axis]:
+            raise ValueError("axis_aligned: axis %r, index %r, extents %r" % (axis, index, dims))
+        if not (float(pixels_per_voxel) > 0.0 and math.isfinite(float(pixels_per_voxel))):
+            raise ValueError("pixels_per_voxel must be positive, not %r" % (pixels_per_voxel,))
+        cu, cv = _SLICE_IMAGE_AXES[axis]
+        W, H = max(1, int(round(dims[cu] * pixels_per_voxel))), max(1, int(round(dims[cv] * pixels_per_voxel)))
+        origin, du, dv, dw = [0.0] * 3, [0.0] * 3, [0.0] * 3, [0.0] * 3
+        du[cu], dv[cv], dw[axis] = 1.0 / W, 1.0 / H, 1.0 / dims[axis]
+        origin[cu], origin[cv], origin[axis] = 0.5 / W, 0.5 / H, (int(index) + 0.5) / dims[axis]
+        return cls(W, H, origin, du, dv, dw, layers, filter)
+
+    @classmethod
+    def from_frame(cls, center, right, down, width, height, pitch, layers=1, layer_pitch=None, filter="linear"):
+        """An oblique slice: the frame is centred on `center` (texture space), its columns run along `right` and its
+        rows along `down` (texture-space directions, normalised here), `pitch` apart; the layers are stacked along
+        right x down, `layer_pitch` (default: pitch) apart and centred on `center` too."""
+        # plain double arithmetic in a fixed order: vrhip::slice_from_frame (include/vrhip/Slice.hpp) is the same rule
+        c, r, d = _vec3(center, "center"), _vec3(right, "right"), _vec3(down, "down")
+        for name, v in (("width", width), ("height", height), ("layers", layers)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError("%s must be a positive integer, not %r" % (name, v))
+
+        def unit(v, what):
+            l = math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+            if not l > 0.0:
+                raise ValueError(what)
+            return (v[0] / l, v[1] / l, v[2] / l)
+
+        r, d = unit(r, "right must not be zero"), unit(d, "down must not be zero")
+        n = unit((r[1] * d[2] - r[2] * d[1], r[2] * d[0] - r[0] * d[2], r[0] * d[1] - r[1] * d[0]),
+                 "right and down must not be parallel")
+        pitch = float(pitch)
+        lp = pitch if layer_pitch is None else float(layer_pitch)
+        if not (math.isfinite(pitch) and pitch > 0.0 and math.isfinite(lp)):
+            raise ValueError("pitch must be positive and layer_pitch finite")
+        du, dv, dw = [q * pitch for q in r], [q * pitch for q in d], [q * lp for q in n]
+        hw, hh, hl = 0.5 * (int(width) - 1), 0.5 * (int(height) - 1), 0.5 * (int(layers) - 1)
+        origin = [c[k] - hw * du[k] - hh * dv[k] - hl * dw[k] for k in range(3)]
+        return cls(width, height, origin, du, dv, dw, layers, filter)
+
+    def desc(self):
+        d = _lib.SlicePlaneDesc()
+        d.width, d.height, d.layers, d.filter = self.width, self.height, self.layers, self.filter
+        d.origin[:], d.du[:], d.dv[:], d.dw[:] = self.origin, self.du, self.dv, self.dw
+        d.box_min[:], d.box_max[:] = self.box_min, self.box_max
+        d.global_dims[:], d.vol_origin[:] = self.global_dims, self.vol_origin
+        return d
+
+
+def _check_plane(plane):
+    if not isinstance(plane, SlicePlane):
+        raise ValueError("plane must be a SlicePlane, not %s" % type(plane).__name__)
+
+
+def _slice_out(out, plane, device):
+    if out is None:
+        return torch.empty((plane.height, plane.width, 4), dtype=torch.float32, device=device)
+    _check_buf(out, "out", torch.float32, plane.height * plane.width * 4, device)
+    return out
+
+
+def _reslice_dense(fn, volume, dims, plane, proj, out, stream):
+    v, d = _dense_source(volume, dims)
+    _check_plane(plane)
+    _check_projection(proj, v.device)
+    out = _slice_out(out, plane, v.device)
+    pd, desc = plane.desc(), proj.desc()
+    check(getattr(_lib.lib(), fn)(C.c_void_p(v.data_ptr()), d, C.byref(pd), C.byref(desc), C.c_void_p(out.data_ptr()),
+                                  _stream_ptr(stream)), fn)
+    return out
+
+
+def reslice(volume, dims, plane, proj, out=None, stream=None):
+    """The slice `plane` of a dense volume (vr_reslice): per pixel the maximum, minimum or mean (proj.op) of the plane's
+    layers of samples, windowed, grey or through proj.lut; one layer is a thin slice.  Returns float32 CUDA [H][W][4];
+    (background, 0) where no sample lies inside the volume."""
+    return _reslice_dense("vr_reslice", volume, dims, plane, proj, out, stream)
+
+
+def reslice_partial(volume, dims, plane, proj, out=None, stream=None):
+    """The projection partial of reslice for sort-last compositing (vr_reslice_partial): float32 CUDA [H][W][4] =
+    (v, n, 0, 0); it combines and finishes through composite_combine_proj / composite_finish_proj."""
+    return _reslice_dense("vr_reslice_partial", volume, dims, plane, proj, out, stream)
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}

@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 from .render import (POOL_ENTRY, assemble_bricks, build_skip_grid_pool, default_camera, default_params, lod_pool_layout,
                      raycast, raycast_pool, raycast_pool_projection, raycast_pool_tf, raycast_pool_tf_shaded, raycast_projection,
-                     raycast_tf, raycast_tf_shaded, select_lod, use_skip_grid)
+                     raycast_tf, raycast_tf_shaded, reslice, select_lod, use_skip_grid)
 
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
@@ -166,6 +166,11 @@ class HeadlessViewer:
         if tf is not None:
             return raycast_pool_tf(self._pool, self._poolTable, bd, g, cam, P, tf, out), cuts
         return raycast_pool(self._pool, self._poolTable, bd, g, cam, P, out), cuts
+
+    def draw_slice(self, volume, dims, plane, projection, out=None):
+        """The slice `plane` (a SlicePlane) of `volume` through the Projection `projection`: reslice.  A slice has its
+        own geometry: the viewer's camera and frame size play no part."""
+        return reslice(volume, dims, plane, projection, out)
 
     @staticmethod
     def dump_ppm(path, rgba):
