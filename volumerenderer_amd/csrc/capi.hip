@@ -3,6 +3,7 @@
 // the reference's file format.  No CPU compute path exists behind these entry points.
 #include "../../include/vrhip.h"
 #include "brickset.h"
+#include "raymarch.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,38 +16,6 @@
 #include <new>
 
 using namespace vr;
-
-namespace vr {
-int raycast_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, const vr_transfer_function *,
-                   const vr_shading *, bool partial, float *, hipStream_t);
-int raycast_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
-                        const vr_render_params *, const vr_transfer_function *, const vr_shading *, bool partial, float *,
-                        hipStream_t);
-int composite_over_tf_launch(float *, const float *, int64_t, hipStream_t);
-int composite_finish_tf_launch(const float *, const vr_transfer_function *, float *, int64_t, hipStream_t);
-int composite_slabs_tf_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *,
-                              const vr_transfer_function *, float *, hipStream_t);
-int composite_over_launch(float *, const float *, int64_t, hipStream_t);
-int skip_grid_launch(const uint8_t *, const int64_t dims[3], int, uint8_t *, hipStream_t);
-int skip_grid_pool_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], int, uint8_t *,
-                          hipStream_t);
-int composite_finish_launch(const float *, float *, int64_t, hipStream_t);
-int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
-int assemble_launch(bool, const uint8_t *, uint8_t *, int, const int64_t bd[3], const int64_t *, const int64_t grid[3], hipStream_t);
-int measure_error_launch(const uint8_t *, const uint8_t *, int64_t, int *, unsigned long long *, hipStream_t);
-int query_error_launch(const uint8_t *, const uint8_t *, int64_t, uint8_t *, hipStream_t);
-int raycast_proj_launch(const uint8_t *, const int64_t dims[3], const vr_camera *, const vr_render_params *, const vr_projection *,
-                        bool partial, float *, hipStream_t);
-int raycast_pool_proj_launch(const uint8_t *, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
-                             const vr_render_params *, const vr_projection *, bool partial, float *, hipStream_t);
-int composite_combine_proj_launch(float *, const float *, int64_t, int, hipStream_t);
-int composite_finish_proj_launch(const float *, const vr_projection *, float *, int64_t, hipStream_t);
-int composite_slabs_proj_launch(const float *, int, int64_t, const vr_projection *, float *, hipStream_t);
-int reslice_launch(const uint8_t *, const int64_t dims[3], const vr_slice_plane *, const vr_projection *, bool partial, float *,
-                   hipStream_t);
-extern std::atomic<int> g_skipGridV1;
-extern std::atomic<int> g_resliceTileLog2;
-}
 
 struct vr_brickset { BrickSet s; };
 
@@ -61,7 +30,7 @@ static bool device_ok()
     return e == hipSuccess && n > 0;
 }
 
-// a vr_projection (vrhip.h); vr_compositor_composite_proj (compositor.hip) makes the same check
+// a vr_projection (vrhip.h); vr_compositor_composite_proj (compositor.hip) makes the same check through raymarch.h
 namespace vr {
 bool projection_ok(const vr_projection *pj)
 {
@@ -718,19 +687,8 @@ vr_status vr_brickset_decode_lod_pool(vr_brickset *h, const int32_t *cuts, const
     return lod_decode(b, cuts, nullptr, &d, stream);
 }
 
-// The frame of vr_raycast (raymarch.hip raycast_launch): glm::lookAt basis and glm::perspectiveFov half-angle tangents,
-// the same float operations.  Every ray of the frame is dir = f + nx tanX s + ny tanY u, |nx|, |ny| < 1; its ray
-// parameter is the view depth d . f (d = point - pos), and its march starts at depth >= z_near.
-static void lod_cross3(const float *a, const float *b, float *o)
-{
-    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-static void lod_norm3(float *v)
-{
-    float l = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (l > 0.0f) { v[0] /= l; v[1] /= l; v[2] /= l; } else { v[0] = v[1] = v[2] = 0.0f; }
-}
-
+// The frame of vr_raycast is view_basis (raymarch.h).  Every ray of the frame is dir = f + nx tanX s + ny tanY u,
+// |nx|, |ny| < 1; its ray parameter is the view depth d . f (d = point - pos), and its march starts at depth >= z_near.
 vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *P, int32_t num_bricks, const int64_t brick_dims[3],
                         const int64_t *brick_ijk, const int64_t grid[3], int32_t orig_tree_depth, int32_t max_tree_depth,
                         float pixel_tolerance, int32_t *cuts_out)
@@ -753,14 +711,9 @@ vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *P, int32_t
     for (int k = 0; k < 3; ++k) grow[k] = vs[k] + (P->mode == VR_RENDER_ISOSURFACE ? 0.01 + stepMax : 0.0);
     if (P->mode == VR_RENDER_SHADED)    // the lattice gradient's taps reach one voxel beyond the trilinear taps
         for (int k = 0; k < 3; ++k) grow[k] = 2.0 * vs[k];
-    float f[3] = {cam->front[0], cam->front[1], cam->front[2]}, sv[3], u[3];
-    lod_norm3(f);
-    lod_cross3(f, cam->up, sv);
-    lod_norm3(sv);
-    lod_cross3(sv, f, u);
-    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
-    const float tanYf = tanf(0.5f * rad), tanXf = tanYf * (float)P->width / (float)P->height;
-    const double tanY = tanYf, tanX = tanXf;
+    const ViewBasis vb = view_basis(cam, P->width, P->height);
+    const float *f = vb.f, *sv = vb.s, *u = vb.u;
+    const double tanY = vb.tanY, tanX = vb.tanX;
     const bool basis = (sv[0] != 0.0f || sv[1] != 0.0f || sv[2] != 0.0f);
     // a ray marches at most max_samples + 1 steps past its entry point (at depth <= z_far)
     const double zNear = cam->z_near, zFar = (double)cam->z_far + ((double)std::max(P->max_samples, 0) + 1.0) * stepMax;
@@ -1204,29 +1157,7 @@ vr_status vr_skip_grid_build_pool(const uint8_t *pool, const vr_pool_entry *tabl
     return skip_grid_pool_launch(pool, table, bd, grid, cell, out, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
 }
 
-vr_status vr_composite_over(float *front, const float *back, int64_t n, void *stream)
-{
-    if (!front || !back || n <= 0) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_over_launch(front, back, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
-}
-vr_status vr_composite_finish(const float *partial, float *rgba, int64_t n, void *stream)
-{
-    if (!partial || !rgba || n <= 0) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_finish_launch(partial, rgba, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
-}
-
-vr_status vr_composite_slabs(const float *partials, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel, int32_t axis,
-                             const vr_camera *cam, const vr_render_params *P, float *rgba, void *stream)
-{
-    if (!partials || !cam || !P || !rgba || num_slabs <= 0 || num_pixels <= 0 || first_pixel < 0 || axis < 0 || axis > 2)
-        return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || first_pixel + num_pixels > (int64_t)P->width * P->height) return VR_ERR_INVALID;
-    if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_slabs_launch(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, rgba, (hipStream_t)stream) == 0
-               ? VR_OK : VR_ERR_NO_DEVICE;
-}
+// ---- compositing of partial images: nine entry points, three kinds (PartialKind, raymarch.h)
 
 // the combine calls read tf->background only: a null lut_dev is allowed
 static bool background_ok(const vr_transfer_function *tf)
@@ -1236,31 +1167,61 @@ static bool background_ok(const vr_transfer_function *tf)
     return true;
 }
 
+// an element-wise call: two images (front and back, or partial and frame) of n pixels
+static bool images_ok(const float *a, const float *b, int64_t n) { return a && b && n > 0; }
+
+// a slab call of an ordered kind: num_slabs partials of the num_pixels pixels from first_pixel on of cam's frame
+static bool slab_tile_ok(const float *partials, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel, int32_t axis,
+                         const vr_camera *cam, const vr_render_params *P, const float *rgba)
+{
+    if (!partials || !cam || !P || !rgba || num_slabs <= 0 || num_pixels <= 0 || first_pixel < 0 || axis < 0 || axis > 2)
+        return false;
+    return P->width > 0 && P->height > 0 && first_pixel + num_pixels <= (int64_t)P->width * P->height;
+}
+
+static vr_status launched(int rc) { return rc == 0 ? VR_OK : VR_ERR_NO_DEVICE; }
+
+vr_status vr_composite_over(float *front, const float *back, int64_t n, void *stream)
+{
+    if (!images_ok(front, back, n)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return launched(composite_over_launch({PartialKind::GREY}, front, back, n, (hipStream_t)stream));
+}
+vr_status vr_composite_finish(const float *partial, float *rgba, int64_t n, void *stream)
+{
+    if (!images_ok(partial, rgba, n)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return launched(composite_finish_launch({PartialKind::GREY}, partial, rgba, n, (hipStream_t)stream));
+}
+vr_status vr_composite_slabs(const float *partials, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel, int32_t axis,
+                             const vr_camera *cam, const vr_render_params *P, float *rgba, void *stream)
+{
+    if (!slab_tile_ok(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, rgba)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return launched(composite_slabs_launch({PartialKind::GREY}, partials, num_slabs, num_pixels, first_pixel, axis, cam, P, rgba,
+                                           (hipStream_t)stream));
+}
+
 vr_status vr_composite_over_tf(float *front, const float *back, int64_t n, void *stream)
 {
-    if (!front || !back || n <= 0) return VR_ERR_INVALID;
+    if (!images_ok(front, back, n)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_over_tf_launch(front, back, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return launched(composite_over_launch({PartialKind::COLOUR}, front, back, n, (hipStream_t)stream));
 }
-
 vr_status vr_composite_finish_tf(const float *partial, const vr_transfer_function *tf, float *rgba, int64_t n, void *stream)
 {
-    if (!partial || !rgba || n <= 0 || !background_ok(tf)) return VR_ERR_INVALID;
+    if (!images_ok(partial, rgba, n) || !background_ok(tf)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_finish_tf_launch(partial, tf, rgba, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return launched(composite_finish_launch({PartialKind::COLOUR, tf}, partial, rgba, n, (hipStream_t)stream));
 }
-
 vr_status vr_composite_slabs_tf(const float *partials, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel, int32_t axis,
                                 const vr_camera *cam, const vr_render_params *P, const vr_transfer_function *tf, float *rgba,
                                 void *stream)
 {
-    if (!partials || !cam || !P || !rgba || num_slabs <= 0 || num_pixels <= 0 || first_pixel < 0 || axis < 0 || axis > 2)
-        return VR_ERR_INVALID;
-    if (P->width <= 0 || P->height <= 0 || first_pixel + num_pixels > (int64_t)P->width * P->height) return VR_ERR_INVALID;
-    if (!background_ok(tf)) return VR_ERR_INVALID;
+    if (!slab_tile_ok(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, rgba) || !background_ok(tf)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_slabs_tf_launch(partials, num_slabs, num_pixels, first_pixel, axis, cam, P, tf, rgba, (hipStream_t)stream) == 0
-               ? VR_OK : VR_ERR_NO_DEVICE;
+    return launched(composite_slabs_launch({PartialKind::COLOUR, tf}, partials, num_slabs, num_pixels, first_pixel, axis, cam, P,
+                                           rgba, (hipStream_t)stream));
 }
 
 // ---- intensity projections (vrhip.h): the entry points
@@ -1317,25 +1278,25 @@ vr_status vr_raycast_pool_projection_partial(const uint8_t *pool, const vr_pool_
 
 vr_status vr_composite_combine_proj(float *front, const float *back, int64_t n, int32_t op, void *stream)
 {
-    if (!front || !back || n <= 0 || op < VR_PROJECT_MAX || op > VR_PROJECT_MEAN) return VR_ERR_INVALID;
+    if (!images_ok(front, back, n) || op < VR_PROJECT_MAX || op > VR_PROJECT_MEAN) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_combine_proj_launch(front, back, n, op, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    vr_projection pj = {};      // a fold reads the op alone
+    pj.op = op;
+    return launched(composite_over_launch({PartialKind::PROJECTION, nullptr, &pj}, front, back, n, (hipStream_t)stream));
 }
-
 vr_status vr_composite_finish_proj(const float *partial, const vr_projection *pj, float *rgba, int64_t n, void *stream)
 {
-    if (!partial || !rgba || n <= 0 || !projection_ok(pj)) return VR_ERR_INVALID;
+    if (!images_ok(partial, rgba, n) || !projection_ok(pj)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_finish_proj_launch(partial, pj, rgba, n, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+    return launched(composite_finish_launch({PartialKind::PROJECTION, nullptr, pj}, partial, rgba, n, (hipStream_t)stream));
 }
-
 vr_status vr_composite_slabs_proj(const float *partials, int32_t num_slabs, int64_t num_pixels, const vr_projection *pj,
                                   float *rgba, void *stream)
 {
-    if (!partials || !rgba || num_slabs <= 0 || num_pixels <= 0 || !projection_ok(pj)) return VR_ERR_INVALID;
+    if (!images_ok(partials, rgba, num_pixels) || num_slabs <= 0 || !projection_ok(pj)) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
-    return composite_slabs_proj_launch(partials, num_slabs, num_pixels, pj, rgba, (hipStream_t)stream) == 0 ? VR_OK
-                                                                                                            : VR_ERR_NO_DEVICE;
+    return launched(composite_slabs_launch({PartialKind::PROJECTION, nullptr, pj}, partials, num_slabs, num_pixels, 0, 0, nullptr,
+                                           nullptr, rgba, (hipStream_t)stream));
 }
 
 // ---- slice views (vrhip.h): the entry points

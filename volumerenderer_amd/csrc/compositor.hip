@@ -2,9 +2,9 @@
 // the one real exchange step of the path.  Rank r holds the partial (c, tau) image of slab r of the
 // volume; the frame is cut into `world` row tiles; ONE grouped RCCL call moves tile t of every rank's partial image
 // to rank t (direct send: ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd over xGMI, 4 MB per peer at 1080p and
-// eight ranks); rank t combines its `world` partials per pixel in that pixel's view order (k_composite_slabs, or
-// k_composite_slabs_tf for the colour partials of vr_raycast_tf_partial: "over" is associative but not commutative,
-// raycaster.frag:69-72); a second grouped call gathers the finished tiles on rank 0.  The reference is single-GPU:
+// eight ranks); rank t combines its `world` partials per pixel in that pixel's view order (k_composite_slabs over the
+// kind of the partial: "over" is associative but not commutative, raycaster.frag:69-72; a projection has no order); a
+// second grouped call gathers the finished tiles on rank 0.  The reference is single-GPU:
 // this is new, in the form SURVEY 8b proposed (vr_composite_init(comm) / vr_composite).
 //
 // RCCL is bound at run time (dlopen of the copy already in the process -- PyTorch brings its own -- or of
@@ -14,6 +14,7 @@
 // one, a host (or a test, tests/loopback_transport.cpp) may bring its own with vr_compositor_create_with_transport.
 #include "../../include/vrhip.h"
 #include "kd_common.h"
+#include "raymarch.h"
 #include <dlfcn.h>
 #include <math.h>
 #include <rccl/rccl.h>
@@ -22,14 +23,6 @@
 #include <string.h>
 #include <mutex>
 #include <new>
-
-namespace vr {
-int composite_slabs_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *, float *, hipStream_t);
-int composite_slabs_tf_launch(const float *, int, int64_t, int64_t, int, const vr_camera *, const vr_render_params *,
-                              const vr_transfer_function *, float *, hipStream_t);
-int composite_slabs_proj_launch(const float *, int, int64_t, const vr_projection *, float *, hipStream_t);
-bool projection_ok(const vr_projection *);      // capi.hip
-}
 
 namespace {
 
@@ -107,6 +100,37 @@ struct vr_compositor {
     float *tile = nullptr;      // my finished tile
 };
 
+static vr_status compositor_alloc(vr_compositor *c)
+{
+    int lo, hi;
+    rows_of(c->H, c->rank, c->world, lo, hi);
+    const size_t npix = (size_t)(hi - lo) * c->W;
+    if (c->world > 1 && npix) {
+        if (hipMalloc(&c->recv, (size_t)c->world * npix * 4 * sizeof(float)) != hipSuccess) return VR_ERR_OOM;
+        if (hipMalloc(&c->tile, npix * 4 * sizeof(float)) != hipSuccess) return VR_ERR_OOM;
+    }
+    return VR_OK;
+}
+
+// What the three ways to make a compositor share: the checks (extraOk: the caller's own), the handle, its buffers.
+// bind(c) gives the handle its communicator or transport; a failure of it or of the allocation destroys the handle.
+template <class BIND>
+static vr_status compositor_create(vr_compositor **out, bool extraOk, int32_t rank, int32_t world, int32_t width, int32_t height,
+                                   BIND &&bind)
+{
+    if (!out || !extraOk || world < 1 || rank < 0 || rank >= world || width <= 0 || height < world) return VR_ERR_INVALID;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VR_ERR_NO_DEVICE;
+    vr_compositor *c = new (std::nothrow) vr_compositor();
+    if (!c) return VR_ERR_OOM;
+    c->rank = rank; c->world = world; c->W = width; c->H = height;
+    vr_status rc = bind(c);
+    if (rc == VR_OK) rc = compositor_alloc(c);
+    if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
+    *out = c;
+    return VR_OK;
+}
+
 extern "C" {
 
 vr_status vr_rccl_unique_id(uint8_t id[128])
@@ -120,75 +144,39 @@ vr_status vr_rccl_unique_id(uint8_t id[128])
     return VR_OK;
 }
 
-static vr_status compositor_alloc(vr_compositor *c)
-{
-    int lo, hi;
-    rows_of(c->H, c->rank, c->world, lo, hi);
-    const size_t npix = (size_t)(hi - lo) * c->W;
-    if (c->world > 1 && npix) {
-        if (hipMalloc(&c->recv, (size_t)c->world * npix * 4 * sizeof(float)) != hipSuccess) return VR_ERR_OOM;
-        if (hipMalloc(&c->tile, npix * 4 * sizeof(float)) != hipSuccess) return VR_ERR_OOM;
-    }
-    return VR_OK;
-}
-
 vr_status vr_compositor_create(vr_compositor **out, const uint8_t id[128], int32_t rank, int32_t world, int32_t width, int32_t height)
 {
-    if (!out || world < 1 || rank < 0 || rank >= world || width <= 0 || height < world) return VR_ERR_INVALID;
-    if (world > 1 && !id) return VR_ERR_INVALID;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VR_ERR_NO_DEVICE;
-    vr_compositor *c = new (std::nothrow) vr_compositor();
-    if (!c) return VR_ERR_OOM;
-    c->rank = rank; c->world = world; c->W = width; c->H = height;
-    if (world > 1) {
-        if (!rccl().ok) { delete c; return VR_ERR_UNSUPPORTED; }
+    return compositor_create(out, world <= 1 || id, rank, world, width, height, [&](vr_compositor *c) {
+        if (world == 1) return VR_OK;
+        if (!rccl().ok) return VR_ERR_UNSUPPORTED;
         ncclUniqueId u;
         memcpy(&u, id, 128);
-        if (!nccl_ok(rccl().CommInitRank(&c->comm, world, u, rank), "ncclCommInitRank")) { delete c; return VR_ERR_NO_DEVICE; }
+        if (!nccl_ok(rccl().CommInitRank(&c->comm, world, u, rank), "ncclCommInitRank")) return VR_ERR_NO_DEVICE;
         c->ownComm = true;
         c->ctx = c->comm;
-    }
-    const vr_status rc = compositor_alloc(c);
-    if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
-    *out = c;
-    return VR_OK;
+        return VR_OK;
+    });
 }
 
 vr_status vr_compositor_create_from_comm(vr_compositor **out, void *nccl_comm, int32_t rank, int32_t world, int32_t width, int32_t height)
 {
-    if (!out || world < 1 || rank < 0 || rank >= world || width <= 0 || height < world) return VR_ERR_INVALID;
-    if (world > 1 && !nccl_comm) return VR_ERR_INVALID;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VR_ERR_NO_DEVICE;
-    if (world > 1 && !rccl().ok) return VR_ERR_UNSUPPORTED;
-    vr_compositor *c = new (std::nothrow) vr_compositor();
-    if (!c) return VR_ERR_OOM;
-    c->rank = rank; c->world = world; c->W = width; c->H = height;
-    c->comm = (ncclComm_t)nccl_comm;
-    c->ctx = c->comm;
-    const vr_status rc = compositor_alloc(c);
-    if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
-    *out = c;
-    return VR_OK;
+    return compositor_create(out, world <= 1 || nccl_comm, rank, world, width, height, [&](vr_compositor *c) {
+        if (world > 1 && !rccl().ok) return VR_ERR_UNSUPPORTED;
+        c->comm = (ncclComm_t)nccl_comm;
+        c->ctx = c->comm;
+        return VR_OK;
+    });
 }
 
 vr_status vr_compositor_create_with_transport(vr_compositor **out, const vr_transport *t, void *ctx, int32_t rank,
                                               int32_t world, int32_t width, int32_t height)
 {
-    if (!out || !t || !t->group_start || !t->group_end || !t->send || !t->recv) return VR_ERR_INVALID;
-    if (world < 1 || rank < 0 || rank >= world || width <= 0 || height < world) return VR_ERR_INVALID;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VR_ERR_NO_DEVICE;
-    vr_compositor *c = new (std::nothrow) vr_compositor();
-    if (!c) return VR_ERR_OOM;
-    c->rank = rank; c->world = world; c->W = width; c->H = height;
-    c->t = *t;
-    c->ctx = ctx;
-    const vr_status rc = compositor_alloc(c);
-    if (rc != VR_OK) { vr_compositor_destroy(c); return rc; }
-    *out = c;
-    return VR_OK;
+    return compositor_create(out, t && t->group_start && t->group_end && t->send && t->recv, rank, world, width, height,
+                             [&](vr_compositor *c) {
+        c->t = *t;
+        c->ctx = ctx;
+        return VR_OK;
+    });
 }
 
 vr_status vr_compositor_destroy(vr_compositor *c)
@@ -201,16 +189,12 @@ vr_status vr_compositor_destroy(vr_compositor *c)
 }
 
 // The exchange of the three composite calls: a grey, a colour and a projection partial are the same width * height * 4
-// floats, and only the combine differs -- proj: k_composite_slabs_proj (v, n), which needs no view order; else tf == NULL:
-// k_composite_slabs (c, tau, covered), else k_composite_slabs_tf (C, T).
-static vr_status exchange_and_combine(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
-                                      const vr_render_params *params, const vr_transfer_function *tf,
-                                      const vr_projection *proj, float *rgba_dev, hipStream_t st)
+// floats, and only the kind of the combine differs (a projection has no view order: it comes without axis, cam, params).
+static vr_status exchange_and_combine(vr_compositor *c, const vr::PartialKind &kind, const float *partial_dev, int32_t axis,
+                                      const vr_camera *cam, const vr_render_params *params, float *rgba_dev, hipStream_t st)
 {
     auto combine = [&](const float *parts, int n, int64_t npix, int64_t first, float *dst) -> int {
-        if (proj) return vr::composite_slabs_proj_launch(parts, n, npix, proj, dst, st);
-        return tf ? vr::composite_slabs_tf_launch(parts, n, npix, first, axis, cam, params, tf, dst, st)
-                  : vr::composite_slabs_launch(parts, n, npix, first, axis, cam, params, dst, st);
+        return vr::composite_slabs_launch(kind, parts, n, npix, first, axis, cam, params, dst, st);
     };
     const int64_t frame = (int64_t)c->W * c->H;
     if (c->world == 1) return combine(partial_dev, 1, frame, 0, rgba_dev) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
@@ -260,7 +244,7 @@ vr_status vr_compositor_composite(vr_compositor *c, const float *partial_dev, in
                                   const vr_render_params *params, float *rgba_dev, void *stream)
 {
     if (!composite_args_ok(c, partial_dev, axis, cam, params, rgba_dev)) return VR_ERR_INVALID;
-    return exchange_and_combine(c, partial_dev, axis, cam, params, nullptr, nullptr, rgba_dev, (hipStream_t)stream);
+    return exchange_and_combine(c, {vr::PartialKind::GREY}, partial_dev, axis, cam, params, rgba_dev, (hipStream_t)stream);
 }
 
 vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev, int32_t axis, const vr_camera *cam,
@@ -269,14 +253,15 @@ vr_status vr_compositor_composite_tf(vr_compositor *c, const float *partial_dev,
 {
     if (!composite_args_ok(c, partial_dev, axis, cam, params, rgba_dev) || !tf) return VR_ERR_INVALID;
     for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return VR_ERR_INVALID;
-    return exchange_and_combine(c, partial_dev, axis, cam, params, tf, nullptr, rgba_dev, (hipStream_t)stream);
+    return exchange_and_combine(c, {vr::PartialKind::COLOUR, tf}, partial_dev, axis, cam, params, rgba_dev, (hipStream_t)stream);
 }
 
 vr_status vr_compositor_composite_proj(vr_compositor *c, const float *partial_dev, const vr_projection *proj, float *rgba_dev,
                                        void *stream)
 {
     if (!c || !partial_dev || (c->rank == 0 && !rgba_dev) || !vr::projection_ok(proj)) return VR_ERR_INVALID;
-    return exchange_and_combine(c, partial_dev, 0, nullptr, nullptr, nullptr, proj, rgba_dev, (hipStream_t)stream);
+    return exchange_and_combine(c, {vr::PartialKind::PROJECTION, nullptr, proj}, partial_dev, 0, nullptr, nullptr, rgba_dev,
+                                (hipStream_t)stream);
 }
 
 // ---- streams, events, pinned host memory: what a C++ host needs to overlap the stages of a timestep stream

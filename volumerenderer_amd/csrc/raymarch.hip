@@ -3,18 +3,18 @@
 // (volume_renderer/isosurface.frag:23-159), the vertex stage / proxy cube they run on
 // (raycaster.vert:10-21, UnitBrick.h:54-100, main.cpp:396-402), plus the small
 // data-parallel helpers of the path: brick assembly (VolumeReader.h:151-223), error
-// metrics (VolumeKdTree_recover.cpp:386-411) and sort-last compositing.
+// metrics (VolumeKdTree_recover.cpp:386-411) and sort-last compositing: the three kinds of partial image (grey,
+// colour, projection) as small structs and one fold, one finish and one slab kernel over the kind.  raymarch.h
+// declares what the other units call.
 //
 // One thread per pixel; a 64-lane wave covers an 8x8 pixel tile so neighbouring rays
 // touch neighbouring voxels (L1/L2 locality of the 8 trilinear taps).  The cube
 // rasteriser is replaced by its per-pixel equivalent: nearest cube-surface point along
 // the view ray inside [near, far] (GL_LESS, no culling: main.cpp:367-369).
-#include "../../include/vrhip.h"
+#include "raymarch.h"
 #include "kd_common.h"
-#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
-#include <atomic>
 
 namespace vr {
 
@@ -678,27 +678,6 @@ k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
     else { o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T; }
 }
 
-__global__ void k_composite_over(float4 *front, const float4 *back, int64_t n)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 f = front[i], b = back[i];
-    f.x = f.x + f.y * b.x;       // (c1 + t1*c2, t1*t2)
-    f.y = f.y * b.y;
-    f.z = fmaxf(f.z, b.z);
-    front[i] = f;
-}
-
-__global__ void k_composite_finish(const float4 *partial, float4 *rgba, int64_t n)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 p = partial[i], o;
-    if (p.z > 0.0f) { o.x = 1.0f - p.x; o.y = 1.0f - p.x; o.z = 1.0f; o.w = 1.0f - p.y; }
-    else { o.x = o.y = o.z = o.w = 1.0f; }
-    rgba[i] = o;
-}
-
 // ---- colour partials (vr_raycast_tf_partial): one float4 (C.r, C.g, C.b, T) per pixel.  "Over" and the finish are
 // written with the marcher's own expressions (C + w c, T t; C + T bg, 1 - T), so a fold of slabs rounds like one march.
 struct Bg { float c[3]; };
@@ -717,84 +696,10 @@ __device__ __forceinline__ float4 finish_tf(const float4 &p, const Bg &bg)
     return o;
 }
 
-__global__ void __launch_bounds__(256)
-k_composite_over_tf(float4 *front, const float4 *back, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 f = front[i];
-    over_tf(f, back[i]);
-    front[i] = f;
-}
-
-__global__ void __launch_bounds__(256)
-k_composite_finish_tf(const float4 *partial, Bg bg, float4 *rgba, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    rgba[i] = finish_tf(partial[i], bg);
-}
-
-static void cross3(const float *a, const float *b, float *o);
-static void hnorm3(float *v);
-
-struct SlabArgs {
-    const float4 *partials;
-    int num_slabs;
-    int64_t npix, first;
-    int axis, W, H;
-    float f[3], s[3], u[3], tanX, tanY;
-    float4 *out;
-};
-
-__global__ void __launch_bounds__(256)
-k_composite_slabs(SlabArgs a)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.npix) return;
-    const int64_t gp = a.first + i;
-    const int px = (int)(gp % a.W), py = (int)(gp / a.W);
-    const float nx = 2.0f * ((float)px + 0.5f) / (float)a.W - 1.0f;
-    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)a.H;
-    const float d = a.f[a.axis] + nx * a.tanX * a.s[a.axis] + ny * a.tanY * a.u[a.axis];
-    float c = 0.0f, tau = 1.0f, cov = 0.0f;
-    for (int k = 0; k < a.num_slabs; ++k) {
-        const int sidx = d >= 0.0f ? k : a.num_slabs - 1 - k;
-        const float4 p = a.partials[(int64_t)sidx * a.npix + i];
-        c = c + tau * p.x;          // (c1 + t1*c2, t1*t2)
-        tau = tau * p.y;
-        cov = fmaxf(cov, p.z);
-    }
-    float4 o;
-    if (cov > 0.0f) { o.x = 1.0f - c; o.y = 1.0f - c; o.z = 1.0f; o.w = 1.0f - tau; }   // raycaster.frag:82-85
-    else { o.x = o.y = o.z = o.w = 1.0f; }
-    a.out[i] = o;
-}
-
-// k_composite_slabs for colour partials: the same pixel, the same d and the same slab order; a streaming kernel --
-// num_slabs 16-byte loads and one 16-byte store per lane, consecutive lanes on consecutive pixels
-__global__ void __launch_bounds__(256)
-k_composite_slabs_tf(SlabArgs a, Bg bg)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.npix) return;
-    const int64_t gp = a.first + i;
-    const int px = (int)(gp % a.W), py = (int)(gp / a.W);
-    const float nx = 2.0f * ((float)px + 0.5f) / (float)a.W - 1.0f;
-    const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)a.H;
-    const float d = a.f[a.axis] + nx * a.tanX * a.s[a.axis] + ny * a.tanY * a.u[a.axis];
-    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    for (int k = 0; k < a.num_slabs; ++k) {
-        const int sidx = d >= 0.0f ? k : a.num_slabs - 1 - k;
-        over_tf(acc, a.partials[(int64_t)sidx * a.npix + i]);
-    }
-    a.out[i] = finish_tf(acc, bg);
-}
-
 // ---- intensity projections (vr_raycast_projection; the rule is in vrhip.h) -------------------------------------------
 // A projection partial is (v, n, 0, 0): n owned samples, v their maximum, minimum or float32 sum.  One combine and one
-// finish serve the marcher's final store and the three element-wise kernels, so finish(partial) == frame and pairwise
-// folds == the slab call hold by construction.
+// finish serve the marchers' final store and the compositing kernels (ProjKind), so finish(partial) == frame and
+// pairwise folds == the slab call hold by construction.
 struct ProjArgs {
     const float4 *lut;      // NULL = grey; else 256 (r, g, b, a), 16-byte aligned
     int op;                 // VR_PROJECT_*
@@ -911,33 +816,91 @@ k_raycast_proj(RayArgs a, SAMPLER tex, ProjArgs A)
     o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
 }
 
+// ---- the three kinds of partial image: identity, fold (front = front then back), finish into a frame, and whether slabs
+// fold in the pixel's view order.  A kind carries what its finish needs.
+struct GreyKind {       // (c, tau, covered, 0)
+    static constexpr bool ordered = true;
+    __device__ static float4 identity() { return make_float4(0.0f, 1.0f, 0.0f, 0.0f); }
+    __device__ void fold(float4 &f, const float4 &b) const
+    {
+        f.x = f.x + f.y * b.x;       // (c1 + t1*c2, t1*t2)
+        f.y = f.y * b.y;
+        f.z = fmaxf(f.z, b.z);
+    }
+    __device__ float4 finish(const float4 &p) const
+    {
+        if (p.z > 0.0f) return make_float4(1.0f - p.x, 1.0f - p.x, 1.0f, 1.0f - p.y);      // raycaster.frag:82-85
+        return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    }
+};
+struct ColourKind {     // (C.r, C.g, C.b, T)
+    Bg bg;
+    static constexpr bool ordered = true;
+    __device__ static float4 identity() { return make_float4(0.0f, 0.0f, 0.0f, 1.0f); }
+    __device__ void fold(float4 &f, const float4 &b) const { over_tf(f, b); }
+    __device__ float4 finish(const float4 &p) const { return finish_tf(p, bg); }
+};
+struct ProjKind {       // (v, n, 0, 0); the order only matters to MEAN's rounding
+    ProjArgs A;
+    static constexpr bool ordered = false;
+    __device__ static float4 identity() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    __device__ void fold(float4 &f, const float4 &b) const { combine_proj(f, b, A.op); }
+    __device__ float4 finish(const float4 &p) const { return finish_proj(p, A); }
+};
+
+template <class KIND>
 __global__ void __launch_bounds__(256)
-k_composite_combine_proj(float4 *front, const float4 *back, int64_t n, int op)
+k_composite_over(KIND kind, float4 *front, const float4 *back, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float4 f = front[i];
-    combine_proj(f, back[i], op);
+    kind.fold(f, back[i]);
     front[i] = f;
 }
 
+template <class KIND>
 __global__ void __launch_bounds__(256)
-k_composite_finish_proj(const float4 *partial, ProjArgs A, float4 *rgba, int64_t n)
+k_composite_finish(KIND kind, const float4 *partial, float4 *rgba, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    rgba[i] = finish_proj(partial[i], A);
+    rgba[i] = kind.finish(partial[i]);
 }
 
-// the slabs in ascending index (the order only matters to MEAN's rounding): num_slabs 16-byte loads, one 16-byte store
+struct SlabArgs {
+    const float4 *partials;
+    int num_slabs;
+    int64_t npix, first;
+    float4 *out;
+    int axis, W, H;         // an ordered kind's frame: pixel i of the call is pixel first + i of W x H
+    ViewBasis b;
+};
+
+// Pixel i of num_slabs partial images folded front to back and finished: a streaming kernel -- num_slabs 16-byte loads
+// and one 16-byte store per lane, consecutive lanes on consecutive pixels.  An ordered kind walks the slabs in the
+// order the pixel's ray crosses them: ascending where its direction's component d along the axis is >= 0.
+template <class KIND>
 __global__ void __launch_bounds__(256)
-k_composite_slabs_proj(const float4 *partials, int num_slabs, int64_t npix, ProjArgs A, float4 *rgba)
+k_composite_slabs(SlabArgs a, KIND kind)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (int k = 0; k < num_slabs; ++k) combine_proj(acc, partials[(int64_t)k * npix + i], A.op);
-    rgba[i] = finish_proj(acc, A);
+    if (i >= a.npix) return;
+    bool ascending = true;
+    if constexpr (KIND::ordered) {
+        const int64_t gp = a.first + i;
+        const int px = (int)(gp % a.W), py = (int)(gp / a.W);
+        const float nx = 2.0f * ((float)px + 0.5f) / (float)a.W - 1.0f;
+        const float ny = 1.0f - 2.0f * ((float)py + 0.5f) / (float)a.H;
+        const float d = a.b.f[a.axis] + nx * a.b.tanX * a.b.s[a.axis] + ny * a.b.tanY * a.b.u[a.axis];
+        ascending = d >= 0.0f;
+    }
+    float4 acc = KIND::identity();
+    for (int k = 0; k < a.num_slabs; ++k) {
+        const int sidx = ascending ? k : a.num_slabs - 1 - k;
+        kind.fold(acc, a.partials[(int64_t)sidx * a.npix + i]);
+    }
+    a.out[i] = kind.finish(acc);
 }
 
 // ---- slice views (vr_reslice; the rule is in vrhip.h) ------------------------------------------------------------------
@@ -1055,19 +1018,29 @@ static void hnorm3(float *v)
     if (l > 0.0f) { v[0] /= l; v[1] /= l; v[2] /= l; } else { v[0] = v[1] = v[2] = 0.0f; }
 }
 
-// the frame (glm::lookAt basis and glm::perspectiveFov half-angle tangents, main.cpp:396-397) and the output
+// the frame's basis (raymarch.h): these float operations, in this order, for everything that needs it
+ViewBasis view_basis(const vr_camera *cam, int width, int height)
+{
+    ViewBasis b;
+    for (int k = 0; k < 3; ++k) b.f[k] = cam->front[k];
+    hnorm3(b.f);
+    cross3(b.f, cam->up, b.s);
+    hnorm3(b.s);
+    cross3(b.s, b.f, b.u);
+    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
+    b.tanY = tanf(0.5f * rad);
+    b.tanX = b.tanY * (float)width / (float)height;
+    return b;
+}
+
+// the camera, the parameters, the frame's basis and the output
 static void ray_frame(RayArgs &a, const vr_camera *cam, const vr_render_params *P, float *rgba)
 {
     a.cam = *cam;
     a.P = *P;
-    for (int k = 0; k < 3; ++k) a.f[k] = cam->front[k];
-    hnorm3(a.f);
-    cross3(a.f, cam->up, a.s);
-    hnorm3(a.s);
-    cross3(a.s, a.f, a.u);
-    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
-    a.tanY = tanf(0.5f * rad);
-    a.tanX = a.tanY * (float)P->width / (float)P->height;
+    const ViewBasis b = view_basis(cam, P->width, P->height);
+    for (int k = 0; k < 3; ++k) { a.f[k] = b.f[k]; a.s[k] = b.s[k]; a.u[k] = b.u[k]; }
+    a.tanX = b.tanX; a.tanY = b.tanY;
     a.out = rgba;
 }
 
@@ -1238,61 +1211,6 @@ int skip_grid_launch(const uint8_t *vol, const int64_t dims[3], int S, uint8_t *
     return launch_status("skip_grid");
 }
 
-// the frame and buffers of both slab kernels: one set-up, so that they form d from the same basis
-static SlabArgs slab_args(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
-                          const vr_render_params *P, float *rgba)
-{
-    SlabArgs a;
-    a.partials = (const float4 *)partials; a.num_slabs = nslabs; a.npix = npix; a.first = first;
-    a.axis = axis; a.W = P->width; a.H = P->height;
-    for (int k = 0; k < 3; ++k) a.f[k] = cam->front[k];
-    hnorm3(a.f);
-    cross3(a.f, cam->up, a.s);
-    hnorm3(a.s);
-    cross3(a.s, a.f, a.u);
-    const float rad = cam->fov_deg * 0.01745329251994329576923690768489f;
-    a.tanY = tanf(0.5f * rad);
-    a.tanX = a.tanY * (float)P->width / (float)P->height;
-    a.out = (float4 *)rgba;
-    return a;
-}
-
-int composite_slabs_launch(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
-                           const vr_render_params *P, float *rgba, hipStream_t st)
-{
-    const SlabArgs a = slab_args(partials, nslabs, npix, first, axis, cam, P, rgba);
-    hipLaunchKernelGGL(k_composite_slabs, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, a);
-    return launch_status("composite_slabs");
-}
-
-static Bg background_of(const vr_transfer_function *tf)
-{
-    Bg b;
-    for (int k = 0; k < 3; ++k) b.c[k] = tf->background[k];
-    return b;
-}
-
-int composite_slabs_tf_launch(const float *partials, int nslabs, int64_t npix, int64_t first, int axis, const vr_camera *cam,
-                              const vr_render_params *P, const vr_transfer_function *tf, float *rgba, hipStream_t st)
-{
-    const SlabArgs a = slab_args(partials, nslabs, npix, first, axis, cam, P, rgba);
-    hipLaunchKernelGGL(k_composite_slabs_tf, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, a, background_of(tf));
-    return launch_status("composite_slabs_tf");
-}
-
-int composite_over_tf_launch(float *front, const float *back, int64_t n, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_composite_over_tf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float4 *)front,
-                       (const float4 *)back, n);
-    return launch_status("composite_over_tf");
-}
-int composite_finish_tf_launch(const float *partial, const vr_transfer_function *tf, float *rgba, int64_t n, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_composite_finish_tf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)partial,
-                       background_of(tf), (float4 *)rgba, n);
-    return launch_status("composite_finish_tf");
-}
-
 static ProjArgs proj_args(const vr_projection *pj)
 {
     ProjArgs A;
@@ -1339,24 +1257,51 @@ int raycast_pool_proj_launch(const uint8_t *pool, const vr_pool_entry *tab, cons
     return proj_launch(a, pt, pj, partial, "raymarch_pool_proj", st);
 }
 
-int composite_combine_proj_launch(float *front, const float *back, int64_t n, int op, hipStream_t st)
+// ---- the compositing launches: a PartialKind (raymarch.h) picks the instantiation
+static const char *const kCompositeLabel[3][3] = {{"raymarch", "raymarch", "composite_slabs"},
+                                                  {"composite_over_tf", "composite_finish_tf", "composite_slabs_tf"},
+                                                  {"composite_combine_proj", "composite_finish_proj", "composite_slabs_proj"}};
+
+// launch(kind) with the device struct of k
+template <class F>
+static void with_kind(const PartialKind &k, F &&launch)
 {
-    hipLaunchKernelGGL(k_composite_combine_proj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float4 *)front,
-                       (const float4 *)back, n, op);
-    return launch_status("composite_combine_proj");
+    if (k.which == PartialKind::GREY) launch(GreyKind());
+    else if (k.which == PartialKind::COLOUR) {
+        ColourKind c = {};      // a fold comes without tf: it does not read the background
+        if (k.tf) for (int q = 0; q < 3; ++q) c.bg.c[q] = k.tf->background[q];
+        launch(c);
+    } else launch(ProjKind{proj_args(k.proj)});
 }
-int composite_finish_proj_launch(const float *partial, const vr_projection *pj, float *rgba, int64_t n, hipStream_t st)
+
+int composite_over_launch(const PartialKind &k, float *front, const float *back, int64_t n, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_composite_finish_proj, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)partial,
-                       proj_args(pj), (float4 *)rgba, n);
-    return launch_status("composite_finish_proj");
+    with_kind(k, [&](auto kind) {
+        hipLaunchKernelGGL(k_composite_over<decltype(kind)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kind,
+                           (float4 *)front, (const float4 *)back, n);
+    });
+    return launch_status(kCompositeLabel[k.which][0]);
 }
-int composite_slabs_proj_launch(const float *partials, int nslabs, int64_t npix, const vr_projection *pj, float *rgba,
-                                hipStream_t st)
+int composite_finish_launch(const PartialKind &k, const float *partial, float *rgba, int64_t n, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_composite_slabs_proj, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, (const float4 *)partials,
-                       nslabs, npix, proj_args(pj), (float4 *)rgba);
-    return launch_status("composite_slabs_proj");
+    with_kind(k, [&](auto kind) {
+        hipLaunchKernelGGL(k_composite_finish<decltype(kind)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kind,
+                           (const float4 *)partial, (float4 *)rgba, n);
+    });
+    return launch_status(kCompositeLabel[k.which][1]);
+}
+int composite_slabs_launch(const PartialKind &k, const float *partials, int nslabs, int64_t npix, int64_t first, int axis,
+                           const vr_camera *cam, const vr_render_params *P, float *rgba, hipStream_t st)
+{
+    with_kind(k, [&](auto kind) {
+        SlabArgs a = {(const float4 *)partials, nslabs, npix, first, (float4 *)rgba};
+        if (decltype(kind)::ordered) {
+            a.axis = axis; a.W = P->width; a.H = P->height;
+            a.b = view_basis(cam, P->width, P->height);
+        }
+        hipLaunchKernelGGL(k_composite_slabs<decltype(kind)>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, a, kind);
+    });
+    return launch_status(kCompositeLabel[k.which][2]);
 }
 
 // process-wide debugging switch (vr_debug_set("reslice_tile_w", 8 | 16 | 64)): the width of the wave's pixel tile in
@@ -1419,18 +1364,6 @@ int reslice_launch(const uint8_t *vol, const int64_t dims[3], const vr_slice_pla
     return slice_launch(a, DenseSampler(), pl, pj, partial, "reslice", st);
 }
 
-int composite_over_launch(float *front, const float *back, int64_t n, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_composite_over, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float4 *)front,
-                       (const float4 *)back, n);
-    return launch_status("raymarch");
-}
-int composite_finish_launch(const float *partial, float *rgba, int64_t n, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_composite_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       (const float4 *)partial, (float4 *)rgba, n);
-    return launch_status("raymarch");
-}
 int assemble_launch(bool toVolume, const uint8_t *src, uint8_t *dst, int nb, const int64_t bd[3], const int64_t *ijkDev,
                     const int64_t grid[3], hipStream_t st)
 {

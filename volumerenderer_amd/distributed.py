@@ -46,38 +46,46 @@ def tile_rows(height, world):
     return [shard_range(height, r, world) for r in range(world)]
 
 
-def _gpu_combine(parts, first_pixel, axis, cam, params):
+def _gpu_slabs(fn, parts, *args):
+    """The slab call `fn` on parts = [slabs][pixels][4]; args: what it takes between the pixel count and the output."""
     from . import _lib
     from .codec import _stream_ptr
     from ._lib import check
     out = torch.empty((parts.shape[1], 4), dtype=torch.float32, device=parts.device)
-    check(_lib.lib().vr_composite_slabs(C.c_void_p(parts.data_ptr()), parts.shape[0], parts.shape[1], int(first_pixel),
-                                        int(axis), C.byref(cam), C.byref(params), C.c_void_p(out.data_ptr()),
-                                        _stream_ptr()), "vr_composite_slabs")
+    check(getattr(_lib.lib(), fn)(C.c_void_p(parts.data_ptr()), parts.shape[0], parts.shape[1], *args,
+                                  C.c_void_p(out.data_ptr()), _stream_ptr()), fn)
     return out
+
+
+def _gpu_combine(parts, first_pixel, axis, cam, params):
+    return _gpu_slabs("vr_composite_slabs", parts, int(first_pixel), int(axis), C.byref(cam), C.byref(params))
 
 
 def _gpu_combine_tf(parts, first_pixel, axis, cam, params, tf):
-    from . import _lib
-    from .codec import _stream_ptr
-    from ._lib import check
-    out = torch.empty((parts.shape[1], 4), dtype=torch.float32, device=parts.device)
     desc = tf.desc()
-    check(_lib.lib().vr_composite_slabs_tf(C.c_void_p(parts.data_ptr()), parts.shape[0], parts.shape[1], int(first_pixel),
-                                           int(axis), C.byref(cam), C.byref(params), C.byref(desc),
-                                           C.c_void_p(out.data_ptr()), _stream_ptr()), "vr_composite_slabs_tf")
-    return out
+    return _gpu_slabs("vr_composite_slabs_tf", parts, int(first_pixel), int(axis), C.byref(cam), C.byref(params), C.byref(desc))
 
 
 def _gpu_combine_proj(parts, proj):
-    from . import _lib
-    from .codec import _stream_ptr
-    from ._lib import check
-    out = torch.empty((parts.shape[1], 4), dtype=torch.float32, device=parts.device)
     desc = proj.desc()
-    check(_lib.lib().vr_composite_slabs_proj(C.c_void_p(parts.data_ptr()), parts.shape[0], parts.shape[1], C.byref(desc),
-                                             C.c_void_p(out.data_ptr()), _stream_ptr()), "vr_composite_slabs_proj")
-    return out
+    return _gpu_slabs("vr_composite_slabs_proj", parts, C.byref(desc))
+
+
+def _slab_cut(who, dims, axis, rank, world, halo):
+    """The cut slab_params and slab_plane share: (dims, box_min, box_max, vol_origin, local_dims, (a0, a1)) of rank
+    `rank`'s slab; the last rank's box_max is 2.0 (it owns the far face).  ValueError in the name of `who`."""
+    dims = [int(q) for q in dims]
+    if len(dims) != 3 or axis not in (0, 1, 2) or not 0 <= rank < world or halo < 0 or world > dims[axis]:
+        raise ValueError("%s: axis %r, rank %r of %r, halo %r, extents %r" % (who, axis, rank, world, halo, dims))
+    n = dims[axis]
+    lo, hi = shard_range(n, rank, world)
+    a0, a1 = max(0, lo - halo), min(n, hi + halo)
+    bmin, bmax, org, local = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0, 0, 0], list(dims)
+    bmin[axis] = lo / n
+    bmax[axis] = hi / n if rank < world - 1 else 2.0
+    org[axis] = a0
+    local[axis] = a1 - a0
+    return dims, bmin, bmax, org, tuple(local), (a0, a1)
 
 
 def slab_params(params, dims, axis, rank, world, halo):
@@ -87,26 +95,15 @@ def slab_params(params, dims, axis, rank, world, halo):
     (P, local_dims, (a0, a1)): P = a copy of `params` with box_min / box_max (the last rank's box_max is 2.0: it owns
     the far face), vol_origin and global_dims set, local_dims the extents of the voxels [a0, a1) along `axis` that the
     rank has to hold."""
-    dims = [int(q) for q in dims]
-    if len(dims) != 3 or axis not in (0, 1, 2) or not 0 <= rank < world or halo < 0 or world > dims[axis]:
-        raise ValueError("slab_params: axis %r, rank %r of %r, halo %r, extents %r" % (axis, rank, world, halo, dims))
-    n = dims[axis]
-    lo, hi = shard_range(n, rank, world)
-    a0, a1 = max(0, lo - halo), min(n, hi + halo)
+    dims, bmin, bmax, org, local, held = _slab_cut("slab_params", dims, axis, rank, world, halo)
     P = type(params).from_buffer_copy(params)
     if hasattr(params, "_keep_grid"):
         P._keep_grid = params._keep_grid
-    bmin, bmax, org = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0, 0, 0]
-    bmin[axis] = lo / n
-    bmax[axis] = hi / n if rank < world - 1 else 2.0
-    org[axis] = a0
     P.box_min[:] = bmin
     P.box_max[:] = bmax
     P.vol_origin[:] = org
     P.global_dims[:] = dims
-    local = list(dims)
-    local[axis] = a1 - a0
-    return P, tuple(local), (a0, a1)
+    return P, local, held
 
 
 def slab_plane(plane, dims, axis, rank, world, halo=1):
@@ -115,21 +112,10 @@ def slab_plane(plane, dims, axis, rank, world, halo=1):
     Returns (plane, local_dims, (a0, a1)) with box_min / box_max (the last rank's box_max is 2.0), vol_origin and
     global_dims set.  The partials of reslice_partial go through composite_sort_last_proj unchanged."""
     import copy
-    dims = [int(q) for q in dims]
-    if len(dims) != 3 or axis not in (0, 1, 2) or not 0 <= rank < world or halo < 0 or world > dims[axis]:
-        raise ValueError("slab_plane: axis %r, rank %r of %r, halo %r, extents %r" % (axis, rank, world, halo, dims))
-    n = dims[axis]
-    lo, hi = shard_range(n, rank, world)
-    a0, a1 = max(0, lo - halo), min(n, hi + halo)
+    dims, bmin, bmax, org, local, held = _slab_cut("slab_plane", dims, axis, rank, world, halo)
     p = copy.copy(plane)
-    bmin, bmax, org = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0, 0, 0]
-    bmin[axis] = lo / n
-    bmax[axis] = hi / n if rank < world - 1 else 2.0
-    org[axis] = a0
     p.box_min, p.box_max, p.vol_origin, p.global_dims = tuple(bmin), tuple(bmax), tuple(org), tuple(dims)
-    local = list(dims)
-    local[axis] = a1 - a0
-    return p, tuple(local), (a0, a1)
+    return p, local, held
 
 
 _compositors = {}
@@ -175,7 +161,7 @@ def composite_sort_last(partial, cam, params, axis=2, group=None, combine=None, 
     gather -- what a C++ host calls); it reads `partial` (and writes `out`) through raw pointers, so anything but a
     contiguous float32 (H, W, 4) device tensor raises ValueError before any C call.  With an injected `combine` (the
     CPU tests: gloo, the oracle's combine) the same exchange runs over torch.distributed point-to-point operations."""
-    return _sort_last(partial, cam, params, None, axis, group, combine, out)
+    return _sort_last("grey", None, partial, cam, params, axis, group, combine, out)
 
 
 def composite_sort_last_tf(partial, cam, params, tf, axis=2, group=None, combine=None, out=None):
@@ -186,7 +172,7 @@ def composite_sort_last_tf(partial, cam, params, tf, axis=2, group=None, combine
     from .render import TransferFunction
     if not isinstance(tf, TransferFunction):
         raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
-    return _sort_last(partial, cam, params, tf, axis, group, combine, out)
+    return _sort_last("colour", tf, partial, cam, params, axis, group, combine, out)
 
 
 def composite_sort_last_proj(partial, proj, group=None, combine=None, out=None):
@@ -197,17 +183,12 @@ def composite_sort_last_proj(partial, proj, group=None, combine=None, out=None):
     torch.distributed point-to-point operations.  MAX and MIN frames equal the single-GPU frame bit for bit."""
     from .render import _check_projection
     _check_projection(proj, partial.device)        # a table goes to C as a raw pointer: it must live where the partial does
-    return _sort_last(partial, None, None, None, 0, group, combine, out, proj)
+    return _sort_last("proj", proj, partial, None, None, 0, group, combine, out)
 
 
-def _sort_last(partial, cam, params, tf, axis, group, combine, out, proj=None):
-    """The exchange of the three calls; proj: projection partials (vr_composite_slabs_proj, no view order); else
-    tf = None: grey partials (vr_composite_slabs), else colour (vr_composite_slabs_tf)."""
-    if proj is not None:
-        inner = combine if combine is not None else _gpu_combine_proj
-        tile_combine = lambda parts, first_pixel, axis, cam, params: inner(parts, proj)     # noqa: E731
-    else:
-        tile_combine = combine
+def _sort_last(kind, finish, partial, cam, params, axis, group, combine, out):
+    """The exchange of the three calls.  kind: "grey" partials, "colour" partials, which `finish` (a TransferFunction)
+    finishes, or "proj" partials, which `finish` (a Projection) combines and finishes without a view order."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     if combine is None and partial.is_cuda:
@@ -225,27 +206,34 @@ def _sort_last(partial, cam, params, tf, axis, group, combine, out, proj=None):
         frame = None
         if rank == 0:
             frame = out if out is not None else torch.empty((H, W, 4), dtype=torch.float32, device=partial.device)
-        dst = C.c_void_p(frame.data_ptr()) if rank == 0 else None
-        if proj is not None:
-            desc = proj.desc()
-            check(_lib.lib().vr_compositor_composite_proj(h, C.c_void_p(partial.data_ptr()), C.byref(desc), dst,
-                                                          _stream_ptr()), "vr_compositor_composite_proj")
-        elif tf is None:
-            check(_lib.lib().vr_compositor_composite(h, C.c_void_p(partial.data_ptr()), int(axis), C.byref(cam),
-                                                     C.byref(params), dst, _stream_ptr()), "vr_compositor_composite")
+        src, dst = C.c_void_p(partial.data_ptr()), C.c_void_p(frame.data_ptr()) if rank == 0 else None
+        if kind == "grey":
+            check(_lib.lib().vr_compositor_composite(h, src, int(axis), C.byref(cam), C.byref(params), dst, _stream_ptr()),
+                  "vr_compositor_composite")
+        elif kind == "colour":
+            desc = finish.desc()
+            check(_lib.lib().vr_compositor_composite_tf(h, src, int(axis), C.byref(cam), C.byref(params), C.byref(desc), dst,
+                                                        _stream_ptr()), "vr_compositor_composite_tf")
         else:
-            desc = tf.desc()
-            check(_lib.lib().vr_compositor_composite_tf(h, C.c_void_p(partial.data_ptr()), int(axis), C.byref(cam),
-                                                        C.byref(params), C.byref(desc), dst, _stream_ptr()),
-                  "vr_compositor_composite_tf")
+            desc = finish.desc()
+            check(_lib.lib().vr_compositor_composite_proj(h, src, C.byref(desc), dst, _stream_ptr()),
+                  "vr_compositor_composite_proj")
         return frame
     H, W = partial.shape[0], partial.shape[1]
-    combine = tile_combine
-    if combine is None:
-        combine = _gpu_combine if tf is None else (lambda *a: _gpu_combine_tf(*a, tf))
+
+    def tile(parts, first_pixel):
+        """The finished pixels of a tile: the injected combine, else the kind's slab call."""
+        if kind == "proj":
+            return (combine or _gpu_combine_proj)(parts, finish)
+        if combine is not None:
+            return combine(parts, first_pixel, axis, cam, params)
+        if kind == "grey":
+            return _gpu_combine(parts, first_pixel, axis, cam, params)
+        return _gpu_combine_tf(parts, first_pixel, axis, cam, params, finish)
+
     rows = tile_rows(H, world)
     if world == 1:
-        return combine(partial.reshape(1, H * W, 4), 0, axis, cam, params).reshape(H, W, 4)
+        return tile(partial.reshape(1, H * W, 4), 0).reshape(H, W, 4)
     # send tile t to rank t, receive my tile from everybody (slab order = rank order)
     send = [partial[lo:hi].reshape(-1, 4).contiguous() for lo, hi in rows]
     my_lo, my_hi = rows[rank]
@@ -263,16 +251,16 @@ def _sort_last(partial, cam, params, tf, axis, group, combine, out, proj=None):
     for req in dist.batch_isend_irecv(ops):
         req.wait()
     parts = torch.stack(recv, 0)
-    tile = combine(parts, my_lo * W, axis, cam, params)
+    done = tile(parts, my_lo * W)
     # gather the finished tiles on rank 0 (tiles may differ by one row: pad to the largest)
     max_rows = max(hi - lo for lo, hi in rows)
-    padded = torch.zeros((max_rows * W, 4), dtype=tile.dtype, device=tile.device)
-    padded[:npix] = tile
+    padded = torch.zeros((max_rows * W, 4), dtype=done.dtype, device=done.device)
+    padded[:npix] = done
     gathered = [torch.empty_like(padded) for _ in range(world)] if rank == 0 else None
     dist.gather(padded, gathered, dst=0, group=group)
     if rank != 0:
         return None
-    frame = torch.empty((H, W, 4), dtype=tile.dtype, device=tile.device)
+    frame = torch.empty((H, W, 4), dtype=done.dtype, device=done.device)
     for r, (lo, hi) in enumerate(rows):
         frame[lo:hi] = gathered[r][:(hi - lo) * W].reshape(hi - lo, W, 4)
     return frame

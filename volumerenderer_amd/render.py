@@ -5,6 +5,7 @@
   UnitBrick      volume_renderer/UnitBrick.h:17-119 (Setup/Bind/Draw/Unbind/Delete;
                  Draw() launches the ray-march kernel on the cube's pixel footprint)
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -68,13 +69,22 @@ def _skip_grid_bytes(dims, cell):
     return n
 
 
+# A volume the frame calls read, dense or a pool: `args` the leading ctypes arguments of its C entry points, `device` where
+# it lives, `dims` its (virtual) extents, `keep` the tensors `args` points into.
+_Source = collections.namedtuple("_Source", "args device dims keep")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
 def _dense_source(volume, dims):
-    """A dense volume and its extents as ctypes int64[3]; ValueError where they do not match."""
+    """A dense volume of `dims` voxels; ValueError where they do not match."""
     v = _as_dev_u8(volume)
     d = (C.c_int64 * 3)(*[int(q) for q in dims])
     if any(q <= 0 for q in d) or v.numel() != d[0] * d[1] * d[2]:
         raise ValueError("volume size does not match dims")
-    return v, d
+    return _Source((_ptr(v), d), v.device, list(d), v)
 
 
 def _check_attached_grid(params, dims, device):
@@ -86,11 +96,25 @@ def _check_attached_grid(params, dims, device):
         _check_buf(g, "skip grid", torch.uint8, _skip_grid_bytes(dims, params.skip_cell), device)
 
 
-def _frame_out(out, params, device):
-    """The [H][W][4] float32 frame: `out` checked, or a new tensor."""
+def _out_or_new(out, shape, device, dtype=torch.float32):
+    """`out` checked to hold `shape`'s elements on `device`, or a new tensor of that shape."""
     if out is None:
-        return torch.empty((params.height, params.width, 4), dtype=torch.float32, device=device)
-    _check_buf(out, "out", torch.float32, params.height * params.width * 4, device)
+        return torch.empty(shape, dtype=dtype, device=device)
+    _check_buf(out, "out", dtype, math.prod(shape), device)
+    return out
+
+
+def _frame(fn, src, cam, params, descriptors, out, stream):
+    """The frame call `fn` of the source `src`: the attached skip grid, then each (check, object) of `descriptors` in turn,
+    then `out` are checked; the objects' desc() follow cam and params in the C call (None: a NULL argument).  Returns the
+    [H][W][4] float32 frame."""
+    _check_attached_grid(params, src.dims, src.device)
+    for chk, obj in descriptors:
+        chk(obj, src.device)
+    out = _out_or_new(out, (params.height, params.width, 4), src.device)
+    descs = [obj.desc() if obj is not None else None for _, obj in descriptors]
+    check(getattr(_lib.lib(), fn)(*src.args, C.byref(cam), C.byref(params),
+                                  *[C.byref(d) if d is not None else None for d in descs], _ptr(out), _stream_ptr(stream)), fn)
     return out
 
 
@@ -104,13 +128,8 @@ def build_skip_grid(volume, dims, cell=8, out=None, stream=None):
         raise ValueError("volume size does not match dims")
     if not 1 <= int(cell) <= 64:
         raise ValueError("cell must be 1..64, not %d" % int(cell))
-    nbytes = _skip_grid_bytes(dims, cell)
-    if out is None:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
-    else:
-        _check_buf(out, "out", torch.uint8, nbytes, v.device)
-    check(_lib.lib().vr_skip_grid_build(C.c_void_p(v.data_ptr()), d, int(cell), C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
-          "vr_skip_grid_build")
+    out = _out_or_new(out, (_skip_grid_bytes(dims, cell),), v.device, torch.uint8)
+    check(_lib.lib().vr_skip_grid_build(_ptr(v), d, int(cell), _ptr(out), _stream_ptr(stream)), "vr_skip_grid_build")
     return out
 
 
@@ -123,39 +142,38 @@ def use_skip_grid(params, grid, cell=8):
 
 def raycast(volume, dims, cam, params, out=None, stream=None):
     """volume: CUDA uint8 (X*Y*Z, x fastest). Returns float32 CUDA [H][W][4], row 0 = top."""
-    v, d = _dense_source(volume, dims)
-    _check_attached_grid(params, dims, v.device)
-    out = _frame_out(out, params, v.device)
-    check(_lib.lib().vr_raycast(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params),
-                                C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast")
-    return out
+    return _frame("vr_raycast", _dense_source(volume, dims), cam, params, (), out, stream)
+
+
+_GREY_PIXEL, _COLOUR_PIXEL = "(c, tau, covered, 0)", "(C.r, C.g, C.b, T)"
+
+
+def _check_partial(t, what, pixel=_COLOUR_PIXEL):
+    """A partial image handed to the combine calls: a contiguous float32 CUDA tensor of whole `pixel`s."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("%s must be a CUDA tensor" % what)
+    if t.numel() == 0 or t.numel() % 4:
+        raise ValueError("%s must hold whole %s pixels, not %d floats" % (what, pixel, t.numel()))
+    _check_buf(t, what, torch.float32, t.numel(), t.device)
+
+
+def _check_pair(front, back, pixel=_COLOUR_PIXEL):
+    _check_partial(front, "front", pixel)
+    _check_buf(back, "back", torch.float32, front.numel(), front.device)
 
 
 def composite_over(front, back, stream=None):
     """front = front OVER back, in place; both contiguous float32 (c, tau, covered, 0) images of the same size."""
-    if not isinstance(front, torch.Tensor) or not front.is_cuda:
-        raise ValueError("front must be a CUDA tensor")
-    if front.numel() == 0 or front.numel() % 4:
-        raise ValueError("front must hold whole (c, tau, covered, 0) pixels, not %d floats" % front.numel())
-    _check_buf(front, "front", torch.float32, front.numel(), front.device)
-    _check_buf(back, "back", torch.float32, front.numel(), front.device)
-    check(_lib.lib().vr_composite_over(C.c_void_p(front.data_ptr()), C.c_void_p(back.data_ptr()),
-                                       front.numel() // 4, _stream_ptr(stream)), "vr_composite_over")
+    _check_pair(front, back, _GREY_PIXEL)
+    check(_lib.lib().vr_composite_over(_ptr(front), _ptr(back), front.numel() // 4, _stream_ptr(stream)), "vr_composite_over")
     return front
 
 
 def composite_finish(partial, out=None, stream=None):
-    if not isinstance(partial, torch.Tensor) or not partial.is_cuda:
-        raise ValueError("partial must be a CUDA tensor")
-    if partial.numel() == 0 or partial.numel() % 4:
-        raise ValueError("partial must hold whole (c, tau, covered, 0) pixels, not %d floats" % partial.numel())
-    _check_buf(partial, "partial", torch.float32, partial.numel(), partial.device)
-    if out is None:
-        out = torch.empty_like(partial)
-    else:
-        _check_buf(out, "out", torch.float32, partial.numel(), partial.device)
-    check(_lib.lib().vr_composite_finish(C.c_void_p(partial.data_ptr()), C.c_void_p(out.data_ptr()),
-                                         partial.numel() // 4, _stream_ptr(stream)), "vr_composite_finish")
+    _check_partial(partial, "partial", _GREY_PIXEL)
+    out = _out_or_new(out, partial.shape, partial.device)
+    check(_lib.lib().vr_composite_finish(_ptr(partial), _ptr(out), partial.numel() // 4, _stream_ptr(stream)),
+          "vr_composite_finish")
     return out
 
 
@@ -241,31 +259,22 @@ def _check_pool(pool, table, grid, device):
 
 
 def _pool_source(pool, table, brick_dims, grid):
-    """A pool and its table checked; the brick extents and the grid as ctypes int64[3]."""
+    """A pool and its table, checked; the source's extents are the virtual volume's."""
     if not isinstance(pool, torch.Tensor):
         raise ValueError("pool must be a torch tensor")
     _check_pool(pool, table, grid, pool.device)
-    return (C.c_int64 * 3)(*[int(q) for q in brick_dims]), (C.c_int64 * 3)(*[int(q) for q in grid])
+    bd, g = (C.c_int64 * 3)(*[int(q) for q in brick_dims]), (C.c_int64 * 3)(*[int(q) for q in grid])
+    return _Source((_ptr(pool), _ptr(table), bd, g), pool.device, [g[k] * bd[k] for k in range(3)], (pool, table))
 
 
 def build_skip_grid_pool(pool, table, brick_dims, grid, cell=8, out=None, stream=None):
     """build_skip_grid of the virtual volume of a pool (vr_skip_grid_build_pool): the same bytes as build_skip_grid of
     that volume assembled densely.  pool, table: as BrickSet.decode_lod_pool returns them."""
-    if not isinstance(pool, torch.Tensor):
-        raise ValueError("pool must be a torch tensor")
-    _check_pool(pool, table, grid, pool.device)
+    src = _pool_source(pool, table, brick_dims, grid)
     if not 1 <= int(cell) <= 64:
         raise ValueError("cell must be 1..64, not %d" % int(cell))
-    bd = (C.c_int64 * 3)(*[int(q) for q in brick_dims])
-    g = (C.c_int64 * 3)(*[int(q) for q in grid])
-    dims = [g[k] * bd[k] for k in range(3)]
-    nbytes = _skip_grid_bytes(dims, cell)
-    if out is None:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=pool.device)
-    else:
-        _check_buf(out, "out", torch.uint8, nbytes, pool.device)
-    check(_lib.lib().vr_skip_grid_build_pool(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, int(cell),
-                                             C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_skip_grid_build_pool")
+    out = _out_or_new(out, (_skip_grid_bytes(src.dims, cell),), src.device, torch.uint8)
+    check(_lib.lib().vr_skip_grid_build_pool(*src.args, int(cell), _ptr(out), _stream_ptr(stream)), "vr_skip_grid_build_pool")
     return out
 
 
@@ -273,12 +282,7 @@ def raycast_pool(pool, table, brick_dims, grid, cam, params, out=None, stream=No
     """raycast of the virtual volume of a pool (vr_raycast_pool): bit-identical to raycast of that volume assembled
     densely (absent bricks 0).  A skip grid attached with use_skip_grid must come from build_skip_grid_pool (or
     build_skip_grid of the dense volume).  Returns float32 CUDA [H][W][4]."""
-    bd, g = _pool_source(pool, table, brick_dims, grid)
-    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
-    out = _frame_out(out, params, pool.device)
-    check(_lib.lib().vr_raycast_pool(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
-                                     C.byref(params), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_pool")
-    return out
+    return _frame("vr_raycast_pool", _pool_source(pool, table, brick_dims, grid), cam, params, (), out, stream)
 
 
 # ---- direct volume rendering with a user transfer function (vr_raycast_tf; the rule is in vrhip.h) -------------------
@@ -314,28 +318,44 @@ def transfer_function_table(points):
     return out
 
 
+def _lut_host(lut, device):
+    """A (256, 4) table of (r, g, b, a) in [0, 1] as contiguous float32 numpy, and the device it goes to (a CUDA
+    tensor's own, else `device`)."""
+    if isinstance(lut, torch.Tensor):
+        device = lut.device if lut.is_cuda else device
+        host = lut.detach().to("cpu", torch.float32).numpy()
+    else:
+        host = np.asarray(lut, np.float32)
+    if host.shape != (256, 4):
+        raise ValueError("lut must be 256 x (r, g, b, a), not %s" % (tuple(host.shape),))
+    if not np.all(np.isfinite(host)) or host.min() < 0.0 or host.max() > 1.0:
+        raise ValueError("lut values must lie in [0, 1]")
+    return np.ascontiguousarray(host), device
+
+
+def _enum_arg(value, names, what):
+    """The int of a "string or enum int" argument: `names` maps the strings; ValueError(`what`, not ...) otherwise."""
+    if isinstance(value, str) and value in names:
+        return names[value]
+    if isinstance(value, int) and not isinstance(value, bool) and value in names.values():
+        return value
+    raise ValueError("%s, not %r" % (what, value))
+
+
 class TransferFunction:
     """A transfer function for raycast_tf / raycast_pool_tf (vr_transfer_function): `lut` the (256, 4) float32 CUDA
     tensor of (r, g, b, a) in [0, 1], entry k for the scalar k / 255; `opacity_unit` the texture-space distance the
     alphas are defined for (0: no correction); `background` the colour behind the volume."""
 
     def __init__(self, lut, opacity_unit=0.0, background=(1.0, 1.0, 1.0), device="cuda"):
-        if isinstance(lut, torch.Tensor):
-            device = lut.device if lut.is_cuda else device
-            host = lut.detach().to("cpu", torch.float32).numpy()
-        else:
-            host = np.asarray(lut, np.float32)
-        if host.shape != (256, 4):
-            raise ValueError("lut must be 256 x (r, g, b, a), not %s" % (tuple(host.shape),))
-        if not np.all(np.isfinite(host)) or host.min() < 0.0 or host.max() > 1.0:
-            raise ValueError("lut values must lie in [0, 1]")
+        host, device = _lut_host(lut, device)
         self.opacity_unit = float(opacity_unit)
         if not math.isfinite(self.opacity_unit) or self.opacity_unit < 0.0:
             raise ValueError("opacity_unit must be finite and >= 0, not %r" % opacity_unit)
         self.background = tuple(float(v) for v in background)
         if len(self.background) != 3 or not all(math.isfinite(v) for v in self.background):
             raise ValueError("background must be three finite values")
-        self.lut = torch.from_numpy(np.ascontiguousarray(host)).to(device)
+        self.lut = torch.from_numpy(host).to(device)
 
     @classmethod
     def from_points(cls, points, opacity_unit=0.0, background=(1.0, 1.0, 1.0), device="cuda"):
@@ -360,28 +380,13 @@ def raycast_tf(volume, dims, cam, params, tf, out=None, stream=None):
     """raycast's frame set-up with the transfer function `tf` (vr_raycast_tf): each sample is looked up in tf's table
     and composited front to back.  params.mode must be RENDER_COMPOSITE.  Returns float32 CUDA [H][W][4] =
     (C + T * background, 1 - T), row 0 = top."""
-    v, d = _dense_source(volume, dims)
-    _check_attached_grid(params, dims, v.device)
-    _check_tf(tf, v.device)
-    out = _frame_out(out, params, v.device)
-    desc = tf.desc()
-    check(_lib.lib().vr_raycast_tf(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
-                                   C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_tf")
-    return out
+    return _frame("vr_raycast_tf", _dense_source(volume, dims), cam, params, [(_check_tf, tf)], out, stream)
 
 
 def raycast_pool_tf(pool, table, brick_dims, grid, cam, params, tf, out=None, stream=None):
     """raycast_tf of the virtual volume of a pool (vr_raycast_pool_tf): bit-identical to raycast_tf of that volume
     assembled densely.  Restrictions and skip grids as raycast_pool."""
-    bd, g = _pool_source(pool, table, brick_dims, grid)
-    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
-    _check_tf(tf, pool.device)
-    out = _frame_out(out, params, pool.device)
-    desc = tf.desc()
-    check(_lib.lib().vr_raycast_pool_tf(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
-                                        C.byref(params), C.byref(desc), C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
-          "vr_raycast_pool_tf")
-    return out
+    return _frame("vr_raycast_pool_tf", _pool_source(pool, table, brick_dims, grid), cam, params, [(_check_tf, tf)], out, stream)
 
 
 # ---- gradient-shaded direct volume rendering (vr_raycast_tf_shaded; the rule is in vrhip.h) ---------------------------
@@ -409,38 +414,28 @@ class Shading:
         return d
 
 
-def _check_shading(shading):
+def _check_shading(shading, device=None):
     if not isinstance(shading, Shading):
         raise ValueError("shading must be a Shading, not %s" % type(shading).__name__)
+
+
+def _check_shading_or_none(shading, device=None):
+    if shading is not None:
+        _check_shading(shading)
 
 
 def raycast_tf_shaded(volume, dims, cam, params, tf, shading, out=None, stream=None):
     """raycast_tf with gradient lighting (vr_raycast_tf_shaded): each sample that contributes is lit by `shading`
     through its lattice gradient.  params.mode must be RENDER_SHADED.  Returns float32 CUDA [H][W][4]."""
-    v, d = _dense_source(volume, dims)
-    _check_attached_grid(params, dims, v.device)
-    _check_tf(tf, v.device)
-    _check_shading(shading)
-    out = _frame_out(out, params, v.device)
-    desc, sh = tf.desc(), shading.desc()
-    check(_lib.lib().vr_raycast_tf_shaded(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
-                                          C.byref(sh), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_tf_shaded")
-    return out
+    return _frame("vr_raycast_tf_shaded", _dense_source(volume, dims), cam, params, [(_check_tf, tf), (_check_shading, shading)],
+                  out, stream)
 
 
 def raycast_pool_tf_shaded(pool, table, brick_dims, grid, cam, params, tf, shading, out=None, stream=None):
     """raycast_tf_shaded of the virtual volume of a pool (vr_raycast_pool_tf_shaded): bit-identical to
     raycast_tf_shaded of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
-    bd, g = _pool_source(pool, table, brick_dims, grid)
-    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
-    _check_tf(tf, pool.device)
-    _check_shading(shading)
-    out = _frame_out(out, params, pool.device)
-    desc, sh = tf.desc(), shading.desc()
-    check(_lib.lib().vr_raycast_pool_tf_shaded(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g,
-                                               C.byref(cam), C.byref(params), C.byref(desc), C.byref(sh),
-                                               C.c_void_p(out.data_ptr()), _stream_ptr(stream)), "vr_raycast_pool_tf_shaded")
-    return out
+    return _frame("vr_raycast_pool_tf_shaded", _pool_source(pool, table, brick_dims, grid), cam, params,
+                  [(_check_tf, tf), (_check_shading, shading)], out, stream)
 
 
 # ---- sort-last colour partials (vr_raycast_tf_partial and the combine calls; the rule is in vrhip.h) -------------------
@@ -448,51 +443,23 @@ def raycast_tf_partial(volume, dims, cam, params, tf, shading=None, out=None, st
     """The colour partial of raycast_tf (shading=None, params.mode RENDER_COMPOSITE) or raycast_tf_shaded (a Shading,
     RENDER_SHADED) for sort-last compositing (vr_raycast_tf_partial): float32 CUDA [H][W][4] = (C.r, C.g, C.b, T) of the
     samples in params' box; (0, 0, 0, 1) where the ray owns none.  tf.background is not used."""
-    v, d = _dense_source(volume, dims)
-    _check_attached_grid(params, dims, v.device)
-    _check_tf(tf, v.device)
-    if shading is not None:
-        _check_shading(shading)
-    out = _frame_out(out, params, v.device)
-    desc, sh = tf.desc(), shading.desc() if shading is not None else None
-    check(_lib.lib().vr_raycast_tf_partial(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
-                                           C.byref(sh) if sh is not None else None, C.c_void_p(out.data_ptr()),
-                                           _stream_ptr(stream)), "vr_raycast_tf_partial")
-    return out
+    return _frame("vr_raycast_tf_partial", _dense_source(volume, dims), cam, params,
+                  [(_check_tf, tf), (_check_shading_or_none, shading)], out, stream)
 
 
 def raycast_pool_tf_partial(pool, table, brick_dims, grid, cam, params, tf, shading=None, out=None, stream=None):
     """raycast_tf_partial of the virtual volume of a pool (vr_raycast_pool_tf_partial): bit-identical to the dense partial
     of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
-    bd, g = _pool_source(pool, table, brick_dims, grid)
-    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
-    _check_tf(tf, pool.device)
-    if shading is not None:
-        _check_shading(shading)
-    out = _frame_out(out, params, pool.device)
-    desc, sh = tf.desc(), shading.desc() if shading is not None else None
-    check(_lib.lib().vr_raycast_pool_tf_partial(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g,
-                                                C.byref(cam), C.byref(params), C.byref(desc),
-                                                C.byref(sh) if sh is not None else None, C.c_void_p(out.data_ptr()),
-                                                _stream_ptr(stream)), "vr_raycast_pool_tf_partial")
-    return out
-
-
-def _check_partial(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError("%s must be a CUDA tensor" % what)
-    if t.numel() == 0 or t.numel() % 4:
-        raise ValueError("%s must hold whole (C.r, C.g, C.b, T) pixels, not %d floats" % (what, t.numel()))
-    _check_buf(t, what, torch.float32, t.numel(), t.device)
+    return _frame("vr_raycast_pool_tf_partial", _pool_source(pool, table, brick_dims, grid), cam, params,
+                  [(_check_tf, tf), (_check_shading_or_none, shading)], out, stream)
 
 
 def composite_over_tf(front, back, stream=None):
     """front = front OVER back on colour partials, in place: (C1 + T1 C2, T1 T2); both contiguous float32 (C.r, C.g,
     C.b, T) images of the same size."""
-    _check_partial(front, "front")
-    _check_buf(back, "back", torch.float32, front.numel(), front.device)
-    check(_lib.lib().vr_composite_over_tf(C.c_void_p(front.data_ptr()), C.c_void_p(back.data_ptr()), front.numel() // 4,
-                                          _stream_ptr(stream)), "vr_composite_over_tf")
+    _check_pair(front, back)
+    check(_lib.lib().vr_composite_over_tf(_ptr(front), _ptr(back), front.numel() // 4, _stream_ptr(stream)),
+          "vr_composite_over_tf")
     return front
 
 
@@ -501,13 +468,10 @@ def composite_finish_tf(partial, tf, out=None, stream=None):
     _check_partial(partial, "partial")
     if not isinstance(tf, TransferFunction):
         raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
-    if out is None:
-        out = torch.empty_like(partial)
-    else:
-        _check_buf(out, "out", torch.float32, partial.numel(), partial.device)
+    out = _out_or_new(out, partial.shape, partial.device)
     desc = tf.desc()
-    check(_lib.lib().vr_composite_finish_tf(C.c_void_p(partial.data_ptr()), C.byref(desc), C.c_void_p(out.data_ptr()),
-                                            partial.numel() // 4, _stream_ptr(stream)), "vr_composite_finish_tf")
+    check(_lib.lib().vr_composite_finish_tf(_ptr(partial), C.byref(desc), _ptr(out), partial.numel() // 4, _stream_ptr(stream)),
+          "vr_composite_finish_tf")
     return out
 
 
@@ -522,14 +486,7 @@ class Projection:
     colour map of (r, g, b, a) in [0, 1] looked up with the displayed value.  Raises ValueError on bad values."""
 
     def __init__(self, op="max", window=(0.0, 1.0), background=(0.0, 0.0, 0.0), lut=None, device="cuda"):
-        if isinstance(op, str):
-            if op not in _PROJECT_OPS:
-                raise ValueError("op must be 'max', 'min' or 'mean', not %r" % op)
-            self.op = _PROJECT_OPS[op]
-        elif isinstance(op, int) and not isinstance(op, bool) and op in _PROJECT_OPS.values():
-            self.op = op
-        else:
-            raise ValueError("op must be 'max', 'min' or 'mean', not %r" % (op,))
+        self.op = _enum_arg(op, _PROJECT_OPS, "op must be 'max', 'min' or 'mean'")
         try:
             self.window = tuple(float(v) for v in window)
         except TypeError:
@@ -544,16 +501,8 @@ class Projection:
             raise ValueError("background must be three finite values")
         self.lut = None
         if lut is not None:
-            if isinstance(lut, torch.Tensor):
-                device = lut.device if lut.is_cuda else device
-                host = lut.detach().to("cpu", torch.float32).numpy()
-            else:
-                host = np.asarray(lut, np.float32)
-            if host.shape != (256, 4):
-                raise ValueError("lut must be 256 x (r, g, b, a), not %s" % (tuple(host.shape),))
-            if not np.all(np.isfinite(host)) or host.min() < 0.0 or host.max() > 1.0:
-                raise ValueError("lut values must lie in [0, 1]")
-            self.lut = torch.from_numpy(np.ascontiguousarray(host)).to(device)
+            host, device = _lut_host(lut, device)
+            self.lut = torch.from_numpy(host).to(device)
 
     def desc(self):
         d = _lib.Projection()
@@ -571,62 +520,41 @@ def _check_projection(proj, device):
         _check_buf(proj.lut, "proj.lut", torch.float32, 256 * 4, device)
 
 
-def _projection_dense(fn, volume, dims, cam, params, proj, out, stream):
-    v, d = _dense_source(volume, dims)
-    _check_attached_grid(params, dims, v.device)
-    _check_projection(proj, v.device)
-    out = _frame_out(out, params, v.device)
-    desc = proj.desc()
-    check(getattr(_lib.lib(), fn)(C.c_void_p(v.data_ptr()), d, C.byref(cam), C.byref(params), C.byref(desc),
-                                  C.c_void_p(out.data_ptr()), _stream_ptr(stream)), fn)
-    return out
-
-
-def _projection_pool(fn, pool, table, brick_dims, grid, cam, params, proj, out, stream):
-    bd, g = _pool_source(pool, table, brick_dims, grid)
-    _check_attached_grid(params, [g[k] * bd[k] for k in range(3)], pool.device)
-    _check_projection(proj, pool.device)
-    out = _frame_out(out, params, pool.device)
-    desc = proj.desc()
-    check(getattr(_lib.lib(), fn)(C.c_void_p(pool.data_ptr()), C.c_void_p(table.data_ptr()), bd, g, C.byref(cam),
-                                  C.byref(params), C.byref(desc), C.c_void_p(out.data_ptr()), _stream_ptr(stream)), fn)
-    return out
-
-
 def raycast_projection(volume, dims, cam, params, proj, out=None, stream=None):
     """The intensity projection `proj` of a dense volume (vr_raycast_projection): raycast's rays, no early exit; the
     maximum, minimum or mean of every ray's samples in params' box, windowed, grey or through proj.lut.  params.mode must
     be RENDER_PROJECTION.  Returns float32 CUDA [H][W][4], row 0 = top; (background, 0) where the ray owns no sample."""
-    return _projection_dense("vr_raycast_projection", volume, dims, cam, params, proj, out, stream)
+    return _frame("vr_raycast_projection", _dense_source(volume, dims), cam, params, [(_check_projection, proj)], out, stream)
 
 
 def raycast_pool_projection(pool, table, brick_dims, grid, cam, params, proj, out=None, stream=None):
     """raycast_projection of the virtual volume of a pool (vr_raycast_pool_projection): bit-identical to
     raycast_projection of that volume assembled densely.  Restrictions and skip grids as raycast_pool."""
-    return _projection_pool("vr_raycast_pool_projection", pool, table, brick_dims, grid, cam, params, proj, out, stream)
+    return _frame("vr_raycast_pool_projection", _pool_source(pool, table, brick_dims, grid), cam, params,
+                  [(_check_projection, proj)], out, stream)
 
 
 def raycast_projection_partial(volume, dims, cam, params, proj, out=None, stream=None):
     """The projection partial of raycast_projection for sort-last compositing (vr_raycast_projection_partial): float32
     CUDA [H][W][4] = (v, n, 0, 0), n the owned samples and v their maximum, minimum or sum; zeros where n = 0."""
-    return _projection_dense("vr_raycast_projection_partial", volume, dims, cam, params, proj, out, stream)
+    return _frame("vr_raycast_projection_partial", _dense_source(volume, dims), cam, params, [(_check_projection, proj)], out,
+                  stream)
 
 
 def raycast_pool_projection_partial(pool, table, brick_dims, grid, cam, params, proj, out=None, stream=None):
     """raycast_projection_partial of the virtual volume of a pool (vr_raycast_pool_projection_partial)."""
-    return _projection_pool("vr_raycast_pool_projection_partial", pool, table, brick_dims, grid, cam, params, proj, out,
-                            stream)
+    return _frame("vr_raycast_pool_projection_partial", _pool_source(pool, table, brick_dims, grid), cam, params,
+                  [(_check_projection, proj)], out, stream)
 
 
 def composite_combine_proj(front, back, proj, stream=None):
     """front = combine(front, back) on projection partials, in place: n adds, v is the max, the min or the sum by
     proj.op; a partial with n = 0 is ignored.  Both contiguous float32 (v, n, 0, 0) images of the same size."""
-    _check_partial(front, "front")
-    _check_buf(back, "back", torch.float32, front.numel(), front.device)
+    _check_pair(front, back)
     if not isinstance(proj, Projection):
         raise ValueError("proj must be a Projection, not %s" % type(proj).__name__)
-    check(_lib.lib().vr_composite_combine_proj(C.c_void_p(front.data_ptr()), C.c_void_p(back.data_ptr()), front.numel() // 4,
-                                               proj.op, _stream_ptr(stream)), "vr_composite_combine_proj")
+    check(_lib.lib().vr_composite_combine_proj(_ptr(front), _ptr(back), front.numel() // 4, proj.op, _stream_ptr(stream)),
+          "vr_composite_combine_proj")
     return front
 
 
@@ -634,13 +562,10 @@ def composite_finish_proj(partial, proj, out=None, stream=None):
     """The frame of a projection partial (vr_composite_finish_proj): the window, then grey or proj.lut."""
     _check_partial(partial, "partial")
     _check_projection(proj, partial.device)
-    if out is None:
-        out = torch.empty_like(partial)
-    else:
-        _check_buf(out, "out", torch.float32, partial.numel(), partial.device)
+    out = _out_or_new(out, partial.shape, partial.device)
     desc = proj.desc()
-    check(_lib.lib().vr_composite_finish_proj(C.c_void_p(partial.data_ptr()), C.byref(desc), C.c_void_p(out.data_ptr()),
-                                              partial.numel() // 4, _stream_ptr(stream)), "vr_composite_finish_proj")
+    check(_lib.lib().vr_composite_finish_proj(_ptr(partial), C.byref(desc), _ptr(out), partial.numel() // 4,
+                                              _stream_ptr(stream)), "vr_composite_finish_proj")
     return out
 
 
@@ -676,14 +601,7 @@ class SlicePlane:
         self.width, self.height, self.layers = int(width), int(height), int(layers)
         if self.layers > 1 << 24 or self.width >= 1 << 31 or self.height >= 1 << 31:
             raise ValueError("width, height must fit an int32 and layers 2^24, not %r x %r x %r" % (width, height, layers))
-        if isinstance(filter, str):
-            if filter not in _SLICE_FILTERS:
-                raise ValueError("filter must be 'nearest' or 'linear', not %r" % filter)
-            self.filter = _SLICE_FILTERS[filter]
-        elif isinstance(filter, int) and not isinstance(filter, bool) and filter in _SLICE_FILTERS.values():
-            self.filter = filter
-        else:
-            raise ValueError("filter must be 'nearest' or 'linear', not %r" % (filter,))
+        self.filter = _enum_arg(filter, _SLICE_FILTERS, "filter must be 'nearest' or 'linear'")
         self.origin, self.du, self.dv, self.dw = _vec3(origin, "origin"), _vec3(du, "du"), _vec3(dv, "dv"), _vec3(dw, "dw")
         self.box_min, self.box_max = _vec3(box_min, "box_min"), _vec3(box_max, "box_max")
         self.global_dims = tuple(int(q) for q in global_dims)
@@ -753,20 +671,16 @@ def _check_plane(plane):
 
 
 def _slice_out(out, plane, device):
-    if out is None:
-        return torch.empty((plane.height, plane.width, 4), dtype=torch.float32, device=device)
-    _check_buf(out, "out", torch.float32, plane.height * plane.width * 4, device)
-    return out
+    return _out_or_new(out, (plane.height, plane.width, 4), device)
 
 
 def _reslice_dense(fn, volume, dims, plane, proj, out, stream):
-    v, d = _dense_source(volume, dims)
+    src = _dense_source(volume, dims)
     _check_plane(plane)
-    _check_projection(proj, v.device)
-    out = _slice_out(out, plane, v.device)
+    _check_projection(proj, src.device)
+    out = _slice_out(out, plane, src.device)
     pd, desc = plane.desc(), proj.desc()
-    check(getattr(_lib.lib(), fn)(C.c_void_p(v.data_ptr()), d, C.byref(pd), C.byref(desc), C.c_void_p(out.data_ptr()),
-                                  _stream_ptr(stream)), fn)
+    check(getattr(_lib.lib(), fn)(*src.args, C.byref(pd), C.byref(desc), _ptr(out), _stream_ptr(stream)), fn)
     return out
 
 

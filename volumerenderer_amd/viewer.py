@@ -14,6 +14,25 @@ from .render import (POOL_ENTRY, assemble_bricks, build_skip_grid_pool, default_
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
 
+_DENSE_FRAMES = (raycast, raycast_tf, raycast_tf_shaded, raycast_projection)
+_POOL_FRAMES = (raycast_pool, raycast_pool_tf, raycast_pool_tf_shaded, raycast_pool_projection)
+
+
+def _style(mode, tf, shading, projection):
+    """How draw and draw_lod_pool draw a frame: (the mode of its params, the index of its call in _DENSE_FRAMES /
+    _POOL_FRAMES, the arguments that call takes between params and out)."""
+    if projection is not None:
+        if tf is not None or shading is not None:
+            raise ValueError("a projection takes neither a transfer function nor shading")
+        if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_PROJECTION):
+            raise ValueError("a projection is drawn in RENDER_PROJECTION mode, not mode %r" % (mode,))
+        return _lib.RENDER_PROJECTION, 3, (projection,)
+    if shading is not None:
+        if tf is None:
+            raise ValueError("shading requires a transfer function (tf=)")
+        return _lib.RENDER_SHADED, 2, (tf, shading)
+    return (mode, 1, (tf,)) if tf is not None else (mode, 0, ())
+
 
 class HeadlessViewer:
     def __init__(self, width=1600, height=1200):
@@ -84,23 +103,9 @@ class HeadlessViewer:
         """One frame of `volume`: raycast, or raycast_tf through the TransferFunction `tf` (composite mode only).
         shading: a Shading (requires tf): the frame is drawn with raycast_tf_shaded in RENDER_SHADED mode.
         projection: a Projection (neither tf nor shading): drawn with raycast_projection in RENDER_PROJECTION mode."""
-        if projection is not None:
-            if tf is not None or shading is not None:
-                raise ValueError("a projection takes neither a transfer function nor shading")
-            if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_PROJECTION):
-                raise ValueError("a projection is drawn in RENDER_PROJECTION mode, not mode %r" % (mode,))
-            P = default_params(self.width, self.height, brick_dims, _lib.RENDER_PROJECTION, float(self.currIsoVal) / 255.0)
-            return raycast_projection(volume, dims, self.camera(), P, projection, out)
-        if shading is not None:
-            if tf is None:
-                raise ValueError("shading requires a transfer function (tf=)")
-            mode = _lib.RENDER_SHADED
+        mode, call, extra = _style(mode, tf, shading, projection)
         P = default_params(self.width, self.height, brick_dims, mode, float(self.currIsoVal) / 255.0)
-        if shading is not None:
-            return raycast_tf_shaded(volume, dims, self.camera(), P, tf, shading, out)
-        if tf is not None:
-            return raycast_tf(volume, dims, self.camera(), P, tf, out)
-        return raycast(volume, dims, self.camera(), P, out)
+        return _DENSE_FRAMES[call](volume, dims, self.camera(), P, *extra, out)
 
     def draw_lod(self, bset, brick_ijk, grid, pixel_tolerance=1.0, mode=_lib.RENDER_COMPOSITE, out=None):
         """One frame from a BrickSet: select_lod for this frame's camera, decode_lod, assemble, ray-cast.  The bricks
@@ -132,16 +137,7 @@ class HeadlessViewer:
         Shading, drawn with raycast_pool_tf_shaded in RENDER_SHADED mode (select_lod included); projection (neither tf nor
         shading): a Projection, drawn with raycast_pool_projection in RENDER_PROJECTION mode.  Returns (frame, cuts)."""
         import torch
-        if projection is not None:
-            if tf is not None or shading is not None:
-                raise ValueError("a projection takes neither a transfer function nor shading")
-            if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_PROJECTION):
-                raise ValueError("a projection is drawn in RENDER_PROJECTION mode, not mode %r" % (mode,))
-            mode = _lib.RENDER_PROJECTION
-        if shading is not None:
-            if tf is None:
-                raise ValueError("shading requires a transfer function (tf=)")
-            mode = _lib.RENDER_SHADED
+        mode, call, extra = _style(mode, tf, shading, projection)
         bd = tuple(int(q) for q in bset.dims)
         g = tuple(int(q) for q in grid)
         info = bset.info(0)
@@ -159,13 +155,7 @@ class HeadlessViewer:
         if skip_cell > 0:
             sg = build_skip_grid_pool(self._pool, self._poolTable, bd, g, skip_cell)
             use_skip_grid(P, sg, skip_cell)
-        if projection is not None:
-            return raycast_pool_projection(self._pool, self._poolTable, bd, g, cam, P, projection, out), cuts
-        if shading is not None:
-            return raycast_pool_tf_shaded(self._pool, self._poolTable, bd, g, cam, P, tf, shading, out), cuts
-        if tf is not None:
-            return raycast_pool_tf(self._pool, self._poolTable, bd, g, cam, P, tf, out), cuts
-        return raycast_pool(self._pool, self._poolTable, bd, g, cam, P, out), cuts
+        return _POOL_FRAMES[call](self._pool, self._poolTable, bd, g, cam, P, *extra, out), cuts
 
     def draw_slice(self, volume, dims, plane, projection, out=None):
         """The slice `plane` (a SlicePlane) of `volume` through the Projection `projection`: reslice.  A slice has its
