@@ -27,6 +27,7 @@ struct Switches {
     bool decodeFineV1 = false;   // VRHIP_DECODE_FINE_V1: round 1's k_decode_fine
     bool decodeQuad = false;     // VRHIP_DECODE_QUAD: round 2's k_decode_quad instead of k_decode_region
     bool noSkipBlocks = false;   // VRHIP_NO_SKIP_BLOCKS
+    bool noUniformBlocks = false; // VRHIP_NO_UNIFORM_BLOCKS: constant 4096-leaf blocks go through k_prune_emit12, not k_prune_emit12_const
 };
 
 // vr_brickset_decode_lod: the device state of one call.  Calls take the slots of a ring in turn; a call waits on the

@@ -245,6 +245,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         w.decodeFineV1 = getenv("VRHIP_DECODE_FINE_V1") != nullptr;
         w.decodeQuad = getenv("VRHIP_DECODE_QUAD") != nullptr;
         w.noSkipBlocks = getenv("VRHIP_NO_SKIP_BLOCKS") != nullptr;
+        w.noUniformBlocks = getenv("VRHIP_NO_UNIFORM_BLOCKS") != nullptr;
     }
     make_geom(b.g, dims);
     b.D = b.g.D;
@@ -307,6 +308,7 @@ vr_status vr_brickset_set_switch(vr_brickset *h, const char *name, int32_t value
     else if (!strcmp(name, "decode_fine_v1")) w.decodeFineV1 = on;
     else if (!strcmp(name, "decode_quad")) w.decodeQuad = on;
     else if (!strcmp(name, "no_skip_blocks")) w.noSkipBlocks = on;
+    else if (!strcmp(name, "no_uniform_blocks")) w.noUniformBlocks = on;
     else return VR_ERR_INVALID;
     return VR_OK;
 }

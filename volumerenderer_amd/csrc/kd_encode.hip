@@ -1593,6 +1593,7 @@ struct PruneEmitArgs {
     uint8_t *gap, *gapR;           // the streams' block-gapped buffers (Stream2::tree)
     int64_t treeCap;
     SkipBlocks sk, skR;            // blocks the level loop left alone below depth D-2: all "keep", exactly reproduced (per stream)
+    int uniformBlocks;             // constant blocks (flag bit 0) are k_prune_emit12_const's: k_prune_emit12<false, true> leaves them alone
 };
 
 __device__ __forceinline__ void pe_put(uint32_t *W, uint32_t bitpos, unsigned long long v, int ntok)
@@ -1604,6 +1605,59 @@ __device__ __forceinline__ void pe_put(uint32_t *W, uint32_t bitpos, unsigned lo
     if ((uint32_t)(lo >> 32)) atomicOr(&W[w + 1], (uint32_t)(lo >> 32));
     const uint32_t hi = sh ? (uint32_t)(v >> (64u - sh)) : 0u;
     if (hi) atomicOr(&W[w + 2], hi);
+}
+
+// The leaf stage of k_prune_emit12 for one sibling pair in packed 16-bit lanes (k_prune_emit12_const evaluates one pair
+// per constant block with the same code).  dl: truth minus reconstruction, cl2: the pair's level-loop codes.  Prune
+// (R.cpp:618-626), then the grown branch from the table (k_chain_lut) where no clamp can matter; the lanes in `act`
+// are left to pe_leaf_step.  bothMask gets bit 2j where both leaves are pruned tokens.
+template <class LUT>     // lut(k): entry k of k_chain_lut's signed-key table, wherever the caller keeps it
+__device__ __forceinline__ void pe_leaf_table(uint32_t T2, vr_s16x2 dl, uint32_t cl2, uint32_t tol2, const LUT &lut, vr_s16x2 &mxB,
+                                                  uint32_t &m, uint32_t &sg, uint32_t &act, uint32_t &Lb, uint32_t &nt,
+                                                  uint32_t &bothMask, int j)
+{
+    const vr_s16x2 mm = pk_abs(dl);
+    m = pk_u(mm);
+    sg = pk_u(dl >> 15);
+    mxB = __builtin_elementwise_max(mxB, mm);
+    const uint32_t lt = pk_u((mm - pk_s(tol2)) >> 15);                                     // err < tol
+    const uint32_t isz = pk_u((pk_s(cl2) - pk_s(0x00010001u)) >> 15), is3 = pk_u((pk_s(0x00020002u) - pk_s(cl2)) >> 15);
+    const uint32_t newp = isz & lt;
+    const uint32_t pruned = newp | is3;
+    const uint32_t lcode = cl2 | (newp & 0x00030003u);
+    bothMask |= ((pruned & (pruned >> 16)) & 1u) << (2 * j);     // at the bit of the pair node's code (k_prune_emit12's upper levels)
+    const vr_s16x2 lim = __builtin_elementwise_min(pk_s(T2), pk_s(T2 ^ 0x00FF00FFu));
+    const uint32_t viol = pk_u((lim - mm) >> 15);                                          // a clamp could matter
+    const uint32_t e0 = lut(pk_u(dl) & 511u), e1 = lut((pk_u(dl) >> 16) & 511u);           // keyed by the signed error
+    const uint32_t useL = ~pruned & ~viol;
+    const uint32_t ch2 = __builtin_amdgcn_perm(e1, e0, 0x07060302u);                           // the two token strings
+    Lb = lcode | ((useL & ch2) << 2);
+    nt = 0x00010001u + (useL & __builtin_amdgcn_perm(e1, e0, 0x0c050c01u));            // the two counts
+    m = (useL & __builtin_amdgcn_perm(e1, e0, 0x0c040c00u)) | (~useL & m);         // the two final errors
+    act = ~pruned & viol;
+}
+// ... and step i (distance d2 = (64 >> i) in both lanes) of the exact path for the lanes in `act`, the leaves the table does not cover
+__device__ __forceinline__ void pe_leaf_step(int i, int nsteps, uint32_t d2, uint32_t tol2, uint32_t T2, uint32_t &m, uint32_t &sg, uint32_t &act,
+                                             uint32_t &Lb, uint32_t &nt, uint32_t &keepEnd, uint32_t &anyAct)
+{
+    const vr_s16x2 mm = pk_s(m);
+    const uint32_t gt = pk_u((pk_s(tol2) - mm) >> 15);
+    nt = pk_u(pk_s(nt) - pk_s(act));
+    const uint32_t go = act & gt;
+    const uint32_t term = (act ^ go) & 0x00030003u;                                 // R.cpp:699-703
+    const uint32_t lim = (sg & T2) | (~sg & (T2 ^ 0x00FF00FFu));
+    const vr_s16x2 x = __builtin_elementwise_min(pk_s(d2) - mm, pk_s(lim));
+    const vr_s16x2 nx = (vr_s16x2)(0) - x, ax = __builtin_elementwise_max(x, nx);
+    const uint32_t take = go & pk_u((ax - mm) >> 15);
+    const uint32_t dir = pk_u(pk_s(0x00010001u) - pk_s(sg));                        // add = 1, sub = 2
+    Lb |= ((take & dir) | term) << (2 * i + 2);
+    // an evaluated node that keeps leaves its error (> tol) unchanged, so the branch goes on unless this
+    // was the last level: only there can a branch end on a "keep" (zero-run rewrite, see Ctrl::zeroRun)
+    if (i == nsteps - 1) keepEnd |= go & ~take;
+    m = (take & pk_u(ax)) | (~take & m);
+    sg ^= take & pk_u(nx >> 15);
+    act = go;
+    anyAct |= go;
 }
 
 // RANGE (MidRangeTree, M.cpp:864-865, 871-982): the half-range stream has the mid stream's STRUCTURE -- a node is
@@ -1628,6 +1682,11 @@ k_prune_emit12(PruneEmitArgs a)
     if (cConst) return;
     const uint32_t blk = blockIdx.x, base = blk << 12;
     uint8_t *Cb = a.codes + (int64_t)brick * a.codeStride;
+    uint32_t bflag = 0;
+    if (!RANGE && LEAFLESS && a.uniformBlocks) {     // a constant block has a kernel of its own (k_prune_emit12_const)
+        bflag = a.sk.flag[(int64_t)brick * a.sk.nBlk + blk];
+        if (bflag & 1u) return;
+    }
     // ---- every global load of the block, in one batch
     const uint32_t lutV = a.chainLut[VR_CHAIN_LUT_SIGNED + t], lutV2 = a.chainLut[VR_CHAIN_LUT_SIGNED + 256 + t];
     const int hU = t ? t : 1, lqU = 31 - __clz(hU);
@@ -1639,7 +1698,8 @@ k_prune_emit12(PruneEmitArgs a)
     const int64_t li = ((int64_t)1 << D) + base + t * 16;
     // a block the level loop skipped (SkipBlocks) has no codes and no reconstruction in memory at depths D-1 and D:
     // they are all "keep" and exact, which is what zeros here say
-    const bool skipB = a.sk.flag && (a.sk.flag[(int64_t)brick * a.sk.nBlk + blk] & 2u) != 0u;
+    const bool skipB = (!RANGE && LEAFLESS && a.uniformBlocks) ? (bflag & 2u) != 0u
+                                                                : a.sk.flag && (a.sk.flag[(int64_t)brick * a.sk.nBlk + blk] & 2u) != 0u;
     uint32_t c1H = 0, cpk = 0;
     uint4 tv = make_uint4(0, 0, 0, 0), rv = make_uint4(0, 0, 0, 0);
     uint2 pv = make_uint2(0, 0), pvR = make_uint2(0, 0);      // leafless: my leaves' eight parents (the level loop's last parents buffer but one)
@@ -1747,25 +1807,7 @@ k_prune_emit12(PruneEmitArgs a)
                 dl = pk_s(T2[jj]) - pk_s(__builtin_amdgcn_perm(0, rw[j >> 1], sel));
                 cl2 = ((cpk >> (4 * j)) & 3u) | (((cpk >> (4 * j + 2)) & 3u) << 16);
             }
-            const vr_s16x2 mm = pk_abs(dl);
-            m[jj] = pk_u(mm);
-            sg[jj] = pk_u(dl >> 15);
-            mxB = __builtin_elementwise_max(mxB, mm);
-            const uint32_t lt = pk_u((mm - pk_s(tol2)) >> 15);                                     // err < tol
-            const uint32_t isz = pk_u((pk_s(cl2) - pk_s(0x00010001u)) >> 15), is3 = pk_u((pk_s(0x00020002u) - pk_s(cl2)) >> 15);
-            const uint32_t newp = isz & lt;
-            const uint32_t pruned = newp | is3;
-            const uint32_t lcode = cl2 | (newp & 0x00030003u);
-            bothMask |= ((pruned & (pruned >> 16)) & 1u) << (2 * j);     // at the bit of the pair node's code (below)
-            const vr_s16x2 lim = __builtin_elementwise_min(pk_s(T2[jj]), pk_s(T2[jj] ^ 0x00FF00FFu));
-            const uint32_t viol = pk_u((lim - mm) >> 15);                                          // a clamp could matter
-            const uint32_t e0 = lutS[pk_u(dl) & 511u], e1 = lutS[(pk_u(dl) >> 16) & 511u];         // keyed by the signed error
-            const uint32_t useL = ~pruned & ~viol;
-            const uint32_t ch2 = __builtin_amdgcn_perm(e1, e0, 0x07060302u);                           // the two token strings
-            Lb[j] = lcode | ((useL & ch2) << 2);
-            nt[j] = 0x00010001u + (useL & __builtin_amdgcn_perm(e1, e0, 0x0c050c01u));            // the two counts
-            m[jj] = (useL & __builtin_amdgcn_perm(e1, e0, 0x0c040c00u)) | (~useL & m[jj]);         // the two final errors
-            act[jj] = ~pruned & viol;
+            pe_leaf_table(T2[jj], dl, cl2, tol2, [&](uint32_t k) { return lutS[k]; }, mxB, m[jj], sg[jj], act[jj], Lb[j], nt[j], bothMask, j);
             anyAct |= act[jj];
         }
         for (int i = 0; i < nsteps; ++i) {    // exact stepping for the leaves the table does not cover
@@ -1776,24 +1818,7 @@ k_prune_emit12(PruneEmitArgs a)
             for (int jj = 0; jj < 4; ++jj) {
                 const int j = half * 4 + jj;
                 if (__ballot(act[jj] != 0u) == 0ull) continue;     // such leaves are rare: usually one pair slot of the wave at most
-                const vr_s16x2 mm = pk_s(m[jj]);
-                const uint32_t gt = pk_u((pk_s(tol2) - mm) >> 15);
-                nt[j] = pk_u(pk_s(nt[j]) - pk_s(act[jj]));
-                const uint32_t go = act[jj] & gt;
-                const uint32_t term = (act[jj] ^ go) & 0x00030003u;                                 // R.cpp:699-703
-                const uint32_t lim = (sg[jj] & T2[jj]) | (~sg[jj] & (T2[jj] ^ 0x00FF00FFu));
-                const vr_s16x2 x = __builtin_elementwise_min(pk_s(d2) - mm, pk_s(lim));
-                const vr_s16x2 nx = (vr_s16x2)(0) - x, ax = __builtin_elementwise_max(x, nx);
-                const uint32_t take = go & pk_u((ax - mm) >> 15);
-                const uint32_t dir = pk_u(pk_s(0x00010001u) - pk_s(sg[jj]));                        // add = 1, sub = 2
-                Lb[j] |= ((take & dir) | term) << (2 * i + 2);
-                // an evaluated node that keeps leaves its error (> tol) unchanged, so the branch goes on unless this
-                // was the last level: only there can a branch end on a "keep" (zero-run rewrite, see Ctrl::zeroRun)
-                if (i == nsteps - 1) keepEnd |= go & ~take;
-                m[jj] = (take & pk_u(ax)) | (~take & m[jj]);
-                sg[jj] ^= take & pk_u(nx >> 15);
-                act[jj] = go;
-                anyAct |= go;
+                pe_leaf_step(i, nsteps, d2, tol2, T2[jj], m[jj], sg[jj], act[jj], Lb[j], nt[j], keepEnd, anyAct);
             }
         }
         if (!RANGE && keepEnd) atomicAdd(&c.zeroRun, (int)((keepEnd & 1u) + ((keepEnd >> 16) & 1u)));
@@ -2012,6 +2037,200 @@ k_prune_emit12(PruneEmitArgs a)
     for (uint32_t i = t; i < nw; i += 256u) slot[i] = W[i];
 }
 
+
+// ---- constant 4096-leaf blocks (flag bit 0 of k_pyramid12) of a leafless SkipBlocks build: closed form ----------
+// By induction from its root such a block is uniform: every node of a level has the same truth, the same parent
+// reconstruction, hence the same code and error, and every leaf grows the same branch.  What k_prune_emit12 computes
+// for it is a function of a few scalars -- the value, one code per level, the leaf's parent reconstruction, the two
+// final distances -- and this kernel writes the same bytes from them: one leaf pair through the leaf stage's own code
+// (leaf_pair_encode, pe_leaf_table, pe_leaf_step), the bottom-up prune (R.cpp:596-629) on twelve scalars, and the
+// string, the preorder of a perfect tree with one token per level, at closed-form positions: thread t's tokens start
+// at t * len[8] + sum over the live in-block levels lq <= 7 of ceil(t / 2^(8-lq)) -- no scan, no prune levels in LDS.
+// A workgroup takes PEC_BOXES consecutive blocks: one batch of scalar loads, one lane per block for the chain, the
+// one-token blocks (two thirds of all constant ones) written by a few lanes each, the others composed one after the other:
+// the 16-leaf subtree, one string for all 256 threads, is made once and shifted to each thread's position.
+// k_prune_emit12<false, true> returns on the blocks this kernel owns (PruneEmitArgs::uniformBlocks).
+#ifndef PEC_BOXES
+#define PEC_BOXES 16
+#endif
+__global__ void __launch_bounds__(256)
+k_prune_emit12_const(PruneEmitArgs a)
+{
+    __shared__ uint32_t lutS[512];
+    __shared__ uint32_t W[PE_WORDS];
+    // per block: the codes of in-block levels 0 .. 11, [12] the value, [13] the leaves' parent reconstruction, [14] the flags
+    __shared__ __attribute__((aligned(16))) uint8_t sc[PEC_BOXES][16];
+    __shared__ uint32_t res[PEC_BOXES][6];
+    __shared__ uint32_t Pc[12];                       // the 16-leaf subtree's string (at most 159 tokens), zero behind it
+    const int brick = blockIdx.y, t = threadIdx.x, D = a.D, tol = a.tol;
+    Ctrl &c = a.ctrls[brick];
+    const int cConst = c.constBrick, cRa = c.ra, cDistR = c.finalReconDist, cDistC = c.finalCodesDist;     // one scalar round trip
+    if (cConst) return;
+    const uint32_t nBlk = (uint32_t)a.sk.nBlk, blk0 = blockIdx.x * (uint32_t)PEC_BOXES;
+    uint8_t *Cb = a.codes + (int64_t)brick * a.codeStride;
+    const uint8_t *Tb = a.temp + (int64_t)brick * a.heapStride;
+    const uint8_t *Pb = (cRa == 0 ? a.rb.b[0] : (cRa == 1 ? a.rb.b[1] : a.rb.b[2])) + (int64_t)brick * a.leafStride;
+    lutS[t] = a.chainLut[VR_CHAIN_LUT_SIGNED + t]; lutS[256 + t] = a.chainLut[VR_CHAIN_LUT_SIGNED + 256 + t];
+    // ---- the blocks' scalars.  A skipped block (bit 1) has nothing in memory at depths D-1 and D: "keep" and exact
+    for (int i = t; i < PEC_BOXES * 16; i += 256) {
+        const int b = i >> 4, l = i & 15;
+        const uint32_t blk = blk0 + (uint32_t)b;
+        uint32_t val = 0;
+        if (blk < nBlk) {
+            const uint32_t f = a.sk.flag[(int64_t)brick * a.sk.nBlk + blk];
+            const bool filled = (f & 3u) == 1u;
+            if (l == 14) val = f;
+            else if (f & 1u) {
+                if (l < 11 || (l == 11 && filled)) val = (uint32_t)cget(Cb, ((int64_t)1 << (D - 12 + l)) + ((int64_t)blk << l));
+                else if (l == 12) val = Tb[((int64_t)1 << (D - 12)) + blk];
+                else if (l == 13 && filled) val = Pb[(int64_t)blk << 11];
+            }
+        }
+        sc[b][l] = (uint8_t)val;
+    }
+    __syncthreads();
+    // ---- one lane per block: leaf, prune, subtree lengths
+    if (t < PEC_BOXES) {
+        const uint4 q = *(const uint4 *)sc[t];
+        const uint32_t f = (q.w >> 16) & 255u;
+        uint32_t kind = 0;                                  // 0: not mine, 1: the one-token early exit, 2: a string
+        if (f & 1u) {
+            const bool filled = (f & 3u) == 1u;
+            const uint32_t v = q.w & 255u, p = filled ? (q.w >> 8) & 255u : v;
+            uint32_t uc = 0;                                // the twelve codes, level l at bits 2l
+#pragma unroll
+            for (int l = 0; l < 12; ++l) uc |= (((l < 4 ? q.x : (l < 8 ? q.y : q.z)) >> (8 * (l & 3))) & 3u) << (2 * l);
+            const uint32_t tword = v * 0x01010101u, pword = p * 0x01010101u, tol2 = (uint32_t)tol * 0x10001u;
+            vr_s16x2 dl, mxB = (vr_s16x2)(0);
+            uint32_t cl2, m, sg, act, Lb, nt, keepEnd = 0;
+            leaf_pair_encode(tword, 0, pword, 0, (uint32_t)cDistR * 0x10001u, (uint32_t)cDistC * 0x10001u, dl, cl2);
+            const uint32_t T2 = __builtin_amdgcn_perm(0, tword, 0x0c010c00u);
+            uint32_t both = 0;                              // bit 0: the leaf is a pruned token
+            pe_leaf_table(T2, dl, cl2, tol2, [&](uint32_t k) { return lutS[k]; }, mxB, m, sg, act, Lb, nt, both, 0);
+            const int nsteps = a.maxDepth - D;
+            uint32_t anyAct = act;
+            for (int i = 0; i < nsteps && anyAct; ++i) {
+                anyAct = 0;
+                pe_leaf_step(i, nsteps, (uint32_t)(64 >> i) * 0x10001u, tol2, T2, m, sg, act, Lb, nt, keepEnd, anyAct);
+            }
+            const bool early = v == p && uc == 0u;          // what k_prune_emit12 leaves on before its string buffer
+            bool F = both != 0u;
+            uint32_t len = nt & 0xFFFFu, len8 = 0, len10 = 0, changed = 0, P = 12;
+#pragma unroll
+            for (int l = 11; l >= 0; --l) {
+                if (F && ((uc >> (2 * l)) & 3u) == 0u) { uc |= 3u << (2 * l); changed |= 1u << l; }
+                F = ((uc >> (2 * l)) & 3u) == 3u;
+                len = F ? 1u : 1u + 2u * len;
+                if (F) P = (uint32_t)l;
+                if (l == 10) len10 = len;
+                if (l == 8) len8 = len;
+            }
+            kind = early ? 1u : 2u;
+            res[t][1] = uc;
+            res[t][2] = (Lb & 0xFFFFu) | ((nt & 0xFFFFu) << 16);
+            res[t][3] = len8 | (len10 << 16);
+            res[t][4] = len;
+            res[t][5] = (m & 0xFFFFu) | ((uint32_t)(int)mxB.x << 16);
+            res[t][0] = kind | (P << 4) | (changed << 8) | ((keepEnd & 1u) << 20);
+        } else
+            res[t][0] = 0;
+    }
+    __syncthreads();
+    // ---- the one-token blocks: root code 3, one token, zero statistics, 64 dead index entries
+    for (int i = t; i < PEC_BOXES * 16; i += 256) {
+        const int b = i >> 4, l = i & 15;
+        if ((res[b][0] & 15u) != 1u) continue;
+        const uint32_t blk = blk0 + (uint32_t)b;
+        *(uint4 *)(a.idxOff + (int64_t)brick * a.nIdx + ((int64_t)blk << 6) + l * 4) = make_uint4(VR_IDX_DEAD, VR_IDX_DEAD, VR_IDX_DEAD, VR_IDX_DEAD);
+        if (l < 4) a.blockL1[(int64_t)brick * a.nEmitBlk + (size_t)blk * 4 + l] = stat_pack(0, 0, 0);
+        if (l == 0) {
+            cset3(Cb, ((int64_t)1 << (D - 12)) + blk);
+            a.subTok[(int64_t)brick * a.nEmitBlk + blk] = 1;
+            *((uint32_t *)(a.gap + (int64_t)brick * a.treeCap) + (size_t)blk * PE_WORDS) = 3u;
+        }
+    }
+    // ---- the others, one after the other
+    const int jmin = t ? 8 - (__ffs(t) - 1) : 0;
+    for (int b = 0; b < PEC_BOXES; ++b) {
+        const uint32_t r0 = res[b][0];
+        if ((r0 & 15u) != 2u) continue;                     // (the same answer in every thread)
+        const uint32_t blk = blk0 + (uint32_t)b, base = blk << 12;
+        const int P = (int)((r0 >> 4) & 15u);
+        const uint32_t changed = (r0 >> 8) & 0xFFFu, uc = res[b][1], LbL = res[b][2] & 0xFFFFu, ntL = res[b][2] >> 16;
+        const uint32_t len8 = res[b][3] & 0xFFFFu, len10 = res[b][3] >> 16, tot = res[b][4];
+        const uint32_t nw = min((tot + 15u) / 16u + 1u, (uint32_t)PE_WORDS);
+        for (uint32_t i = t; i < nw; i += 256u) W[i] = 0;
+        if (t < 12) Pc[t] = 0;
+        // code write-back, depths D-12 .. D-5, by k_prune_emit12's rule: whole bytes below heap node 3, bits above
+        if (t >= 1 && t < 64) {
+            const int h = t * 4, lq = 31 - __clz(h);
+            if ((changed >> lq) & 1u) Cb[(((int64_t)1 << (D - 12 + lq)) + ((int64_t)blk << lq) + (h - (1 << lq))) >> 2] = 0xFFu;
+        }
+        if (t >= 1 && t < 4) {
+            const int lq = 31 - __clz(t);
+            if ((changed >> lq) & 1u) cset3(Cb, ((int64_t)1 << (D - 12 + lq)) + ((int64_t)blk << lq) + (t - (1 << lq)));
+        }
+        if (t == 0) a.subTok[(int64_t)brick * a.nEmitBlk + blk] = tot;
+        if (t < 4) {
+            const uint32_t fe = res[b][5] & 0xFFFFu, eB = res[b][5] >> 16;
+            a.blockL1[(int64_t)brick * a.nEmitBlk + (size_t)blk * 4 + t] = stat_pack((unsigned long long)fe * 1024ull, (int)eB, (int)fe);
+        }
+        if ((r0 >> 20) & 1u) atomicAdd(&c.zeroRun, 4);     // (k_prune_emit12: two per thread and half of its leaves)
+        __syncthreads();
+        // thread t: the live ancestors whose first leaf is its first leaf, then its 16-leaf subtree
+        const int top = P < 7 ? P : 7;
+        const int ns = jmin <= top ? top - jmin + 1 : 0;
+        uint32_t pos = P >= 8 ? (uint32_t)t * len8 : 0u;
+        for (int lq = 0; lq <= top; ++lq) pos += ((uint32_t)t + (1u << (8 - lq)) - 1u) >> (8 - lq);
+        uint32_t bitpos = 2u * pos;
+        pe_put(W, bitpos, (unsigned long long)((uc >> (2 * jmin)) & ((1u << (2 * ns)) - 1u)), ns);
+        bitpos += 2u * (uint32_t)ns;
+        // a subtree that reaches its leaf pairs is the same string for every thread: eight threads write one pair's
+        // piece each into Pc, and after a barrier every thread shifts the whole string to its own position
+        if (P >= 11 && t < 8) {
+            const uint32_t a4 = (uc >> 16) & 3u, a3 = (uc >> 18) & 3u, a2 = (uc >> 20) & 3u, a1 = (uc >> 22) & 3u;
+            unsigned long long H = a1;
+            int Hn = 1;
+            if (a1 != 3u) { H |= ((unsigned long long)LbL << 2) | ((unsigned long long)LbL << (2 + 2 * ntL)); Hn = 1 + 2 * (int)ntL; }
+            // internal tokens in front of pair t: a4 a3 a2 | - | a2 | - | a3 a2 | - | a2 | -
+            const int pn = (int)((0x01020103u >> (4 * t)) & 15u);
+            const int pre = (0x76644330u >> (4 * t)) & 15;                      // ... and in front of those, over pairs 0 .. t-1
+            const uint32_t pb = t == 0 ? a4 | (a3 << 2) | (a2 << 4) : (t == 4 ? a3 | (a2 << 2) : a2);
+            pe_put(Pc, 2u * (uint32_t)(pre + t * Hn), (unsigned long long)(pn ? pb : 0u) | (H << (2 * pn)), pn + Hn);
+        }
+        if (P >= 8 && P < 11) {                             // pruned above the pairs: a4 | a4 a3 a3 | a4 a3 a2 a2 a3 a2 a2
+            const uint32_t a4 = (uc >> 16) & 3u, a3 = (uc >> 18) & 3u, a2 = (uc >> 20) & 3u;
+            const uint32_t pc = P == 8 ? a4 : (P == 9 ? a4 | (a3 * 0x14u) : a4 | (a3 * 0x104u) | (a2 * 0x1450u));
+            pe_put(W, bitpos, (unsigned long long)pc, (int)len8);
+        }
+        if (P >= 11) {                                      // (the same answer in every thread)
+            __syncthreads();
+            const uint32_t b1 = bitpos + 2u * len8 - 1u, w0 = bitpos >> 5, w1 = b1 >> 5, sh = bitpos & 31u;
+            uint32_t lo = 0;
+            for (uint32_t w = w0; w <= w1; ++w) {
+                const uint32_t hi = Pc[w - w0];
+                const uint32_t val = sh ? (hi << sh) | (lo >> (32u - sh)) : hi;
+                lo = hi;
+                // the words in between are this thread's alone; its first and last one it shares with its neighbours
+                if (w == w0 || w == w1) atomicOr(&W[w], val); else W[w] = val;
+            }
+        }
+        if ((t & 3) == 0)
+            a.idxOff[(int64_t)brick * a.nIdx + (base >> 6) + (t >> 2)] = P >= 6 ? pos + (uint32_t)(6 - jmin) : VR_IDX_DEAD;
+        {
+            const uint32_t nsIn = jmin <= 6 ? (P >= 6 ? (uint32_t)(top - 5) : 0u) : (uint32_t)ns;
+            const bool alive = P >= 8, l4 = P >= 9, l3 = P >= 10;
+            const uint32_t f0 = nsIn + (alive ? 1u + (l4 ? 1u + (l3 ? len10 : 0u) : 0u) : 0u);
+            const uint32_t f1 = l3 ? len10 : 0u;
+            const uint32_t f2 = l4 ? 1u + (l3 ? len10 : 0u) : 0u;
+            a.fineIdx[((int64_t)brick * a.nIdx + (base >> 6)) * 4 + t] = f0 | (f1 << 8) | (f2 << 16) | (f1 << 24);
+        }
+        __syncthreads();
+        uint32_t *slot = (uint32_t *)(a.gap + (int64_t)brick * a.treeCap) + (size_t)blk * PE_WORDS;
+        for (uint32_t i = t; i < nw; i += 256u) slot[i] = W[i];
+        __syncthreads();
+    }
+}
 
 __global__ void __launch_bounds__(EMIT_RANKS_PER_BLOCK)
 k_emit_count(EmitArgs a)
@@ -2834,6 +3053,11 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         pa.rbR = rbR;
         pa.gap = bs->mid.tree; pa.gapR = mr ? bs->rng.tree : nullptr; pa.treeCap = bs->treeCap;
         const dim3 peGrid((unsigned)((int64_t)1 << (D - 12)), B);
+        // constant blocks of a leafless SkipBlocks build have a closed form (k_prune_emit12_const); the two launches
+        // write disjoint blocks, and heap nodes 1 .. 3 of a block, whose bytes neighbours share, only through cset3
+        pa.uniformBlocks = skipOn && bs->leafless && !mr && !bs->sw.noUniformBlocks;
+        if (pa.uniformBlocks)
+            hipLaunchKernelGGL(k_prune_emit12_const, dim3((unsigned)cdiv((int64_t)1 << (D - 12), PEC_BOXES), B), dim3(256), 0, st, pa);
         if (bs->leafless) {
             hipLaunchKernelGGL((k_prune_emit12<false, true>), peGrid, dim3(256), 0, st, pa);
             if (mr) hipLaunchKernelGGL((k_prune_emit12<true, true>), peGrid, dim3(256), 0, st, pa);
