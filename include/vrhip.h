@@ -253,6 +253,54 @@ vr_status vr_measure_error(const uint8_t *decoded_dev, const uint8_t *original_d
 vr_status vr_query_error(const uint8_t *decoded_dev, const uint8_t *original_dev, int64_t n,
                          uint8_t *error_dev, void *stream);
 
+/* ---- error-bounded level of detail (new): what every cut of every brick costs in accuracy, and the cuts a bound allows
+ * The error of brick b between two buffers of num_bricks bricks x V bytes (brick b at byte b * V of each) is four exact
+ * integers over its V byte pairs (a, r): */
+typedef struct vr_brick_error {
+    uint64_t sum_abs;   /* sum |a-r|            */
+    uint64_t sum_sq;    /* sum (a-r)^2          */
+    uint32_t max_abs;   /* max |a-r|            */
+    uint32_t num_diff;  /* voxels with a != r   */
+} vr_brick_error;       /* 24 bytes */
+
+/* The rule of the three calls below:
+ *  - the ERROR TABLE of a set for the cuts cut_lo .. cut_hi against a reference (the original voxels, or any decode, in
+ *    vr_brickset_build's layout) has one row per cut: entry (c - cut_lo) * B + b is the error between brick b of
+ *    vr_brickset_decode(bs, c, ...) and brick b of the reference.  The decodes are the set's own uniform decodes, the same
+ *    bytes, into the caller's scratch; each is followed by one reduction kernel.  Every field is exact and independent of
+ *    the launch shape: only integer adds and maxima cross lanes, waves and workgroups.  Against the set's own full-depth
+ *    decode the row of cut max_tree_depth is all zero.
+ *  - the SELECTION: for brick b, h = cuts_in ? cuts_in[b] : cut_hi.  h == -1 stays -1 (a culled brick).  Otherwise the
+ *    candidates are the cuts c in [cut_lo, min(h, cut_hi)]; c qualifies iff max_abs <= max_abs_bound and, when
+ *    mean_sq_bound >= 0, (double)sum_sq <= mean_sq_bound * (double)voxels_per_brick (one double multiply, one comparison);
+ *    cuts_out[b] = the smallest qualifying candidate, or h if there is none (also when h < cut_lo).  Error need not fall
+ *    with the cut and the rule does not assume it.  cuts_in is what vr_lod_select returns: geometry first, then data.
+ *    Bound 0 against the set's full-depth decode gives cuts whose vr_brickset_decode_lod output equals the full decode bit
+ *    for bit, in fewer pool bytes and less decode work.
+ * vr_measure_error_bricks is the reduction on its own, for any two device buffers.  VR_ERR_INVALID for a null pointer,
+ * num_bricks < 1 or voxels_per_brick outside 1 .. 2^32 - 1 (inside it num_diff is exact and sum_sq below 2^48); then
+ * VR_ERR_NO_DEVICE.  It synchronises `stream` before it returns.
+ * vr_brickset_error_table: scratch_dev holds num_bricks * X*Y*Z bytes and is left with the decode at cut_hi; table_host
+ * receives (cut_hi - cut_lo + 1) * num_bricks entries.  All cuts are queued on `stream` with no host synchronisation in
+ * between (a set opened from a file fills the cut values of a cut above its index level on the host, as
+ * vr_brickset_decode does: such a cut waits for the stream first); one download and one synchronisation end the call.
+ * The device table belongs to the set: allocated on first use, cleared on the stream, freed by vr_brickset_destroy.
+ * Every variant, and sets opened from a file.  VR_ERR_INVALID (nothing launched) for a null pointer, cut_lo < 0,
+ * cut_hi > max_tree_depth, cut_lo > cut_hi, or a scratch_dev that vr_brickset_decode would refuse at one of the cuts;
+ * VR_ERR_STATE before build.
+ * vr_lod_select_error is host-only (no device needed).  VR_ERR_INVALID for a null table or cuts_out, num_bricks < 1,
+ * cut_lo < 0, cut_lo > cut_hi, voxels_per_brick < 1, max_abs_bound < 0, a NaN mean_sq_bound, or a cuts_in[b] < -1
+ * (cuts_out is then not written).
+ * Alignment: decoded_dev, reference_dev at any byte offset, each independently (16-byte loads where a brick starts at the
+ * same offset modulo 16 in both, single bytes otherwise); scratch_dev as vr_brickset_decode's out_dev. */
+vr_status vr_measure_error_bricks(const uint8_t *decoded_dev, const uint8_t *reference_dev, int32_t num_bricks,
+                                  int64_t voxels_per_brick, vr_brick_error *out_host, void *stream);
+vr_status vr_brickset_error_table(vr_brickset *bs, const uint8_t *reference_dev, uint8_t *scratch_dev, int32_t cut_lo,
+                                  int32_t cut_hi, vr_brick_error *table_host, void *stream);
+vr_status vr_lod_select_error(const vr_brick_error *table, int32_t num_bricks, int32_t cut_lo, int32_t cut_hi,
+                              int64_t voxels_per_brick, const int32_t *cuts_in, int32_t max_abs_bound, double mean_sq_bound,
+                              int32_t *cuts_out);
+
 /* ---- ingest: VolumeReader<T>::LoadBricksToTexture (VolumeReader.h:151-223) ------
  * Places brick b (brick_dims, x-fastest, contiguous at bricks_dev + b*brick_voxels)
  * at grid cell brick_ijk[3*b..3*b+2] of a global x-fastest volume of

@@ -11,7 +11,8 @@ __all__ = ["BrickSet", "VolumeKdtree", "MidRangeTree", "HashedKdtree", "VolumeRe
 
 
 def __getattr__(name):  # torch is imported lazily so that `import volumerenderer_amd` stays cheap
-    if name in ("BrickSet", "VolumeKdtree", "MidRangeTree", "HashedKdtree", "measure_error", "query_error"):
+    if name in ("BrickSet", "VolumeKdtree", "MidRangeTree", "HashedKdtree", "measure_error", "query_error",
+                "measure_error_bricks", "BRICK_ERROR"):
         from . import codec
         return getattr(codec, name)
     if name in ("VolumeReader", "UnitBrick", "raycast", "default_camera", "default_params", "composite_over",
@@ -21,7 +22,7 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
                 "raycast_pool_tf_shaded", "raycast_tf_partial", "raycast_pool_tf_partial", "composite_over_tf",
                 "composite_finish_tf", "Projection", "raycast_projection", "raycast_pool_projection",
                 "raycast_projection_partial", "raycast_pool_projection_partial", "composite_combine_proj",
-                "composite_finish_proj", "SlicePlane", "reslice", "reslice_partial"):
+                "composite_finish_proj", "SlicePlane", "reslice", "reslice_partial", "select_lod_error", "rate_distortion"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

@@ -74,6 +74,11 @@ class PoolEntry(C.Structure):
     _fields_ = [("offset", C.c_int64), ("shift", C.c_uint8 * 3), ("pad", C.c_uint8 * 5)]
 
 
+class BrickError(C.Structure):
+    """vr_brick_error (24 bytes)."""
+    _fields_ = [("sum_abs", C.c_uint64), ("sum_sq", C.c_uint64), ("max_abs", C.c_uint32), ("num_diff", C.c_uint32)]
+
+
 # every symbol include/vrhip.h declares, with its signature
 _P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -112,6 +117,9 @@ SIGNATURES = {
     "vr_brickset_open_variant": (_I32, [C.POINTER(_P), C.c_char_p, _I32]),
     "vr_measure_error": (_I32, [_P, _P, _I64, C.POINTER(_I32), C.POINTER(C.c_double), _P]),
     "vr_query_error": (_I32, [_P, _P, _I64, _P, _P]),
+    "vr_measure_error_bricks": (_I32, [_P, _P, _I32, _I64, _P, _P]),
+    "vr_brickset_error_table": (_I32, [_P, _P, _P, _I32, _I32, _P, _P]),
+    "vr_lod_select_error": (_I32, [_P, _I32, _I32, _I32, _I64, C.POINTER(_I32), _I32, C.c_double, C.POINTER(_I32)]),
     "vr_assemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_disassemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_raycast": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),

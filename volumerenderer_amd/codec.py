@@ -174,6 +174,30 @@ class BrickSet:
               "vr_brickset_decode_lod_pool")
         return pool, table
 
+    def error_table(self, reference=None, cuts=None, scratch=None, stream=None):
+        """What every cut of every brick costs in accuracy (vr_brickset_error_table; the rule is in vrhip.h).
+        reference: the voxels to compare with, in build()'s layout -- the original volume or any decode; None = the
+        set's own full-depth decode, against which the last row (cut max_tree_depth) is all zero.  cuts: (cut_lo, cut_hi),
+        inclusive; None = every cut 0 .. max_tree_depth.  scratch: a CUDA uint8 tensor of num_bricks * voxels_per_brick
+        bytes for the decodes (None: allocated); it is left with the decode at cut_hi.  Returns a BRICK_ERROR numpy
+        array of shape (cut_hi - cut_lo + 1, num_bricks); the call synchronises the stream."""
+        n = self.num_bricks * self.voxels_per_brick
+        lo, hi = (0, self.info(0)["max_tree_depth"]) if cuts is None else (int(cuts[0]), int(cuts[1]))
+        if hi < lo:
+            raise ValueError("error_table: cuts (%d, %d)" % (lo, hi))
+        ref = self.decode(stream=stream) if reference is None else _as_dev_u8(reference).reshape(-1)
+        if ref.numel() != n:
+            raise ValueError("reference has %d bytes, expected %d" % (ref.numel(), n))
+        if scratch is None:
+            scratch = torch.empty(n, dtype=torch.uint8, device=ref.device)
+        if not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.dtype == torch.uint8
+                and scratch.is_contiguous() and scratch.numel() == n):
+            raise ValueError("bad scratch buffer")
+        table = np.zeros((hi - lo + 1, self.num_bricks), BRICK_ERROR)
+        check(self._L.vr_brickset_error_table(self._h, C.c_void_p(ref.data_ptr()), C.c_void_p(scratch.data_ptr()), lo, hi,
+                                              C.c_void_p(table.ctypes.data), _stream_ptr(stream)), "vr_brickset_error_table")
+        return table
+
     def decode_range(self, out=None, cut_depth=-1, stream=None):
         """MidRangeTree sets: the half-range stream decoded like the mid stream (vr_brickset_decode_range)."""
         if out is None:
@@ -221,6 +245,23 @@ def measure_error(decoded, original, stream=None):
     check(_lib.lib().vr_measure_error(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), a.numel(),
                                       C.byref(mx), C.byref(mean), _stream_ptr(stream)), "vr_measure_error")
     return mx.value, mean.value
+
+
+# vr_brick_error as numpy
+BRICK_ERROR = np.dtype([("sum_abs", "<u8"), ("sum_sq", "<u8"), ("max_abs", "<u4"), ("num_diff", "<u4")])
+
+
+def measure_error_bricks(decoded, reference, num_bricks, stream=None):
+    """Per-brick error of two buffers of num_bricks equal bricks (vr_measure_error_bricks): a BRICK_ERROR numpy array of
+    num_bricks entries, every field an exact integer.  Either buffer may start at any byte."""
+    a, b = _as_dev_u8(decoded), _as_dev_u8(reference)
+    nb = int(num_bricks)
+    if nb < 1 or a.numel() != b.numel() or a.numel() == 0 or a.numel() % nb:
+        raise ValueError("measure_error_bricks: %d and %d bytes for %d bricks" % (a.numel(), b.numel(), nb))
+    out = np.zeros(nb, BRICK_ERROR)
+    check(_lib.lib().vr_measure_error_bricks(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), nb, a.numel() // nb,
+                                             C.c_void_p(out.ctypes.data), _stream_ptr(stream)), "vr_measure_error_bricks")
+    return out
 
 
 def query_error(decoded, original, stream=None):

@@ -147,6 +147,9 @@ struct BrickSet {
     uint8_t *poolStage = nullptr;
     hipEvent_t stageDone = nullptr;
     bool stagePending = false;
+    // vr_brickset_error_table: (maxDepth + 1) rows of B entries (first needed); a call clears the rows it fills on its
+    // stream and synchronises that stream before it returns, so no two calls ever share it
+    vr_brick_error *errTable = nullptr;
 };
 
 // vr_brickset_decode_lod_pool's destinations (vr_lod_pool_layout, computed by the caller): brick b with cut >= 0 goes
@@ -178,6 +181,8 @@ int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, b
 // per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
 int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st, const PoolDest *pool = nullptr);
 void free_lod_slots(BrickSet *bs);
+// error_table.hip: per-brick error of two buffers of B bricks x V bytes, added into out[0 .. B) (cleared by the caller)
+int brick_error_launch(const uint8_t *a, const uint8_t *b, int64_t B, int64_t V, vr_brick_error *out, hipStream_t st);
 int build_general_geometry(BrickSet *bs);   // srcIdx / ownerRank for general extents (0, -3 out of memory, -1 device error)
 
 } // namespace vr

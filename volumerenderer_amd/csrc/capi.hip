@@ -204,6 +204,7 @@ vr_status vr_brickset_destroy(vr_brickset *h)
     if (!h) return VR_OK;
     BrickSet &b = h->s;
     free_lod_slots(&b);
+    hipFree(b.errTable);
     free_encoder_buffers(b);
     free_stream2(b.mid);
     free_stream2(b.rng);
@@ -957,6 +958,55 @@ vr_status vr_query_error(const uint8_t *dec, const uint8_t *orig, int64_t n, uin
     if (!dec || !orig || !err || n <= 0) return VR_ERR_INVALID;
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     return query_error_launch(dec, orig, n, err, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// the reduction alone (error_table.hip): a device table of its own for the call
+vr_status vr_measure_error_bricks(const uint8_t *dec, const uint8_t *ref, int32_t num_bricks, int64_t voxels_per_brick,
+                                  vr_brick_error *out, void *stream)
+{
+    if (!dec || !ref || !out || num_bricks < 1 || voxels_per_brick < 1 || voxels_per_brick > 0xFFFFFFFFll) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    const size_t bytes = (size_t)num_bricks * sizeof(vr_brick_error);
+    vr_brick_error *dTab = nullptr;
+    HIPCHK(hipMalloc(&dTab, bytes));
+    hipError_t e = hipMemsetAsync(dTab, 0, bytes, (hipStream_t)stream);
+    int rc = 0;
+    if (e == hipSuccess) rc = brick_error_launch(dec, ref, num_bricks, voxels_per_brick, dTab, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dTab, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(dTab);
+    return rc != 0 || e != hipSuccess || es != hipSuccess ? VR_ERR_NO_DEVICE : VR_OK;
+}
+
+// vrhip.h "error-bounded level of detail": per cut the set's uniform decode into the scratch, then the reduction into
+// that cut's row of the set's device table
+vr_status vr_brickset_error_table(vr_brickset *h, const uint8_t *ref, uint8_t *scratch, int32_t cut_lo, int32_t cut_hi,
+                                  vr_brick_error *table, void *stream)
+{
+    if (!h || !ref || !scratch || !table) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    if (cut_lo < 0 || cut_hi > b.maxDepth || cut_lo > cut_hi) return VR_ERR_INVALID;
+    if (!b.built) return VR_ERR_STATE;
+    for (int c = cut_lo; c <= cut_hi; ++c)
+        if (decode_stores_vectors(&b, c, false) && misaligned16(scratch)) return VR_ERR_INVALID;
+    const size_t row = (size_t)b.B * sizeof(vr_brick_error), bytes = row * (size_t)(cut_hi - cut_lo + 1);
+    if (!b.errTable) HIPCHK(hipMalloc(&b.errTable, row * (size_t)(b.maxDepth + 1)));
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(b.errTable, 0, bytes, st));
+    for (int c = cut_lo; c <= cut_hi; ++c) {
+        // a foreign set's cut values above the index level are written by a blocking copy from the host: the decode
+        // of the cut before must have read its own first
+        if (b.foreign && c < b.Ds) HIPCHK(hipStreamSynchronize(st));
+        const vr_status rc = decode_common(h, c, scratch, stream, false);
+        if (rc != VR_OK) { hipStreamSynchronize(st); return rc; }
+        if (brick_error_launch(scratch, ref, b.B, b.g.voxels, b.errTable + (size_t)(c - cut_lo) * b.B, st) != 0) {
+            hipStreamSynchronize(st);
+            return VR_ERR_NO_DEVICE;
+        }
+    }
+    const hipError_t e = hipMemcpyAsync(table, b.errTable, bytes, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    return e != hipSuccess || es != hipSuccess ? VR_ERR_NO_DEVICE : VR_OK;
 }
 
 static vr_status assemble_common(bool toVolume, const uint8_t *src, int32_t nb, const int64_t bd[3], const int64_t *ijk,

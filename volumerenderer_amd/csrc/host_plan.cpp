@@ -1,5 +1,6 @@
 // host_plan.cpp -- see host_plan.h.  Plain C++: nothing here touches a device.
 #include "host_plan.h"
+#include "../../include/vrhip.h"
 #include <string.h>
 #include <algorithm>
 
@@ -273,3 +274,26 @@ bool read_header(FILE *f, Header &h)
 bool write_header(FILE *f, const Header &h) { return fwrite(&h, VR_HEADER_BYTES, 1, f) == 1; }
 
 } // namespace vr
+
+// ---- error-bounded selection of cuts: the rule is stated in vrhip.h ("error-bounded level of detail") ----
+extern "C" vr_status vr_lod_select_error(const vr_brick_error *table, int32_t num_bricks, int32_t cut_lo, int32_t cut_hi,
+                                         int64_t voxels_per_brick, const int32_t *cuts_in, int32_t max_abs_bound,
+                                         double mean_sq_bound, int32_t *cuts_out)
+{
+    if (!table || !cuts_out || num_bricks < 1 || cut_lo < 0 || cut_lo > cut_hi || voxels_per_brick < 1) return VR_ERR_INVALID;
+    if (max_abs_bound < 0 || mean_sq_bound != mean_sq_bound) return VR_ERR_INVALID;
+    for (int32_t b = 0; cuts_in && b < num_bricks; ++b) if (cuts_in[b] < -1) return VR_ERR_INVALID;
+    for (int32_t b = 0; b < num_bricks; ++b) {
+        const int32_t h = cuts_in ? cuts_in[b] : cut_hi;
+        int32_t pick = h;
+        for (int32_t c = cut_lo; h >= 0 && c <= std::min(h, cut_hi); ++c) {
+            const vr_brick_error &e = table[(int64_t)(c - cut_lo) * num_bricks + b];
+            if (e.max_abs > (uint32_t)max_abs_bound) continue;
+            if (mean_sq_bound >= 0.0 && !((double)e.sum_sq <= mean_sq_bound * (double)voxels_per_brick)) continue;
+            pick = c;
+            break;
+        }
+        cuts_out[b] = pick;
+    }
+    return VR_OK;
+}

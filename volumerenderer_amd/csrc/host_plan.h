@@ -1,6 +1,7 @@
 // host_plan.h -- the codec's host logic that needs no device: the split rule and what follows from it, the launch
 // geometry of the tiled kernels (planned once per set, at vr_brickset_create), the walker of foreign streams and the
-// file header.  Includes no HIP header: compiles with a plain C++17 compiler (tests/host_plan_main.cpp links it
+// file header; and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
+// host_plan.cpp: a rule on a host table).  Includes no HIP header: compiles with a plain C++17 compiler (tests/host_plan_main.cpp links it
 // directly) and with hipcc.
 #pragma once
 #include <stdint.h>

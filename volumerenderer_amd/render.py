@@ -229,6 +229,50 @@ def select_lod(cam, params, brick_dims, brick_ijk, grid, orig_tree_depth, max_tr
     return cuts
 
 
+def select_lod_error(table, cut_lo, voxels_per_brick, cuts_in=None, max_abs=0, mean_sq=-1.0):
+    """Per-brick cuts bounded by error (vr_lod_select_error, host only; the rule is in vrhip.h): for every brick the
+    smallest cut of the table, not above cuts_in[b], whose max_abs is at most `max_abs` and, when mean_sq >= 0, whose
+    mean squared error is at most `mean_sq`; cuts_in[b] where none is, -1 where cuts_in[b] is -1.  table: as
+    BrickSet.error_table returns it, its row 0 being cut `cut_lo`; cuts_in: what select_lod returns, or None for the
+    table's last cut everywhere.  Returns an int32 numpy array."""
+    from .codec import BRICK_ERROR
+    t = np.ascontiguousarray(table, BRICK_ERROR)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("select_lod_error: the table must have shape (cuts, bricks)")
+    ci = None
+    if cuts_in is not None:
+        ci = np.ascontiguousarray(np.asarray(cuts_in).reshape(-1), dtype=np.int32)
+        if ci.size != t.shape[1]:
+            raise ValueError("select_lod_error: %d cuts for %d bricks" % (ci.size, t.shape[1]))
+    cuts = np.empty(t.shape[1], np.int32)
+    check(_lib.lib().vr_lod_select_error(C.c_void_p(t.ctypes.data), int(t.shape[1]), int(cut_lo),
+                                         int(cut_lo) + t.shape[0] - 1, int(voxels_per_brick),
+                                         None if ci is None else ci.ctypes.data_as(C.POINTER(C.c_int32)), int(max_abs),
+                                         float(mean_sq), cuts.ctypes.data_as(C.POINTER(C.c_int32))), "vr_lod_select_error")
+    return cuts
+
+
+# one row of rate_distortion
+RATE_DISTORTION = np.dtype([("cut", "<i4"), ("pool_bytes", "<i8"), ("psnr", "<f8")])
+
+
+def rate_distortion(bs, table, brick_ijk, grid, cut_lo=0):
+    """The rate / distortion curve of a set cut uniformly: per row of `table` (BrickSet.error_table; row 0 = cut
+    `cut_lo`) the bytes of the level-of-detail pool with every brick at that cut (lod_pool_layout) and the PSNR of the
+    whole volume, 10 log10(255^2 N / sum of sum_sq) dB (inf where the sum is 0).  Host arithmetic only; power-of-two
+    brick extents (the pool's).  Returns a RATE_DISTORTION numpy array."""
+    info = bs.info(0)
+    out = np.zeros(len(table), RATE_DISTORTION)
+    n = float(bs.num_bricks) * float(bs.voxels_per_brick)
+    for r in range(len(table)):
+        cut = int(cut_lo) + r
+        _, nbytes = lod_pool_layout(bs.dims, brick_ijk, grid, np.full(bs.num_bricks, cut, np.int32),
+                                    info["orig_tree_depth"], info["max_tree_depth"])
+        sq = sum(int(v) for v in table[r]["sum_sq"])
+        out[r] = (cut, nbytes, math.inf if sq == 0 else 10.0 * math.log10(255.0 * 255.0 * n / sq))
+    return out
+
+
 # vr_pool_entry as numpy: one row per grid cell, x fastest
 POOL_ENTRY = np.dtype([("offset", "<i8"), ("shift", "u1", (3,)), ("pad", "u1", (5,))])
 
