@@ -301,6 +301,62 @@ vr_status vr_lod_select_error(const vr_brick_error *table, int32_t num_bricks, i
                               int64_t voxels_per_brick, const int32_t *cuts_in, int32_t max_abs_bound, double mean_sq_bound,
                               int32_t *cuts_out);
 
+/* ---- volume histograms (new): what values a volume holds -- per brick, of a pool, and by value and gradient ------------
+ * Every count is an exact integer, and counts add: the tables of parts of a volume (bricks, cells, the own boxes of
+ * several GPUs) sum to the table of the whole with no tolerance.  No result depends on the launch shape.
+ *
+ * vr_histogram_bricks: vr_measure_error_bricks' layout, brick b at byte b * V of data_dev, which may start at any byte
+ * (bytes up to the next 16-byte boundary one by one, aligned 16-byte loads, the last bytes one by one).
+ * bricks_host[b * 256 + k] = the number of bytes of brick b that equal k; total_host[k] = the sum over the bricks,
+ * carried in 64 bits on the device as well.  Either output may be NULL.  V lies in 1 .. 2^32 - 1, so a per-brick count
+ * fits 32 bits.  VR_ERR_INVALID for a null data_dev, both outputs null, num_bricks < 1 or V outside that range; then
+ * VR_ERR_NO_DEVICE.  The device tables are the call's own: allocated, cleared on `stream`, downloaded, freed; the call
+ * synchronises `stream` before it returns.
+ *
+ * vr_histogram_pool: the histogram of the virtual volume vr_raycast_pool reads, per grid cell (x fastest) and in total.
+ * A cell with offset >= 0 counts every stored voxel 1 << (shift_x + shift_y + shift_z) times; an absent cell counts
+ * X*Y*Z in bin 0, for the pool reads as 0 there, and its pool bytes are not touched.  Per cell and in total the result
+ * equals vr_histogram_bricks of that volume laid out brick by brick.  The table is read on the device.  Restrictions:
+ * vr_raycast_pool's (power-of-two brick_dims, virtual extents below 2^31), X*Y*Z <= 2^32 - 1 and fewer than 2^31 cells;
+ * VR_ERR_INVALID otherwise, for a null pointer, or with both outputs null.  pool_dev at any byte.  Synchronises `stream`.
+ *
+ * vr_histogram2d: the joint histogram of value and gradient magnitude of a dense volume, the design space of a
+ * two-dimensional transfer function.  volume_dev holds the voxels [vol_origin, vol_origin + dims) of a global volume of
+ * G = global_dims voxels (a global_dims extent of 0 means dims' own).  For every OWNED voxel p, own_lo <= p < own_hi in
+ * global coordinates: v = its value; d_x = v(p + e_x) - v(p - e_x), d_y and d_z likewise, every index clamped to
+ * [0, G - 1] -- the integers the lit marcher interpolates (gradient-shaded rendering, above); s = d_x^2 + d_y^2 + d_z^2;
+ * r = isqrt(s) >> 2 with isqrt the exact integer square root (a float sqrt corrected by one step either way); the voxel
+ * counts in hist_host[r * 256 + v], a table of VR_HIST_GRAD_BINS x VR_HIST_BINS 64-bit counts.
+ * VR_ERR_INVALID, nothing launched: a null pointer; dims or global_dims as vr_raycast refuses them; a local volume that
+ * leaves the global one; and, per axis, an own box that is empty (own_lo >= own_hi), that leaves the local volume
+ * (own_lo < vol_origin or own_hi > vol_origin + dims), or one of whose clamped neighbours would:
+ * max(own_lo - 1, 0) < vol_origin or min(own_hi, G - 1) > vol_origin + dims - 1.  With that check the kernel cannot form
+ * an address outside volume_dev.  A slab of several GPUs therefore holds ONE halo layer beyond its own box.  Invariants:
+ * the column sums of the table are the 256-bin histogram of the owned voxels; the tables of disjoint own boxes that
+ * tile the volume add up to the table of the whole volume.  volume_dev at any byte.  Synchronises `stream`.
+ *
+ * vr_window_from_histogram is host-only (no device needed): a display window from the percentiles of a 256-bin
+ * histogram, for the window_lo / window_hi of a projection.  N = the sum of hist[k] over k >= first_bin (first_bin = 1
+ * leaves the background out); cum_k = the sum of hist[first_bin .. k].  lo_k = the smallest k >= first_bin with
+ * (double)cum_k > lo_fraction * (double)N, or, where there is none (lo_fraction = 1), the largest k with hist[k] != 0;
+ * hi_k = the smallest k >= first_bin with (double)cum_k >= hi_fraction * (double)N.  If hi_k <= lo_k then hi_k = lo_k + 1,
+ * and if that is 256 both move down by one.  *window_lo = (float)lo_k / 255.0f, *window_hi = (float)hi_k / 255.0f: always
+ * 0 <= window_lo < window_hi <= 1, a window vr_raycast_projection accepts.  VR_ERR_INVALID for a null pointer, first_bin
+ * outside 0 .. 255, a fraction outside [0, 1] or NaN, lo_fraction > hi_fraction, or N == 0. */
+#define VR_HIST_BINS      256
+#define VR_HIST_GRAD_BINS 111      /* isqrt(3 * 255^2) >> 2 = 110 */
+vr_status vr_histogram_bricks(const uint8_t *data_dev, int32_t num_bricks, int64_t voxels_per_brick,
+                              uint32_t *bricks_host /* B*256 or NULL */, uint64_t *total_host /* 256 or NULL */,
+                              void *stream);
+vr_status vr_histogram_pool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                            const int64_t grid[3], uint32_t *cells_host /* cells*256 or NULL */,
+                            uint64_t *total_host /* 256 or NULL */, void *stream);
+vr_status vr_histogram2d(const uint8_t *volume_dev, const int64_t dims[3], const int64_t global_dims[3],
+                         const int64_t vol_origin[3], const int64_t own_lo[3], const int64_t own_hi[3],
+                         uint64_t *hist_host /* 111*256 */, void *stream);
+vr_status vr_window_from_histogram(const uint64_t *hist /* 256 */, int32_t first_bin, double lo_fraction,
+                                   double hi_fraction, float *window_lo, float *window_hi);
+
 /* ---- ingest: VolumeReader<T>::LoadBricksToTexture (VolumeReader.h:151-223) ------
  * Places brick b (brick_dims, x-fastest, contiguous at bricks_dev + b*brick_voxels)
  * at grid cell brick_ijk[3*b..3*b+2] of a global x-fastest volume of
@@ -743,7 +799,8 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
  * time.  Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks", "no_uniform_blocks"; any other name is VR_ERR_INVALID.
  * Results never depend on a switch; the tests use them to check the kernels against each other.
  * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1"; "reslice_tile_w" = 8, 16 or 64, the width of
- * the 64-pixel tile a wave of vr_reslice covers (16 is the default, chosen by measurement: DESIGN.md 3.5g). */
+ * the 64-pixel tile a wave of vr_reslice covers (16 is the default, chosen by measurement: DESIGN.md 3.5g); "hist_plain" = 1
+ * runs the histogram kernels without their data-aware paths (the same counts; DESIGN.md 3.5i prices them with it). */
 vr_status vr_brickset_set_switch(vr_brickset *bs, const char *name, int32_t value);
 vr_status vr_debug_set(const char *name, int32_t value);
 

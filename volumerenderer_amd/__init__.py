@@ -22,7 +22,9 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
                 "raycast_pool_tf_shaded", "raycast_tf_partial", "raycast_pool_tf_partial", "composite_over_tf",
                 "composite_finish_tf", "Projection", "raycast_projection", "raycast_pool_projection",
                 "raycast_projection_partial", "raycast_pool_projection_partial", "composite_combine_proj",
-                "composite_finish_proj", "SlicePlane", "reslice", "reslice_partial", "select_lod_error", "rate_distortion"):
+                "composite_finish_proj", "SlicePlane", "reslice", "reslice_partial", "select_lod_error", "rate_distortion",
+                "histogram_bricks", "histogram", "histogram_pool", "histogram2d", "window_from_histogram",
+                "projection_from_histogram"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

@@ -120,6 +120,10 @@ SIGNATURES = {
     "vr_measure_error_bricks": (_I32, [_P, _P, _I32, _I64, _P, _P]),
     "vr_brickset_error_table": (_I32, [_P, _P, _P, _I32, _I32, _P, _P]),
     "vr_lod_select_error": (_I32, [_P, _I32, _I32, _I32, _I64, C.POINTER(_I32), _I32, C.c_double, C.POINTER(_I32)]),
+    "vr_histogram_bricks": (_I32, [_P, _I32, _I64, _P, _P, _P]),
+    "vr_histogram_pool": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), _P, _P, _P]),
+    "vr_histogram2d": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
+    "vr_window_from_histogram": (_I32, [_P, _I32, C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vr_assemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_disassemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_raycast": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),

@@ -330,6 +330,7 @@ vr_status vr_debug_set(const char *name, int32_t value)
         vr::g_resliceTileLog2.store(value == 8 ? 3 : (value == 16 ? 4 : 6));
         return VR_OK;
     }
+    if (!strcmp(name, "hist_plain")) { vr::g_histPlain.store(value ? 1 : 0); return VR_OK; }
     return VR_ERR_INVALID;
 }
 

@@ -297,3 +297,31 @@ extern "C" vr_status vr_lod_select_error(const vr_brick_error *table, int32_t nu
     }
     return VR_OK;
 }
+
+// ---- a display window from a histogram's percentiles: the rule is stated in vrhip.h ("volume histograms") ----
+extern "C" vr_status vr_window_from_histogram(const uint64_t *hist, int32_t first_bin, double lo_fraction, double hi_fraction,
+                                              float *window_lo, float *window_hi)
+{
+    if (!hist || !window_lo || !window_hi || first_bin < 0 || first_bin > 255) return VR_ERR_INVALID;
+    if (!(lo_fraction >= 0.0 && lo_fraction <= 1.0) || !(hi_fraction >= 0.0 && hi_fraction <= 1.0)) return VR_ERR_INVALID;   // (NaN too)
+    if (lo_fraction > hi_fraction) return VR_ERR_INVALID;
+    uint64_t n = 0;
+    for (int k = first_bin; k < 256; ++k) n += hist[k];
+    if (n == 0) return VR_ERR_INVALID;
+    const double lo_at = lo_fraction * (double)n, hi_at = hi_fraction * (double)n;
+    int lo_k = -1, hi_k = -1, last = first_bin;
+    uint64_t cum = 0;
+    for (int k = first_bin; k < 256; ++k) {
+        cum += hist[k];
+        if (hist[k] != 0) last = k;
+        if (lo_k < 0 && (double)cum > lo_at) lo_k = k;
+        if (hi_k < 0 && (double)cum >= hi_at) hi_k = k;
+    }
+    if (lo_k < 0) lo_k = last;
+    if (hi_k < 0) hi_k = 255;                  // (cum_255 = N >= hi_fraction N: never taken)
+    if (hi_k <= lo_k) hi_k = lo_k + 1;
+    if (hi_k > 255) { --lo_k; --hi_k; }
+    *window_lo = (float)lo_k / 255.0f;
+    *window_hi = (float)hi_k / 255.0f;
+    return VR_OK;
+}

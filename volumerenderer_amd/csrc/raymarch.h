@@ -58,5 +58,6 @@ bool projection_ok(const vr_projection *);
 // process-wide debugging switches (vr_debug_set), defined beside the launchers that read them
 extern std::atomic<int> g_skipGridV1;
 extern std::atomic<int> g_resliceTileLog2;
+extern std::atomic<int> g_histPlain;          // histogram.hip: the kernels without their data-aware paths
 
 } // namespace vr

@@ -118,6 +118,35 @@ def slab_plane(plane, dims, axis, rank, world, halo=1):
     return p, local, held
 
 
+def slab_voxels(dims, axis, rank, world, halo=1):
+    """slab_params' twin for the voxel-space calls (render.histogram2d): rank `rank`'s slab when a volume of `dims`
+    voxels is cut into `world` slabs along `axis`, stored with `halo` voxel layers beyond each cut (1: the central
+    differences reach one voxel).  Returns (vol_origin, own_lo, own_hi, local_dims, (a0, a1)): the rank holds the
+    voxels [a0, a1) along `axis` and owns [own_lo, own_hi) in global coordinates; the own boxes of the ranks tile the
+    volume."""
+    dims, _, _, org, local, held = _slab_cut("slab_voxels", dims, axis, rank, world, halo)
+    lo, hi = [0, 0, 0], list(dims)
+    lo[axis], hi[axis] = shard_range(dims[axis], rank, world)
+    return tuple(org), tuple(lo), tuple(hi), local, held
+
+
+def histogram_all_reduce(hist, group=None):
+    """The sum of every rank's histogram (any of render's tables: counts add exactly): an int64 all-reduce over `group`
+    (None: the default group).  Without a process group -- torch.distributed not initialised -- it is the identity.
+    hist: an integer numpy array or torch tensor; returns the same kind, shape and dtype."""
+    import numpy as np
+    is_np = not isinstance(hist, torch.Tensor)
+    if not dist.is_initialized():
+        return hist
+    t = torch.from_numpy(np.ascontiguousarray(hist).astype(np.int64)) if is_np else hist.to(torch.int64).clone()
+    if dist.get_backend(group) == "nccl":
+        t = t.cuda()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    if is_np:
+        return t.cpu().numpy().astype(np.asarray(hist).dtype)
+    return t.to(device=hist.device, dtype=hist.dtype)
+
+
 _compositors = {}
 
 

@@ -741,6 +741,119 @@ def reslice_partial(volume, dims, plane, proj, out=None, stream=None):
     return _reslice_dense("vr_reslice_partial", volume, dims, plane, proj, out, stream)
 
 
+# ---- volume histograms (vr_histogram_bricks & co.; the rule is in vrhip.h) ----------------------------------------------
+HIST_BINS, HIST_GRAD_BINS = 256, 111
+
+
+def histogram_bricks(data, num_bricks, stream=None):
+    """The 256-bin histograms of `num_bricks` equal bricks laid out back to back (vr_histogram_bricks): returns
+    (bricks, total), a (num_bricks, 256) uint32 and a (256,) uint64 numpy array of exact counts; the rows of `bricks` sum
+    to `total`.  `data` may start at any byte."""
+    d = _as_dev_u8(data)
+    nb = int(num_bricks)
+    if nb < 1 or nb >= 1 << 31 or d.numel() == 0 or d.numel() % nb or d.numel() // nb > 0xFFFFFFFF:
+        raise ValueError("histogram_bricks: %d bytes for %d bricks (of 1 .. 2^32 - 1 bytes each)" % (d.numel(), nb))
+    bricks, total = np.zeros((nb, HIST_BINS), np.uint32), np.zeros(HIST_BINS, np.uint64)
+    check(_lib.lib().vr_histogram_bricks(_ptr(d), nb, d.numel() // nb, C.c_void_p(bricks.ctypes.data),
+                                         C.c_void_p(total.ctypes.data), _stream_ptr(stream)), "vr_histogram_bricks")
+    return bricks, total
+
+
+def histogram(volume, stream=None):
+    """The 256-bin histogram of a device buffer of up to 2^32 - 1 bytes (one brick = the whole tensor): a (256,) uint64
+    numpy array.  Larger buffers: histogram_bricks, whose total is carried in 64 bits."""
+    d = _as_dev_u8(volume)
+    if d.numel() == 0 or d.numel() > 0xFFFFFFFF:
+        raise ValueError("histogram: %d bytes (1 .. 2^32 - 1; cut larger buffers into bricks)" % d.numel())
+    total = np.zeros(HIST_BINS, np.uint64)
+    check(_lib.lib().vr_histogram_bricks(_ptr(d), 1, d.numel(), None, C.c_void_p(total.ctypes.data), _stream_ptr(stream)),
+          "vr_histogram_bricks")
+    return total
+
+
+def histogram_pool(pool, table, brick_dims, grid, stream=None):
+    """The histogram of the virtual volume of a pool (vr_histogram_pool), per grid cell and in total: (cells, total), a
+    (cells, 256) uint32 and a (256,) uint64 numpy array.  Equal to histogram_bricks of that volume laid out brick by
+    brick: a coarse cell's stored voxels count for the box they stand for, an absent cell is all zeros."""
+    src = _pool_source(pool, table, brick_dims, grid)
+    bd, g = [int(q) for q in brick_dims], [int(q) for q in grid]
+    if len(bd) != 3 or len(g) != 3 or any(q < 1 or q & (q - 1) for q in bd) or any(q < 1 for q in g) \
+            or bd[0] * bd[1] * bd[2] > 0xFFFFFFFF or g[0] * g[1] * g[2] >= 1 << 31 or any(g[k] >= (1 << 31) // bd[k] for k in range(3)):
+        raise ValueError("histogram_pool: bricks %r (powers of two, at most 2^32 - 1 voxels) on a grid %r" % (bd, g))
+    cells, total = np.zeros((g[0] * g[1] * g[2], HIST_BINS), np.uint32), np.zeros(HIST_BINS, np.uint64)
+    check(_lib.lib().vr_histogram_pool(*src.args, C.c_void_p(cells.ctypes.data), C.c_void_p(total.ctypes.data),
+                                       _stream_ptr(stream)), "vr_histogram_pool")
+    return cells, total
+
+
+def _int3(v, what):
+    try:
+        t = tuple(int(q) for q in v)
+    except TypeError:
+        raise ValueError("%s must be three integers, not %r" % (what, v))
+    if len(t) != 3:
+        raise ValueError("%s must be three integers, not %r" % (what, v))
+    return t
+
+
+def histogram2d(volume, dims, global_dims=None, vol_origin=(0, 0, 0), own_lo=None, own_hi=None, stream=None):
+    """The joint histogram of value and gradient magnitude (vr_histogram2d): a (111, 256) uint64 numpy array, entry
+    [r, v] the owned voxels of value v whose central-difference gradient has isqrt(dx^2 + dy^2 + dz^2) >> 2 == r.
+    `volume` holds the voxels [vol_origin, vol_origin + dims) of a volume of `global_dims` (default: dims); the owned
+    voxels are [own_lo, own_hi) in global coordinates (default: all the volume holds).  The volume must hold every
+    clamped neighbour of every owned voxel -- one halo layer beyond the own box (distributed.slab_voxels) -- else
+    ValueError, raised before anything touches a device.  Its column sums are the histogram of the owned voxels; the tables of boxes that tile a volume add up
+    to the whole volume's."""
+    d = _int3(dims, "dims")
+    G = d if global_dims is None else tuple(g or q for g, q in zip(_int3(global_dims, "global_dims"), d))
+    org = _int3(vol_origin, "vol_origin")
+    lo = org if own_lo is None else _int3(own_lo, "own_lo")
+    hi = tuple(o + q for o, q in zip(org, d)) if own_hi is None else _int3(own_hi, "own_hi")
+    for k in range(3):
+        end = org[k] + d[k]
+        if not (0 < d[k] < 1 << 31 and 0 < G[k] < 1 << 31 and 0 <= org[k] and end <= G[k]):
+            raise ValueError("histogram2d: axis %d: %d voxels at %d of %d" % (k, d[k], org[k], G[k]))
+        if not (org[k] <= lo[k] < hi[k] <= end):
+            raise ValueError("histogram2d: axis %d: own box [%d, %d) of the voxels [%d, %d)" % (k, lo[k], hi[k], org[k], end))
+        if max(lo[k] - 1, 0) < org[k] or min(hi[k], G[k] - 1) > end - 1:
+            raise ValueError("histogram2d: axis %d: the volume holds [%d, %d) and no halo layer around the own box [%d, %d)"
+                             % (k, org[k], end, lo[k], hi[k]))
+    src = _dense_source(volume, d)
+    I3 = C.c_int64 * 3
+    hist = np.zeros((HIST_GRAD_BINS, HIST_BINS), np.uint64)
+    check(_lib.lib().vr_histogram2d(src.args[0], src.args[1], I3(*G), I3(*org), I3(*lo), I3(*hi), C.c_void_p(hist.ctypes.data),
+                                    _stream_ptr(stream)), "vr_histogram2d")
+    return hist
+
+
+def window_from_histogram(hist, first_bin=0, lo_fraction=0.01, hi_fraction=0.99):
+    """A display window (lo, hi) from the percentiles of a 256-bin histogram (vr_window_from_histogram, host only; the
+    rule is in vrhip.h): lo is the bin where the cumulative count of the bins from `first_bin` on passes lo_fraction of
+    their sum, hi where it reaches hi_fraction; both as value / 255, always 0 <= lo < hi <= 1.  first_bin = 1 leaves the
+    background out.  A (111, 256) table of histogram2d is summed over its rows first."""
+    h = np.asarray(hist)
+    if h.shape == (HIST_GRAD_BINS, HIST_BINS):
+        h = h.sum(0)
+    if h.shape != (HIST_BINS,) or h.dtype.kind not in "ui" or (h.dtype.kind == "i" and h.min() < 0):
+        raise ValueError("window_from_histogram: 256 counts, not %s %s" % (h.dtype, h.shape))
+    h = np.ascontiguousarray(h, np.uint64)
+    fb, lf, hf = int(first_bin), float(lo_fraction), float(hi_fraction)
+    if not 0 <= fb <= 255 or not (0.0 <= lf <= hf <= 1.0):
+        raise ValueError("window_from_histogram: first_bin %r, fractions %r .. %r" % (first_bin, lo_fraction, hi_fraction))
+    if not h[fb:].any():
+        raise ValueError("window_from_histogram: no counts from bin %d on" % fb)
+    lo, hi = C.c_float(), C.c_float()
+    check(_lib.lib().vr_window_from_histogram(C.c_void_p(h.ctypes.data), fb, lf, hf, C.byref(lo), C.byref(hi)),
+          "vr_window_from_histogram")
+    return lo.value, hi.value
+
+
+def projection_from_histogram(hist, op="max", first_bin=0, lo_fraction=0.01, hi_fraction=0.99, background=(0.0, 0.0, 0.0),
+                              lut=None, device="cuda"):
+    """A Projection whose window is window_from_histogram(hist, first_bin, lo_fraction, hi_fraction)."""
+    return Projection(op, window_from_histogram(hist, first_bin, lo_fraction, hi_fraction), background, lut, device)
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}
