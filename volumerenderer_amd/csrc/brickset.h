@@ -28,6 +28,7 @@ struct Switches {
     bool decodeQuad = false;     // VRHIP_DECODE_QUAD: round 2's k_decode_quad instead of k_decode_region
     bool noSkipBlocks = false;   // VRHIP_NO_SKIP_BLOCKS
     bool noUniformBlocks = false; // VRHIP_NO_UNIFORM_BLOCKS: constant 4096-leaf blocks go through k_prune_emit12, not k_prune_emit12_const
+    bool noUniformDecode = false; // VRHIP_NO_UNIFORM_DECODE: k_decode_region ignores BrickSet::boxUniform (every live box is parsed).  Read per call
 };
 
 // vr_brickset_decode_lod: the device state of one call.  Calls take the slots of a ring in turn; a call waits on the
@@ -98,6 +99,8 @@ struct BrickSet {
     bool fineAll = false;         // ... of every brick: kept by fine_has_changed() wherever fineHas is assigned
     uint32_t *decTables = nullptr; // B * FD_TABLE_WORDS: k_decode_fine's tables of every brick for the current cut
     uint8_t *idxVal3 = nullptr;   // B * nIdx * 8   decoded scalar of every depth-(D-3) node (k_decode_quad; with fineIdx)
+    uint32_t *boxUniform = nullptr; // B * 2^(D-12)  1: every voxel of the 4096-leaf box decodes to one byte at every cut >= D-3 (written by
+                                  // k_prune_emit12_const for the strings it composes; cleared by every build; k_decode_region's hint, with fineIdx)
     uint32_t *chainTab = nullptr; // 8 x 16384 entries: k_decode_quad's grown-branch tables, one per number of refining levels (0..7),
     bool chainTabReady = false;   // all written once (never rewritten: decodes of one set on several streams may share them)
     std::vector<std::vector<uint8_t>> hostTree; // foreign streams keep their bytes for progressive cuts

@@ -209,7 +209,7 @@ vr_status vr_brickset_destroy(vr_brickset *h)
     free_stream2(b.mid);
     free_stream2(b.rng);
     hipFree(b.brickOff); hipFree(b.compactOverflow);
-    hipFree(b.idxOff); hipFree(b.idxVal); hipFree(b.idxValCut); hipFree(b.fineIdx); hipFree(b.idxVal3); hipFree(b.chainTab); hipFree(b.decTables); hipFree(b.lut); hipFree(b.spread); hipFree(b.srcIdx); hipFree(b.ownerRank); hipFree(b.ownerSurv); hipFree(b.rankVals);
+    hipFree(b.idxOff); hipFree(b.idxVal); hipFree(b.idxValCut); hipFree(b.fineIdx); hipFree(b.idxVal3); hipFree(b.boxUniform); hipFree(b.chainTab); hipFree(b.decTables); hipFree(b.lut); hipFree(b.spread); hipFree(b.srcIdx); hipFree(b.ownerRank); hipFree(b.ownerSurv); hipFree(b.rankVals);
     for (int i = 0; i < 8; ++i) if (b.ev[i]) hipEventDestroy(b.ev[i]);
     if (b.evFork) hipEventDestroy(b.evFork);
     for (int i = 0; i < 3; ++i) { if (b.evJoinN[i]) hipEventDestroy(b.evJoinN[i]); if (b.auxN[i]) hipStreamDestroy(b.auxN[i]); }
@@ -247,6 +247,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         w.decodeQuad = getenv("VRHIP_DECODE_QUAD") != nullptr;
         w.noSkipBlocks = getenv("VRHIP_NO_SKIP_BLOCKS") != nullptr;
         w.noUniformBlocks = getenv("VRHIP_NO_UNIFORM_BLOCKS") != nullptr;
+        w.noUniformDecode = getenv("VRHIP_NO_UNIFORM_DECODE") != nullptr;
     }
     make_geom(b.g, dims);
     b.D = b.g.D;
@@ -310,6 +311,7 @@ vr_status vr_brickset_set_switch(vr_brickset *h, const char *name, int32_t value
     else if (!strcmp(name, "decode_quad")) w.decodeQuad = on;
     else if (!strcmp(name, "no_skip_blocks")) w.noSkipBlocks = on;
     else if (!strcmp(name, "no_uniform_blocks")) w.noUniformBlocks = on;
+    else if (!strcmp(name, "no_uniform_decode")) w.noUniformDecode = on;
     else return VR_ERR_INVALID;
     return VR_OK;
 }

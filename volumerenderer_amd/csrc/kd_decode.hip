@@ -1203,6 +1203,7 @@ struct RegionArgs {
     int nreg;                   // regions of a brick
     const int32_t *list, *cuts; // per-brick decode (lod_brick / lod_cut); null: every brick at `cut`
     const int64_t *obase;       // per-row output offsets (lod_obase); null: brick * voxels
+    const uint32_t *uni;        // BrickSet::boxUniform (one word per emit block: nIdx / 64 per brick); null: every live block is parsed
 };
 
 __device__ __forceinline__ uint32_t wave_incl_scan_max_dpp(uint32_t v)
@@ -1313,6 +1314,7 @@ __device__ __forceinline__ void rg_vm_wait(uint32_t n)
                  : "=&s"(keep_) : "v"(gptr), "s"(ldsByte) : "memory"); } while (0)
 
 #define RG_IDXD 3           // regions the index entries run ahead
+#define RG_IDXV 20          // words of a landed scalar slot: 16 + the flag, 16-byte aligned
 
 __global__ void __launch_bounds__(64 * RG_WAVES, RG_MINW)
 k_decode_region(RegionArgs a)
@@ -1324,7 +1326,7 @@ k_decode_region(RegionArgs a)
     struct Shared {
         RegionShared t;
         uint32_t idxOff[RG_WAVES][RG_IDXD][64];     // landed index entries: token offset of every 64-leaf block's root ...
-        uint32_t idxVal[RG_WAVES][RG_IDXD][16];     // ... and its scalar (64 bytes)
+        uint32_t idxVal[RG_WAVES][RG_IDXD][RG_IDXV]; // ... and its scalar (64 bytes); word 16: the emit block's uniform flag
         uint32_t blkTab[3][64];                     // emit block number = blkTab[0][x >> 4] | blkTab[1][y >> 4] | blkTab[2][z >> 4]
     };
     __shared__ __attribute__((aligned(16))) Shared smw;
@@ -1431,17 +1433,21 @@ k_decode_region(RegionArgs a)
         const uint32_t blk = smw.blkTab[0][rx * (uint32_t)RG_WAVES + (uint32_t)wave] | smw.blkTab[1][ry] | smw.blkTab[2][rz];
         return (int64_t)brick * a.nIdx + ((int64_t)blk << 6);
     };
+    const int idxLanes = a.uni ? 17 : 16;
     const auto request_index = [&](int r, int slot) {    // 256 + 64 bytes into index slot `slot`
         const int64_t io = index_of(r);
         RG_DMA("dword", a.idxOff + io + lane, idxOffLds + (uint32_t)slot * 256u);
-        if (lane < 16) RG_DMA("dword", (const uint32_t *)(a.idxVal + io) + lane, idxValLds + (uint32_t)slot * 64u);
+        // (the flag word rides in a seventeenth lane of the scalars' request: still two operations per request)
+        const uint32_t *vp = a.uni && lane == 16 ? a.uni + (io >> 6) : (const uint32_t *)(a.idxVal + io) + lane;
+        if (lane < idxLanes) RG_DMA("dword", vp, idxValLds + (uint32_t)slot * (4u * RG_IDXV));
         ops += 2;
 #pragma unroll
         for (int i = 0; i < RG_IDXD; ++i) markIdx[i] = slot == i ? ops : markIdx[i];
     };
-    const auto issue_piece = [&](uint32_t wbase, uint32_t p) {      // piece p of a string: words [wbase + 256 p, + 256) -> ring slot p mod RG_NP
+    // piece p of a string: words [wbase + 256 p, + 256) -> ring slot p mod RG_NP; its first nl lanes only (lane 0 is always one)
+    const auto issue_piece = [&](uint32_t wbase, uint32_t p, int nl = 64) {
         const uint32_t w = wbase + 256u * p + 4u * (uint32_t)lane;
-        if (w + 4u <= capWords) RG_DMA("dwordx4", W + w, ringLds + (p & (RG_NP - 1)) * 1024u);
+        if (w + 4u <= capWords && lane < nl) RG_DMA("dwordx4", W + w, ringLds + (p & (RG_NP - 1)) * 1024u);
         ++ops;
 #pragma unroll
         for (int i = 0; i < RG_NP; ++i) markP[i] = (p & (RG_NP - 1)) == (uint32_t)i ? ops : markP[i];
@@ -1449,6 +1455,7 @@ k_decode_region(RegionArgs a)
     // the staged state of a region
     unsigned long long liveMask = 0ull;
     uint32_t wbase = 0, totalPieces = 0, issued = 0, markSide = 0, offC = VR_IDX_DEAD, valC = 0;
+    bool uniC = false;      // a live block flagged uniform: its first quad is decoded and broadcast
     // From the offsets alone: the string runs from the first live 64-leaf block's root to (a bound on) the last one's
     // end.  Its first two pieces go to ring slots 0 and 1; the counts (1 KiB) and depth-(D-3) scalars (512 B) of the
     // region land in slots 3 and 2, which the park reads before the string's pieces 2 and 3 are requested: a trip of
@@ -1459,17 +1466,24 @@ k_decode_region(RegionArgs a)
         valC = (smw.idxVal[wave][slot][lane >> 2] >> (8 * (lane & 3))) & 255u;
         const bool liveL = offC != VR_IDX_DEAD;
         liveMask = __ballot(liveL);
-        wbase = 0; totalPieces = 0; issued = 0;
+        wbase = 0; totalPieces = 0; issued = 0; uniC = false;
         if (liveMask == 0ull) return;
+        uniC = a.uni && (liveMask & 1ull) != 0ull && __builtin_amdgcn_readfirstlane((int)smw.idxVal[wave][slot][16]) != 0;
         const int firstL = __ffsll((long long)liveMask) - 1, lastL = 63 - __clzll((long long)liveMask);
         const uint32_t firstOff = (uint32_t)__builtin_amdgcn_readlane((int)offC, firstL), lastOff = (uint32_t)__builtin_amdgcn_readlane((int)offC, lastL);
         wbase = (firstOff >> 4) & ~3u;                                  // first word, 16-byte aligned
         const uint32_t tp = ((((lastOff + 575u + 15u) >> 4) - wbase) + 255u) >> 8;    // (a 64-leaf subtree is at most 63 + 64 * 8 tokens)
         totalPieces = min(tp, (capWords - wbase + 255u) >> 8);                        // (every piece has a lane inside the buffer)
-        for (uint32_t p = 0; p < 2u && p < totalPieces; ++p) { issue_piece(wbase, p); ++issued; }
+        // A uniform block: the first quad's tokens (4 ancestors + 1 + 2 (1 + 2 * 8) = 39, starting inside the first four
+        // words) lie in the first eight words of piece 0, its count and depth-(D-3) scalar in lane 0's part of the
+        // side-cars.  The same three requests with fewer lanes; no further piece (ops, markP and markSide count
+        // instructions, not lanes: lane 0 takes part in each, so none is skipped)
+        if (uniC) totalPieces = min(totalPieces, 1u);
+        const int pieceLanes = uniC ? 2 : 64, fineLanes = uniC ? 1 : 64, val3Lanes = uniC ? 1 : 32;
+        for (uint32_t p = 0; p < 2u && p < totalPieces; ++p) { issue_piece(wbase, p, pieceLanes); ++issued; }
         const int64_t io = index_of(r);
-        RG_DMA("dwordx4", a.fine + (io + lane) * 16, ringLds + 3u * 1024u);
-        if (lane < 32) RG_DMA("dwordx4", a.val3 + io * 8 + lane * 16, ringLds + 2u * 1024u);
+        if (lane < fineLanes) RG_DMA("dwordx4", a.fine + (io + lane) * 16, ringLds + 3u * 1024u);
+        if (lane < val3Lanes) RG_DMA("dwordx4", a.val3 + io * 8 + lane * 16, ringLds + 2u * 1024u);
         ops += 2;
         markSide = ops;
     };
@@ -1484,6 +1498,21 @@ k_decode_region(RegionArgs a)
         if (liveMask == 0ull) {
             // an emit block under pruned nodes: one value per 64-leaf block, no stream, no further side-car
             const uint32_t rep = valC * 0x01010101u;
+#pragma unroll
+            for (int gg = 0; gg < 16; ++gg) buf[laneTerm ^ ((a.parkP[gg >> 2] >> (8 * (gg & 3))) & 255u)] = rep;
+            if (rid + RG_IDXD * G < nreg) request_index(rid + RG_IDXD * G, slot);
+        } else if (uniC) {
+            // a uniform block (BrickSet::boxUniform): all 4096 voxels are the byte of its first one.  The park word of
+            // 4-leaf subtree 0 of 64-leaf block 0, as the park below makes it for lane 0, gg = 0 (own = 4: p0 = 8,
+            // p1 = 10), decoded by rg_quad with the launch's tables -- the same in every lane, from wave-uniform LDS
+            // reads -- and written like a dead block's value.  The side-cars were requested after piece 0: loads
+            // return in issue order, so markSide covers the piece too.
+            rg_vm_wait(ops - markSide);
+            const uint32_t c0 = ringW[768] & 255u, v0 = ringW[512] & 255u;
+            const uint32_t run = (uint32_t)__builtin_amdgcn_readfirstlane((int)offC) - wbase * 16u;
+            const uint32_t pw = v0 | (run << 8) | ((4u - c0) & 0x01000000u);
+            const uint32_t *r0 = ringW + ((pw >> 12) & RG_RING_MASK);
+            const uint32_t rep = (rg_quad(pw, r0[0], r0[1], r0[2], r0[3], 8u, 10u, sm) & 255u) * 0x01010101u;
 #pragma unroll
             for (int gg = 0; gg < 16; ++gg) buf[laneTerm ^ ((a.parkP[gg >> 2] >> (8 * (gg & 3))) & 255u)] = rep;
             if (rid + RG_IDXD * G < nreg) request_index(rid + RG_IDXD * G, slot);
@@ -1753,6 +1782,8 @@ static int launch_decode(BrickSet *bs, DecodeKernel k, uint8_t *out, int cut, hi
         r.blkX = p.blkX; r.blkY = p.blkY; r.blkZ = p.blkZ; r.nreg = p.nreg;
         common(r, out, obase);
         r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.spread = bs->spread;
+        // the uniform hint describes the mid stream of this handle's own last build (an installed stream has none)
+        r.uni = bs->foreign || rangeStream || bs->sw.noUniformDecode ? nullptr : bs->boxUniform;
         // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
         // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
         unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);

@@ -1594,6 +1594,7 @@ struct PruneEmitArgs {
     int64_t treeCap;
     SkipBlocks sk, skR;            // blocks the level loop left alone below depth D-2: all "keep", exactly reproduced (per stream)
     int uniformBlocks;             // constant blocks (flag bit 0) are k_prune_emit12_const's: k_prune_emit12<false, true> leaves them alone
+    uint32_t *boxUniform;          // BrickSet::boxUniform: zero when the prune starts; k_prune_emit12_const sets the boxes it composes a string for
 };
 
 __device__ __forceinline__ void pe_put(uint32_t *W, uint32_t bitpos, unsigned long long v, int ntok)
@@ -2170,7 +2171,10 @@ k_prune_emit12_const(PruneEmitArgs a)
             const int lq = 31 - __clz(t);
             if ((changed >> lq) & 1u) cset3(Cb, ((int64_t)1 << (D - 12 + lq)) + ((int64_t)blk << lq) + (t - (1 << lq)));
         }
-        if (t == 0) a.subTok[(int64_t)brick * a.nEmitBlk + blk] = tot;
+        if (t == 0) {
+            a.subTok[(int64_t)brick * a.nEmitBlk + blk] = tot;
+            a.boxUniform[(int64_t)brick * a.sk.nBlk + blk] = 1u;     // uniform by induction: one byte per cut (k_decode_region)
+        }
         if (t < 4) {
             const uint32_t fe = res[b][5] & 0xFFFFu, eB = res[b][5] >> 16;
             a.blockL1[(int64_t)brick * a.nEmitBlk + (size_t)blk * 4 + t] = stat_pack((unsigned long long)fe * 1024ull, (int)eB, (int)fe);
@@ -3048,7 +3052,11 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         pa.chainLut = bs->chainLut; pa.idxOff = bs->idxOff; pa.nIdx = bs->nIdx;
         if (!bs->fineIdx && hipMalloc(&bs->fineIdx, (size_t)B * bs->nIdx * 16) != hipSuccess) return -3;
         if (!bs->idxVal3 && hipMalloc(&bs->idxVal3, (size_t)B * bs->nIdx * 8) != hipSuccess) return -3;
-        pa.fineIdx = (uint32_t *)bs->fineIdx;
+        // the uniform hint of k_decode_region: no flag of an earlier build survives, whichever kernels serve this one
+        const size_t boxBytes = (size_t)B * ((size_t)1 << (D - 12)) * sizeof(uint32_t);
+        if (!bs->boxUniform && hipMalloc(&bs->boxUniform, boxBytes) != hipSuccess) return -3;
+        if (hipMemsetAsync(bs->boxUniform, 0, boxBytes, st) != hipSuccess) return -1;
+        pa.fineIdx = (uint32_t *)bs->fineIdx; pa.boxUniform = bs->boxUniform;
         pa.ctrlsR = mr ? bs->rng.ctrl : nullptr; pa.tempR = mr ? bs->rng.temp : nullptr; pa.codesR = mr ? bs->rng.codes : nullptr;
         pa.rbR = rbR;
         pa.gap = bs->mid.tree; pa.gapR = mr ? bs->rng.tree : nullptr; pa.treeCap = bs->treeCap;
