@@ -226,7 +226,21 @@ vr_status vr_brickset_decode_lod_pool(vr_brickset *bs, const int32_t *cuts_host,
 vr_status vr_brickset_decode_range(vr_brickset *bs, int32_t cut_depth, uint8_t *out_dev, void *stream);
 
 /* Install a foreign preorder stream (e.g. read from a reference-written file) as
- * brick `brick`: builds the decode side-car index from the bytes alone. */
+ * brick `brick`: builds the decode side-car index from the bytes alone.
+ * Any stream of the grammar of SURVEY.md Appendix A.4 is accepted, with any distance
+ * map: not only what an encoder emits (prunes at any depth, grown branches of any
+ * length 0 .. 7, distances of any byte value).  vr_brickset_decode, _decode_lod and
+ * _decode_lod_pool then give the values that grammar defines, at every cut.
+ * A stream that ends early, has tokens left over or ends inside a grown branch is
+ * VR_ERR_FORMAT and leaves the set as it was.
+ * Extents that the tiled decoders serve: k_decode_region and k_decode_quad hold the
+ * grown-branch distances (map entries origTreeDepth + 1 .. + 7) as the constants
+ * 64 >> i, so a brick whose map says otherwise is decoded by the walking kernel,
+ * which reads them from the map, and one such brick sends its whole set there (the
+ * results are the same).  Installing the brick again decides anew.  At all other
+ * extents one kernel decodes every stream and reads the distances from the map.
+ * A set may hold bricks that were never installed: vr_brickset_decode_lod and
+ * _decode_lod_pool skip them with cut -1. */
 vr_status vr_brickset_set_tree(vr_brickset *bs, int32_t brick, const uint8_t *tree_host, int64_t tree_bytes,
                                int64_t num_active_nodes, const uint8_t *distance_map_host, int32_t map_len);
 

@@ -307,6 +307,10 @@ __device__ __forceinline__ void chain_tables(const uint8_t *dmS, uint32_t *lutC1
             LO += dl; LO = LO < 0 ? 0 : (LO > 255 ? 255 : LO);
             HI += dl; HI = HI < 0 ? 0 : (HI > 255 ? 255 : HI);
         }
+        // the entry holds A + 256 in ten bits.  The encoder's distances (64 >> i) keep |A| <= 120; a foreign map may hold
+        // any bytes (k_decode_tile reads the grown-branch distances from it), and a sum below -256 would spill into every
+        // other field.  For v in [0, 255], A and A clamped to [-255, 255] give the same min(max(v + A, LO), HI)
+        A = A < -255 ? -255 : (A > 255 ? 255 : A);
         // k_decode_fine (no table 1) takes LO / HI as whole bytes: min / max read them without a separate extract
         const uint32_t ent = lutC1 ? (uint32_t)(A + 256) | ((uint32_t)LO << 10) | ((uint32_t)HI << 18) | ((uint32_t)len << 26) |
                                          ((uint32_t)term << 29)
@@ -603,6 +607,8 @@ k_decode_tile(TileArgs a)
 // voxel-leaf table (256 threads, 1024 entries): a leaf's code and the first four tokens of its grown branch,
 // composed like chain_tables: v -> min(max(v + A, LO), HI).  [0:10) A + 512, [10:13) tokens consumed (code included),
 // 13 ended (pruned leaf or terminator; otherwise branch tokens 5-7 follow: lutC2), byte 2 LO, byte 3 HI.
+// (|A| <= 255 + 120 fits the field only because vr_brickset_set_tree keeps maps with other grown-branch distances than
+// 64 >> i away from k_decode_fine.)
 __device__ __forceinline__ void leaf_table(const uint8_t *dmS, uint32_t *lutL)
 {
     for (int idx = threadIdx.x; idx < 1024; idx += 256) {
