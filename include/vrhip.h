@@ -118,7 +118,14 @@ vr_status vr_download(void *dst_host, const void *src_dev, int64_t bytes, void *
  * reference's brick sizes 256x256x128 / 256^3) take the tiled fast kernels, everything else table-driven ones.
  * Limits of one tree: origTreeDepth <= 31, fewer than 2^32 voxels and at most 2^20 cells per axis; deeper than 28
  * levels (a stream can then pass 2^32 tokens: 64-bit token offsets, table-driven kernels) only with num_bricks == 1
- * -> VR_ERR_UNSUPPORTED beyond.  The reference program's own 2048x2048x768 tree (main.cpp:242-251) is 31 levels. */
+ * -> VR_ERR_UNSUPPORTED beyond.  The reference program's own 2048x2048x768 tree (main.cpp:242-251) is 31 levels.
+ * tolerance: any non-negative value.  A leaf error never exceeds 255, so every tolerance >= 256 means the same thing:
+ * the kernels are given min(tolerance, 256); vr_brickset_info keeps reporting the caller's value.
+ * max_epochs: 0 .. VR_MAX_EPOCHS.  A build issues max_epochs x origTreeDepth x (3 to 4) launches whatever the data
+ * does (no level used more than 13 epochs on the volumes measured), so a larger value is refused
+ * with VR_ERR_UNSUPPORTED by vr_brickset_create and vr_brickset_set_max_epochs (the set then keeps its setting),
+ * before anything is launched. */
+#define VR_MAX_EPOCHS 1024
 vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_t dims[3],
                              int32_t tolerance, int32_t max_epochs, int32_t variant);
 vr_status vr_brickset_destroy(vr_brickset *bs);

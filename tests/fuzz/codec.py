@@ -12,7 +12,7 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t0 = time.time(); bad = 0
 for it in range(n):
     shape = shapes[rng.integers(0, len(shapes))]
-    kind = int(rng.integers(0, 5)); tol = int(rng.choice([0, 1, 1, 2, 5, 9])); ep = int(rng.choice([1, 2, 2, 3, 5])); var = int(rng.choice([0, 0, 1]))
+    kind = int(rng.integers(0, 5)); tol = int(rng.choice([0, 1, 1, 2, 5, 9, 13, 31, 64, 100, 255, 256, 32767, 32769, 40000, 65536, 2 ** 31 - 1])); ep = int(rng.choice([0, 1, 2, 2, 3, 5, 6, 8, 13, 40])); var = int(rng.choice([0, 0, 1]))
     vol = gen(rng, shape, kind)
     z, y, x = shape
     ref = oracle.OracleTree(vol.copy(), tolerance=tol, max_epochs=ep, guarded=bool(var)).build()

@@ -12,7 +12,7 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t0 = time.time(); bad = 0
 for it in range(n):
     shape = shapes[rng.integers(0, len(shapes))]
-    kind = int(rng.integers(0, 5)); tol = int(rng.choice([0, 1, 1, 2, 5])); ep = int(rng.choice([1, 2, 2, 3]))
+    kind = int(rng.integers(0, 5)); tol = int(rng.choice([0, 1, 1, 2, 5, 13, 64, 255, 256, 32767, 32769, 65536, 2 ** 31 - 1])); ep = int(rng.choice([0, 1, 2, 2, 3, 6, 13, 40]))
     vol = gen(rng, shape, kind)
     z, y, x = shape
     ref = oracle.OracleTree(vol.copy(), tolerance=tol, max_epochs=ep, midrange=True, guarded=True).build()

@@ -16,7 +16,7 @@ def report(tag, what):
     print("MISMATCH", tag, what, flush=True)
 for it in range(n):
     mode = it % 3
-    tol = int(rng.choice([0, 1, 1, 2, 5])); ep = int(rng.choice([1, 2, 2, 3])); kind = int(rng.integers(0, 5))
+    tol = int(rng.choice([0, 1, 1, 2, 5, 13, 64, 255, 256, 32767, 32769, 65536, 2 ** 31 - 1])); ep = int(rng.choice([0, 1, 2, 2, 3, 6, 13, 40])); kind = int(rng.integers(0, 5))
     if mode == 0:      # general extents
         shape = tuple(int(v) for v in (rng.integers(2, 40), rng.integers(2, 40), rng.integers(2, 70)))
         vol = gen(rng, shape, kind)

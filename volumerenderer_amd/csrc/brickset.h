@@ -170,6 +170,11 @@ struct PoolDest {
 // level (BrickSet::leafless).
 inline bool leafless_build(const BrickSet &b) { return b.D >= 12 && b.maxEpochs >= 1; }
 
+// The tolerance the kernels get.  A leaf error never exceeds 255, so every tolerance >= 256 means the same thing; the
+// fused prune kernels carry it in two signed 16-bit lanes (kd_encode.hip pe_leaf_table), which the caller's value
+// (any non-negative int32) would overflow from 32769 up.
+inline int kernel_tolerance(const BrickSet &b) { return b.tolerance < 256 ? b.tolerance : 256; }
+
 inline void fine_has_changed(BrickSet &b) { b.fineAll = (int)b.fineHas.size() == b.B && std::find(b.fineHas.begin(), b.fineHas.end(), 0) == b.fineHas.end(); }
 
 // kd_encode.hip

@@ -229,6 +229,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
     if (!out || !dims || num_bricks <= 0) return VR_ERR_INVALID;
     if (tolerance < 0 || max_epochs < 0 || variant < 0 || variant > 2) return VR_ERR_INVALID;
     for (int k = 0; k < 3; ++k) if (dims[k] <= 0) return VR_ERR_INVALID;
+    if (max_epochs > VR_MAX_EPOCHS) return VR_ERR_UNSUPPORTED;   // the level loop's launches grow with it, whatever the data does
     // power-of-two extents up to 1024 per axis take the tiled kernels; anything else (the reference accepts any
     // extents, R.cpp:26-36,151-162) goes through the general-extent tables.  Limits: origTreeDepth <= 31, fewer than
     // 2^32 voxels per tree, and above depth 28 (64-bit token offsets) one tree per set.
@@ -345,6 +346,7 @@ vr_status vr_brickset_set_error_tolerance(vr_brickset *h, int32_t tol)
 vr_status vr_brickset_set_max_epochs(vr_brickset *h, int32_t e)
 {
     if (!h || e < 0) return VR_ERR_INVALID;
+    if (e > VR_MAX_EPOCHS) return VR_ERR_UNSUPPORTED;      // (the set keeps its previous setting)
     h->s.maxEpochs = e;
     return VR_OK;
 }

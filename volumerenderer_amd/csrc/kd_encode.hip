@@ -2875,7 +2875,7 @@ static void fill_emit_args(BrickSet *bs, EmitArgs &a)
     a.rbR = ReconBufs{{bs->rng.recon[0], bs->rng.recon[1], bs->rng.recon[2]}};
     a.ctrls = bs->mid.ctrl; a.ctrlsR = mr ? bs->rng.ctrl : nullptr;
     a.heapStride = bs->heapStride; a.leafStride = bs->reconStride; a.codeStride = bs->codeStride;
-    a.D = bs->D; a.maxDepth = bs->maxDepth; a.tol = bs->tolerance; a.Ds = bs->Ds; a.K = bs->K;
+    a.D = bs->D; a.maxDepth = bs->maxDepth; a.tol = kernel_tolerance(*bs); a.Ds = bs->Ds; a.K = bs->K;
     a.blockTot = bs->blockTot; a.blockOff = bs->blockOff; a.nEmitBlk = bs->nEmitBlk;
     a.blockOff64 = bs->blockOff64; a.idxBase = bs->idxBase;
     a.blockL1 = bs->blockL1;
@@ -3036,7 +3036,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     hipEventRecord(bs->ev[2], st);
     dbg_sync(st, "compress");
     // ---- PRUNE
-    hipLaunchKernelGGL(k_chain_lut, dim3(1), dim3(256), 0, st, bs->tolerance, bs->maxDepth - D, bs->chainLut);
+    hipLaunchKernelGGL(k_chain_lut, dim3(1), dim3(256), 0, st, kernel_tolerance(*bs), bs->maxDepth - D, bs->chainLut);
     ReconBufs rb{{bs->mid.recon[0], bs->mid.recon[1], bs->mid.recon[2]}};
     ReconBufs rbR{{bs->rng.recon[0], bs->rng.recon[1], bs->rng.recon[2]}};
     int pruneFrom = D - 1;
@@ -3045,7 +3045,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     if (fused) {
         PruneEmitArgs pa;
         pa.sk = sk; pa.skR = skR;
-        pa.D = D; pa.tol = bs->tolerance; pa.maxDepth = bs->maxDepth; pa.ctrls = bs->mid.ctrl;
+        pa.D = D; pa.tol = kernel_tolerance(*bs); pa.maxDepth = bs->maxDepth; pa.ctrls = bs->mid.ctrl;
         pa.temp = bs->mid.temp; pa.codes = bs->mid.codes;
         pa.heapStride = bs->heapStride; pa.codeStride = bs->codeStride; pa.leafStride = bs->reconStride;
         pa.rb = rb; pa.subTok = bs->blockOff; pa.nEmitBlk = bs->nEmitBlk; pa.blockL1 = bs->blockL1;
@@ -3077,7 +3077,7 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         bs->fineHas.assign((size_t)B, 1);
         fine_has_changed(*bs);
     } else
-        hipLaunchKernelGGL(k_prune_leaf, dim3(cdiv((int64_t)1 << D, 256), B), dim3(256), 0, st, D, bs->tolerance,
+        hipLaunchKernelGGL(k_prune_leaf, dim3(cdiv((int64_t)1 << D, 256), B), dim3(256), 0, st, D, kernel_tolerance(*bs),
                            bs->mid.ctrl, bs->mid.temp, bs->mid.codes, mr ? bs->rng.codes : nullptr, bs->heapStride,
                            bs->codeStride, rb, bs->reconStride, bs->maxDepth, bs->blockL1, bs->nEmitBlk);
     for (int d = pruneFrom; d >= 0; --d)
