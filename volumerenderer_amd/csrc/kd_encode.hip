@@ -535,6 +535,34 @@ __device__ __forceinline__ int seg_min_i32_dpp(int v)
 // segments per wave (one per row, 64 nodes per lane) need 138 VGPRs, three waves per SIMD, and measured slower.
 // With h = (t>p ? 255-t : t) the reference's "forced" cases are pd > h, so under the hypothesis
 // floor(S/(2C+1)) == Th node k counts  <=>  pd_k > min(Th, h_k).
+//
+// QUADS (the first round's kernel): sufficient bounds from byte-packed quads.  k_est_walk checks every record against
+// the exact start state and walks the segment node by node when the check fails, so the sums must be exact under the
+// hypothesis, but A and B only have to be SUFFICIENT: a record with A' >= A and B' <= B passes only where the exact one
+// passes, and can never change a byte of the output, only cause a fallback.  The lane's 32 nodes are 8 quads of four
+// consecutive nodes; once per lane and quad (candidate-independent):
+//     pd4   the four pd bytes
+//     hi    0x80 in each byte whose node counts under EVERY candidate Th <= 127: pd >= 128, or forced.  With
+//           u = t + (t - p) in a 16-bit lane, t > p gives 0 <= u <= 510 and 2t-p > 255 <=> bit 8 of u; t < p gives
+//           u < 255, and 2t < p <=> u < 0 <=> bit 8 of u; t == p gives u = t.  So bit 8 of u is "forced".
+//     x7    pd4 & 0x7F7F7F7F
+// and per candidate  ind = ((x7 + (0x7F - Th) * 0x01010101) & 0x80808080) | hi : 0x80 where the node counts.  x7 <= 127
+// and 0x7F - Th <= 127 for 0 <= Th <= 127: no byte carries into its neighbour, and bit 7 of a byte's sum is set
+// <=> x7 + 127 - Th >= 128 <=> x7 > Th.  A node with pd >= 128 > Th is in hi.  Forced and pd > Th both imply pd > 0, so
+// the clamp term h needs no case of its own.  No reachable threshold is above 127 (every counted pd <= 255, so
+// S / (2C + 1) < 127.5): such a candidate's record is written to fail always (A = INT_MAX).
+// The sums are dot products, scaled by 128: s128 = udot4(ind, pd4, s128), cc128 = udot4(ind, 0x01010101, cc128).
+// The extremes are taken from the state BEFORE each quad (on the scaled accumulators, unscaled by an exact >> 7):
+//     A_q = max over quad starts of 2 Th cc - s,         B_q = min over quad starts of 2 (Th + 1) cc - s.
+// A position inside a quad differs from the quad's start by at most three counted nodes.  A counted node adds
+// 2 Th - pd to `low`: at most Th - 1 if it is not forced (pd > Th), at most 2 Th - 1 if it is (pd >= 1); it adds
+// 2 Th + 2 - pd >= 2 Th + 2 - pdmax to `low + 2 cc`, pdmax the lane's largest pd.  Hence, per lane,
+//     A' = A_q + 3 max(anyForcedInLane ? 2 Th - 1 : Th - 1, 0) >= A,      B' = B_q - 3 max(pdmax - 2 Th - 2, 0) <= B
+// and the cross-lane epilogue (offsets by the exact sums of the lanes before) keeps both inequalities.  (Bounds exact
+// only at lane granularity had a slack of ~100 against a true excursion of ~10 and failed almost every segment of a
+// brick near a threshold boundary; here it is a handful of units.)  Lane-uniform waves keep their closed form, which
+// is exact.  8 instructions per quad and candidate instead of 9 per node pair.
+template <bool QUADS>
 __global__ void __launch_bounds__(256)
 k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
            int64_t leafStride, uint32_t *__restrict__ summ, int64_t summStride, SkipBlocks sk)
@@ -592,8 +620,24 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
         for (int j = 0; j < PW; ++j) mixed |= pw[j] ^ p0;
     }
     const bool uniform = __ballot(mixed != 0u) == 0ull;
-    vr_s16x2 pd[NP], h[NP];
+    constexpr int NU = QUADS ? 1 : NP, NQ = QUADS ? TW : 1;      // QUADS unpacks pair 0 only (lane-uniform waves)
+    vr_s16x2 pd[NU], h[NU];
     uint32_t anyPd = 0;
+    uint32_t pd4[NQ], hi[NQ], anyF = 0;                  // QUADS: see the header comment
+    vr_s16x2 pm = (vr_s16x2)(0);
+    const auto unpack4 = [&](const int q) {
+        // nodes 4q .. 4q+3: even and odd bytes of the truth word share the parents (byte 2q, byte 2q+1)
+        const uint32_t psel = (uint32_t)((2 * q) & 3);
+        const vr_s16x2 P2 = pk_s(__builtin_amdgcn_perm(0, pw[q >> 1], 0x0c000c00u | psel | ((psel + 1u) << 16)));
+        const vr_s16x2 Te = pk_s(__builtin_amdgcn_perm(0, tw[q], 0x0c020c00u)), To = pk_s(__builtin_amdgcn_perm(0, tw[q], 0x0c030c01u));
+        const vr_s16x2 de = Te - P2, dO = To - P2;
+        const vr_s16x2 pe = __builtin_elementwise_max(de, (vr_s16x2)(0) - de), po = __builtin_elementwise_max(dO, (vr_s16x2)(0) - dO);
+        const uint32_t fb = __builtin_amdgcn_perm(pk_u(To + dO), pk_u(Te + de), 0x07030501u);     // bit 0 of each byte: forced
+        pd4[q] = __builtin_amdgcn_perm(pk_u(po), pk_u(pe), 0x06020400u);
+        hi[q] = ((fb << 7) | pd4[q]) & 0x80808080u;
+        anyF |= fb;
+        pm = __builtin_elementwise_max(pm, __builtin_elementwise_max(pe, po));
+    };
     const auto unpack = [&](const int k) {
         // lanes: (node k, node k+NP); their parents are bytes k>>1 and NP/2 + (k>>1) of the lane's parent bytes
         const uint32_t bsel = (uint32_t)(k & 3), psel = (uint32_t)((k >> 1) & 3);
@@ -605,7 +649,11 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
         anyPd |= pk_u(pd[k]);
     };
     if (uniform) unpack(0);
-    else
+    else if constexpr (QUADS) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) unpack4(q);
+        anyPd = pk_u(pm);
+    } else
 #pragma unroll
         for (int k = 0; k < NP; ++k) unpack(k);
     fetch(g + step);                         // after the unpacking: these bytes and those loads are not live together
@@ -617,11 +665,37 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
     vr_s16x2 hmin = h[0];
     if (!uniform)
 #pragma unroll
-        for (int k = 1; k < NP; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
-    const bool hBig = !uniform && __ballot(min((int)hmin.x, (int)hmin.y) < Tbase + nc - 1) == 0ull;
+        for (int k = 1; k < NU; ++k) hmin = __builtin_elementwise_min(hmin, h[k]);
+    const bool hBig = !QUADS && !uniform && __ballot(min((int)hmin.x, (int)hmin.y) < Tbase + nc - 1) == 0ull;
+    const int pdmax = max((int)pm.x, (int)pm.y), forcedLane = (anyF & 0x01010101u) != 0u ? 1 : 0;
 #pragma unroll 1
     for (int ci = 0; ci < nc; ++ci) {
         const int Th = Tbase + ci;
+        int a, b, lowT, ccT;
+        if (QUADS && Th > 127) {             // unreachable threshold: a record that always fails
+            if (segLive && rl == L - 1) *(uint4 *)(out + est_at(ci, seg)) = make_uint4(0, 0, 0x7FFFFFFFu, 0x7FFFFFFFu);
+            continue;
+        }
+        if (QUADS && !uniform) {
+            const uint32_t kadd = (uint32_t)(0x7F - Th) * 0x01010101u;
+            const int m2 = -2 * Th, m22 = -2 * Th - 2;
+            uint32_t s128 = 0, cc128 = 0;
+            int mn = 0, mx = 0;              // min of s - 2 Th cc (= -A_q) and max of s - 2 (Th + 1) cc (= -B_q), x 128
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                if (q > 0) {
+                    mn = min(mn, __mul24((int)cc128, m2) + (int)s128);
+                    mx = max(mx, __mul24((int)cc128, m22) + (int)s128);
+                }
+                const uint32_t ind = (((pd4[q] & 0x7F7F7F7Fu) + kadd) & 0x80808080u) | hi[q];
+                s128 = __builtin_amdgcn_udot4(ind, pd4[q], s128, false);
+                cc128 = __builtin_amdgcn_udot4(ind, 0x01010101u, cc128, false);
+            }
+            ccT = (int)(cc128 >> 7);
+            lowT = 2 * Th * ccT - (int)(s128 >> 7);
+            a = -(mn >> 7) + 3 * max(forcedLane ? 2 * Th - 1 : Th - 1, 0);
+            b = -(mx >> 7) - 3 * max(pdmax - 2 * Th - 2, 0);
+        } else {
         const vr_s16x2 Th2 = pk_s((uint32_t)Th * 0x10001u), w2 = pk_s((uint32_t)(2 * Th) * 0x10001u);
         // per chain: low = 2*Th*cc - s, and the extremes of low / low + 2cc over the positions BEFORE each node
         vr_s16x2 low = (vr_s16x2)(0), cc = (vr_s16x2)(0), amax = (vr_s16x2)(0), bmin = (vr_s16x2)(0);
@@ -660,9 +734,10 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
             }
         }
         const int low1 = low.x, low2 = low.y, cc1 = cc.x, cc2 = cc.y;
-        const int lowT = low1 + low2, ccT = cc1 + cc2;
-        int a = max((int)amax.x, max((int)amax.y, 0) + low1);          // chain 2 starts at position NP (its own 0 included)
-        int b = min((int)bmin.x, min((int)bmin.y, 0) + low1 + 2 * cc1);
+        lowT = low1 + low2; ccT = cc1 + cc2;
+        a = max((int)amax.x, max((int)amax.y, 0) + low1);          // chain 2 starts at position NP (its own 0 included)
+        b = min((int)bmin.x, min((int)bmin.y, 0) + low1 + 2 * cc1);
+        }
         const uint32_t sT = (uint32_t)(2 * Th * ccT - lowT);
         // one scan for both sums: s < 2^18 per segment, cc <= 1024
         const uint32_t packed = sT | ((uint32_t)ccT << 20);
@@ -679,7 +754,7 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
 }
 
 __global__ void __launch_bounds__(64)
-k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
+k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
            int64_t leafStride, const uint32_t *__restrict__ summ, int64_t summStride, SkipBlocks sk)
 {
     const int brick = blockIdx.x, lane = threadIdx.x;
@@ -714,7 +789,10 @@ k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, Ctrl *ctrls,
     };
     while (seg < nseg) {
         const long long ci = Tc - Tbase;
-        if (ci < 0 || ci >= nc) {            // threshold left the candidate window
+        // budget >= 0 (the first round, whose records carry sufficient bounds only): a brick that has walked more than
+        // `budget` segments node by node leaves the round as if the threshold had left the window, and the next round
+        // continues from here with exact records -- no launch lasts as long as its unluckiest brick
+        if (ci < 0 || ci >= nc || (budget >= 0 && !lastRound && fallbacks > budget)) {   // threshold left the candidate window
             if (!lastRound) {                // next round: new summaries around the new threshold
                 if (lane == 0) {
                     c.estS = S; c.estC = C; c.estSeg = (int)seg;
@@ -2821,10 +2899,13 @@ static void compress_stream(BrickSet *bs, Stream2 &s0, hipStream_t st, const uin
                 const int nc = r < 2 ? 4 : EST_CAND, ncNext = r + 1 < 2 ? 4 : EST_CAND;   // two 4-wide windows, then 8-wide ones
                 // eight segments per workgroup and sweep (two per wave); the first round makes four sweeps
                 const unsigned gx = r == 0 ? cdiv(nseg, 32) : (cdiv(nseg, 8) < 64 ? cdiv(nseg, 8) : 64);
-                hipLaunchKernelGGL(k_est_summ, dim3(gx, B), dim3(256), 0, st, d, nc, s.ctrl, s.temp,
+                // the first round: byte-packed quads with sufficient bounds, and a budget of node-by-node segments per
+                // brick (est_exact_bounds: the exact kernel, no budget); later rounds: exact records
+                const bool quads = r == 0 && !bs->sw.estExactBounds;
+                hipLaunchKernelGGL(quads ? k_est_summ<true> : k_est_summ<false>, dim3(gx, B), dim3(256), 0, st, d, nc, s.ctrl, s.temp,
                                    bs->heapStride, rb, bs->reconStride, (uint32_t *)estSumm, bs->estSummStride, sk);
                 hipLaunchKernelGGL(k_est_walk, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, nc, ncNext,
-                                   r == EST_ROUNDS - 1 ? 1 : 0, s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride,
+                                   r == EST_ROUNDS - 1 ? 1 : 0, quads ? bs->sw.estBudget : -1, s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride,
                                    (const uint32_t *)estSumm, bs->estSummStride, sk);
             }
         }
