@@ -815,11 +815,12 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
 /* ---- debugging switches (new) ----------------------------------------------------------------------------------
  * Which kernel serves a call is decided by the set's geometry and by a few switches kept IN THE HANDLE: they are
  * initialised from the environment (VRHIP_DECODE_WALK, VRHIP_DECODE_FINE_V1, VRHIP_DECODE_QUAD, VRHIP_NO_SKIP_BLOCKS,
- * VRHIP_NO_UNIFORM_BLOCKS, VRHIP_NO_UNIFORM_DECODE, VRHIP_EST_EXACT_BOUNDS)
+ * VRHIP_NO_UNIFORM_BLOCKS, VRHIP_NO_UNIFORM_DECODE, VRHIP_EST_EXACT_BOUNDS, VRHIP_PYRAMID_BOXES)
  * once, when the set is created, and changed afterwards only through this call -- never by the environment at launch
  * time.  Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks", "no_uniform_blocks",
  * "no_uniform_decode", "est_exact_bounds" (the distance estimator's first round computes exact bounds per node instead
- * of sufficient ones per quad of nodes, and has no fallback budget); any other name is VR_ERR_INVALID.
+ * of sufficient ones per quad of nodes, and has no fallback budget), "pyramid_boxes" (the pyramid's bottom twelve levels
+ * by one 16^3 box per workgroup also where eight boxes per workgroup apply); any other name is VR_ERR_INVALID.
  * Results never depend on a switch; the tests use them to check the kernels against each other.
  * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1"; "reslice_tile_w" = 8, 16 or 64, the width of
  * the 64-pixel tile a wave of vr_reslice covers (16 is the default, chosen by measurement: DESIGN.md 3.5g); "hist_plain" = 1

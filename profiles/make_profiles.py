@@ -27,7 +27,7 @@ dk = "vr::k_decode_region"
 dec = int((2 * kern[dk]["FETCH_SIZE_KiB_per_launch_avg"] + kern[dk]["WRITE_SIZE_KiB_per_launch_avg"]) * 1024)
 # one build(): every encoder kernel's launches of ONE build (the command runs setup builds of the pipelined sets, one
 # timed step and the serial passes: all builds are the same work, so per-build = total / number of k_pyramid12 launches)
-nbuild = kern["vr::k_pyramid12"]["launches"]
+nbuild = sum(kern[k]["launches"] for k in ("vr::k_pyramid12", "vr::k_pyramid12_lines") if k in kern)   # (one of the two per build)
 enc = 0
 enc_by_kernel = {}
 for k, e in kern.items():

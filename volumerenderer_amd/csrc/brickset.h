@@ -31,6 +31,7 @@ struct Switches {
     bool noUniformBlocks = false; // VRHIP_NO_UNIFORM_BLOCKS: constant 4096-leaf blocks go through k_prune_emit12, not k_prune_emit12_const
     bool estExactBounds = false; // VRHIP_EST_EXACT_BOUNDS: the estimator's first round runs the exact k_est_summ<false>, with no fallback budget
     int estBudget = EST_R0_BUDGET; // VRHIP_EST_BUDGET=<n>: node-by-node segments a brick may walk in the estimator's first round (measurement aid)
+    bool pyramidBoxes = false;   // VRHIP_PYRAMID_BOXES: k_pyramid12 (one box per workgroup) where k_pyramid12_lines applies
     bool noUniformDecode = false; // VRHIP_NO_UNIFORM_DECODE: k_decode_region ignores BrickSet::boxUniform (every live box is parsed).  Read per call
 };
 

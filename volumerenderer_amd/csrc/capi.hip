@@ -249,6 +249,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         w.noSkipBlocks = getenv("VRHIP_NO_SKIP_BLOCKS") != nullptr;
         w.noUniformBlocks = getenv("VRHIP_NO_UNIFORM_BLOCKS") != nullptr;
         w.noUniformDecode = getenv("VRHIP_NO_UNIFORM_DECODE") != nullptr;
+        w.pyramidBoxes = getenv("VRHIP_PYRAMID_BOXES") != nullptr;
         w.estExactBounds = getenv("VRHIP_EST_EXACT_BOUNDS") != nullptr;
         if (const char *eb = getenv("VRHIP_EST_BUDGET")) { const int v = atoi(eb); if (v >= 0) w.estBudget = v; }
     }
@@ -315,6 +316,7 @@ vr_status vr_brickset_set_switch(vr_brickset *h, const char *name, int32_t value
     else if (!strcmp(name, "no_skip_blocks")) w.noSkipBlocks = on;
     else if (!strcmp(name, "no_uniform_blocks")) w.noUniformBlocks = on;
     else if (!strcmp(name, "no_uniform_decode")) w.noUniformDecode = on;
+    else if (!strcmp(name, "pyramid_boxes")) w.pyramidBoxes = on;
     else if (!strcmp(name, "est_exact_bounds")) w.estExactBounds = on;
     else return VR_ERR_INVALID;
     return VR_OK;

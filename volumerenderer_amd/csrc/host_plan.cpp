@@ -208,6 +208,7 @@ static bool pyr12_plan(const Geom &g, bool generalGeom, Pyr12Plan &pg)
     pg.swz = (perLine == 8 && Bx % 8 == 0 && ((Bx / 8) * By * Bz) % 8 == 0) ? 1 : 0;
     pg.nbx = (int)Bx; pg.nby = (int)By;
     pg.lnbx = g.nb[0] - pg.ax; pg.lnby = g.nb[1] - pg.ay;
+    pg.lines = pg.ax == 4 && g.X >= 128;               // (then nbx % 8 == 0: the extents are powers of two)
     return true;
 }
 

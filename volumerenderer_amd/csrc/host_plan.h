@@ -83,6 +83,7 @@ struct Pyr12Plan {              // k_pyramid12: the geometry fields of Pyr12Geom
     bool use12;                 // every thread loads a 16-byte x-run of the caller's voxels (vrhip.h "alignment of caller buffers")
     int ax, ay, az, swz, nbx, nby, lnbx, lnby;
     uint16_t sx[16];
+    bool lines;                 // k_pyramid12_lines applies: 16-voxel-wide boxes (ax == 4), eight of them per 128-byte line (X >= 128)
 };
 void make_plans(const Geom &g, int K, bool generalGeom, bool idx64, int64_t treeCap, TilePlan &tile, RegionPlan &region,
                 Pyr12Plan &pyr12);

@@ -146,6 +146,47 @@ __device__ __forceinline__ vr_s16x2 pk_pair_max(uint32_t A, uint32_t B)
 __device__ __forceinline__ uint32_t pk_mid(vr_s16x2 mn, vr_s16x2 mx) { return pk_u((mn + mx) >> 1); }   // R.cpp:198
 __device__ __forceinline__ uint32_t pk_half_range(vr_s16x2 mn, vr_s16x2 mx) { return pk_u((mx - mn) >> 1); } // M.cpp:235
 
+// the parts k_pyramid12 and k_pyramid12_lines share (defined behind k_pyramid12)
+__device__ __forceinline__ void pyr12_reduce_box(const uint8_t *leaf, int D, uint32_t base, int t, uint8_t *__restrict__ T,
+                                                 uint8_t *__restrict__ TR, uint32_t *mm);
+__device__ __forceinline__ void pyr12_box_root(const uint32_t *mm, int D, uint32_t base, int brick, uint8_t *__restrict__ T,
+                                               uint8_t *__restrict__ TR, uint8_t *__restrict__ outMin, uint8_t *__restrict__ outMax,
+                                               int64_t outStride, uint8_t *__restrict__ blockFlag, uint8_t *__restrict__ blockFlagR);
+
+// What a constant box (every voxel c0 & 0xFF; c0 = that byte x 4) writes, in 128 slots of at most 16 bytes: levels
+// D-2 .. D-12 of both heaps, the root's (min, max) and flag 1.  Levels D-1 and D stay unwritten (k_pyramid12 below).
+__device__ __forceinline__ void pyr12_const_slot(int s, uint32_t c0, int D, uint32_t base, int brick, uint8_t *__restrict__ T,
+                                                 uint8_t *__restrict__ TR, uint8_t *__restrict__ outMin, uint8_t *__restrict__ outMax,
+                                                 int64_t outStride, uint8_t *__restrict__ blockFlag, uint8_t *__restrict__ blockFlagR)
+{
+    const uint4 cv = make_uint4(c0, c0, c0, c0), zv = make_uint4(0, 0, 0, 0);
+    if (s < 127) {
+        // 16 bytes per slot: slots 0 .. 63 level D-2, 64 .. 95 D-3, 96 .. 111 D-4, .. , 126 D-8
+        const int m = s < 64 ? 0 : 5 - (31 - __clz(127 - s));             // slots 64 ..: level D-3-m
+        const int k = s < 64 ? 2 : 3 + m, within = s < 64 ? s : (s - 64) - (64 - (64 >> m));
+        const int64_t o = ((int64_t)1 << (D - k)) + (base >> k) + within * 16;
+        st16(T + o, cv);
+        if (TR) *(uint4 *)(TR + o) = zv;
+    } else if (s == 127) {                      // levels D-9 .. D-12 (8, 4, 2, 1 bytes), the block's root
+        const int64_t o9 = ((int64_t)1 << (D - 9)) + (base >> 9), o10 = ((int64_t)1 << (D - 10)) + (base >> 10);
+        const int64_t o11 = ((int64_t)1 << (D - 11)) + (base >> 11), o12 = ((int64_t)1 << (D - 12)) + (base >> 12);
+        *(uint2 *)(T + o9) = make_uint2(c0, c0);
+        *(uint32_t *)(T + o10) = c0;
+        *(uint16_t *)(T + o11) = (uint16_t)c0;
+        T[o12] = (uint8_t)c0;
+        if (TR) {
+            *(uint2 *)(TR + o9) = make_uint2(0, 0);
+            *(uint32_t *)(TR + o10) = 0;
+            *(uint16_t *)(TR + o11) = 0;
+            TR[o12] = 0;
+        }
+        outMin[(int64_t)brick * outStride + (base >> 12)] = (uint8_t)c0;
+        outMax[(int64_t)brick * outStride + (base >> 12)] = (uint8_t)c0;
+        blockFlag[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = 1u;
+        if (blockFlagR) blockFlagR[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = 1u;
+    }
+}
+
 __global__ void __launch_bounds__(256)
 k_pyramid12(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__restrict__ temp, int64_t heapStride,
             uint8_t *__restrict__ tempRange, uint8_t *__restrict__ outMin, uint8_t *__restrict__ outMax,
@@ -191,32 +232,7 @@ k_pyramid12(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__re
         __syncthreads();
         const uint32_t c0 = waveMM[0];
         if (c0 != 0x100u && waveMM[1] == c0 && waveMM[2] == c0 && waveMM[3] == c0) {
-            const uint4 cv = make_uint4(c0, c0, c0, c0), zv = make_uint4(0, 0, 0, 0);
-            if (t < 127) {
-                // 16 bytes per thread: threads 0 .. 63 level D-2, 64 .. 95 D-3, 96 .. 111 D-4, .. , 126 D-8
-                const int m = t < 64 ? 0 : 5 - (31 - __clz(127 - t));             // threads 64 ..: level D-3-m
-                const int k = t < 64 ? 2 : 3 + m, within = t < 64 ? t : (t - 64) - (64 - (64 >> m));
-                const int64_t o = ((int64_t)1 << (D - k)) + (base >> k) + within * 16;
-                st16(T + o, cv);
-                if (TR) *(uint4 *)(TR + o) = zv;
-            } else if (t == 127) {                      // levels D-9 .. D-12 (8, 4, 2, 1 bytes), the block's root
-                const int64_t o9 = ((int64_t)1 << (D - 9)) + (base >> 9), o10 = ((int64_t)1 << (D - 10)) + (base >> 10);
-                const int64_t o11 = ((int64_t)1 << (D - 11)) + (base >> 11), o12 = ((int64_t)1 << (D - 12)) + (base >> 12);
-                *(uint2 *)(T + o9) = make_uint2(c0, c0);
-                *(uint32_t *)(T + o10) = c0;
-                *(uint16_t *)(T + o11) = (uint16_t)c0;
-                T[o12] = (uint8_t)c0;
-                if (TR) {
-                    *(uint2 *)(TR + o9) = make_uint2(0, 0);
-                    *(uint32_t *)(TR + o10) = 0;
-                    *(uint16_t *)(TR + o11) = 0;
-                    TR[o12] = 0;
-                }
-                outMin[(int64_t)brick * outStride + (base >> 12)] = (uint8_t)c0;
-                outMax[(int64_t)brick * outStride + (base >> 12)] = (uint8_t)c0;
-                blockFlag[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = 1u;
-                if (blockFlagR) blockFlagR[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = 1u;
-            }
+            if (t < 128) pyr12_const_slot(t, c0, D, base, brick, T, TR, outMin, outMax, outStride, blockFlag, blockFlagR);
             return;
         }
         // (waveMM is written again further down, behind the barrier that follows)
@@ -224,6 +240,17 @@ k_pyramid12(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__re
 #pragma unroll
     for (int i = 0; i < 16; ++i) leaf[r0 | pg.sx[i]] = (uint8_t)(vw[i >> 2] >> ((i & 3) * 8));
     __syncthreads();
+    pyr12_reduce_box(leaf, D, base, t, T, TR, waveMM);
+    __syncthreads();
+    if (t == 0) pyr12_box_root(waveMM, D, base, brick, T, TR, outMin, outMax, outStride, blockFlag, blockFlagR);
+}
+
+// Levels D .. D-10 of one box from its Morton-ordered image `leaf` (4096 bytes of LDS, complete: the caller's barrier),
+// by the 256 threads of the workgroup; mm[wave] receives the wave's packed (min, 255 - max) for pyr12_box_root.
+__device__ __forceinline__ void pyr12_reduce_box(const uint8_t *leaf, int D, uint32_t base, int t, uint8_t *__restrict__ T,
+                                                 uint8_t *__restrict__ TR, uint32_t *mm)
+{
+    const int lane = t & 63;
     // 16 Morton-consecutive leaves per thread: they and the four levels above them never leave registers
     const uint4 lv = *(const uint4 *)(&leaf[t * 16]);
     st16(T + ((int64_t)1 << D) + base + t * 16, lv);                                // leaf: (v+v)/2 = v
@@ -286,13 +313,19 @@ k_pyramid12(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__re
             if (TR) TR[o] = (uint8_t)((b - a) >> 1);
         }
     }
-    if (lane == 0) waveMM[t >> 6] = p;
-    __syncthreads();
-    if (t == 0) {                                       // levels D-11 (two nodes) and D-12 (the block's root)
+    if (lane == 0) mm[t >> 6] = p;
+}
+
+// Levels D-11 (two nodes) and D-12 (the box's root) from the four waves' mm[] of pyr12_reduce_box, behind a barrier: one thread
+__device__ __forceinline__ void pyr12_box_root(const uint32_t *mm, int D, uint32_t base, int brick, uint8_t *__restrict__ T,
+                                               uint8_t *__restrict__ TR, uint8_t *__restrict__ outMin, uint8_t *__restrict__ outMax,
+                                               int64_t outStride, uint8_t *__restrict__ blockFlag, uint8_t *__restrict__ blockFlagR)
+{
+    {
         int a[2], b[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const uint32_t u = pk_u(__builtin_elementwise_min(pk_s(waveMM[2 * h]), pk_s(waveMM[2 * h + 1])));
+            const uint32_t u = pk_u(__builtin_elementwise_min(pk_s(mm[2 * h]), pk_s(mm[2 * h + 1])));
             a[h] = (int)(u & 0xFFFFu); b[h] = 255 - (int)(u >> 16);
             const int64_t o = ((int64_t)1 << (D - 11)) + (base >> 11) + h;
             T[o] = (uint8_t)((a[h] + b[h]) >> 1);
@@ -308,6 +341,105 @@ k_pyramid12(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__re
         if (blockFlag) blockFlag[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = ra == rbm ? 1u : 0u;
         if (blockFlagR) blockFlagR[(int64_t)brick * ((int64_t)1 << (D - 12)) + (base >> 12)] = ra == rbm ? 1u : 0u;   // half ranges all 0
     }
+}
+
+// k_pyramid12 for 16-voxel-wide boxes (ax == 4) of bricks at least 128 voxels wide: one workgroup takes the EIGHT
+// x-adjacent boxes that share every 128-byte line of their rows, a 128 x 2^ay x 2^az slab of 256 rows.  Thread t loads
+// the 16-byte chunk t & 7 (= box t & 7) of rows (t >> 3) + 32 k, k = 0 .. 7: a wave-instruction reads 8 rows x 128
+// contiguous bytes, where k_pyramid12's reads 16 bytes of each of 64 lines, and the eight loads of a thread are all
+// issued before the first is used (eight times the bytes in flight).  Everything a box writes is what k_pyramid12
+// writes for it, by the same functions: a constant box (SkipBlocks builds) its 128 slots, 32 threads per box; the
+// others are scattered to Morton-ordered images in LDS and reduced one after the other by all 256 threads, their
+// roots behind one last barrier.  A group of eight constant boxes never touches the images.
+#ifndef VR_PYR_LINES_IMAGE_BOXES
+#define VR_PYR_LINES_IMAGE_BOXES 8      // boxes held in LDS at once: 8, or 4 (two rounds); DESIGN.md 3.2
+#endif
+// the images lie 16 bytes further apart than they are long: the lanes t & 7 of one row then store to eight different
+// groups of four banks, not all to one
+#define PYR_LINES_IMAGE_STRIDE (4096 + 16)
+
+__global__ void __launch_bounds__(256)
+k_pyramid12_lines(Geom g, Pyr12Geom pg, const uint8_t *__restrict__ vox, uint8_t *__restrict__ temp, int64_t heapStride,
+                  uint8_t *__restrict__ tempRange, uint8_t *__restrict__ outMin, uint8_t *__restrict__ outMax,
+                  int64_t outStride, uint8_t *__restrict__ blockFlag, uint8_t *__restrict__ blockFlagR)
+{
+    constexpr int NB = VR_PYR_LINES_IMAGE_BOXES;
+    static_assert(NB == 8 || NB == 4, "images per round");
+    __shared__ __attribute__((aligned(16))) uint8_t leaf[NB * PYR_LINES_IMAGE_STRIDE];
+    __shared__ uint32_t boxConst[4][8];     // [wave][box]: the byte x 4 all its rows of the box hold, or 0x100
+    __shared__ uint32_t waveMM[8][4];       // [box][wave]
+    const int brick = blockIdx.y, D = g.D;
+    const int t = threadIdx.x, lane = t & 63, c = t & 7;
+    // which group: group coordinates (x fastest) from shifts, as k_pyramid12's box coordinates; nbx / 8 groups in a row
+    const uint32_t gid = blockIdx.x;
+    const int lgx = pg.lnbx - 3;
+    const int gx = (int)((gid & ((1u << lgx) - 1u)) << 7), by = (int)(((gid >> lgx) & ((1u << pg.lnby) - 1u)) << pg.ay),
+              bz = (int)((gid >> (lgx + pg.lnby)) << pg.az);
+    const int ymask = (1 << pg.ay) - 1;
+    const uint8_t *src = vox + (int64_t)brick * g.voxels + (gx + c * 16) + (int64_t)g.X * (by + (int64_t)g.Y * bz);
+    uint4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int row = (t >> 3) + 32 * k;              // y + (z << ay) inside the slab
+        v[k] = *(const uint4 *)(src + (int64_t)g.X * ((row & ymask) + (int64_t)g.Y * (row >> pg.ay)));
+    }
+    const uint32_t *sp = pg.spread;
+    const uint32_t rowBase = sp[g.X + by] | sp[g.X + g.Y + bz];    // Morton rank of box b's origin: sp[gx + 16 b] | rowBase
+    uint8_t *T = temp + (int64_t)brick * heapStride;
+    uint8_t *TR = tempRange ? tempRange + (int64_t)brick * heapStride : nullptr;
+    // SkipBlocks builds: the constant boxes of the group leave here, as in k_pyramid12.  A box is constant if every
+    // thread's 128 bytes are one byte, the 8 threads of a wave that hold the box (lanes c, c + 8, ..) agree, and the
+    // four waves do.
+    uint32_t constMask = 0u;                // bit b: box b is constant (the same in every thread)
+    bool myConst = false;                   // box c is
+    if (blockFlag) {
+        const uint32_t v0 = __builtin_amdgcn_perm(0, v[0].x, 0u);                  // byte 0 x 4
+        uint32_t diff = 0u;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) diff |= (v[k].x ^ v0) | (v[k].y ^ v0) | (v[k].z ^ v0) | (v[k].w ^ v0);
+        const uint32_t ref = (uint32_t)__shfl((int)v0, c);                         // of the box's first lane in my wave
+        const uint64_t same = __ballot(diff == 0u && v0 == ref), boxLanes = 0x0101010101010101ull << c;
+        if (lane < 8) boxConst[t >> 6][lane] = (same & boxLanes) == boxLanes ? v0 : 0x100u;   // (lane == c; 0x100: no byte x 4)
+        __syncthreads();
+        const uint32_t c0 = boxConst[0][c];
+        myConst = c0 != 0x100u && boxConst[1][c] == c0 && boxConst[2][c] == c0 && boxConst[3][c] == c0;
+        constMask = (uint32_t)__ballot(myConst) & 0xFFu;                           // lanes 0 .. 7 are boxes 0 .. 7
+        if (constMask) {
+            const int b = t >> 5, j = t & 31;           // 32 threads write a box's 128 slots
+            const uint32_t cv = (uint32_t)__shfl((int)c0, b);
+            if ((constMask >> b) & 1u) {
+                const uint32_t base = sp[gx + 16 * b] | rowBase;
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    pyr12_const_slot(j + 32 * m, cv, D, base, brick, T, TR, outMin, outMax, outStride, blockFlag, blockFlagR);
+            }
+            if (constMask == 0xFFu) return;
+        }
+    }
+    // Morton rank of row (t >> 3) + 32 k inside a box: rank bits are an OR over coordinate bits, and the two terms
+    // share no bit of the row number
+    const uint32_t rlo = sp[g.X + ((t >> 3) & ymask)] | sp[g.X + g.Y + ((t >> 3) >> pg.ay)];
+    for (int h = 0; h < 8 / NB; ++h) {
+        if (h) __syncthreads();                         // the round before reads its images no more
+        if (!myConst && c / NB == h) {
+            uint8_t *img = leaf + (c % NB) * PYR_LINES_IMAGE_STRIDE;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t r0 = rlo | sp[g.X + ((32 * k) & ymask)] | sp[g.X + g.Y + ((32 * k) >> pg.ay)];
+                const uint32_t vw[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+                for (int i = 0; i < 16; ++i) img[r0 | pg.sx[i]] = (uint8_t)(vw[i >> 2] >> ((i & 3) * 8));
+            }
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int b = h * NB; b < (h + 1) * NB; ++b)
+            if (!((constMask >> b) & 1u))
+                pyr12_reduce_box(leaf + (b % NB) * PYR_LINES_IMAGE_STRIDE, D, sp[gx + 16 * b] | rowBase, t, T, TR, waveMM[b]);
+    }
+    __syncthreads();
+    if (t < 8 && !((constMask >> t) & 1u))
+        pyr12_box_root(waveMM[t], D, sp[gx + 16 * t] | rowBase, brick, T, TR, outMin, outMax, outStride, blockFlag, blockFlagR);
 }
 
 // --------------------------------------------------------------- compress ----
@@ -3050,9 +3182,15 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
             memcpy(pg.sx, pp.sx, sizeof(pg.sx));
             pg.swz = pp.swz; pg.nbx = pp.nbx; pg.nby = pp.nby; pg.lnbx = pp.lnbx; pg.lnby = pp.lnby;
             pg.spread = bs->spread;
-            hipLaunchKernelGGL(k_pyramid12, dim3((unsigned)((int64_t)1 << (D - 12)), B), dim3(256), 0, st, bs->g, pg, vox,
-                               bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr, bs->mmMin[0], bs->mmMax[0],
-                               oStride, skipOn ? bs->blockFlag : nullptr, skipOn && mr ? bs->blockFlagR : nullptr);
+            // eight boxes per workgroup where they share their 128-byte lines (no XCD order: the sharers are one workgroup)
+            if (pp.lines && !bs->sw.pyramidBoxes)
+                hipLaunchKernelGGL(k_pyramid12_lines, dim3((unsigned)((int64_t)1 << (D - 15)), B), dim3(256), 0, st, bs->g, pg, vox,
+                                   bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr, bs->mmMin[0], bs->mmMax[0],
+                                   oStride, skipOn ? bs->blockFlag : nullptr, skipOn && mr ? bs->blockFlagR : nullptr);
+            else
+                hipLaunchKernelGGL(k_pyramid12, dim3((unsigned)((int64_t)1 << (D - 12)), B), dim3(256), 0, st, bs->g, pg, vox,
+                                   bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr, bs->mmMin[0], bs->mmMax[0],
+                                   oStride, skipOn ? bs->blockFlag : nullptr, skipOn && mr ? bs->blockFlagR : nullptr);
             dLeaf = D - 12;
             inMin = bs->mmMin[0]; inMax = bs->mmMax[0]; inStride = oStride;
             rootMinP = inMin; rootMaxP = inMax;
