@@ -820,7 +820,8 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
  * time.  Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks", "no_uniform_blocks",
  * "no_uniform_decode", "est_exact_bounds" (the distance estimator's first round computes exact bounds per node instead
  * of sufficient ones per quad of nodes, and has no fallback budget), "pyramid_boxes" (the pyramid's bottom twelve levels
- * by one 16^3 box per workgroup also where eight boxes per workgroup apply); any other name is VR_ERR_INVALID.
+ * by one 16^3 box per workgroup also where eight boxes per workgroup apply), "index_per_block" (the decode index of a
+ * build by one wave per 4096-leaf block, not 32 blocks per workgroup); any other name is VR_ERR_INVALID.
  * Results never depend on a switch; the tests use them to check the kernels against each other.
  * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1"; "reslice_tile_w" = 8, 16 or 64, the width of
  * the 64-pixel tile a wave of vr_reslice covers (16 is the default, chosen by measurement: DESIGN.md 3.5g); "hist_plain" = 1

@@ -32,6 +32,7 @@ struct Switches {
     bool estExactBounds = false; // VRHIP_EST_EXACT_BOUNDS: the estimator's first round runs the exact k_est_summ<false>, with no fallback budget
     int estBudget = EST_R0_BUDGET; // VRHIP_EST_BUDGET=<n>: node-by-node segments a brick may walk in the estimator's first round (measurement aid)
     bool pyramidBoxes = false;   // VRHIP_PYRAMID_BOXES: k_pyramid12 (one box per workgroup) where k_pyramid12_lines applies
+    bool indexPerBlock = false;  // VRHIP_INDEX_PER_BLOCK: k_index12_block (a wave per 4096-leaf block) + k_const_finish over every index entry, not k_index12
     bool noUniformDecode = false; // VRHIP_NO_UNIFORM_DECODE: k_decode_region ignores BrickSet::boxUniform (every live box is parsed).  Read per call
 };
 

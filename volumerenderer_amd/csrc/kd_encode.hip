@@ -2670,8 +2670,9 @@ k_block_alive(EmitArgs a, int64_t nblk, int sub)     // sub: log2 of the leaves 
 // The decode index of a fused build: block-local offsets -> offsets into the gapped stream buffer (slot b starts at
 // token b * PE_TOKENS), the scalar decoded down to depth Ds, and the scalars of the eight depth-(D-3) nodes below it
 // (k_decode_quad).  Codes under a pruned node are all 3, so the walks are the same for live and dead entries.
+// This kernel: a wave per block; the `index_per_block` switch launches it, and it is the reference for k_index12 below.
 __global__ void __launch_bounds__(256)
-k_index12(EmitArgs a, uint32_t nblk)
+k_index12_block(EmitArgs a, uint32_t nblk)
 {   // a wave per block, four per workgroup (one-wave workgroups: two million of them were dispatch-bound)
     const int brick = blockIdx.y, t = threadIdx.x & 63, D = a.D;
     Ctrl &c = a.ctrls[brick];
@@ -2736,6 +2737,175 @@ k_index12(EmitArgs a, uint32_t nblk)
         if (i < 4) lo3 |= (uint32_t)v << (8 * i); else hi3 |= (uint32_t)v << (8 * (i - 4));
     }
     *(uint2 *)(a.idxVal3 + io * 8) = make_uint2(lo3, hi3);
+}
+
+// apply_code without branches: + dist for code 1, - dist for code 2, nothing for 0 and 3 (v and dist are bytes, so one
+// clamp to 0 .. 255 serves both directions)
+__device__ __forceinline__ int idx_step(int v, uint32_t code, int dist)
+{
+    const int m = (int)(code & 1u) - (int)((code >> 1) & 1u);
+    return min(max(v + __mul24(m, dist), 0), 255);
+}
+
+// What a lane of k_index12 loads for its entry of a live block: the block-local offset k_prune_emit12 left, the code
+// bytes of the six nodes on its path below the block's root (whose code the prologue left in LDS), and the 2 + 4 + 8
+// codes below its node.  Raw bytes: the shifts wait for the evaluation, so that nothing waits for a load issued one
+// block ahead.
+struct IdxLoads {
+    uint32_t local, cb[7], c5, c4, c3;      // (cb[0] stays unused)
+};
+
+// first node of block blk at depth D-12+q (q = 0 .. 6), and where lane's node of that depth sits from the byte of it
+__device__ __forceinline__ uint64_t idx_first(int D, uint32_t blk, int q) { return ((uint64_t)1 << (D - 12 + q)) + ((uint64_t)blk << q); }
+__device__ __forceinline__ uint32_t idx_off(uint64_t u, uint32_t lane, int q) { return (uint32_t)(u & 3u) + (lane >> (6 - q)); }
+
+__device__ __forceinline__ IdxLoads idx_loads(const EmitArgs &a, const uint8_t *Cb, int64_t io0, uint32_t blk, uint32_t lane)
+{   // blk is wave-uniform: every address is a scalar base and a small lane offset
+    IdxLoads L;
+    const int D = a.D;
+    L.local = a.idxOff[io0 + ((int64_t)blk << 6) + lane];
+#pragma unroll
+    for (int q = 1; q < 7; ++q) {
+        const uint64_t u = idx_first(D, blk, q);
+        L.cb[q] = (Cb + (u >> 2))[idx_off(u, lane, q) >> 2];
+    }
+    // depths D-5, D-4, D-3: 2, 4 and 8 codes per entry, so 4, 8 and 16 bits at fixed places
+    L.c5 = (Cb + (((uint64_t)1 << (D - 7)) + ((uint64_t)blk << 5)))[lane >> 1];
+    L.c4 = (Cb + (((uint64_t)1 << (D - 6)) + ((uint64_t)blk << 6)))[lane];
+    L.c3 = ((const uint16_t *)(Cb + (((uint64_t)1 << (D - 5)) + ((uint64_t)blk << 7))))[lane];
+    return L;
+}
+
+// The decode index of a fused build, IDX_BLOCKS consecutive 4096-leaf blocks of a brick per workgroup (the same bytes
+// as k_index12_block).  Two thirds of the bench volume's blocks are dead -- their root is a pruned token or lies under
+// one -- and all their 64 entries are one value: one byte of flags, one of value and the root's code byte decide that,
+// loaded for all blocks in one batch by the first lanes.  The blocks' index ranges are contiguous (IDX_BLOCKS * 256
+// bytes of idxOff, * 64 of idxVal, * 512 of idxVal3): all 256 threads walk them in aligned 16-byte pieces and store
+// those of dead blocks, so a run of dead blocks is whole 128-byte lines.  Live blocks go to a list in LDS; wave w takes
+// entries w, w + 4, ... with the next block's loads issued before this one is evaluated; the level distances come from
+// LDS, once per workgroup.  The eight depth-(D-3) scalars of an entry are the leaves of one 2 + 4 + 8 tree: 14 steps
+// with shared parents.  A constant brick is IDX_BLOCKS dead blocks of its value (idxOff and idxVal only: what
+// k_const_finish wrote for it; idxVal3 of such a brick has no reader).
+#ifndef IDX_BLOCKS
+#define IDX_BLOCKS 32
+#endif
+static_assert(IDX_BLOCKS == 16 || IDX_BLOCKS == 32 || IDX_BLOCKS == 64, "one lane of the first wave per block; whole pieces per thread");
+__global__ void __launch_bounds__(256)
+k_index12(EmitArgs a, uint32_t nblk)
+{
+    __shared__ uint8_t deadS[IDX_BLOCKS], valS[IDX_BLOCKS], rootS[IDX_BLOCKS], listS[IDX_BLOCKS];
+    __shared__ uint32_t distS[10], nLiveS;
+    const int brick = blockIdx.y, t = threadIdx.x, D = a.D;
+    Ctrl &c = a.ctrls[brick];
+    const uint32_t blk0 = blockIdx.x * (uint32_t)IDX_BLOCKS;
+    const uint32_t nb = nblk - blk0 < (uint32_t)IDX_BLOCKS ? nblk - blk0 : (uint32_t)IDX_BLOCKS;      // D = 12 .. 16: fewer blocks than lanes
+    const int64_t io0 = (int64_t)brick * a.nIdx;
+    uint4 *const pOff = (uint4 *)(a.idxOff + io0 + ((int64_t)blk0 << 6));
+    uint4 *const pVal = (uint4 *)(a.idxVal + io0 + ((int64_t)blk0 << 6));
+    uint4 *const pVal3 = (uint4 *)(a.idxVal3 + (io0 + ((int64_t)blk0 << 6)) * 8);
+    const uint4 dead4 = make_uint4(VR_IDX_DEAD, VR_IDX_DEAD, VR_IDX_DEAD, VR_IDX_DEAD);
+    if (c.constBrick) {
+        const uint32_t v4 = (uint32_t)(uint8_t)c.constVal * 0x01010101u;
+#pragma unroll
+        for (int k = 0; k < IDX_BLOCKS / 16; ++k) {
+            const uint32_t p = (uint32_t)t + 256u * k;
+            if ((p >> 4) < nb) pOff[p] = dead4;
+        }
+        if (t < IDX_BLOCKS * 4 && ((uint32_t)t >> 2) < nb) pVal[t] = make_uint4(v4, v4, v4, v4);
+        return;
+    }
+    const uint8_t *Cb = a.codes + (int64_t)brick * a.codeStride;
+    // ---- prologue: the blocks' classes and values, the live list, the level distances
+    if (t < 64) {
+        bool live = false;
+        if ((uint32_t)t < nb) {
+            const uint32_t blk = blk0 + (uint32_t)t;
+            const int64_t bo = (int64_t)brick * a.nEmitBlk + blk;
+            const int bflags = a.blockAlive[bo];
+            const int bval = a.blockVal[bo];
+            const int64_t nr = ((int64_t)1 << (D - 12)) + blk;
+            const uint32_t rootCode = ((uint32_t)Cb[nr >> 2] >> ((int)(nr & 3) * 2)) & 3u;
+            live = !(rootCode == 3u || !(bflags & 2));
+            deadS[t] = live ? 0 : 1;
+            valS[t] = (uint8_t)bval;
+            rootS[t] = (uint8_t)rootCode;
+            if (a.idxBase) a.idxBase[bo] = (unsigned long long)blk * PE_TOKENS;
+        }
+        const unsigned long long lm = __ballot(live);
+        if (live) listS[__popcll(lm & (((unsigned long long)1 << t) - 1ull))] = (uint8_t)t;
+        if (t == 0) nLiveS = (uint32_t)__popcll(lm);
+    } else if (t < 74)
+        distS[t - 64] = c.distanceMap[D - 12 + (t - 64)];       // depths D-12 .. D-3
+    __syncthreads();
+    const uint32_t nLive = nLiveS;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(t >> 6), lane = (uint32_t)t & 63u;
+    IdxLoads cur = {};
+    if (w < nLive) cur = idx_loads(a, Cb, io0, blk0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)listS[w]), lane);
+    // ---- dead blocks: at most 2 + 1 + 4 pieces per thread
+    if (nLive < nb) {
+#pragma unroll
+        for (int k = 0; k < IDX_BLOCKS / 16; ++k) {
+            const uint32_t p = (uint32_t)t + 256u * k, b = p >> 4;
+            if (b < nb && deadS[b]) pOff[p] = dead4;
+        }
+        if (t < IDX_BLOCKS * 4) {
+            const uint32_t b = (uint32_t)t >> 2;
+            if (b < nb && deadS[b]) { const uint32_t v4 = (uint32_t)valS[b] * 0x01010101u; pVal[t] = make_uint4(v4, v4, v4, v4); }
+        }
+#pragma unroll
+        for (int k = 0; k < IDX_BLOCKS / 8; ++k) {
+            const uint32_t p = (uint32_t)t + 256u * k, b = p >> 5;
+            if (b < nb && deadS[b]) { const uint32_t v4 = (uint32_t)valS[b] * 0x01010101u; pVal3[p] = make_uint4(v4, v4, v4, v4); }
+        }
+    }
+    if (w >= nLive) return;
+    // ---- live blocks
+    int dist[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) dist[i] = __builtin_amdgcn_readfirstlane((int)distS[i]);
+    if (D == 12) dist[0] = 0;                       // the brick's root has no code to apply: its scalar is the root distance
+    const auto entry = [&](const IdxLoads &L, uint32_t b) {
+        const uint32_t blk = blk0 + b;
+        int val = idx_step(valS[b], rootS[b], dist[0]);         // valS: the scalar of the block root's parent
+        uint32_t code6 = 0;
+#pragma unroll
+        for (int q = 1; q < 7; ++q) {
+            code6 = L.cb[q] >> ((idx_off(idx_first(D, blk, q), lane, q) & 3u) * 2u);
+            val = idx_step(val, code6, dist[q]);
+        }
+        const uint32_t c5 = L.c5 >> ((lane & 1u) * 4u);
+        // an entry whose own token is a 3 is as good as one under a pruned node (k_index12_block)
+        const bool root3 = (code6 & 3u) == 3u;
+        const int64_t io = io0 + ((int64_t)blk << 6) + lane;
+        a.idxOff[io] = (L.local != VR_IDX_DEAD && !root3) ? (a.idxBase ? 0u : blk * (uint32_t)PE_TOKENS) + L.local : VR_IDX_DEAD;
+        a.idxVal[io] = (uint8_t)val;
+        // depth D-5: two nodes; D-4: four; D-3: eight -- each parent evaluated once
+        int v5[2], v4[4];
+        uint32_t lo3 = 0, hi3 = 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) v5[i] = idx_step(val, c5 >> (2 * i), dist[7]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] = idx_step(v5[i >> 1], L.c4 >> (2 * i), dist[8]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t v = (uint32_t)idx_step(v4[i >> 1], L.c3 >> (2 * i), dist[9]);
+            if (i < 4) lo3 |= v << (8 * i); else hi3 |= v << (8 * (i - 4));
+        }
+        *(uint2 *)(a.idxVal3 + io * 8) = make_uint2(lo3, hi3);
+    };
+    const auto block_of = [&](uint32_t e) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)listS[e]); };
+    // two entries per trip, so that the loads of one are in flight while the other is evaluated, without a copy; the
+    // loads are unconditional (past the end of the list: the entry at hand again, from L1, evaluated by nobody), so that
+    // the wait before an evaluation counts exactly the loads issued after its own
+    for (uint32_t e = w; e < nLive; e += 8u) {
+        const uint32_t e1 = e + 4u < nLive ? e + 4u : e;
+        const IdxLoads oth = idx_loads(a, Cb, io0, blk0 + block_of(e1), lane);
+        entry(cur, block_of(e));
+        if (e1 == e) break;
+        const uint32_t e2 = e + 8u < nLive ? e + 8u : e1;
+        cur = idx_loads(a, Cb, io0, blk0 + block_of(e2), lane);
+        entry(oth, block_of(e1));
+    }
 }
 
 // The reference's contiguous layout (R.cpp:631-718 writes one array): block b contributes the upper spine its first rank
@@ -3319,15 +3489,22 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     // contiguous stream is made when the host asks for it (compact_launch)
     bs->gapped = fused;
     bs->compactValid = false;
-    if (fused) hipLaunchKernelGGL(k_index12, dim3(cdiv(nblk, 4), B), dim3(256), 0, st, a, (uint32_t)nblk);
+    // (k_index12 writes the index entries of constant bricks too; the per-block kernel leaves them to k_const_finish)
+    const bool idxBatched = fused && !bs->sw.indexPerBlock;
+    if (idxBatched) hipLaunchKernelGGL(k_index12, dim3(cdiv(nblk, IDX_BLOCKS), B), dim3(256), 0, st, a, (uint32_t)nblk);
+    else if (fused) hipLaunchKernelGGL(k_index12_block, dim3(cdiv(nblk, 4), B), dim3(256), 0, st, a, (uint32_t)nblk);
     else {
         hipLaunchKernelGGL(k_emit_zero, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk);
         hipLaunchKernelGGL(k_emit_write, dim3((unsigned)nblk, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
     }
     // statistics records: one per 1024 leaves from k_prune_emit12, one per 256 from k_prune_leaf
     hipLaunchKernelGGL(k_emit_stats, dim3(B), dim3(1024), 0, st, a, (int64_t)(D >= 12 ? cdiv((int64_t)1 << D, 1024) : cdiv((int64_t)1 << D, 256)));
-    hipLaunchKernelGGL(k_const_finish, dim3(cdiv(bs->nIdx, 256), B), dim3(256), 0, st, D, bs->mid.ctrl, bs->mid.tree,
-                       bs->treeCap, bs->idxOff, bs->idxVal, bs->nIdx);
+    if (idxBatched)
+        hipLaunchKernelGGL(k_const_finish, dim3(1, B), dim3(64), 0, st, D, bs->mid.ctrl, bs->mid.tree,
+                           bs->treeCap, bs->idxOff, bs->idxVal, (int64_t)0);
+    else
+        hipLaunchKernelGGL(k_const_finish, dim3(cdiv(bs->nIdx, 256), B), dim3(256), 0, st, D, bs->mid.ctrl, bs->mid.tree,
+                           bs->treeCap, bs->idxOff, bs->idxVal, bs->nIdx);
     if (mr) hipLaunchKernelGGL(k_const_finish_range, dim3(B), dim3(64), 0, st, D, bs->rng.ctrl, bs->rng.tree, bs->treeCap);
     // the reference's build() ends with the contiguous stream (tree.swap(preorderTree), R.cpp:714-718): so does this one,
     // unless the caller turned it off (vr_brickset_set_compaction): the decoders read the block strings where they are
