@@ -405,7 +405,7 @@ typedef struct vr_camera {
 
 enum { VR_RENDER_COMPOSITE = 0 /* raycaster.frag */, VR_RENDER_ISOSURFACE = 1 /* isosurface.frag */,
        VR_RENDER_PARTIAL = 2 /* raycaster.frag accumulation as an (rgb-premultiplied c, transmittance) pair for sort-last compositing */,
-       VR_RENDER_SHADED = 3 /* transfer function with gradient lighting: vr_raycast_tf_shaded only */,
+       VR_RENDER_SHADED = 3 /* transfer function with gradient lighting, or a two-dimensional one: vr_raycast_tf_shaded, vr_raycast_tf2d & co. only */,
        VR_RENDER_PROJECTION = 4 /* intensity projections: vr_raycast_projection & co. only */ };
 
 typedef struct vr_render_params {
@@ -596,6 +596,66 @@ vr_status vr_composite_finish_tf(const float *partial_dev, const vr_transfer_fun
 vr_status vr_composite_slabs_tf(const float *partials_dev, int32_t num_slabs, int64_t num_pixels, int64_t first_pixel,
                                 int32_t axis, const vr_camera *cam, const vr_render_params *params,
                                 const vr_transfer_function *tf, float *rgba_dev, void *stream);
+
+/* ---- two-dimensional transfer functions (new): colour and opacity by value AND gradient magnitude --------------------
+ * The table is rows x 256 entries of (r, g, b, a) float32, row-major, values in [0, 1]: entry [j][k] belongs to the scalar
+ * k / 255 and the gradient coordinate j.  2 <= rows <= VR_TF2D_MAX_ROWS.  Ray set-up and steps 1, 2, 4, 5, 6 of
+ * vr_raycast_tf's rule are unchanged; step 3 becomes:
+ *  - x, i, f exactly as vr_raycast_tf forms them;
+ *  - g = the lattice gradient of the sample exactly as vr_raycast_tf_shaded forms it, for EVERY fetched sample (not only
+ *    those with a > 0), and m = sqrtf(g0*g0 + g1*g1 + g2*g2), the lit path's expression;
+ *  - y = fminf(fmaxf(m * grad_scale, 0), (float)(rows - 1)); j = min((int)y, rows - 2); h = y - (float)j;
+ *  - per channel eA = lut[j][i] + f * (lut[j][i+1] - lut[j][i]), eB likewise from row j + 1, e = eA + h * (eB - eA);
+ *    e.a is clamped to [0, 1].
+ * With grad_scale = 127.5 and rows = VR_HIST_GRAD_BINS, y = |d| / 4 (d the integer central differences): the row axis of
+ * vr_histogram2d -- at a voxel centre floor(y) is that voxel's histogram row.
+ * With a shading the lit colour c is formed from e.rgb and the same g and m by vr_raycast_tf_shaded's rule; with
+ * shading == NULL, c = e.rgb.  params->mode must be VR_RENDER_SHADED in BOTH cases: the mode tells vr_lod_select that taps
+ * reach two voxels.  A slab under vol_origin / global_dims holds TWO halo layers, lit or not.
+ * Skip grid: columns[k] = the first j >= k at which ANY row has alpha != 0 at entry j, or 256 (vr_tf2d_columns_build).  A
+ * sample whose grid bounds are (mn, mx) is not fetched when columns[max(mn - 1, 0)] > min(mx + 1, 255): then eA.a = eB.a
+ * = 0, e.a = 0 + h * 0 = 0 exactly and both updates are exact no-ops, so frames are bit-identical with and without the
+ * grid.  A skip grid attached (skip_grid_dev non-null and skip_cell > 0) with columns_dev == NULL is VR_ERR_INVALID.
+ * Invariants:
+ *  - a table whose rows are all equal draws vr_raycast_tf's frame with shading NULL, vr_raycast_tf_shaded's with a
+ *    shading and vr_raycast_tf_partial's partials bit for bit (params differing in the mode only), for any grad_scale:
+ *    eB - eA is exactly 0 and the build has no FMA contraction;
+ *  - the pool call equals the dense call on the pool's volume assembled densely;
+ *  - a full-box partial finished by vr_composite_finish_tf equals the frame.  Partials are colour partials: they go
+ *    through vr_composite_over_tf / _finish_tf / _slabs_tf and vr_compositor_composite_tf unchanged, with a
+ *    vr_transfer_function that carries the background. */
+#define VR_TF2D_MAX_ROWS 256       /* 256 x 256 x 16 bytes = 1 MiB */
+typedef struct vr_transfer_function2d {
+    const float    *lut_dev;      /* rows x 256 x (r,g,b,a), 16-byte aligned */
+    const uint16_t *columns_dev;  /* 256 x uint16 from vr_tf2d_columns_build of THE SAME table, 16-byte aligned; may be NULL when no skip grid is attached */
+    int32_t rows;
+    float   grad_scale;           /* > 0, finite: row coordinate y = m * grad_scale */
+    float   opacity_unit;         /* as vr_transfer_function */
+    float   background[3];
+} vr_transfer_function2d;         /* 40 bytes */
+
+/* columns_dev[k] for k = 0..255 (see above).  VR_ERR_INVALID for a null or misaligned lut_dev or columns_dev or rows out
+ * of range. */
+vr_status vr_tf2d_columns_build(const float *lut_dev, int32_t rows, uint16_t *columns_dev, void *stream);
+
+/* The checks of vr_raycast_tf_shaded / vr_raycast_pool_tf_shaded (shading may be NULL = unlit; a shading given is
+ * checked), plus VR_ERR_INVALID (nothing launched) for a null or misaligned lut_dev, a misaligned columns_dev, rows out
+ * of range, a grad_scale that is not finite or <= 0, the missing-columns case above, or a mode other than
+ * VR_RENDER_SHADED.  Then VR_ERR_NO_DEVICE.  The _partial calls write the colour partial (C.r, C.g, C.b, T). */
+vr_status vr_raycast_tf2d(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                          const vr_render_params *params, const vr_transfer_function2d *tf,
+                          const vr_shading *shading /* NULL = unlit */, float *rgba_dev, void *stream);
+vr_status vr_raycast_pool_tf2d(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                               const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
+                               const vr_transfer_function2d *tf, const vr_shading *shading /* NULL = unlit */,
+                               float *rgba_dev, void *stream);
+vr_status vr_raycast_tf2d_partial(const uint8_t *volume_dev, const int64_t dims[3], const vr_camera *cam,
+                                  const vr_render_params *params, const vr_transfer_function2d *tf,
+                                  const vr_shading *shading /* NULL = unlit */, float *partial_dev, void *stream);
+vr_status vr_raycast_pool_tf2d_partial(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
+                                       const int64_t grid[3], const vr_camera *cam, const vr_render_params *params,
+                                       const vr_transfer_function2d *tf, const vr_shading *shading /* NULL = unlit */,
+                                       float *partial_dev, void *stream);
 
 /* ---- intensity projections (new): MIP, MinIP and the mean along the ray, exact across GPUs ----------------------------
  * Ray set-up is vr_raycast's, unchanged: positions are formed by the same repeated float additions pos += st, with the

@@ -1,5 +1,6 @@
 // vrhip/TransferFunction.hpp -- a transfer-function table for vr_raycast_tf / vr_raycast_pool_tf from control points,
-// without Python: the rule of volumerenderer_amd.render.transfer_function_table; and SortLastTf, the sort-last colour
+// without Python: the rule of volumerenderer_amd.render.transfer_function_table; a separable two-dimensional table for
+// vr_raycast_tf2d; and SortLastTf, the sort-last colour
 // partials of such frames (vr_raycast_tf_partial and its combine calls).  Plain C++14, host only.
 #pragma once
 #include "../vrhip.h"
@@ -48,6 +49,30 @@ inline std::vector<float> transfer_function_from_points(const std::vector<TfPoin
     return lut;
 }
 
+// rows x 256 x (r, g, b, a) float32 for vr_raycast_tf2d: row j holds the 1-D table's colours and its alpha scaled by
+// weight_by_row[j] -- rgb[j][k] = lut1d[k].rgb, a[j][k] = (float)((double)lut1d[k].a * weight_by_row[j]); the rule of
+// volumerenderer_amd.render.tf2d_separable_table.  Throws std::invalid_argument unless lut1d holds 256 x 4 floats, there
+// are 2 .. VR_TF2D_MAX_ROWS weights and every weight lies in [0, 1].
+inline std::vector<float> transfer_function2d_separable(const std::vector<float> &lut1d, const std::vector<double> &weight_by_row)
+{
+    if (lut1d.size() != 256 * 4) throw std::invalid_argument("transfer function 2d: the 1-D table must hold 256 x 4 floats");
+    if (weight_by_row.size() < 2 || weight_by_row.size() > VR_TF2D_MAX_ROWS)
+        throw std::invalid_argument("transfer function 2d: 2 .. " + std::to_string(VR_TF2D_MAX_ROWS) + " rows");
+    for (double w : weight_by_row)
+        if (!(w >= 0.0 && w <= 1.0)) throw std::invalid_argument("transfer function 2d: weights outside [0, 1]");
+    std::vector<float> lut(weight_by_row.size() * 256 * 4);
+    for (size_t j = 0; j < weight_by_row.size(); ++j)
+        for (int k = 0; k < 256; ++k) {
+            float *e = &lut[(j * 256 + k) * 4];
+            e[0] = lut1d[4 * k]; e[1] = lut1d[4 * k + 1]; e[2] = lut1d[4 * k + 2];
+            e[3] = (float)((double)lut1d[4 * k + 3] * weight_by_row[j]);
+        }
+    return lut;
+}
+
+// the row scale volumerenderer_amd.render.TransferFunction2D defaults to: the rows spread over the whole gradient range
+inline float default_grad_scale(int rows) { return (float)(127.5 * (rows - 1) / 110.0); }
+
 // the lighting volumerenderer_amd.render.Shading() defaults to: ka 0.3, kd 0.7, ks 0.2, shininess 32, head light,
 // grad_min 1/255
 inline vr_shading default_shading()
@@ -61,19 +86,34 @@ inline vr_shading default_shading()
 
 // Sort-last frames through a transfer function, lit or not: what is the same for every slab of a frame (camera, table,
 // lighting) is set once, the calls take what differs.  Buffers are the caller's device memory: a colour partial and a
-// frame are width * height float4 each.  The rule is in vrhip.h (vr_raycast_tf_partial).
+// frame are width * height float4 each.  The rule is in vrhip.h (vr_raycast_tf_partial).  With a vr_transfer_function2d
+// the partials come from vr_raycast_tf2d_partial (the mode is VR_RENDER_SHADED lit or not, two halo layers); the
+// combine calls are the same: they read only the background.
 class SortLastTf {
 public:
     vr_camera cam;
-    vr_transfer_function tf;
+    vr_transfer_function tf;        // two-dimensional: the background the combine calls read, no table
     bool lit;
     vr_shading shading;
+    bool twoD;
+    vr_transfer_function2d tf2d;
 
-    SortLastTf(const vr_camera &c, const vr_transfer_function &t) : cam(c), tf(t), lit(false), shading(default_shading()) {}
-    SortLastTf(const vr_camera &c, const vr_transfer_function &t, const vr_shading &s) : cam(c), tf(t), lit(true), shading(s) {}
+    SortLastTf(const vr_camera &c, const vr_transfer_function &t) : cam(c), tf(t), lit(false), shading(default_shading()), twoD(false), tf2d() {}
+    SortLastTf(const vr_camera &c, const vr_transfer_function &t, const vr_shading &s) : cam(c), tf(t), lit(true), shading(s), twoD(false), tf2d() {}
+    SortLastTf(const vr_camera &c, const vr_transfer_function2d &t) : cam(c), tf(background_of(t)), lit(false), shading(default_shading()), twoD(true), tf2d(t) {}
+    SortLastTf(const vr_camera &c, const vr_transfer_function2d &t, const vr_shading &s) : cam(c), tf(background_of(t)), lit(true), shading(s), twoD(true), tf2d(t) {}
 
-    // halo layers a slab must hold beyond each cut: the trilinear taps, and the gradient's taps one voxel further
-    int halo() const { return lit ? 2 : 1; }
+    static vr_transfer_function background_of(const vr_transfer_function2d &t)
+    {
+        vr_transfer_function b;
+        b.lut_dev = nullptr; b.opacity_unit = t.opacity_unit;
+        for (int k = 0; k < 3; ++k) b.background[k] = t.background[k];
+        return b;
+    }
+
+    // halo layers a slab must hold beyond each cut: the trilinear taps, and the gradient's taps one voxel further (a
+    // two-dimensional table takes the gradient of every sample, lit or not)
+    int halo() const { return (lit || twoD) ? 2 : 1; }
 
     // Rank `rank`'s slab of a volume of `dims` voxels cut into `world` slabs along `axis` (volumerenderer_amd.distributed.
     // slab_params): P with box_min / box_max (the last rank's box_max is 2: it owns the far face), vol_origin and
@@ -100,13 +140,17 @@ public:
     vr_status partial(const uint8_t *vol_dev, const int64_t dims[3], vr_render_params P, float *partial_dev,
                       void *stream = nullptr) const
     {
-        P.mode = lit ? VR_RENDER_SHADED : VR_RENDER_COMPOSITE;
+        P.mode = (lit || twoD) ? VR_RENDER_SHADED : VR_RENDER_COMPOSITE;
+        if (twoD) return vr_raycast_tf2d_partial(vol_dev, dims, &cam, &P, &tf2d, lit ? &shading : nullptr, partial_dev, stream);
         return vr_raycast_tf_partial(vol_dev, dims, &cam, &P, &tf, lit ? &shading : nullptr, partial_dev, stream);
     }
     vr_status partialPool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
                           const int64_t grid[3], vr_render_params P, float *partial_dev, void *stream = nullptr) const
     {
-        P.mode = lit ? VR_RENDER_SHADED : VR_RENDER_COMPOSITE;
+        P.mode = (lit || twoD) ? VR_RENDER_SHADED : VR_RENDER_COMPOSITE;
+        if (twoD)
+            return vr_raycast_pool_tf2d_partial(pool_dev, table_dev, brick_dims, grid, &cam, &P, &tf2d, lit ? &shading : nullptr,
+                                                partial_dev, stream);
         return vr_raycast_pool_tf_partial(pool_dev, table_dev, brick_dims, grid, &cam, &P, &tf, lit ? &shading : nullptr,
                                           partial_dev, stream);
     }

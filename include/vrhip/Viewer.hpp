@@ -128,6 +128,23 @@ public:
         const vr_camera c = camera();
         return vr_raycast_pool_tf_shaded(pool_dev, table_dev, brick_dims, grid, &c, &P, tf, shading, rgba_dev, stream);
     }
+    // the same frames through a two-dimensional transfer function (vr_raycast_tf2d / vr_raycast_pool_tf2d), lit where
+    // shading is not null: P.mode is set to VR_RENDER_SHADED in both cases
+    vr_status draw(const uint8_t *vol, const int64_t dims[3], vr_render_params P, const vr_transfer_function2d *tf,
+                   const vr_shading *shading, float *rgba_dev, void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f; P.mode = VR_RENDER_SHADED;
+        const vr_camera c = camera();
+        return vr_raycast_tf2d(vol, dims, &c, &P, tf, shading, rgba_dev, stream);
+    }
+    vr_status drawPool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3], const int64_t grid[3],
+                       vr_render_params P, const vr_transfer_function2d *tf, const vr_shading *shading, float *rgba_dev,
+                       void *stream = nullptr) const
+    {
+        P.width = width; P.height = height; P.iso_value = currIsoVal / 255.0f; P.mode = VR_RENDER_SHADED;
+        const vr_camera c = camera();
+        return vr_raycast_pool_tf2d(pool_dev, table_dev, brick_dims, grid, &c, &P, tf, shading, rgba_dev, stream);
+    }
     // a slice view (vr_reslice): the plane brings its own geometry and frame size, rgba_dev holds
     // plane.width * plane.height float4; the camera plays no part
     vr_status drawSlice(const uint8_t *vol, const int64_t dims[3], const vr_slice_plane &plane, const vr_projection &proj,

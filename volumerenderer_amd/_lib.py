@@ -14,6 +14,7 @@ STATUS = {0: "VR_OK", -1: "VR_ERR_INVALID", -2: "VR_ERR_NO_DEVICE", -3: "VR_ERR_
 VARIANT_RECOVER, VARIANT_GUARDED, VARIANT_MIDRANGE = 0, 1, 2
 RENDER_COMPOSITE, RENDER_ISOSURFACE, RENDER_PARTIAL, RENDER_SHADED, RENDER_PROJECTION = 0, 1, 2, 3, 4
 PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN = 0, 1, 2
+TF2D_MAX_ROWS, HIST_GRAD_BINS = 256, 111
 SLICE_NEAREST, SLICE_LINEAR = 0, 1
 
 
@@ -48,6 +49,12 @@ class RenderParams(C.Structure):
 class TransferFunctionDesc(C.Structure):
     """vr_transfer_function (24 bytes)."""
     _fields_ = [("lut_dev", C.c_void_p), ("opacity_unit", C.c_float), ("background", C.c_float * 3)]
+
+
+class TransferFunction2DDesc(C.Structure):
+    """vr_transfer_function2d (40 bytes)."""
+    _fields_ = [("lut_dev", C.c_void_p), ("columns_dev", C.c_void_p), ("rows", C.c_int32), ("grad_scale", C.c_float),
+                ("opacity_unit", C.c_float), ("background", C.c_float * 3)]
 
 
 class ShadingDesc(C.Structure):
@@ -140,6 +147,15 @@ SIGNATURES = {
                                      C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
     "vr_raycast_pool_tf_partial": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
                                           C.POINTER(TransferFunctionDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_tf2d_columns_build": (_I32, [_P, _I32, _P, _P]),
+    "vr_raycast_tf2d": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                               C.POINTER(TransferFunction2DDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_raycast_pool_tf2d": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                    C.POINTER(TransferFunction2DDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_raycast_tf2d_partial": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                       C.POINTER(TransferFunction2DDesc), C.POINTER(ShadingDesc), _P, _P]),
+    "vr_raycast_pool_tf2d_partial": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams),
+                                            C.POINTER(TransferFunction2DDesc), C.POINTER(ShadingDesc), _P, _P]),
     "vr_composite_over_tf": (_I32, [_P, _P, _I64, _P]),
     "vr_composite_finish_tf": (_I32, [_P, C.POINTER(TransferFunctionDesc), _P, _I64, _P]),
     "vr_composite_slabs_tf": (_I32, [_P, _I32, _I64, _I64, _I32, C.POINTER(Camera), C.POINTER(RenderParams),

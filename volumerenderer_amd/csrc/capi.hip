@@ -1206,6 +1206,77 @@ vr_status vr_raycast_pool_tf_partial(const uint8_t *pool, const vr_pool_entry *t
     return raycast_pool(sh ? LIT : TABLE, pool, table, bd, grid, cam, P, tf, sh, partial, stream, true);
 }
 
+// ---- two-dimensional transfer functions (vrhip.h) ---------------------------------------------------------------------
+static bool table2d_ok(const float *lut, int32_t rows)
+{
+    return lut && ((uintptr_t)lut & 15u) == 0u && rows >= 2 && rows <= VR_TF2D_MAX_ROWS;
+}
+
+// the table, its scale and (where params attach a skip grid) its column summary; the mode is VR_RENDER_SHADED lit or not
+static bool style2d_ok(const vr_render_params *P, const vr_transfer_function2d *tf, const vr_shading *sh)
+{
+    if (!tf || !table2d_ok(tf->lut_dev, tf->rows)) return false;
+    if (((uintptr_t)tf->columns_dev & 15u) != 0u) return false;
+    if (!tf->columns_dev && P->skip_grid_dev && P->skip_cell > 0) return false;
+    if (!(tf->grad_scale > 0.0f) || !isfinite(tf->grad_scale)) return false;
+    if (!(tf->opacity_unit >= 0.0f) || !isfinite(tf->opacity_unit)) return false;
+    for (int k = 0; k < 3; ++k) if (!isfinite(tf->background[k])) return false;
+    if (sh && !lighting_ok(sh)) return false;
+    return P->mode == VR_RENDER_SHADED;
+}
+
+static vr_status raycast_dense2d(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                                 const vr_transfer_function2d *tf, const vr_shading *sh, float *rgba, void *stream, bool partial)
+{
+    if (!frame_ok(cam, P, rgba) || !dense_ok(vol, dims) || !style2d_ok(P, tf, sh)) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_tf2d_launch(vol, dims, cam, P, tf, sh, partial, rgba, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+static vr_status raycast_pool2d(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                                const vr_camera *cam, const vr_render_params *P, const vr_transfer_function2d *tf,
+                                const vr_shading *sh, float *rgba, void *stream, bool partial)
+{
+    if (!frame_ok(cam, P, rgba) || !pool_ok(pool, table, bd, grid) || !pool_frame_ok(P, bd, grid) || !style2d_ok(P, tf, sh))
+        return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return raycast_pool_tf2d_launch(pool, table, bd, grid, cam, P, tf, sh, partial, rgba, (hipStream_t)stream) == 0
+               ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_tf2d_columns_build(const float *lut, int32_t rows, uint16_t *columns, void *stream)
+{
+    if (!table2d_ok(lut, rows) || !columns || ((uintptr_t)columns & 15u) != 0u) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    return tf2d_columns_launch(lut, rows, columns, (hipStream_t)stream) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+vr_status vr_raycast_tf2d(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                          const vr_transfer_function2d *tf, const vr_shading *sh, float *rgba, void *stream)
+{
+    return raycast_dense2d(vol, dims, cam, P, tf, sh, rgba, stream, false);
+}
+
+vr_status vr_raycast_pool_tf2d(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3],
+                               const vr_camera *cam, const vr_render_params *P, const vr_transfer_function2d *tf,
+                               const vr_shading *sh, float *rgba, void *stream)
+{
+    return raycast_pool2d(pool, table, bd, grid, cam, P, tf, sh, rgba, stream, false);
+}
+
+vr_status vr_raycast_tf2d_partial(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                                  const vr_transfer_function2d *tf, const vr_shading *sh, float *partial, void *stream)
+{
+    return raycast_dense2d(vol, dims, cam, P, tf, sh, partial, stream, true);
+}
+
+vr_status vr_raycast_pool_tf2d_partial(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3],
+                                       const int64_t grid[3], const vr_camera *cam, const vr_render_params *P,
+                                       const vr_transfer_function2d *tf, const vr_shading *sh, float *partial, void *stream)
+{
+    return raycast_pool2d(pool, table, bd, grid, cam, P, tf, sh, partial, stream, true);
+}
+
 vr_status vr_skip_grid_build(const uint8_t *vol, const int64_t dims[3], int32_t cell, uint8_t *grid, void *stream)
 {
     if (!dense_ok(vol, dims) || !grid || cell <= 0 || cell > 64) return VR_ERR_INVALID;

@@ -37,6 +37,12 @@ int raycast_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *,
 int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3], const vr_camera *,
                         const vr_render_params *, const vr_transfer_function *, const vr_shading *, bool partial, float *rgba,
                         hipStream_t);
+int raycast_tf2d_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *, const vr_render_params *,
+                        const vr_transfer_function2d *, const vr_shading *, bool partial, float *rgba, hipStream_t);
+int raycast_pool_tf2d_launch(const uint8_t *pool, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3],
+                             const vr_camera *, const vr_render_params *, const vr_transfer_function2d *, const vr_shading *,
+                             bool partial, float *rgba, hipStream_t);
+int tf2d_columns_launch(const float *lut, int rows, uint16_t *columns, hipStream_t);
 int raycast_proj_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *, const vr_render_params *, const vr_projection *,
                         bool partial, float *rgba, hipStream_t);
 int raycast_pool_proj_launch(const uint8_t *pool, const vr_pool_entry *, const int64_t bd[3], const int64_t grid[3],

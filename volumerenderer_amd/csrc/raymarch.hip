@@ -678,6 +678,135 @@ k_raycast_tf(RayArgs a, SAMPLER tex, TfArgs tf, ShadeArgs sh)
     else { o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T; }
 }
 
+// ---- two-dimensional transfer functions (vr_raycast_tf2d; the rule is in vrhip.h) ------------------------------------
+struct Tf2dArgs {
+    const float4 *lut;          // rows x 256 (r, g, b, a), 16-byte aligned, row-major
+    const uint16_t *columns;    // vr_tf2d_columns_build of the same table; read only where a skip grid is attached
+    int rows;
+    float gscale;               // grad_scale
+    float unit;
+    float bg[3];
+};
+
+// columns[k] = the first j >= k at which any row has alpha != 0 at entry j (256: none).  One workgroup of 256 lanes: lane k
+// ORs column k over the rows, then walks forward to the first flagged column.
+__global__ void __launch_bounds__(256)
+k_tf2d_columns(const float4 *__restrict__ lut, int rows, uint16_t *__restrict__ columns)
+{
+    __shared__ uint8_t opaque[256];
+    const int k = threadIdx.x;
+    bool any = false;
+    for (int j = 0; j < rows; ++j) any = any || lut[(size_t)j * 256 + k].w != 0.0f;
+    opaque[k] = any ? 1 : 0;
+    __syncthreads();
+    int first = k;
+    while (first < 256 && !opaque[first]) ++first;
+    columns[k] = (uint16_t)first;
+}
+
+// k_raycast_tf's march with a table indexed by value and gradient magnitude: a sibling kernel, so k_raycast_tf's
+// instantiations keep their registers.  Every fetched sample gathers its lattice gradient (the row needs |g|); the table
+// stays in global memory (two 32-byte reads per sample: entries i, i + 1 of rows j, j + 1), only the 512-byte column
+// summary is staged, and only when a grid is attached.  A sample the grid bounds by (mn, mx) is skippable when
+// columns[max(mn - 1, 0)] > min(mx + 1, 255): every entry of every row the lookup can touch is transparent.
+__device__ __forceinline__ bool ray_setup(const RayArgs &a, int px, int py, float pos[3], float st[3]);     // below
+
+template <class SAMPLER, bool LIT, bool PARTIAL>
+__global__ void __launch_bounds__(64)
+k_raycast_tf2d(RayArgs a, SAMPLER tex, Tf2dArgs tf, ShadeArgs sh)
+{
+    __shared__ alignas(8) uint16_t columns[256];      // staged as one 8-byte piece per lane
+    const int lane = threadIdx.x;
+    if (a.sg.g) ((uint2 *)columns)[lane] = ((const uint2 *)tf.columns)[lane];
+    __syncthreads();
+    // 8x8 pixel tile per wave
+    const int px = blockIdx.x * 8 + (lane & 7), py = blockIdx.y * 8 + (lane >> 3);
+    const int W = a.P.width, H = a.P.height;
+    if (px >= W || py >= H) return;
+    float *o = a.out + 4 * ((size_t)py * W + px);
+    float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, T = 1.0f;
+    float st[3], pos[3];
+    if (ray_setup(a, px, py, pos, st)) {
+        // opacity correction exponent L / opacity_unit (0 = none, or L = 0: a = 1 - t^0 = 0)
+        const float L = sqrtf(st[0] * st[0] + st[1] * st[1] + st[2] * st[2]);
+        const bool correct = tf.unit > 0.0f;
+        const float ex = correct ? L / tf.unit : 0.0f;
+        // LIT, per ray: V, the light and the half vector; no specular term where L + V = 0.  gd is ray_setup's, formed
+        // again from the same operands (pos is still vUV here)
+        float gd[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gd[k] = (pos[k] - 0.5f) - a.cam.pos[k];
+        norm3(gd[0], gd[1], gd[2]);
+        const float V0 = -gd[0], V1 = -gd[1], V2 = -gd[2];
+        const float L0 = sh.head ? V0 : sh.L[0], L1 = sh.head ? V1 : sh.L[1], L2 = sh.head ? V2 : sh.L[2];
+        float H0 = L0 + V0, H1 = L1 + V1, H2 = L2 + V2;
+        const float ks = (H0 != 0.0f || H1 != 0.0f || H2 != 0.0f) ? sh.ks : 0.0f;
+        norm3(H0, H1, H2);
+        const float top = (float)(tf.rows - 1);
+        const int ns = a.P.max_samples;
+        bool probe = true;      // ask the grid only while the ray is in empty space (the last sample's a was 0)
+        for (int i = 0; i < ns; ++i) {
+            pos[0] = pos[0] + st[0]; pos[1] = pos[1] + st[1]; pos[2] = pos[2] + st[2];
+            if (!inside(pos[0], pos[1], pos[2])) break;
+            bool own = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) own = own && (pos[k] >= a.P.box_min[k] && pos[k] < a.P.box_max[k]);
+            if (!own) continue;
+            if (a.sg.g && probe) {
+                const uint32_t b = skip_bounds(a.sg, a.t, pos[0], pos[1], pos[2]);
+                const int lo = max((int)(b & 255u) - 1, 0), hi = min((int)(b >> 8) + 1, 255);
+                if ((int)columns[lo] > hi) continue;        // every entry of every row the lookup can touch is transparent
+            }
+            const float smp = sample3d(tex, a, pos[0], pos[1], pos[2]);
+            const float x = fminf(fmaxf(smp * 255.0f, 0.0f), 255.0f);
+            const int li = min((int)x, 254);
+            const float f = x - (float)li;
+            const Lattice l = lattice(a.t.GX, a.t.GY, a.t.GZ, pos[0], pos[1], pos[2]);
+            float g[3];
+            lattice_gradient(gather(tex, a, l), l, g);
+            const float m = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+            const float y = fminf(fmaxf(m * tf.gscale, 0.0f), top);
+            const int lj = min((int)y, tf.rows - 2);
+            const float h = y - (float)lj;
+            const float4 *row = tf.lut + ((size_t)lj * 256 + li);
+            const float4 a0 = row[0], a1 = row[1], b0 = row[256], b1 = row[257];
+            const float eAa = a0.w + f * (a1.w - a0.w), eBa = b0.w + f * (b1.w - b0.w);
+            float ea = eAa + h * (eBa - eAa);
+            ea = fminf(fmaxf(ea, 0.0f), 1.0f);
+            float al = ea;
+            if (correct) {
+                // 1 - (1 - ea)^ex: ea = 0 -> log2(1) = 0 -> exactly 0; ea = 1 -> log2(0) = -inf -> exp2(-inf) = 0 -> 1
+                const float p = ex == 0.0f ? 1.0f : exp2f(ex * log2f(1.0f - ea));
+                al = 1.0f - p;
+            }
+            probe = al == 0.0f;
+            if (probe) continue;        // a = 0: both updates would be exact no-ops
+            const float eA0 = a0.x + f * (a1.x - a0.x), eB0 = b0.x + f * (b1.x - b0.x);
+            const float eA1 = a0.y + f * (a1.y - a0.y), eB1 = b0.y + f * (b1.y - b0.y);
+            const float eA2 = a0.z + f * (a1.z - a0.z), eB2 = b0.z + f * (b1.z - b0.z);
+            float c0 = eA0 + h * (eB0 - eA0), c1 = eA1 + h * (eB1 - eA1), c2 = eA2 + h * (eB2 - eA2);
+            if (LIT) {
+                if (m > sh.gmin) {
+                    float N0 = (float)a.t.GX * g[0], N1 = (float)a.t.GY * g[1], N2 = (float)a.t.GZ * g[2];
+                    norm3(N0, N1, N2);
+                    const float cd = fabsf(N0 * L0 + N1 * L1 + N2 * L2);
+                    const float ch = fminf(fmaxf(fabsf(N0 * H0 + N1 * H1 + N2 * H2), 0.00001f), 1.0f);
+                    const float kl = sh.ka + sh.kd * cd, sp = ks * powf(ch, sh.shininess);
+                    c0 = fminf(1.0f, c0 * kl + sp); c1 = fminf(1.0f, c1 * kl + sp); c2 = fminf(1.0f, c2 * kl + sp);
+                }
+            }
+            const float w = T * al;
+            C0 = C0 + w * c0;
+            C1 = C1 + w * c1;
+            C2 = C2 + w * c2;
+            T = T * (1.0f - al);
+            if (!a.P.no_early_exit && T < 0.01f) break;
+        }
+    }
+    if (PARTIAL) { o[0] = C0; o[1] = C1; o[2] = C2; o[3] = T; }
+    else { o[0] = C0 + T * tf.bg[0]; o[1] = C1 + T * tf.bg[1]; o[2] = C2 + T * tf.bg[2]; o[3] = 1.0f - T; }
+}
+
 // ---- colour partials (vr_raycast_tf_partial): one float4 (C.r, C.g, C.b, T) per pixel.  "Over" and the finish are
 // written with the marcher's own expressions (C + w c, T t; C + T bg, 1 - T), so a fold of slabs rounds like one march.
 struct Bg { float c[3]; };
@@ -1140,6 +1269,54 @@ int raycast_pool_launch(const uint8_t *pool, const vr_pool_entry *tab, const int
     const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
     ray_frame(a, cam, P, rgba);
     return march_launch(a, pt, tf, sh, partial, label, st);
+}
+
+// the frame (or colour partial) of a through k_raycast_tf2d, lit where sh is given
+template <class SAMPLER>
+static int march2d_launch(const RayArgs &a, const SAMPLER &tex, const vr_transfer_function2d *tf, const vr_shading *sh,
+                          bool partial, const char *label, hipStream_t st)
+{
+    Tf2dArgs t;
+    t.lut = (const float4 *)tf->lut_dev;
+    t.columns = tf->columns_dev;
+    t.rows = tf->rows;
+    t.gscale = tf->grad_scale;
+    t.unit = tf->opacity_unit;
+    for (int k = 0; k < 3; ++k) t.bg[k] = tf->background[k];
+    const dim3 grid((a.P.width + 7) / 8, (a.P.height + 7) / 8);
+    if (!sh) {
+        auto kern = partial ? k_raycast_tf2d<SAMPLER, false, true> : k_raycast_tf2d<SAMPLER, false, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a, tex, t, ShadeArgs());
+    } else {
+        auto kern = partial ? k_raycast_tf2d<SAMPLER, true, true> : k_raycast_tf2d<SAMPLER, true, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a, tex, t, shade_args(sh));
+    }
+    return launch_status(label);
+}
+
+int raycast_tf2d_launch(const uint8_t *vol, const int64_t dims[3], const vr_camera *cam, const vr_render_params *P,
+                        const vr_transfer_function2d *tf, const vr_shading *sh, bool partial, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    dense_args(a, vol, dims, P);
+    ray_frame(a, cam, P, rgba);
+    return march2d_launch(a, DenseSampler(), tf, sh, partial, "raymarch_tf2d", st);
+}
+
+int raycast_pool_tf2d_launch(const uint8_t *pool, const vr_pool_entry *tab, const int64_t bd[3], const int64_t grid[3],
+                             const vr_camera *cam, const vr_render_params *P, const vr_transfer_function2d *tf,
+                             const vr_shading *sh, bool partial, float *rgba, hipStream_t st)
+{
+    RayArgs a;
+    const PoolTex pt = pool_args(a, pool, tab, bd, grid, P);
+    ray_frame(a, cam, P, rgba);
+    return march2d_launch(a, pt, tf, sh, partial, "raymarch_pool_tf2d", st);
+}
+
+int tf2d_columns_launch(const float *lut, int rows, uint16_t *columns, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_tf2d_columns, dim3(1), dim3(256), 0, st, (const float4 *)lut, rows, columns);
+    return launch_status("tf2d_columns");
 }
 
 // k_skip_grid over a pool's virtual volume: the same cells, rows and bounds; a row's voxels come from the stored voxels of

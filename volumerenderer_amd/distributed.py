@@ -62,7 +62,8 @@ def _gpu_combine(parts, first_pixel, axis, cam, params):
 
 
 def _gpu_combine_tf(parts, first_pixel, axis, cam, params, tf):
-    desc = tf.desc()
+    from .render import background_desc
+    desc = background_desc(tf)
     return _gpu_slabs("vr_composite_slabs_tf", parts, int(first_pixel), int(axis), C.byref(cam), C.byref(params), C.byref(desc))
 
 
@@ -90,8 +91,8 @@ def _slab_cut(who, dims, axis, rank, world, halo):
 
 def slab_params(params, dims, axis, rank, world, halo):
     """Rank `rank`'s slab when a volume of `dims` = (X, Y, Z) voxels is cut into `world` slabs along `axis`, stored with
-    `halo` voxel layers beyond each cut (1 for the grey and the unlit marches and the projections, 2 for the lit one;
-    vrhip.h).  Returns
+    `halo` voxel layers beyond each cut (1 for the grey and the unlit marches and the projections, 2 for the lit one and
+    for a two-dimensional transfer function, lit or not; vrhip.h).  Returns
     (P, local_dims, (a0, a1)): P = a copy of `params` with box_min / box_max (the last rank's box_max is 2.0: it owns
     the far face), vol_origin and global_dims set, local_dims the extents of the voxels [a0, a1) along `axis` that the
     rank has to hold."""
@@ -195,12 +196,12 @@ def composite_sort_last(partial, cam, params, axis=2, group=None, combine=None, 
 
 def composite_sort_last_tf(partial, cam, params, tf, axis=2, group=None, combine=None, out=None):
     """composite_sort_last for colour partials: partial = this rank's (C.r, C.g, C.b, T) image [H][W][4] float32 from
-    raycast_tf_partial (unlit or lit), tf the TransferFunction whose background finishes the frame.  The same exchange;
+    raycast_tf_partial (unlit or lit) or raycast_tf2d_partial, tf the TransferFunction or TransferFunction2D whose
+    background finishes the frame (nothing else of it is read).  The same exchange;
     device tensors take vr_compositor_composite_tf, an injected `combine(parts, first_pixel, axis, cam, params)` runs
     over torch.distributed point-to-point operations."""
-    from .render import TransferFunction
-    if not isinstance(tf, TransferFunction):
-        raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
+    from .render import background_desc
+    background_desc(tf)         # ValueError for anything but the two table classes
     return _sort_last("colour", tf, partial, cam, params, axis, group, combine, out)
 
 
@@ -240,7 +241,8 @@ def _sort_last(kind, finish, partial, cam, params, axis, group, combine, out):
             check(_lib.lib().vr_compositor_composite(h, src, int(axis), C.byref(cam), C.byref(params), dst, _stream_ptr()),
                   "vr_compositor_composite")
         elif kind == "colour":
-            desc = finish.desc()
+            from .render import background_desc
+            desc = background_desc(finish)
             check(_lib.lib().vr_compositor_composite_tf(h, src, int(axis), C.byref(cam), C.byref(params), C.byref(desc), dst,
                                                         _stream_ptr()), "vr_compositor_composite_tf")
         else:

@@ -507,16 +507,146 @@ def composite_over_tf(front, back, stream=None):
     return front
 
 
+def background_desc(tf):
+    """The vr_transfer_function the compositing calls read the background from: tf's own, or for a TransferFunction2D one
+    that carries its background and no table (they read only the background)."""
+    if isinstance(tf, TransferFunction):
+        return tf.desc()
+    if isinstance(tf, TransferFunction2D):
+        d = _lib.TransferFunctionDesc()
+        d.lut_dev = None
+        d.opacity_unit = tf.opacity_unit
+        d.background[:] = tf.background
+        return d
+    raise ValueError("tf must be a TransferFunction or a TransferFunction2D, not %s" % type(tf).__name__)
+
+
 def composite_finish_tf(partial, tf, out=None, stream=None):
-    """The frame (C + T background, 1 - T) of a colour partial; of tf only the background is used."""
+    """The frame (C + T background, 1 - T) of a colour partial; of tf (either table class) only the background is used."""
     _check_partial(partial, "partial")
-    if not isinstance(tf, TransferFunction):
-        raise ValueError("tf must be a TransferFunction, not %s" % type(tf).__name__)
+    desc = background_desc(tf)
     out = _out_or_new(out, partial.shape, partial.device)
-    desc = tf.desc()
     check(_lib.lib().vr_composite_finish_tf(_ptr(partial), C.byref(desc), _ptr(out), partial.numel() // 4, _stream_ptr(stream)),
           "vr_composite_finish_tf")
     return out
+
+
+# ---- two-dimensional transfer functions (vr_raycast_tf2d; the rule is in vrhip.h) --------------------------------------
+def tf2d_separable_table(lut1d, weight_by_row):
+    """The (rows, 256, 4) float32 table whose row j is the 1-D table with its alpha scaled by w[j]: rgb[j][k] =
+    lut1d[k].rgb, a[j][k] = float32(float64(lut1d[k].a) * float64(w[j])), w in [0, 1]
+    (vrhip::transfer_function2d_separable in include/vrhip/TransferFunction.hpp is the same rule)."""
+    lut = np.asarray(lut1d, np.float32)
+    w = np.asarray(weight_by_row, np.float64)
+    if lut.shape != (256, 4):
+        raise ValueError("lut1d must be 256 x (r, g, b, a), not %s" % (tuple(lut.shape),))
+    if w.ndim != 1 or not 2 <= w.shape[0] <= _lib.TF2D_MAX_ROWS:
+        raise ValueError("weight_by_row must hold 2..%d weights" % _lib.TF2D_MAX_ROWS)
+    if not np.all(np.isfinite(w)) or w.min() < 0.0 or w.max() > 1.0:
+        raise ValueError("weights must lie in [0, 1]")
+    out = np.empty((w.shape[0], 256, 4), np.float32)
+    out[:, :, :3] = lut[None, :, :3]
+    out[:, :, 3] = (lut[None, :, 3].astype(np.float64) * w[:, None]).astype(np.float32)
+    return out
+
+
+class TransferFunction2D:
+    """A table indexed by value and gradient magnitude for raycast_tf2d & co. (vr_transfer_function2d): `lut` the
+    (rows, 256, 4) float32 table of (r, g, b, a) in [0, 1], 2 <= rows <= 256; entry [j][k] for the scalar k / 255 and the
+    row coordinate y = |g| * grad_scale = j.  The default grad_scale, 127.5 * (rows - 1) / 110, spreads the rows over the
+    whole gradient range (with 111 rows: the row axis of histogram2d).  The column summary the skip grid needs is built
+    here and kept (`columns`)."""
+
+    def __init__(self, lut, grad_scale=None, opacity_unit=0.0, background=(1.0, 1.0, 1.0), device="cuda"):
+        if isinstance(lut, torch.Tensor):
+            device = lut.device if lut.is_cuda else device
+            host = lut.detach().to("cpu", torch.float32).numpy()
+        else:
+            host = np.asarray(lut, np.float32)
+        if host.ndim != 3 or host.shape[1:] != (256, 4) or not 2 <= host.shape[0] <= _lib.TF2D_MAX_ROWS:
+            raise ValueError("lut must be rows x 256 x (r, g, b, a) with 2 <= rows <= %d, not %s"
+                             % (_lib.TF2D_MAX_ROWS, tuple(host.shape)))
+        if not np.all(np.isfinite(host)) or host.min() < 0.0 or host.max() > 1.0:
+            raise ValueError("lut values must lie in [0, 1]")
+        self.rows = int(host.shape[0])
+        self.grad_scale = 127.5 * (self.rows - 1) / 110.0 if grad_scale is None else float(grad_scale)
+        if not math.isfinite(self.grad_scale) or self.grad_scale <= 0.0:
+            raise ValueError("grad_scale must be finite and > 0, not %r" % grad_scale)
+        if np.float32(self.grad_scale) == 0.0 or not np.isfinite(np.float32(self.grad_scale)):
+            raise ValueError("grad_scale must be finite and > 0 as float32, not %r" % grad_scale)
+        self.opacity_unit = float(opacity_unit)
+        if not math.isfinite(self.opacity_unit) or self.opacity_unit < 0.0:
+            raise ValueError("opacity_unit must be finite and >= 0, not %r" % opacity_unit)
+        self.background = tuple(float(v) for v in background)
+        if len(self.background) != 3 or not all(math.isfinite(v) for v in self.background):
+            raise ValueError("background must be three finite values")
+        self.lut = torch.from_numpy(np.ascontiguousarray(host)).to(device)
+        if self.lut.is_cuda:
+            self.columns = torch.empty(256, dtype=torch.int16, device=self.lut.device)
+            check(_lib.lib().vr_tf2d_columns_build(_ptr(self.lut), self.rows, _ptr(self.columns), _stream_ptr()),
+                  "vr_tf2d_columns_build")
+        else:
+            # a host table (the CPU path of composite_sort_last_tf reads only the background): the same summary in
+            # NumPy; host pointers never reach the kernel, and the frame calls refuse such a table (_check_tf2d)
+            opaque = (host[:, :, 3] != 0.0).any(0)
+            first = np.where(opaque, np.arange(256), 256)
+            self.columns = torch.from_numpy(np.minimum.accumulate(first[::-1])[::-1].astype(np.int16))
+
+    @classmethod
+    def from_separable(cls, lut1d, weight_by_row, grad_scale=None, opacity_unit=0.0, background=(1.0, 1.0, 1.0), device="cuda"):
+        """The table tf2d_separable_table(lut1d, weight_by_row) builds: the 1-D table's colours in every row, its alpha
+        scaled by the row's weight."""
+        if isinstance(lut1d, torch.Tensor):
+            lut1d = lut1d.detach().cpu().numpy()
+        return cls(tf2d_separable_table(lut1d, weight_by_row), grad_scale, opacity_unit, background, device)
+
+    def desc(self):
+        d = _lib.TransferFunction2DDesc()
+        d.lut_dev = self.lut.data_ptr()
+        d.columns_dev = self.columns.data_ptr()
+        d.rows = self.rows
+        d.grad_scale = self.grad_scale
+        d.opacity_unit = self.opacity_unit
+        d.background[:] = self.background
+        return d
+
+
+def _check_tf2d(tf, device):
+    if not isinstance(tf, TransferFunction2D):
+        raise ValueError("tf must be a TransferFunction2D, not %s" % type(tf).__name__)
+    _check_buf(tf.lut, "tf.lut", torch.float32, tf.rows * 256 * 4, device)
+    _check_buf(tf.columns, "tf.columns", torch.int16, 256, device)
+
+
+def _tf2d_frame(fn, src, cam, params, tf, shading, out, stream):
+    return _frame(fn, src, cam, params, [(_check_tf2d, tf), (_check_shading_or_none, shading)], out, stream)
+
+
+def raycast_tf2d(volume, dims, cam, params, tf, shading=None, out=None, stream=None):
+    """raycast_tf's march with the two-dimensional table `tf` (vr_raycast_tf2d): every sample is looked up by its value
+    and the magnitude of its lattice gradient; with a Shading the colour is lit as raycast_tf_shaded lights it.
+    params.mode must be RENDER_SHADED, lit or not; a slab holds two halo layers (slab_params(..., halo=2)).  Returns
+    float32 CUDA [H][W][4]."""
+    return _tf2d_frame("vr_raycast_tf2d", _dense_source(volume, dims), cam, params, tf, shading, out, stream)
+
+
+def raycast_pool_tf2d(pool, table, brick_dims, grid, cam, params, tf, shading=None, out=None, stream=None):
+    """raycast_tf2d of the virtual volume of a pool (vr_raycast_pool_tf2d): bit-identical to raycast_tf2d of that volume
+    assembled densely.  Restrictions and skip grids as raycast_pool."""
+    return _tf2d_frame("vr_raycast_pool_tf2d", _pool_source(pool, table, brick_dims, grid), cam, params, tf, shading, out, stream)
+
+
+def raycast_tf2d_partial(volume, dims, cam, params, tf, shading=None, out=None, stream=None):
+    """The colour partial (C.r, C.g, C.b, T) of raycast_tf2d for sort-last compositing (vr_raycast_tf2d_partial); it
+    goes through composite_over_tf / composite_finish_tf and distributed.composite_sort_last_tf unchanged."""
+    return _tf2d_frame("vr_raycast_tf2d_partial", _dense_source(volume, dims), cam, params, tf, shading, out, stream)
+
+
+def raycast_pool_tf2d_partial(pool, table, brick_dims, grid, cam, params, tf, shading=None, out=None, stream=None):
+    """raycast_tf2d_partial of the virtual volume of a pool (vr_raycast_pool_tf2d_partial): bit-identical to the dense
+    partial of that volume assembled densely."""
+    return _tf2d_frame("vr_raycast_pool_tf2d_partial", _pool_source(pool, table, brick_dims, grid), cam, params, tf, shading,
+                       out, stream)
 
 
 # ---- intensity projections (vr_raycast_projection and the combine calls; the rule is in vrhip.h) ----------------------

@@ -8,14 +8,15 @@ import numpy as np
 
 from . import _lib
 from .render import (POOL_ENTRY, assemble_bricks, build_skip_grid_pool, default_camera, default_params, lod_pool_layout,
-                     raycast, raycast_pool, raycast_pool_projection, raycast_pool_tf, raycast_pool_tf_shaded, raycast_projection,
-                     raycast_tf, raycast_tf_shaded, reslice, select_lod, use_skip_grid)
+                     raycast, raycast_pool, raycast_pool_projection, raycast_pool_tf, raycast_pool_tf2d, raycast_pool_tf_shaded,
+                     raycast_projection, raycast_tf, raycast_tf2d, raycast_tf_shaded, reslice, select_lod, use_skip_grid,
+                     TransferFunction2D)
 
 KEYS = ("UP", "DOWN", "LEFT", "RIGHT", "ENTER", "0", "1", "ESCAPE")
 _f = np.float32
 
-_DENSE_FRAMES = (raycast, raycast_tf, raycast_tf_shaded, raycast_projection)
-_POOL_FRAMES = (raycast_pool, raycast_pool_tf, raycast_pool_tf_shaded, raycast_pool_projection)
+_DENSE_FRAMES = (raycast, raycast_tf, raycast_tf_shaded, raycast_projection, raycast_tf2d)
+_POOL_FRAMES = (raycast_pool, raycast_pool_tf, raycast_pool_tf_shaded, raycast_pool_projection, raycast_pool_tf2d)
 
 
 def _style(mode, tf, shading, projection):
@@ -27,6 +28,10 @@ def _style(mode, tf, shading, projection):
         if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_PROJECTION):
             raise ValueError("a projection is drawn in RENDER_PROJECTION mode, not mode %r" % (mode,))
         return _lib.RENDER_PROJECTION, 3, (projection,)
+    if isinstance(tf, TransferFunction2D):       # RENDER_SHADED lit or not: its taps reach two voxels (select_lod)
+        if mode not in (_lib.RENDER_COMPOSITE, _lib.RENDER_SHADED):
+            raise ValueError("a two-dimensional transfer function is drawn in RENDER_SHADED mode, not mode %r" % (mode,))
+        return _lib.RENDER_SHADED, 4, (tf, shading)
     if shading is not None:
         if tf is None:
             raise ValueError("shading requires a transfer function (tf=)")
@@ -102,7 +107,8 @@ class HeadlessViewer:
              projection=None):
         """One frame of `volume`: raycast, or raycast_tf through the TransferFunction `tf` (composite mode only).
         shading: a Shading (requires tf): the frame is drawn with raycast_tf_shaded in RENDER_SHADED mode.
-        projection: a Projection (neither tf nor shading): drawn with raycast_projection in RENDER_PROJECTION mode."""
+        projection: a Projection (neither tf nor shading): drawn with raycast_projection in RENDER_PROJECTION mode.
+        tf may be a TransferFunction2D, with or without shading: drawn with raycast_tf2d in RENDER_SHADED mode."""
         mode, call, extra = _style(mode, tf, shading, projection)
         P = default_params(self.width, self.height, brick_dims, mode, float(self.currIsoVal) / 255.0)
         return _DENSE_FRAMES[call](volume, dims, self.camera(), P, *extra, out)
@@ -135,7 +141,8 @@ class HeadlessViewer:
         only when a frame needs more.  skip_cell > 0: a skip grid of that cell size is built from the pool for the frame.
         Power-of-two brick extents only.  tf: a TransferFunction, drawn with raycast_pool_tf; shading (requires tf): a
         Shading, drawn with raycast_pool_tf_shaded in RENDER_SHADED mode (select_lod included); projection (neither tf nor
-        shading): a Projection, drawn with raycast_pool_projection in RENDER_PROJECTION mode.  Returns (frame, cuts)."""
+        shading): a Projection, drawn with raycast_pool_projection in RENDER_PROJECTION mode.  A TransferFunction2D as tf, with
+        or without shading: raycast_pool_tf2d in RENDER_SHADED mode (select_lod included).  Returns (frame, cuts)."""
         import torch
         mode, call, extra = _style(mode, tf, shading, projection)
         bd = tuple(int(q) for q in bset.dims)
