@@ -462,6 +462,13 @@ __device__ __forceinline__ bool skip_block(const SkipBlocks &sk, int brick, int 
     return sk.flag && d > sk.Dm2 && (sk.flag[(int64_t)brick * sk.nBlk + (node >> (10 + d - sk.Dm2))] & 2u) != 0u;
 }
 
+// 1: k_fill16 fetches the skip flags of all its chunks in one batch in the prologue and walks its live chunks two loads
+// deep, with no conditional memory operation in the loop.  0: the loop as it was (a flag load and a drained memory
+// counter per chunk), for a trace of the old behaviour.
+#ifndef VR_FLAGS_BATCHED
+#define VR_FLAGS_BATCHED 1
+#endif
+
 __device__ inline int phys_buf(const Ctrl &c, int role) { return role == 0 ? c.ra : c.rb; }
 
 // rootMin/rootMax: the pyramid's (min, max) of each brick's root, or null.  A brick whose voxels are
@@ -1071,6 +1078,7 @@ __device__ __forceinline__ void leaf_pair_encode(uint32_t tword, int tsel, uint3
 }
 
 #define FILL_ITERS 8        // chunks of 4096 nodes per workgroup of k_fill16 (large levels)
+static_assert(FILL_ITERS < 32, "k_fill16 keeps a workgroup's chunks as the bits of a 32-bit mask and the lanes of a wave");
 template <bool STORE>     // false (the leaf level of a leafless build): errors only -- k_prune_emit12 recomputes codes and reconstruction
 __global__ void __launch_bounds__(256)
 k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, uint8_t *__restrict__ codes, int64_t heapStride,
@@ -1082,7 +1090,18 @@ k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, ui
     // spent a third of the launch being dispatched and reading the control block (a level-D fill in which every wave
     // skipped took 0.94 ms).
     __shared__ unsigned long long shm[4], shp[4];
-    const int brick = blockIdx.y;
+    const int brick = blockIdx.y, lane = threadIdx.x & 63;
+#if VR_FLAGS_BATCHED
+    // The flag bytes of all my wave's chunks in one batch (lane j: chunk j of the workgroup), in flight beside the
+    // control block: at level D-2 bit 0 of my own block's byte (the pyramid's), below it bit 1 of the block above the
+    // chunk, which its own wave wrote at level D-2 and nobody changes after that level.  A flag load in front of
+    // every chunk's prefetch was a dependent round trip per chunk.
+    uint32_t flagByte = 0;
+    if (sk.flag && d >= sk.Dm2) {
+        const uint32_t nch = (uint32_t)(((size_t)1 << d) >> 12), cj = blockIdx.x * (uint32_t)iters + (uint32_t)lane;
+        if (lane < iters && cj < nch) flagByte = sk.flag[(int64_t)brick * sk.nBlk + ((cj * 4u + (threadIdx.x >> 6)) >> (d - sk.Dm2))];
+    }
+#endif
     // everything the wave needs from the brick's control block is fetched in ONE scalar round trip, before the
     // first branch (field by field behind branches it was seven dependent ones in front of the data loads)
     Ctrl &c = ctrls[brick];
@@ -1107,34 +1126,22 @@ k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, ui
     uint32_t chunk = blockIdx.x * (uint32_t)iters;
     const uint32_t chunkEnd = chunk + (uint32_t)iters < nchunk ? chunk + (uint32_t)iters : nchunk;
     unsigned long long accM = 0, accP = 0;
-    // my wave's 1024 nodes inside a skipped block (SkipBlocks): no error, nothing to load, nothing anybody will read
-    bool skippedN = skip_block(sk, brick, d, (chunk * 4u + (uint32_t)w) << 10);
-    uint4 tvN = make_uint4(0, 0, 0, 0);
-    uint2 pvN = make_uint2(0, 0);
-    if (!skippedN) { const size_t i0 = ((size_t)chunk * 256u + threadIdx.x) * 16u; tvN = ld16(T + i0); pvN = ld8(P + (i0 >> 1)); }
-    for (; chunk < chunkEnd; ++chunk) {
-    const size_t i0 = ((size_t)chunk * 256u + threadIdx.x) * 16u;
-    const bool skipped = skippedN;
-    const uint4 tv = tvN;
-    const uint2 pv = pvN;
-    if (chunk + 1 < chunkEnd) {
-        skippedN = skip_block(sk, brick, d, ((chunk + 1u) * 4u + (uint32_t)w) << 10);
-        tvN = make_uint4(0, 0, 0, 0); pvN = make_uint2(0, 0);
-        if (!skippedN) { const size_t i1 = i0 + 4096u; tvN = ld16(T + i1); pvN = ld8(P + (i1 >> 1)); }
-    }
+#if VR_FLAGS_BATCHED
+    const uint32_t skipMask = d > sk.Dm2 ? (uint32_t)__ballot((flagByte & 2u) != 0u) : 0u;
+    const uint32_t constMask = d == sk.Dm2 ? (uint32_t)__ballot((flagByte & 1u) != 0u) : 0u;
+#endif
+    // One chunk of my wave (1024 nodes, 16 per lane): codes and reconstruction words of the lane, the wave's err^2 sums
+    // at the three distances, and whether any truth differs from its parent's reconstruction.
+    const auto eval = [&](const uint4 tv, const uint2 pv, const bool skipped, uint32_t &cpk, uint32_t (&rw)[4], uint32_t &s0,
+                          uint32_t &sm, uint32_t &sp) -> bool {
     const uint32_t tw[4] = {tv.x, tv.y, tv.z, tv.w}, pw[2] = {pv.x, pv.y};
-    uint32_t e0 = 0, em = 0, ep = 0, wa = 0, wb = 0, rw[4] = {tw[0], tw[1], tw[2], tw[3]}, rprev = 0;
+    uint32_t e0 = 0, em = 0, ep = 0, wa = 0, wb = 0, rprev = 0;
+    rw[0] = tw[0]; rw[1] = tw[1]; rw[2] = tw[2]; rw[3] = tw[3];
     // a wave whose 1024 truths all equal their parents' reconstruction (constant regions) has nothing to decide:
     // every code is "keep", the reconstruction is the truth, the error 0 at any distance (pd = 0 in encodeNode)
     const uint32_t differs = (tw[0] ^ __builtin_amdgcn_perm(0, pw[0], 0x01010000u)) | (tw[1] ^ __builtin_amdgcn_perm(0, pw[0], 0x03030202u)) |
                              (tw[2] ^ __builtin_amdgcn_perm(0, pw[1], 0x01010000u)) | (tw[3] ^ __builtin_amdgcn_perm(0, pw[1], 0x03030202u));
     const bool busy = !skipped && __ballot(differs != 0u) != 0ull;
-    // level D-2: my wave IS one 4096-leaf block's nodes of this level.  Constant block (k_pyramid12) and every truth
-    // equal to its parent's reconstruction: the two levels below need not be visited (SkipBlocks)
-    if (sk.flag && d == sk.Dm2 && !busy && (threadIdx.x & 63) == 0) {
-        uint8_t *f = sk.flag + (int64_t)brick * sk.nBlk + (size_t)chunk * 4 + w;
-        if (*f & 1u) *f = 3u;        // the same answer in every epoch of the level: it depends on truths and parents only
-    }
     const auto pair = [&](const int j) {                 // sibling pair j: nodes 2j, 2j+1, parent byte j
         const EncPair c = enc_pair(tw[j >> 1], j & 1, pw[j >> 2], j & 3);
         const vr_s16x2 x = enc_pair_x(c, d2), ax = pk_abs(x);
@@ -1174,27 +1181,111 @@ k_fill16(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, ui
 #pragma unroll
         for (int j = 0; j < 8; ++j) pair(j);
     // even nodes sit at bits 4j, odd ones at 16+4j: fold to 2 bits per node
-    const uint32_t cpk = ((wa | (wa >> 14)) & 0xFFFFu) | ((wb | (wb >> 14)) << 16);
-    if (!skipped && STORE) {
-        st4(Cd + (i0 >> 2), cpk);
-        st16(R + i0, make_uint4(rw[0], rw[1], rw[2], rw[3]));
-    }
+    cpk = ((wa | (wa >> 14)) & 0xFFFFu) | ((wb | (wb >> 14)) << 16);
     // per-lane sums are < 2^21, a wave's < 2^27: 32-bit DPP scans, the total in lane 63
-    unsigned long long s0 = 0, sm = 0, sp = 0;
+    s0 = sm = sp = 0;
     if (busy) {
         s0 = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_add_dpp(e0), 63);
         sm = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_add_dpp(em), 63);
         sp = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_add_dpp(ep), 63);
     }
-    if ((threadIdx.x & 63) == 0) {
-        blockErr[(int64_t)brick * nErrBlk + (size_t)chunk * 4 + w] = s0;   // 1024 nodes per wave
-        if (!STORE && needDF) {     // the central difference's sums per block too: a following epoch at distance -1 / +1 is these
-            blockErr[errPlane + (int64_t)brick * nErrBlk + (size_t)chunk * 4 + w] = sm;
-            blockErr[2 * errPlane + (int64_t)brick * nErrBlk + (size_t)chunk * 4 + w] = sp;
+    return busy;
+    };
+#if VR_FLAGS_BATCHED
+    // Chunk j of the workgroup is bit j and lane j.  The loop below visits my wave's live chunks only (a skipped one:
+    // no error, nothing to load, nothing anybody will read) and holds no conditional memory operation: two chunks of
+    // inputs are in flight, a chunk's registers are refilled as soon as it is evaluated and stored (with the refill in
+    // front of the stores the compiler loads into fresh registers and copies them at the back edge, behind a wait), and
+    // every wait on them counts the younger operations instead of draining the counter.  Where the live chunks run out
+    // the refill reads one line the wave has just read, for nobody.  The per-chunk sums wait in lane j's registers and
+    // the level D-2 flag bits in a mask; both are stored once, after the loop.
+    const uint32_t cnt = chunkEnd - chunk, liveMask = ((1u << cnt) - 1u) & ~skipMask;
+    uint32_t errS = 0, errM = 0, errP = 0, exactMask = 0;
+    if (liveMask) {
+        uint32_t m = liveMask;
+        const size_t idle = ((size_t)(chunk + (31u - (uint32_t)__builtin_clz(liveMask))) * 256u + (size_t)(w << 6)) * 16u;
+        int kA, kB;
+        uint4 tA, tB;
+        uint2 pA, pB;
+        const auto next = [&](int &k, uint4 &tv, uint2 &pv) {
+            k = m ? __builtin_ctz(m) : -1;
+            m &= m - 1u;
+            const size_t i = k >= 0 ? ((size_t)(chunk + (uint32_t)k) * 256u + threadIdx.x) * 16u : idle;
+            tv = ld16(T + i); pv = ld8(P + (i >> 1));
+        };
+        const auto phase = [&](int &k, uint4 &tv, uint2 &pv) {
+            const int kc = k;
+            const size_t i0 = ((size_t)(chunk + (uint32_t)kc) * 256u + threadIdx.x) * 16u;
+            uint32_t cpk, rw[4], s0, sm, sp;
+            const bool busy = eval(tv, pv, false, cpk, rw, s0, sm, sp);
+            if (STORE) {
+                st4(Cd + (i0 >> 2), cpk);
+                st16(R + i0, make_uint4(rw[0], rw[1], rw[2], rw[3]));
+            }
+            next(k, tv, pv);
+            if (lane == kc) { errS = s0; errM = sm; errP = sp; }
+            accM += sm; accP += sp;
+            if (!busy) exactMask |= 1u << kc;
+        };
+        next(kA, tA, pA);
+        next(kB, tB, pB);
+        phase(kA, tA, pA);
+        // (the loop's head sits behind the first evaluation, so that both ways into it have A's refill and stores
+        // behind B's loads)
+        while (kB >= 0) {
+            phase(kB, tB, pB);
+            if (kA < 0) break;
+            phase(kA, tA, pA);
         }
     }
-    accM += sm; accP += sp;
+    if ((uint32_t)lane < cnt) {
+        const int64_t at = (int64_t)brick * nErrBlk + (size_t)(chunk + (uint32_t)lane) * 4 + w;     // 1024 nodes per wave
+        blockErr[at] = errS;
+        if (!STORE && needDF) {     // the central difference's sums per block too: a following epoch at distance -1 / +1 is these
+            blockErr[errPlane + at] = errM;
+            blockErr[2 * errPlane + at] = errP;
+        }
+        // level D-2: my wave IS one 4096-leaf block's nodes of this level.  Constant block (k_pyramid12) and every truth
+        // equal to its parent's reconstruction: the two levels below need not be visited (SkipBlocks).  The same answer
+        // in every epoch of the level: it depends on truths and parents only.
+        if (((exactMask & constMask) >> lane) & 1u) sk.flag[(int64_t)brick * sk.nBlk + (size_t)(chunk + (uint32_t)lane) * 4 + w] = 3u;
     }
+#else
+    // my wave's 1024 nodes inside a skipped block (SkipBlocks): no error, nothing to load, nothing anybody will read
+    bool skippedN = skip_block(sk, brick, d, (chunk * 4u + (uint32_t)w) << 10);
+    uint4 tvN = make_uint4(0, 0, 0, 0);
+    uint2 pvN = make_uint2(0, 0);
+    if (!skippedN) { const size_t i0 = ((size_t)chunk * 256u + threadIdx.x) * 16u; tvN = ld16(T + i0); pvN = ld8(P + (i0 >> 1)); }
+    for (; chunk < chunkEnd; ++chunk) {
+        const size_t i0 = ((size_t)chunk * 256u + threadIdx.x) * 16u;
+        const bool skipped = skippedN;
+        const uint4 tv = tvN;
+        const uint2 pv = pvN;
+        if (chunk + 1 < chunkEnd) {
+            skippedN = skip_block(sk, brick, d, ((chunk + 1u) * 4u + (uint32_t)w) << 10);
+            tvN = make_uint4(0, 0, 0, 0); pvN = make_uint2(0, 0);
+            if (!skippedN) { const size_t i1 = i0 + 4096u; tvN = ld16(T + i1); pvN = ld8(P + (i1 >> 1)); }
+        }
+        uint32_t cpk, rw[4], s0, sm, sp;
+        const bool busy = eval(tv, pv, skipped, cpk, rw, s0, sm, sp);
+        if (sk.flag && d == sk.Dm2 && !busy && lane == 0) {      // (level D-2, see above)
+            uint8_t *f = sk.flag + (int64_t)brick * sk.nBlk + (size_t)chunk * 4 + w;
+            if (*f & 1u) *f = 3u;
+        }
+        if (!skipped && STORE) {
+            st4(Cd + (i0 >> 2), cpk);
+            st16(R + i0, make_uint4(rw[0], rw[1], rw[2], rw[3]));
+        }
+        if (lane == 0) {
+            blockErr[(int64_t)brick * nErrBlk + (size_t)chunk * 4 + w] = s0;   // 1024 nodes per wave
+            if (!STORE && needDF) {
+                blockErr[errPlane + (int64_t)brick * nErrBlk + (size_t)chunk * 4 + w] = sm;
+                blockErr[2 * errPlane + (int64_t)brick * nErrBlk + (size_t)chunk * 4 + w] = sp;
+            }
+        }
+        accM += sm; accP += sp;
+    }
+#endif
     if ((threadIdx.x & 63) == 0) { shm[w] = accM; shp[w] = accP; }
     __syncthreads();
     if (threadIdx.x == 0) {
