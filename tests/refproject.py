@@ -63,14 +63,24 @@ def finish(v, n, op, window=(0.0, 1.0), background=(0.0, 0.0, 0.0), lut=None):
 
 
 def project_checked(vol, cam, W, H, step, op, window=(0.0, 1.0), background=(0.0, 0.0, 0.0), lut=None, max_samples=300,
-                    box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0)):
+                    box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0), near=0.1, far=100.0, rows=None):
     """The frame and the partial on the camera cam = (pos, front, up, fov_deg), with refmarch.march_checked's per-pixel
     slack of the partial mode (the same positions: cube entry, near / far, inside, the clip box -- the geometric
     decisions; a projection has no exit margin).  Returns (img, v, n, slack); slack > 1: no decision can flip in
-    float32."""
+    float32.  near / far are the camera's planes, `rows` the frame rows to march (default all)."""
     pos, front, up, fov = cam
-    covered, vuv, g = rays(pos, front, up, fov, W, H)
+    covered, vuv, g = rays(pos, front, up, fov, W, H, rows, near, far)
     v, n = project(vol, covered, vuv, g, step, op, max_samples, box_min, box_max)
     _, slack, _ = march_checked(vol, pos, front, up, fov, W, H, step, mode=2, max_samples=max_samples, box_min=box_min,
-                                box_max=box_max)
+                                box_max=box_max, near=near, far=far, rows=rows)
     return finish(v, n, op, window, background, lut), v, n, slack.reshape(covered.shape)
+
+
+def owned_samples_checked(vol, cam, W, H, step, max_samples=300, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0), near=0.1,
+                          far=100.0, rows=None):
+    """(n, slack): the number of samples each ray owns -- inside the cube and in [box_min, box_max), among its first
+    max_samples steps; 0 where the cube does not cover the pixel -- and project_checked's slack.  Every marcher that has
+    no early exit takes exactly these samples, whatever it does with them."""
+    _, _, n, slack = project_checked(vol, cam, W, H, step, MAX, max_samples=max_samples, box_min=box_min, box_max=box_max,
+                                     near=near, far=far, rows=rows)
+    return n, slack

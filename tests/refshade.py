@@ -110,16 +110,18 @@ GRAD_SMALL = 1e-3
 
 
 def march_shaded_checked(vol, cam, W, H, step, lut, shading, opacity_unit=0.0, background=(1.0, 1.0, 1.0),
-                         max_samples=300, early_exit=True, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0)):
+                         max_samples=300, early_exit=True, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0), near=0.1,
+                         far=100.0, rows=None):
     """march_shaded on the camera cam = (pos, front, up, fov_deg) with a per-pixel slack: refmarch.march_checked's for
     the ray's geometric decisions, |T - 0.01| / EXIT_MARGIN for the early exit, |m - grad_min| / LIT_MARGIN for the
-    lit / unlit choice and m / GRAD_SMALL for the normal.  slack > 1: the pixel is decidable in float32."""
+    lit / unlit choice and m / GRAD_SMALL for the normal.  slack > 1: the pixel is decidable in float32.  near / far
+    are the camera's planes, `rows` the frame rows to march (default all)."""
     pos, front, up, fov = cam
-    covered, vuv, g = rays(pos, front, up, fov, W, H)
+    covered, vuv, g = rays(pos, front, up, fov, W, H, rows, near, far)
     img, exit_m, lit_m, gsize = march_shaded(vol, covered, vuv, g, step, lut, shading, opacity_unit, background,
                                              max_samples, early_exit, box_min, box_max)
     _, slack, _ = march_checked(vol, pos, front, up, fov, W, H, step, mode=2, max_samples=max_samples, box_min=box_min,
-                                box_max=box_max)
+                                box_max=box_max, near=near, far=far, rows=rows)
     slack = np.minimum(slack, exit_m / EXIT_MARGIN)
     slack = np.minimum(slack, lit_m / LIT_MARGIN)
     slack = np.minimum(slack, gsize / GRAD_SMALL)

@@ -70,14 +70,15 @@ EXIT_MARGIN = 1e-4
 
 
 def march_tf_checked(vol, cam, W, H, step, lut, opacity_unit=0.0, background=(1.0, 1.0, 1.0), max_samples=300,
-                     early_exit=True, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0)):
+                     early_exit=True, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0), near=0.1, far=100.0, rows=None):
     """march_tf on the camera cam = (pos, front, up, fov_deg) with a per-pixel slack: refmarch.march_checked's for the
     ray's geometric decisions (cube entry, near / far, inside, the clip box: its partial mode marches the same
-    positions), and |T - 0.01| / EXIT_MARGIN for the early exit.  slack > 1: no decision can flip in float32."""
+    positions), and |T - 0.01| / EXIT_MARGIN for the early exit.  slack > 1: no decision can flip in float32.
+    near / far are the camera's planes, `rows` the frame rows to march (default all)."""
     pos, front, up, fov = cam
-    covered, vuv, g = rays(pos, front, up, fov, W, H)
+    covered, vuv, g = rays(pos, front, up, fov, W, H, rows, near, far)
     img, margin = march_tf(vol, covered, vuv, g, step, lut, opacity_unit, background, max_samples, early_exit, box_min,
                            box_max)
     _, slack, _ = march_checked(vol, pos, front, up, fov, W, H, step, mode=2, max_samples=max_samples, box_min=box_min,
-                                box_max=box_max)
+                                box_max=box_max, near=near, far=far, rows=rows)
     return img, np.minimum(slack, margin / EXIT_MARGIN)

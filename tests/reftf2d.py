@@ -86,16 +86,18 @@ def march_tf2d(vol, covered, vuv, g, step, lut, grad_scale, shading=None, opacit
 
 
 def march_tf2d_checked(vol, cam, W, H, step, lut, grad_scale, shading=None, opacity_unit=0.0, background=(1.0, 1.0, 1.0),
-                       max_samples=300, early_exit=True, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0)):
+                       max_samples=300, early_exit=True, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0), near=0.1, far=100.0,
+                       rows=None):
     """march_tf2d on the camera cam = (pos, front, up, fov_deg) with refshade's per-pixel slack: refmarch.march_checked's
     for the ray's geometric decisions, |T - 0.01| / EXIT_MARGIN for the early exit and, lit, |m - grad_min| / LIT_MARGIN
-    and m / GRAD_SMALL.  The row lookup adds no decision: e is continuous in y, also across rows and at the clamp."""
+    and m / GRAD_SMALL.  The row lookup adds no decision: e is continuous in y, also across rows and at the clamp.
+    near / far are the camera's planes, `rows` the frame rows to march (default all; not the table's rows)."""
     pos, front, up, fov = cam
-    covered, vuv, g = rays(pos, front, up, fov, W, H)
+    covered, vuv, g = rays(pos, front, up, fov, W, H, rows, near, far)
     img, exit_m, lit_m, gsize = march_tf2d(vol, covered, vuv, g, step, lut, grad_scale, shading, opacity_unit, background,
                                            max_samples, early_exit, box_min, box_max)
     _, slack, _ = march_checked(vol, pos, front, up, fov, W, H, step, mode=2, max_samples=max_samples, box_min=box_min,
-                                box_max=box_max)
+                                box_max=box_max, near=near, far=far, rows=rows)
     slack = np.minimum(slack, exit_m / EXIT_MARGIN)
     slack = np.minimum(slack, lit_m / LIT_MARGIN)
     slack = np.minimum(slack, gsize / GRAD_SMALL)
