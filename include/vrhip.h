@@ -264,6 +264,71 @@ vr_status vr_brickset_open(vr_brickset **out, const char *path);
  * a shifted range stream: nothing to match); other variants forward to vr_brickset_open. */
 vr_status vr_brickset_open_variant(vr_brickset **out, const char *path, int32_t variant);
 
+/* ---- compressed brick-set archives: stored streams installed on the GPU, and a file of one set -------------
+ * vr_brickset_set_tree parses one stream on the host and installs it with blocking copies; the calls below install
+ * many streams at once and rebuild the decode index on the GPU, in parallel, from a small seek table per stream.
+ *
+ * The block table of a stream, for a brick of depth D = origTreeDepth: Dc = max(D - 12, 0); a block is a depth-Dc
+ * node (a 4096-leaf box where D >= 12, the whole brick otherwise); nBlk = 2^Dc.
+ *   block_off[nBlk]      uint32: the token index of the block root's own token, 0xFFFFFFFF where an ancestor of
+ *                        the root was pruned (the block is dead);
+ *   top_val[2 nBlk]      uint8, a 1-based heap over depths 0 .. Dc: entry (1 << j) + path is the decoded scalar of
+ *                        the depth-j node `path` (the root's is distance_map[0]; every token is applied with
+ *                        distance_map[j] as the decoder does), or of its pruned ancestor where it does not exist.
+ *                        Entry 0 is unused.
+ * vr_stream_block_table makes the table of a stream on the host, with one pass over its tokens; it needs no device.
+ * VR_ERR_FORMAT for a stream the grammar does not produce.
+ *
+ * vr_brickset_set_trees installs descs[i] as brick bricks[i] (no brick twice), for count bricks at once, into a
+ * fresh set or one that holds installed streams only (a built set: VR_ERR_STATE); VR_VARIANT_MIDRANGE sets and sets
+ * with 64-bit token offsets are VR_ERR_UNSUPPORTED.  Per stream, as for vr_brickset_set_tree: num_active below 2^32
+ * (else VR_ERR_UNSUPPORTED), map_len >= maxTreeDepth + 1 (else VR_ERR_INVALID), tree_bytes >= (num_active + 3) / 4
+ * bytes that fit the set's stream slots (else VR_ERR_FORMAT).  A desc with both table pointers null gets its table
+ * from vr_stream_block_table here (slow: a host pass over the stream); one with one of them null is VR_ERR_INVALID.
+ * A table is checked on the host before anything is enqueued (every live offset below num_active, live offsets
+ * strictly increasing, block 0 at token Dc when live): VR_ERR_FORMAT, the set unchanged.  Then everything is enqueued
+ * on `stream`: the copies, the reset of the named bricks' index entries, k_index_from_stream, which parses every token
+ * of every named stream exactly once, and one synchronisation of `stream` at the end.  VR_OK, or VR_ERR_FORMAT if a
+ * named stream is not of the grammar or disagrees with its table's offsets: then EVERY brick named in the call is left
+ * "never installed" (bricks not named keep their state).  Wrong scalars in top_val are not detected: they give other
+ * voxel values, nothing worse.  No input makes the kernel read or write outside its buffers or run forever.
+ * The host pointers are read before the call returns.  No host copy of the streams is kept: decodes at cuts above the
+ * index depth take their scalars from a heap the kernel wrote, without touching the host.  vr_brickset_info,
+ * _get_tree, _get_distance_map and _save return the installed bytes and values; the rule about grown-branch distances
+ * other than 64 >> i is vr_brickset_set_tree's. */
+typedef struct vr_tree_desc {            /* host pointers */
+    const uint8_t *tree; int64_t tree_bytes; int64_t num_active;
+    const uint8_t *distance_map; int32_t map_len;
+    const uint32_t *block_off; const uint8_t *top_val;
+} vr_tree_desc;
+vr_status vr_stream_block_table(const int64_t dims[3], const uint8_t *tree_host, int64_t tree_bytes, int64_t num_active,
+                                const uint8_t *distance_map_host, int32_t map_len, uint32_t *block_off_out,
+                                uint8_t *top_val_out);
+vr_status vr_brickset_set_trees(vr_brickset *bs, int32_t count, const int32_t *bricks, const vr_tree_desc *descs,
+                                void *stream);
+
+/* The archive: one file holds one brick set (one timestep).  Little-endian; every section starts 16-byte aligned and
+ * is zero-padded to a multiple of 16 bytes, so a file read into one pinned buffer is installed from it as it lies.
+ *   header, 64 bytes     char magic[8] = "VRBSET\r\n"; uint32 version = 1; uint32 variant; int64 dims[3] (of a brick);
+ *                        int32 num_bricks, origTreeDepth, maxTreeDepth; uint32 0; int64 file_bytes
+ *   directory            num_bricks entries of 32 bytes: int64 offset of the brick's record from the start of the
+ *                        file (0: the brick is absent), int64 tree_bytes = (num_active + 3) / 4, int64 num_active,
+ *                        uint64 FNV-1a-64 of the record's bytes (padding included)
+ *   record of a brick    distance_map[maxTreeDepth + 1], top_val[2 nBlk], block_off[nBlk], tree[tree_bytes]
+ * vr_brickset_save_set writes a built set or a set of installed streams (VR_ERR_STATE for neither; VR_VARIANT_MIDRANGE:
+ * VR_ERR_UNSUPPORTED); bricks never installed are absent.  The tables are made on the host, on at most 16 threads.
+ * vr_brickset_open_set creates a set from a file (tolerance and max_epochs: vr_brickset_open's defaults) and installs
+ * it; vr_brickset_load_set / _load_set_memory install a file / a file's bytes in host memory (16-byte aligned, else
+ * VR_ERR_INVALID; pinned memory makes the copies asynchronous) into an existing set with vr_brickset_set_trees, every
+ * brick of the file in one call; bricks absent from the file keep their state.  VR_ERR_FORMAT with the set unchanged,
+ * before anything is enqueued: a wrong magic or version, a file_bytes that is not the size, geometry (variant, dims,
+ * num_bricks, depths) that does not match the set, an offset or length outside the file, a checksum mismatch, a
+ * table that fails vr_brickset_set_trees' host check.  VR_ERR_IO for a file that cannot be read or written. */
+vr_status vr_brickset_save_set(vr_brickset *bs, const char *path);
+vr_status vr_brickset_open_set(vr_brickset **out, const char *path, void *stream);
+vr_status vr_brickset_load_set(vr_brickset *bs, const char *path, void *stream);
+vr_status vr_brickset_load_set_memory(vr_brickset *bs, const void *blob_host, int64_t bytes, void *stream);
+
 /* ---- error helpers: measureMaxError / measureMeanError / queryError (R.cpp:386-411)
  * The reference dereferences the input it has already cleared (SURVEY C-7); here the
  * original volume is passed explicitly.  n = number of voxels.

@@ -12,7 +12,7 @@ __all__ = ["BrickSet", "VolumeKdtree", "MidRangeTree", "HashedKdtree", "VolumeRe
 
 def __getattr__(name):  # torch is imported lazily so that `import volumerenderer_amd` stays cheap
     if name in ("BrickSet", "VolumeKdtree", "MidRangeTree", "HashedKdtree", "measure_error", "query_error",
-                "measure_error_bricks", "BRICK_ERROR"):
+                "measure_error_bricks", "BRICK_ERROR", "stream_block_table"):
         from . import codec
         return getattr(codec, name)
     if name in ("VolumeReader", "UnitBrick", "raycast", "default_camera", "default_params", "composite_over",

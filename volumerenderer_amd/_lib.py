@@ -77,6 +77,12 @@ class SlicePlaneDesc(C.Structure):
                 ("global_dims", C.c_int64 * 3), ("vol_origin", C.c_int64 * 3)]
 
 
+class TreeDesc(C.Structure):
+    """vr_tree_desc (56 bytes): host pointers."""
+    _fields_ = [("tree", C.c_void_p), ("tree_bytes", C.c_int64), ("num_active", C.c_int64), ("distance_map", C.c_void_p),
+                ("map_len", C.c_int32), ("block_off", C.c_void_p), ("top_val", C.c_void_p)]
+
+
 class PoolEntry(C.Structure):
     _fields_ = [("offset", C.c_int64), ("shift", C.c_uint8 * 3), ("pad", C.c_uint8 * 5)]
 
@@ -119,6 +125,12 @@ SIGNATURES = {
     "vr_raycast_pool": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),
     "vr_skip_grid_build_pool": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), _I32, _P, _P]),
     "vr_brickset_set_tree": (_I32, [_P, _I32, _P, _I64, _I64, _P, _I32]),
+    "vr_stream_block_table": (_I32, [C.POINTER(_I64), _P, _I64, _I64, _P, _I32, _P, _P]),
+    "vr_brickset_set_trees": (_I32, [_P, _I32, C.POINTER(_I32), C.POINTER(TreeDesc), _P]),
+    "vr_brickset_save_set": (_I32, [_P, C.c_char_p]),
+    "vr_brickset_open_set": (_I32, [C.POINTER(_P), C.c_char_p, _P]),
+    "vr_brickset_load_set": (_I32, [_P, C.c_char_p, _P]),
+    "vr_brickset_load_set_memory": (_I32, [_P, _P, _I64, _P]),
     "vr_brickset_save": (_I32, [_P, _I32, C.c_char_p]),
     "vr_brickset_open": (_I32, [C.POINTER(_P), C.c_char_p]),
     "vr_brickset_open_variant": (_I32, [C.POINTER(_P), C.c_char_p, _I32]),

@@ -216,6 +216,64 @@ class BrickSet:
         check(self._L.vr_brickset_set_tree(self._h, int(brick), t.ctypes.data, t.size, int(num_active_nodes),
                                            d.ctypes.data, d.size), "vr_brickset_set_tree")
 
+    def set_trees(self, bricks, trees, num_active, dmaps, tables=None, stream=None):
+        """Install many stored streams at once; the decode index is rebuilt on the GPU (vr_brickset_set_trees).
+        bricks: brick numbers; trees, num_active, dmaps: per brick the packed stream (uint8), its token count and its
+        distance map; tables: per brick (block_off, top_val) as stream_block_table returns them, or None to have them
+        made on the host (slow).  Synchronises `stream` once."""
+        n = len(bricks)
+        if not (len(trees) == n and len(num_active) == n and len(dmaps) == n and (tables is None or len(tables) == n)):
+            raise ValueError("set_trees: one tree, token count, map and table per brick")
+        keep = []
+        descs = (_lib.TreeDesc * n)()
+        for i in range(n):
+            t = np.ascontiguousarray(trees[i], np.uint8)
+            d = np.ascontiguousarray(dmaps[i], np.uint8)
+            keep += [t, d]
+            descs[i].tree, descs[i].tree_bytes, descs[i].num_active = t.ctypes.data, t.size, int(num_active[i])
+            descs[i].distance_map, descs[i].map_len = d.ctypes.data, d.size
+            if tables is not None and tables[i] is not None:
+                off = np.ascontiguousarray(tables[i][0], np.uint32)
+                top = np.ascontiguousarray(tables[i][1], np.uint8)
+                keep += [off, top]
+                descs[i].block_off, descs[i].top_val = off.ctypes.data, top.ctypes.data
+        b = np.ascontiguousarray(np.asarray(bricks).reshape(-1), dtype=np.int32)
+        check(self._L.vr_brickset_set_trees(self._h, n, b.ctypes.data_as(C.POINTER(C.c_int32)), descs, _stream_ptr(stream)),
+              "vr_brickset_set_trees")
+
+    def save_set(self, path):
+        """The whole set (one timestep) as one archive file (vr_brickset_save_set; layout in include/vrhip.h)."""
+        check(self._L.vr_brickset_save_set(self._h, os.fsencode(path)), "vr_brickset_save_set")
+
+    @classmethod
+    def open_set(cls, path, stream=None):
+        L = _lib.lib()
+        h = C.c_void_p()
+        check(L.vr_brickset_open_set(C.byref(h), os.fsencode(path), _stream_ptr(stream)), "vr_brickset_open_set")
+        with open(path, "rb") as f:
+            head = np.frombuffer(f.read(64), np.uint8)
+        dims = head[16:40].view("<i8")
+        return cls(int(head[40:44].view("<i4")[0]), tuple(int(v) for v in dims), _handle=h)
+
+    def load_set(self, source, nbytes=None, stream=None):
+        """The next timestep into this set: an archive file's path, or a uint8 host tensor / array that holds a file's
+        bytes (16-byte aligned; pinned memory makes the copies asynchronous; nbytes: the file's size if the buffer is
+        longer).  Synchronises `stream` once."""
+        if isinstance(source, (str, bytes, os.PathLike)):
+            check(self._L.vr_brickset_load_set(self._h, os.fsencode(source), _stream_ptr(stream)), "vr_brickset_load_set")
+            return self
+        if isinstance(source, torch.Tensor):
+            if source.is_cuda or source.dtype != torch.uint8 or not source.is_contiguous():
+                raise TypeError("load_set: a contiguous uint8 host tensor")
+            ptr, size = source.data_ptr(), source.numel()
+        else:
+            source = np.ascontiguousarray(source, np.uint8)
+            ptr, size = source.ctypes.data, source.size
+        size = size if nbytes is None else int(nbytes)
+        check(self._L.vr_brickset_load_set_memory(self._h, C.c_void_p(ptr), size, _stream_ptr(stream)),
+              "vr_brickset_load_set_memory")
+        return self
+
     def save(self, path, brick=0):
         check(self._L.vr_brickset_save(self._h, int(brick), os.fsencode(path)), "vr_brickset_save")
 
@@ -237,6 +295,21 @@ class BrickSet:
         ms = (C.c_float * 5)()
         check(self._L.vr_brickset_last_timings(self._h, ms), "last_timings")
         return dict(zip(("BUILD", "COMPRESS", "PRUNE", "CONVERT", "DECODE"), [float(v) for v in ms]))
+
+
+def stream_block_table(dims, tree, num_active, dmap):
+    """(block_off uint32[nBlk], top_val uint8[2 nBlk]) of one packed stream: the seek table vr_brickset_set_trees and
+    the archive take (vr_stream_block_table; host only, no device needed).  VrError(VR_ERR_FORMAT) for a stream the
+    grammar does not produce."""
+    d = (C.c_int64 * 3)(*[int(v) for v in dims])
+    depth = sum(int(v).bit_length() - 1 for v in dims)
+    n_blk = 1 << max(depth - 12, 0)
+    t = np.ascontiguousarray(tree, np.uint8)
+    m = np.ascontiguousarray(dmap, np.uint8)
+    off, top = np.empty(n_blk, np.uint32), np.empty(2 * n_blk, np.uint8)
+    check(_lib.lib().vr_stream_block_table(d, t.ctypes.data, t.size, int(num_active), m.ctypes.data, m.size,
+                                           off.ctypes.data, top.ctypes.data), "vr_stream_block_table")
+    return off, top
 
 
 def measure_error(decoded, original, stream=None):

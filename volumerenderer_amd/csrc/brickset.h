@@ -109,6 +109,12 @@ struct BrickSet {
     uint32_t *chainTab = nullptr; // 8 x 16384 entries: k_decode_quad's grown-branch tables, one per number of refining levels (0..7),
     bool chainTabReady = false;   // all written once (never rewritten: decodes of one set on several streams may share them)
     std::vector<std::vector<uint8_t>> hostTree; // foreign streams keep their bytes for progressive cuts
+    // vr_brickset_set_trees (kd_index.hip): a brick it installed keeps no host bytes (its hostTree entry is empty); its
+    // cuts above depth Ds come from idxTop.  All made by the first such call
+    uint8_t *idxTop = nullptr;    // B * 2 nIdx: 1-based heap of the decoded scalars of depths 0 .. Ds (host_plan.h "block tables")
+    uint32_t *instOff = nullptr;  // B * 2^Dc: the block tables' offsets, as installed
+    int32_t *instFlag = nullptr;  // B: a call's grammar flags, per named row
+    int32_t *instList = nullptr;  // B: a call's named bricks
     uint32_t *lut = nullptr;    // 2^K : local rank -> packed (dx | dy<<10 | dz<<20)
     bool foreignRange = false;   // a foreign MidRangeTree file also supplied the range stream
     uint32_t *spread = nullptr;  // rank bits of every x, y, z coordinate: rank(x,y,z) = spread[x] | spread[X+y] | spread[X+Y+z]
@@ -196,6 +202,17 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hi
 void free_lod_slots(BrickSet *bs);
 // error_table.hip: per-brick error of two buffers of B bricks x V bytes, added into out[0 .. B) (cleared by the caller)
 int brick_error_launch(const uint8_t *a, const uint8_t *b, int64_t B, int64_t V, vr_brick_error *out, hipStream_t st);
+// kd_index.hip: the index of installed streams, rebuilt on the device.  Each enqueues on st and returns 0 or -1.
+// resets the index entries of the n listed bricks (list null: of bricks 0 .. n-1) to "never installed"; onlyFlagged:
+// of those whose flag is set (flags null: of all of them), with their scalar heaps and control blocks' token counts
+int index_reset_launch(BrickSet *bs, const int32_t *listDev, int n, const int32_t *flagsDev, bool onlyFlagged, hipStream_t st);
+int index_from_stream_launch(BrickSet *bs, const int32_t *listDev, int n, int32_t *flagsDev, hipStream_t st);
+// out[brick][path] = idxTop[brick][(1 << cut) + (path >> (Ds - cut))] for the n listed bricks (list null: bricks
+// first .. first + n - 1 at `cut`; else each at cuts[brick])
+int cut_from_top_launch(BrickSet *bs, const int32_t *listDev, const int32_t *cutsDev, int first, int n, int cut, uint8_t *out,
+                        hipStream_t st);
+// does brick br take its cuts above depth Ds from idxTop (installed by vr_brickset_set_trees)?
+inline bool top_indexed(const BrickSet &b, int br) { return b.idxTop && ((size_t)br >= b.hostTree.size() || b.hostTree[(size_t)br].empty()); }
 int build_general_geometry(BrickSet *bs);   // srcIdx / ownerRank for general extents (0, -3 out of memory, -1 device error)
 
 } // namespace vr

@@ -209,6 +209,7 @@ vr_status vr_brickset_destroy(vr_brickset *h)
     free_stream2(b.mid);
     free_stream2(b.rng);
     hipFree(b.brickOff); hipFree(b.compactOverflow);
+    hipFree(b.idxTop); hipFree(b.instOff); hipFree(b.instFlag); hipFree(b.instList);
     hipFree(b.idxOff); hipFree(b.idxVal); hipFree(b.idxValCut); hipFree(b.fineIdx); hipFree(b.idxVal3); hipFree(b.boxUniform); hipFree(b.chainTab); hipFree(b.decTables); hipFree(b.lut); hipFree(b.spread); hipFree(b.srcIdx); hipFree(b.ownerRank); hipFree(b.ownerSurv); hipFree(b.rankVals);
     for (int i = 0; i < 8; ++i) if (b.ev[i]) hipEventDestroy(b.ev[i]);
     if (b.evFork) hipEventDestroy(b.evFork);
@@ -567,9 +568,19 @@ static vr_status decode_common(vr_brickset *h, int32_t cut_depth, uint8_t *out, 
     if (decode_stores_vectors(&b, cut, rangeStream) && misaligned16(out)) return VR_ERR_INVALID;
     if (cut < b.Ds && b.foreign) {
         // ancestor scalars at the cut depth, from the stream bytes kept at set_tree/open time
-        vr_status rc = sync_ctrl(b);
+        // bricks installed by vr_brickset_set_trees: from the heap their install wrote, on the stream, run by run
+        bool hostFill = false;
+        for (int br = 0; br < b.B;) {
+            if (!top_indexed(b, br)) { hostFill = true; ++br; continue; }
+            int e = br;
+            while (e < b.B && top_indexed(b, e)) ++e;
+            if (cut_from_top_launch(&b, nullptr, nullptr, br, e - br, cut, b.idxValCut, (hipStream_t)stream) != 0) return VR_ERR_NO_DEVICE;
+            br = e;
+        }
+        vr_status rc = hostFill ? sync_ctrl(b) : VR_OK;
         if (rc != VR_OK) return rc;
         for (int br = 0; br < b.B; ++br) {
+            if (top_indexed(b, br)) continue;
             std::vector<uint8_t> vals((size_t)b.nIdx, 0);
             if (br < (int)b.hostTree.size() && !b.hostTree[br].empty() &&
                 cut_values_from_stream(b.D, b.Ds, b.K, b.nIdx, b.hostTree[br].data(), (int64_t)b.hostCtrl[br].numActive,
@@ -598,10 +609,10 @@ vr_status vr_brickset_decode_range(vr_brickset *h, int32_t cut_depth, uint8_t *o
 // the launch of the two per-brick decodes (cuts checked); the caller's buffer is out or pool->pool
 static vr_status lod_decode(BrickSet &b, const int32_t *cuts, uint8_t *out, const PoolDest *pool, void *stream)
 {
-    bool above = false;
-    for (int br = 0; br < b.B; ++br) above = above || (cuts[br] >= 0 && cuts[br] < b.Ds);
     if (decode_lod_stores_vectors(&b, cuts, pool) && misaligned16(pool ? pool->pool : out)) return VR_ERR_INVALID;
-    if (above && b.foreign) {
+    bool hostFill = false;
+    for (int br = 0; br < b.B; ++br) hostFill = hostFill || (cuts[br] >= 0 && cuts[br] < b.Ds && !top_indexed(b, br));
+    if (hostFill && b.foreign) {
         vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
         if (rc != VR_OK) return rc;
     }
@@ -834,6 +845,238 @@ vr_status vr_brickset_set_tree(vr_brickset *h, int32_t brick, const uint8_t *tre
     if ((int)b.hostTree.size() != b.B) b.hostTree.assign((size_t)b.B, std::vector<uint8_t>());
     b.hostTree[brick].assign(tree, tree + need);
     return VR_OK;
+}
+
+// vrhip.h "compressed brick-set archives".  Everything that can refuse the call is checked first; then the copies and
+// the kernels of kd_index.hip go to `stream`, and one synchronisation reads the grammar flags.
+vr_status vr_brickset_set_trees(vr_brickset *h, int32_t count, const int32_t *bricks, const vr_tree_desc *descs, void *stream)
+{
+    if (!h || !bricks || !descs || count < 1 || count > h->s.B) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    if (b.variant == VR_VARIANT_MIDRANGE || b.idx64) return VR_ERR_UNSUPPORTED;
+    if (b.built && !b.foreign) return VR_ERR_STATE;
+    const int Dc = block_depth(b.D);
+    const size_t nBlk = (size_t)1 << Dc, B = (size_t)b.B;
+    std::vector<uint8_t> named(B, 0);
+    for (int i = 0; i < count; ++i) {
+        const vr_tree_desc &d = descs[i];
+        if (bricks[i] < 0 || bricks[i] >= b.B || named[(size_t)bricks[i]]) return VR_ERR_INVALID;
+        named[(size_t)bricks[i]] = 1;
+        if (!d.tree || !d.distance_map || (d.block_off == nullptr) != (d.top_val == nullptr)) return VR_ERR_INVALID;
+        if (d.map_len < b.maxDepth + 1 || d.num_active <= 0) return VR_ERR_INVALID;
+        if (d.num_active >= (1ll << 32)) return VR_ERR_UNSUPPORTED;
+        const int64_t need = (d.num_active + 3) / 4;
+        if (d.tree_bytes < need || need > b.treeCap) return VR_ERR_FORMAT;
+    }
+    std::vector<std::vector<uint32_t>> madeOff((size_t)count);
+    std::vector<std::vector<uint8_t>> madeTop((size_t)count);
+    std::atomic<int> bad(0);
+    parallel_for(count, [&](int i) {
+        const vr_tree_desc &d = descs[i];
+        if (d.block_off) { if (!block_table_ok(b.D, d.num_active, d.block_off)) bad = 1; return; }
+        madeOff[(size_t)i].resize(nBlk);
+        madeTop[(size_t)i].resize(2 * nBlk);
+        if (block_table_from_stream(b.D, d.tree, d.num_active, d.distance_map, madeOff[(size_t)i].data(), madeTop[(size_t)i].data()) != 0) bad = 1;
+    });
+    if (bad) return VR_ERR_FORMAT;
+    const bool wantFine = b.K == 6 && b.D >= 6;
+    if (!b.idxTop) {
+        HIPCHK(hipMalloc(&b.idxTop, B * (size_t)b.nIdx * 2));
+        HIPCHK(hipMemset(b.idxTop, 0, B * (size_t)b.nIdx * 2));
+    }
+    if (!b.instOff) HIPCHK(hipMalloc(&b.instOff, B * nBlk * sizeof(uint32_t)));
+    if (!b.instFlag) HIPCHK(hipMalloc(&b.instFlag, B * sizeof(int32_t)));
+    if (!b.instList) HIPCHK(hipMalloc(&b.instList, B * sizeof(int32_t)));
+    if (wantFine && !b.fineIdx) HIPCHK(hipMalloc(&b.fineIdx, B * (size_t)b.nIdx * 16));
+    if (wantFine && !b.idxVal3) HIPCHK(hipMalloc(&b.idxVal3, B * (size_t)b.nIdx * 8));
+    hipStream_t st = (hipStream_t)stream;
+    if (!b.built) {     // a fresh set: every brick starts out never installed (as vr_brickset_set_tree's first call)
+        b.fineHas.assign(B, 1);
+        for (auto &c : b.hostCtrl) memset(&c, 0, sizeof(Ctrl));
+        if (index_reset_launch(&b, nullptr, b.B, nullptr, false, st) != 0) return VR_ERR_NO_DEVICE;
+        b.built = true;
+        b.hostCtrlValid = true;
+    } else {
+        vr_status rc = sync_ctrl(b);
+        if (rc != VR_OK) return rc;
+    }
+    b.foreign = true;
+    b.gapped = false;
+    b.lastStream = stream;
+    if (b.fineHas.size() != B) b.fineHas.assign(B, 0);
+    if (b.hostTree.size() != B) b.hostTree.assign(B, std::vector<uint8_t>());
+    for (int i = 0; i < count; ++i) {
+        const vr_tree_desc &d = descs[i];
+        const size_t br = (size_t)bricks[i];
+        Ctrl &c = b.hostCtrl[br];
+        memset(&c, 0, sizeof(Ctrl));
+        c.numActive = (unsigned long long)d.num_active;
+        memcpy(c.distanceMap, d.distance_map, (size_t)b.maxDepth + 1);
+        std::vector<uint8_t>().swap(b.hostTree[br]);       // no host copy: cuts above depth Ds come from idxTop
+        b.openTreeBytes[br] = -1;
+        const int64_t need = (d.num_active + 3) / 4;
+        // the decoders read past a stream's last token, never further than VR_TREE_TAIL bytes
+        const int64_t tail = std::min<int64_t>(VR_TREE_TAIL, b.treeCap - need);
+        uint8_t *slot = b.mid.tree + br * (size_t)b.treeCap;
+        HIPCHK(hipMemcpyAsync(slot, d.tree, (size_t)need, hipMemcpyHostToDevice, st));
+        if (tail > 0) HIPCHK(hipMemsetAsync(slot + need, 0, (size_t)tail, st));
+        HIPCHK(hipMemcpyAsync(b.instOff + br * nBlk, d.block_off ? d.block_off : madeOff[(size_t)i].data(), nBlk * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        // (the table's heap IS the top of the brick's: the same layout, depths 0 .. Dc)
+        HIPCHK(hipMemcpyAsync(b.idxTop + br * (size_t)b.nIdx * 2, d.top_val ? d.top_val : madeTop[(size_t)i].data(), 2 * nBlk, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(b.mid.ctrl, b.hostCtrl.data(), B * sizeof(Ctrl), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b.instList, bricks, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b.instFlag, 0, (size_t)count * sizeof(int32_t), st));
+    if (index_reset_launch(&b, b.instList, count, nullptr, false, st) != 0) return VR_ERR_NO_DEVICE;
+    if (index_from_stream_launch(&b, b.instList, count, b.instFlag, st) != 0) return VR_ERR_NO_DEVICE;
+    if (index_reset_launch(&b, b.instList, count, b.instFlag, true, st) != 0) return VR_ERR_NO_DEVICE;
+    std::vector<int32_t> flags((size_t)count, 0);
+    HIPCHK(hipMemcpyAsync(flags.data(), b.instFlag, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const bool failed = std::find_if(flags.begin(), flags.end(), [](int32_t f) { return f != 0; }) != flags.end();
+    for (int i = 0; i < count; ++i) {
+        const size_t br = (size_t)bricks[i];
+        bool fine = wantFine && !failed;
+        for (int k = 0; k < VR_CHAIN_LEVELS; ++k) fine = fine && descs[i].distance_map[b.D + 1 + k] == (uint8_t)(64 >> k);
+        b.fineHas[br] = failed ? 1 : (fine ? 1 : 0);        // (a brick never installed: no counts are read)
+        if (failed) memset(&b.hostCtrl[br], 0, sizeof(Ctrl));
+    }
+    fine_has_changed(b);
+    if (failed) {       // every brick named in the call is left never installed
+        if (index_reset_launch(&b, b.instList, count, nullptr, true, st) != 0) return VR_ERR_NO_DEVICE;
+        HIPCHK(hipStreamSynchronize(st));
+        return VR_ERR_FORMAT;
+    }
+    return VR_OK;
+}
+
+static vr_status archive_matches(const BrickSet &b, const ArchiveGeom &g)
+{
+    const bool same = g.variant == b.variant && g.numBricks == b.B && g.D == b.D && g.maxDepth == b.maxDepth &&
+                      g.dims[0] == b.g.X && g.dims[1] == b.g.Y && g.dims[2] == b.g.Z;
+    return same ? VR_OK : VR_ERR_FORMAT;
+}
+
+static vr_status install_archive(BrickSet &b, vr_brickset *h, const void *blob, const ArchiveGeom &g,
+                                 const std::vector<ArchiveEntry> &dir, void *stream)
+{
+    std::vector<int32_t> bricks;
+    std::vector<vr_tree_desc> descs;
+    for (int br = 0; br < g.numBricks; ++br) {
+        const ArchiveEntry &e = dir[(size_t)br];
+        if (e.offset == 0) continue;
+        const ArchiveRecord r = archive_record(blob, g, e);
+        bricks.push_back(br);
+        descs.push_back(vr_tree_desc{r.tree, e.treeBytes, e.numActive, r.dmap, b.maxDepth + 1, r.blockOff, r.topVal});
+    }
+    if (bricks.empty()) return VR_OK;
+    return vr_brickset_set_trees(h, (int32_t)bricks.size(), bricks.data(), descs.data(), stream);
+}
+
+vr_status vr_brickset_load_set_memory(vr_brickset *h, const void *blob, int64_t bytes, void *stream)
+{
+    if (!h || !blob || bytes <= 0 || misaligned16(blob)) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    if (b.variant == VR_VARIANT_MIDRANGE || b.idx64) return VR_ERR_UNSUPPORTED;
+    if (b.built && !b.foreign) return VR_ERR_STATE;
+    ArchiveGeom g;
+    std::vector<ArchiveEntry> dir;
+    if (archive_parse(blob, bytes, g, dir) != 0) return VR_ERR_FORMAT;
+    vr_status rc = archive_matches(b, g);
+    if (rc != VR_OK) return rc;
+    return install_archive(b, h, blob, g, dir, stream);
+}
+
+// a whole file in one pinned buffer (the caller frees it with hipHostFree)
+static vr_status read_archive_file(const char *path, void **blob, int64_t *bytes)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) return VR_ERR_IO;
+    fseek(f, 0, SEEK_END);
+    const int64_t n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (n < VR_ARCHIVE_HEADER_BYTES) { fclose(f); return n < 0 ? VR_ERR_IO : VR_ERR_FORMAT; }
+    void *p = nullptr;
+    if (hipHostMalloc(&p, (size_t)n, hipHostMallocDefault) != hipSuccess) { fclose(f); return VR_ERR_OOM; }
+    const bool ok = fread(p, 1, (size_t)n, f) == (size_t)n;
+    fclose(f);
+    if (!ok) { hipHostFree(p); return VR_ERR_IO; }
+    *blob = p; *bytes = n;
+    return VR_OK;
+}
+
+vr_status vr_brickset_load_set(vr_brickset *h, const char *path, void *stream)
+{
+    if (!h || !path) return VR_ERR_INVALID;
+    void *blob = nullptr;
+    int64_t bytes = 0;
+    vr_status rc = read_archive_file(path, &blob, &bytes);
+    if (rc != VR_OK) return rc;
+    rc = vr_brickset_load_set_memory(h, blob, bytes, stream);     // (synchronises `stream`: the buffer is done with)
+    hipHostFree(blob);
+    return rc;
+}
+
+vr_status vr_brickset_open_set(vr_brickset **out, const char *path, void *stream)
+{
+    if (!out || !path) return VR_ERR_INVALID;
+    if (!device_ok()) return VR_ERR_NO_DEVICE;
+    void *blob = nullptr;
+    int64_t bytes = 0;
+    vr_status rc = read_archive_file(path, &blob, &bytes);
+    if (rc != VR_OK) return rc;
+    ArchiveGeom g;
+    std::vector<ArchiveEntry> dir;
+    vr_brickset *h = nullptr;
+    if (archive_parse(blob, bytes, g, dir) != 0) rc = VR_ERR_FORMAT;
+    if (rc == VR_OK && (g.variant < 0 || g.variant > 2)) rc = VR_ERR_FORMAT;
+    if (rc == VR_OK && g.variant == VR_VARIANT_MIDRANGE) rc = VR_ERR_UNSUPPORTED;
+    if (rc == VR_OK) rc = vr_brickset_create(&h, g.numBricks, g.dims, 6, 5, g.variant);   // (vr_brickset_open's defaults)
+    if (rc == VR_OK) rc = archive_matches(h->s, g);
+    if (rc == VR_OK) rc = install_archive(h->s, h, blob, g, dir, stream);
+    hipHostFree(blob);
+    if (rc != VR_OK) { vr_brickset_destroy(h); return rc; }
+    *out = h;
+    return VR_OK;
+}
+
+vr_status vr_brickset_save_set(vr_brickset *h, const char *path)
+{
+    if (!h || !path) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    if (b.variant == VR_VARIANT_MIDRANGE || b.idx64) return VR_ERR_UNSUPPORTED;
+    vr_status rc = sync_ctrl(b);
+    if (rc != VR_OK) return rc;
+    const int Dc = block_depth(b.D);
+    std::vector<std::vector<uint8_t>> trees((size_t)b.B);
+    std::vector<ArchiveBrick> bricks((size_t)b.B);
+    for (int br = 0; br < b.B; ++br) {
+        const Ctrl &c = b.hostCtrl[(size_t)br];
+        if (c.numActive == 0ull) continue;
+        if (c.numActive >= (1ull << 32)) return VR_ERR_UNSUPPORTED;
+        const uint8_t *src = nullptr;
+        rc = contiguous_stream(b, b.mid, br, &src);
+        if (rc != VR_OK) return rc;
+        if (b.hostCtrl[(size_t)br].emitOverflow) return VR_ERR_STATE;
+        trees[(size_t)br].resize((size_t)(((int64_t)c.numActive + 3) / 4));
+        HIPCHK(hipMemcpy(trees[(size_t)br].data(), src, trees[(size_t)br].size(), hipMemcpyDeviceToHost));
+    }
+    std::atomic<int> bad(0);
+    parallel_for(b.B, [&](int br) {
+        const Ctrl &c = b.hostCtrl[(size_t)br];
+        if (trees[(size_t)br].empty()) return;
+        ArchiveBrick &k = bricks[(size_t)br];
+        k.numActive = (int64_t)c.numActive; k.dmap = c.distanceMap; k.tree = trees[(size_t)br].data();
+        k.blockOff.resize((size_t)1 << Dc);
+        k.topVal.resize((size_t)2 << Dc);
+        if (block_table_from_stream(b.D, k.tree, k.numActive, k.dmap, k.blockOff.data(), k.topVal.data()) != 0) bad = 1;
+    });
+    if (bad) return VR_ERR_STATE;
+    FILE *f = fopen(path, "wb");
+    if (!f) return VR_ERR_IO;
+    const ArchiveGeom g = {b.variant, {b.g.X, b.g.Y, b.g.Z}, b.B, b.D, b.maxDepth};
+    const bool ok = archive_write(f, g, bricks);
+    return (fclose(f) == 0 && ok) ? VR_OK : VR_ERR_IO;
 }
 
 // File layout of VolumeKdtree::save (R.cpp:535-544).

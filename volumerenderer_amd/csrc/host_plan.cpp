@@ -3,6 +3,8 @@
 #include "../../include/vrhip.h"
 #include <string.h>
 #include <algorithm>
+#include <atomic>
+#include <thread>
 
 namespace vr {
 
@@ -266,6 +268,151 @@ int build_index_from_stream(int D, int Ds, int K, int64_t nIdx, const uint8_t *t
         [&](uint32_t path) { own(path, D); });
 }
 
+// ---- block tables ----
+int block_table_from_stream(int D, const uint8_t *tree, int64_t numActive, const uint8_t *dmap, uint32_t *blockOff,
+                            uint8_t *topVal)
+{
+    const int Dc = block_depth(D);
+    std::fill(blockOff, blockOff + ((size_t)1 << Dc), VR_IDX_DEAD);
+    std::fill(topVal, topVal + ((size_t)2 << Dc), (uint8_t)0);
+    return walk_stream(D, tree, numActive, dmap, Dc,
+        [&](int j, uint32_t path, int64_t pos, int, int val) {
+            if (j <= Dc) topVal[((size_t)1 << j) + path] = (uint8_t)val;
+            if (j == Dc) blockOff[path] = (uint32_t)pos;
+        },
+        [&](int j, uint32_t path, int val) {
+            for (int L = j + 1; L <= Dc; ++L)
+                std::fill(topVal + ((size_t)1 << L) + ((size_t)path << (L - j)), topVal + ((size_t)1 << L) + (((size_t)path + 1) << (L - j)), (uint8_t)val);
+        },
+        [](uint32_t) {});
+}
+
+bool block_table_ok(int D, int64_t numActive, const uint32_t *blockOff)
+{
+    const int Dc = block_depth(D);
+    const int64_t nBlk = (int64_t)1 << Dc;
+    if (numActive <= 0 || numActive >= ((int64_t)1 << 32)) return false;
+    if (Dc == 0) return blockOff[0] == 0u;
+    if (blockOff[0] != VR_IDX_DEAD && blockOff[0] != (uint32_t)Dc) return false;
+    int64_t last = -1;
+    for (int64_t p = 0; p < nBlk; ++p) {
+        if (blockOff[p] == VR_IDX_DEAD) continue;
+        // block p's root comes after its Dc ancestors at the least, and after every live block before it
+        if ((int64_t)blockOff[p] >= numActive || (int64_t)blockOff[p] <= last || blockOff[p] < (uint32_t)Dc) return false;
+        last = blockOff[p];
+    }
+    return true;
+}
+
+// ---- the brick-set archive ----
+static const char ARCHIVE_MAGIC[8] = {'V', 'R', 'B', 'S', 'E', 'T', '\r', '\n'};
+struct ArchiveHeader { char magic[8]; uint32_t version, variant; int64_t dims[3]; int32_t numBricks, D, maxDepth; uint32_t zero; int64_t fileBytes; };
+static_assert(sizeof(ArchiveHeader) == VR_ARCHIVE_HEADER_BYTES, "the header is written as it lies in memory");
+
+static int64_t pad16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+uint64_t fnv1a64(const uint8_t *p, int64_t n)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int64_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
+    return h;
+}
+
+void parallel_for(int n, const std::function<void(int)> &fn)
+{
+    const int workers = std::min(n, 16);
+    if (workers <= 1) { for (int i = 0; i < n; ++i) fn(i); return; }
+    std::atomic<int> next(0);
+    const auto run = [&]() { for (int i = next++; i < n; i = next++) fn(i); };
+    std::vector<std::thread> pool;
+    for (int w = 1; w < workers; ++w) pool.emplace_back(run);
+    run();
+    for (auto &t : pool) t.join();
+}
+
+int64_t archive_record_bytes(int D, int maxDepth, int64_t treeBytes)
+{
+    const int Dc = block_depth(D);
+    return pad16(maxDepth + 1) + pad16((int64_t)2 << Dc) + pad16((int64_t)4 << Dc) + pad16(treeBytes);
+}
+
+ArchiveRecord archive_record(const void *blob, const ArchiveGeom &g, const ArchiveEntry &e)
+{
+    const int Dc = block_depth(g.D);
+    const uint8_t *p = (const uint8_t *)blob + e.offset;
+    ArchiveRecord r;
+    r.dmap = p; p += pad16(g.maxDepth + 1);
+    r.topVal = p; p += pad16((int64_t)2 << Dc);
+    r.blockOff = (const uint32_t *)p; p += pad16((int64_t)4 << Dc);
+    r.tree = p;
+    return r;
+}
+
+int archive_parse(const void *blob, int64_t bytes, ArchiveGeom &g, std::vector<ArchiveEntry> &dir)
+{
+    if (!blob || ((uintptr_t)blob & 3) || bytes < VR_ARCHIVE_HEADER_BYTES) return -1;
+    ArchiveHeader h;
+    memcpy(&h, blob, sizeof(h));
+    if (memcmp(h.magic, ARCHIVE_MAGIC, 8) != 0 || h.version != 1u || h.fileBytes != bytes) return -1;
+    if (h.numBricks < 1 || h.D < 0 || h.D > 31 || h.maxDepth != h.D + VR_CHAIN_LEVELS) return -1;
+    for (int k = 0; k < 3; ++k) if (h.dims[k] < 1 || h.dims[k] > ((int64_t)1 << 20)) return -1;
+    const int64_t dirEnd = VR_ARCHIVE_HEADER_BYTES + (int64_t)h.numBricks * VR_ARCHIVE_ENTRY_BYTES;
+    if (dirEnd > bytes) return -1;
+    g.variant = (int32_t)h.variant; g.numBricks = h.numBricks; g.D = h.D; g.maxDepth = h.maxDepth;
+    for (int k = 0; k < 3; ++k) g.dims[k] = h.dims[k];
+    dir.resize((size_t)h.numBricks);
+    memcpy(dir.data(), (const uint8_t *)blob + VR_ARCHIVE_HEADER_BYTES, (size_t)h.numBricks * VR_ARCHIVE_ENTRY_BYTES);
+    for (const ArchiveEntry &e : dir) {
+        if (e.offset == 0) continue;
+        if (e.offset < dirEnd || (e.offset & 15) || e.numActive <= 0 || e.numActive >= ((int64_t)1 << 32)) return -1;
+        if (e.treeBytes != (e.numActive + 3) / 4) return -1;
+        const int64_t rec = archive_record_bytes(g.D, g.maxDepth, e.treeBytes);
+        if (e.offset > bytes || rec > bytes - e.offset) return -1;
+    }
+    std::atomic<int> bad(0);
+    parallel_for(h.numBricks, [&](int b) {
+        const ArchiveEntry &e = dir[(size_t)b];
+        if (e.offset == 0) return;
+        const int64_t rec = archive_record_bytes(g.D, g.maxDepth, e.treeBytes);
+        if (fnv1a64((const uint8_t *)blob + e.offset, rec) != e.hash) { bad = 1; return; }
+        if (!block_table_ok(g.D, e.numActive, archive_record(blob, g, e).blockOff)) bad = 1;
+    });
+    return bad ? -1 : 0;
+}
+
+bool archive_write(FILE *f, const ArchiveGeom &g, const std::vector<ArchiveBrick> &bricks)
+{
+    const int Dc = block_depth(g.D);
+    const int64_t dirEnd = VR_ARCHIVE_HEADER_BYTES + (int64_t)g.numBricks * VR_ARCHIVE_ENTRY_BYTES;
+    std::vector<ArchiveEntry> dir((size_t)g.numBricks, ArchiveEntry{0, 0, 0, 0});
+    std::vector<std::vector<uint8_t>> recs((size_t)g.numBricks);
+    parallel_for(g.numBricks, [&](int b) {
+        const ArchiveBrick &k = bricks[(size_t)b];
+        if (k.numActive <= 0) return;
+        const int64_t tb = (k.numActive + 3) / 4;
+        std::vector<uint8_t> &r = recs[(size_t)b];
+        r.assign((size_t)archive_record_bytes(g.D, g.maxDepth, tb), 0);
+        uint8_t *p = r.data();
+        memcpy(p, k.dmap, (size_t)g.maxDepth + 1); p += pad16(g.maxDepth + 1);
+        memcpy(p, k.topVal.data(), (size_t)2 << Dc); p += pad16((int64_t)2 << Dc);
+        memcpy(p, k.blockOff.data(), (size_t)4 << Dc); p += pad16((int64_t)4 << Dc);
+        memcpy(p, k.tree, (size_t)tb);
+        dir[(size_t)b] = ArchiveEntry{0, tb, k.numActive, fnv1a64(r.data(), (int64_t)r.size())};
+    });
+    int64_t at = dirEnd;
+    for (int b = 0; b < g.numBricks; ++b)
+        if (!recs[(size_t)b].empty()) { dir[(size_t)b].offset = at; at += (int64_t)recs[(size_t)b].size(); }
+    ArchiveHeader h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, ARCHIVE_MAGIC, 8);
+    h.version = 1; h.variant = (uint32_t)g.variant; h.numBricks = g.numBricks; h.D = g.D; h.maxDepth = g.maxDepth; h.fileBytes = at;
+    for (int k = 0; k < 3; ++k) h.dims[k] = g.dims[k];
+    bool ok = fwrite(&h, sizeof(h), 1, f) == 1 && fwrite(dir.data(), VR_ARCHIVE_ENTRY_BYTES, dir.size(), f) == dir.size();
+    for (int b = 0; ok && b < g.numBricks; ++b)
+        if (!recs[(size_t)b].empty()) ok = fwrite(recs[(size_t)b].data(), 1, recs[(size_t)b].size(), f) == recs[(size_t)b].size();
+    return ok;
+}
+
 bool read_header(FILE *f, Header &h)
 {
     if (fread(&h, VR_HEADER_BYTES, 1, f) != 1) return false;
@@ -297,6 +444,21 @@ extern "C" vr_status vr_lod_select_error(const vr_brick_error *table, int32_t nu
         cuts_out[b] = pick;
     }
     return VR_OK;
+}
+
+// ---- the block table of a stream: the definition is in host_plan.h, the contract in vrhip.h ----
+extern "C" vr_status vr_stream_block_table(const int64_t dims[3], const uint8_t *tree_host, int64_t tree_bytes, int64_t num_active,
+                                           const uint8_t *dmap, int32_t map_len, uint32_t *block_off_out, uint8_t *top_val_out)
+{
+    if (!dims || !tree_host || !dmap || !block_off_out || !top_val_out || num_active <= 0) return VR_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) if (dims[k] <= 0 || dims[k] > (1ll << 20)) return VR_ERR_INVALID;
+    if (dims[0] * dims[1] * dims[2] >= (1ll << 32)) return VR_ERR_UNSUPPORTED;
+    vr::Geom g;
+    vr::make_geom(g, dims);
+    if (g.D > 31 || num_active >= (1ll << 32)) return VR_ERR_UNSUPPORTED;
+    if (map_len < g.D + VR_CHAIN_LEVELS + 1) return VR_ERR_INVALID;
+    if (tree_bytes < (num_active + 3) / 4) return VR_ERR_FORMAT;
+    return vr::block_table_from_stream(g.D, tree_host, num_active, dmap, block_off_out, top_val_out) == 0 ? VR_OK : VR_ERR_FORMAT;
 }
 
 // ---- a display window from a histogram's percentiles: the rule is stated in vrhip.h ("volume histograms") ----

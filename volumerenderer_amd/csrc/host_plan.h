@@ -1,12 +1,14 @@
 // host_plan.h -- the codec's host logic that needs no device: the split rule and what follows from it, the launch
 // geometry of the tiled kernels (planned once per set, at vr_brickset_create), the walker of foreign streams and the
-// file header; and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
+// file header, the block tables and per-block index walker of installed streams (shared with kd_index.hip's kernel) and the
+// brick-set archive's parser and writer; and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
 // host_plan.cpp: a rule on a host table).  Includes no HIP header: compiles with a plain C++17 compiler (tests/host_plan_main.cpp links it
 // directly) and with hipcc.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <array>
+#include <functional>
 #include <vector>
 
 #if defined(__HIP__) || defined(__HIPCC__)
@@ -134,6 +136,141 @@ int cut_values_from_stream(int D, int Ds, int K, int64_t nIdx, const uint8_t *tr
 int build_index_from_stream(int D, int Ds, int K, int64_t nIdx, const uint8_t *tree, int64_t numActive,
                             const uint8_t *dmap, std::vector<uint32_t> &offs, std::vector<uint8_t> &vals,
                             std::vector<uint8_t> &fine, std::vector<uint8_t> &val3);
+
+// ---- block tables: the index of a stream rebuilt block by block (vrhip.h "compressed brick-set archives") ----
+// A block is a depth-Dc node, Dc = max(D - 12, 0): a 4096-leaf box where D >= 12, the whole brick otherwise.  The table
+// of a stream: blockOff[2^Dc], the token index of every block root's own token (VR_IDX_DEAD: an ancestor was pruned),
+// and topVal[2^(Dc+1)], a 1-based heap over depths 0 .. Dc ((1 << j) + path; entry 0 unused) of decoded scalars, a
+// pruned node's scalar standing for every node below it.  A walk from blockOff[p] that starts with the scalar
+// topVal[(1 << Dc) + p] sees what walk_stream sees below that node.
+#define VR_BLOCK_LEVELS 12
+#define VR_TREE_TAIL 2048    // bytes zeroed past an installed stream's end: no decoder reads further
+VR_HD inline int block_depth(int D) { return D > VR_BLOCK_LEVELS ? D - VR_BLOCK_LEVELS : 0; }
+
+// one walk_stream pass; 0 or walk_stream's status
+int block_table_from_stream(int D, const uint8_t *tree, int64_t numActive, const uint8_t *dmap, uint32_t *blockOff,
+                            uint8_t *topVal);
+// what the host can say about a table without the stream: every live offset below numActive, live offsets strictly
+// increasing with the block number, block 0 (the path that is never a right child) at token Dc when it is live, the
+// only block of a shallow brick at token 0
+bool block_table_ok(int D, int64_t numActive, const uint32_t *blockOff);
+
+// token `pos` of a stream read as aligned 32-bit words, sixteen tokens each (little-endian: cget's packing)
+VR_HD inline int wget(const uint32_t *W, uint32_t pos) { return (int)((W[pos >> 4] >> ((pos & 15u) * 2u)) & 3u); }
+
+// One brick's index arrays.  fine / val3 null: the brick gets none (K != 6, D < 6 or a map with other grown-branch
+// distances than 64 >> i).  top: 2 * nIdx bytes, a heap like topVal over depths 0 .. Ds.
+struct BlockIndexOut { uint32_t *off; uint8_t *val, *fine, *val3, *top; };
+
+// The walker of one block: the index entries below block `blk`, byte for byte what build_index_from_stream gives them
+// (the entries are at their defaults when it starts: offsets VR_IDX_DEAD, everything else 0), and the scalars of its
+// nodes of depths Dc .. Ds in o.top.  off / v0: the block's table entries.  stack: one byte per level Dc .. D (at most
+// VR_BLOCK_LEVELS + 1), level l at stack[l * stride].  No token at or past numActive is read, nothing outside the
+// block's own entries is written, and every iteration consumes a token: no byte pattern reads or writes elsewhere or
+// runs it forever.  Returns 0 and the token after the block's subtree in *end, or -1 / -2 (the stream ends inside the
+// tree / inside a grown branch).
+VR_HD inline int index_block_walk(const uint32_t *W, uint32_t numActive, const uint8_t *dmap, int D, int K, uint32_t blk,
+                                  uint32_t off, int v0, const BlockIndexOut &o, uint8_t *stack, int stride, uint32_t *end)
+{
+    const int Dc = block_depth(D), Ds = D - K;
+    const bool fine = o.fine != nullptr;
+    // a node pruned at depth j stands for every node below it (fill_below's rule, and the heap's)
+    const auto below = [&](int j, uint32_t path, int val) {
+        for (int L = j + 1; L <= Ds; ++L)
+            for (uint32_t i = path << (L - j), e = (path + 1u) << (L - j); i < e; ++i) o.top[(1u << L) + i] = (uint8_t)val;
+        if (j < Ds) for (uint32_t i = path << (Ds - j), e = (path + 1u) << (Ds - j); i < e; ++i) o.val[i] = (uint8_t)val;
+        if (fine && j < D - 3) for (uint32_t i = path << (D - 3 - j), e = (path + 1u) << (D - 3 - j); i < e; ++i) o.val3[i] = (uint8_t)val;
+    };
+    *end = 0;
+    if (off == VR_IDX_DEAD) { o.top[(1u << Dc) + blk] = (uint8_t)v0; below(Dc, blk, v0); return 0; }
+    // tokens of depth >= Ds belong to the 4-leaf subtree that holds their node's first leaf; in preorder those
+    // subtrees never go back, so one count is open at a time
+    uint32_t grp = 0;
+    int cnt = 0, status = 0;
+    const auto own = [&](uint32_t firstLeaf) {
+        const uint32_t g = firstLeaf >> 2;
+        if (cnt && g != grp) { o.fine[grp] = (uint8_t)cnt; cnt = 0; }
+        grp = g; ++cnt;
+    };
+    uint32_t pos = off, path = blk;
+    int j = Dc;
+    while (true) {
+        if (pos >= numActive) { status = -1; break; }
+        const int tok = wget(W, pos);
+        const int val = j == Dc ? v0 : apply_code(stack[(j - 1 - Dc) * stride], tok, dmap[j]);
+        stack[(j - Dc) * stride] = (uint8_t)val;
+        if (j <= Ds) o.top[(1u << j) + path] = (uint8_t)val;
+        if (j == Ds) { o.off[path] = pos; o.val[path] = (uint8_t)val; }
+        if (fine && j == D - 3) o.val3[path] = (uint8_t)val;
+        if (fine && j >= Ds) own(path << (D - j));
+        ++pos;
+        bool terminal = tok == 3;
+        if (terminal) below(j, path, val);
+        else if (j == D) {
+            for (int c = 1; c <= VR_CHAIN_LEVELS; ++c) {
+                if (pos >= numActive) { status = -2; break; }
+                if (fine) own(path);
+                if (wget(W, pos++) == 3) break;
+            }
+            if (status) break;
+            terminal = true;
+        }
+        if (terminal) {
+            while (j > Dc && (path & 1u)) { path >>= 1; --j; }
+            if (j == Dc) break;
+            path |= 1u;
+        } else { ++j; path <<= 1; }
+    }
+    if (cnt) o.fine[grp] = (uint8_t)cnt;
+    *end = pos;
+    return status;
+}
+
+// The tokens between two blocks: from `pos`, the token after block p's subtree (p < 0: from the root, pos 0), the nodes
+// above depth Dc in preorder up to the next block root the stream holds, which must be where the table says, or to the
+// end of the stream, which must be numActive.  Every block below a node pruned on the way must be dead in the table.
+// With index_block_walk over every live block and this after each of them and from the root, every token of the stream
+// is parsed exactly once.  Returns 0, -1 (the stream ends inside the tree), -3 (tokens left over) or -4 (the table
+// disagrees with the stream).  Reads tokens below numActive and the table; writes nothing.
+VR_HD inline int block_gap_walk(const uint32_t *W, uint32_t numActive, int Dc, const uint32_t *blockOff, int64_t p, uint32_t pos)
+{
+    int j = 0;
+    uint32_t path = 0;
+    if (p >= 0) {
+        j = Dc; path = (uint32_t)p;
+        while (j > 0 && (path & 1u)) { path >>= 1; --j; }
+        if (j == 0) return pos == numActive ? 0 : -3;
+        path |= 1u;
+    }
+    while (true) {
+        if (j == Dc) return blockOff[path] == pos ? 0 : -4;
+        if (pos >= numActive) return -1;
+        if (wget(W, pos++) == 3) {
+            for (uint32_t i = path << (Dc - j), e = (path + 1u) << (Dc - j); i < e; ++i) if (blockOff[i] != VR_IDX_DEAD) return -4;
+            while (j > 0 && (path & 1u)) { path >>= 1; --j; }
+            if (j == 0) return pos == numActive ? 0 : -3;
+            path |= 1u;
+        } else { ++j; path <<= 1; }
+    }
+}
+
+// ---- the brick-set archive (layout: vrhip.h "compressed brick-set archives"); parsing and writing need no device ----
+constexpr int VR_ARCHIVE_HEADER_BYTES = 64, VR_ARCHIVE_ENTRY_BYTES = 32;
+struct ArchiveGeom { int32_t variant; int64_t dims[3]; int32_t numBricks, D, maxDepth; };
+struct ArchiveEntry { int64_t offset, treeBytes, numActive; uint64_t hash; };      // as it lies in the file
+static_assert(sizeof(ArchiveEntry) == VR_ARCHIVE_ENTRY_BYTES, "the directory is read as it lies in memory");
+struct ArchiveRecord { const uint8_t *dmap, *topVal; const uint32_t *blockOff; const uint8_t *tree; };
+struct ArchiveBrick { int64_t numActive = 0; const uint8_t *dmap = nullptr, *tree = nullptr; std::vector<uint32_t> blockOff; std::vector<uint8_t> topVal; };
+uint64_t fnv1a64(const uint8_t *p, int64_t n);
+int64_t archive_record_bytes(int D, int maxDepth, int64_t treeBytes);
+// 0, or -1: a wrong magic or version, a header that does not describe a brick set, an offset or length outside the
+// blob, a record whose checksum or block table is wrong.  blob: 4-byte aligned
+int archive_parse(const void *blob, int64_t bytes, ArchiveGeom &g, std::vector<ArchiveEntry> &dir);
+ArchiveRecord archive_record(const void *blob, const ArchiveGeom &g, const ArchiveEntry &e);
+// bricks[b].numActive == 0: brick b is absent
+bool archive_write(FILE *f, const ArchiveGeom &g, const std::vector<ArchiveBrick> &bricks);
+// workers for the host passes of an archive (checksums, tables): at most 16, never the machine's core count
+void parallel_for(int n, const std::function<void(int)> &fn);
 
 // ---- the file header of VolumeKdtree::save (R.cpp:535-544) and MidRangeTree::save (M.cpp:753-785) ----
 struct Header { int64_t rootMin[3], rootMax[3]; int32_t maxDepth, origDepth; int64_t X, Y, Z, numActive; };

@@ -1950,10 +1950,13 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
     // host image: cuts [0, B), bricks cut above Ds, then the passes' classes' lists
     int32_t *H = s.host;
     const DecodePlan plan(bs, false);
-    int nAbove = 0;
-    for (int b = 0; b < B; ++b) {
-        H[b] = cutsHost[b];
-        if (cutsHost[b] >= 0 && cutsHost[b] < bs->Ds) H[B + nAbove++] = b;
+    // (of a set of installed streams: first the bricks whose scalars come from idxTop, then those the host fills)
+    int nAbove = 0, nTop = 0;
+    for (int b = 0; b < B; ++b) H[b] = cutsHost[b];
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int b = 0; b < B; ++b)
+            if (cutsHost[b] >= 0 && cutsHost[b] < bs->Ds && (bs->foreign && top_indexed(*bs, b)) == (pass == 0)) H[B + nAbove++] = b;
+        if (pass == 0) nTop = nAbove;
     }
     // the passes: [0] full resolution (every decoded brick without a pool), then the staged batches
     const auto coarse = [&](int b) { return pool && (pool->shift[3 * b] | pool->shift[3 * b + 1] | pool->shift[3 * b + 2]) != 0; };
@@ -2003,7 +2006,7 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
     if (nAbove && bs->foreign) {
         // ancestor scalars at each brick's cut, from the stream bytes kept at set_tree/open time (as vr_brickset_decode)
         std::vector<uint8_t> vals;
-        for (int i = 0; i < nAbove; ++i) {
+        for (int i = nTop; i < nAbove; ++i) {
             const int br = H[B + i];
             vals.assign((size_t)bs->nIdx, 0);
             if (br < (int)bs->hostTree.size() && !bs->hostTree[br].empty() &&
@@ -2021,6 +2024,7 @@ int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipSt
     if (at > B && hipMemcpyAsync(s.dev, H, (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     if (pool && (nRows || nDesc) &&
         hipMemcpyAsync(s.obDev, s.obHost, (size_t)(B + 2 * nDesc) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (nTop && cut_from_top_launch(bs, s.dev + B, s.dev, 0, nTop, 0, s.idxValCut, st) != 0) return -1;
     if (nAbove && !bs->foreign)
         hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), nAbove), dim3(256), 0, st,
                            bs->mid.codes, bs->codeStride, bs->mid.ctrl, bs->Ds, 0, bs->nIdx, s.idxValCut, s.dev + B, s.dev);

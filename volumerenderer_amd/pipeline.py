@@ -173,3 +173,109 @@ class TimestepStreamer:
         if th is not None:
             th.join()
         return [{"uploaded": uploaded[t], "built": built[t], "stages": staged[t]} for t in range(T)]
+
+
+class ArchiveSource:
+    """The disk stage of archive playback: one brick-set archive file per timestep (BrickSet.save_set), read whole into
+    a pinned staging buffer."""
+
+    def __init__(self, paths):
+        self.paths = [os.fspath(p) for p in paths]
+        self.sizes = [os.path.getsize(p) for p in self.paths]
+
+    def __len__(self):
+        return len(self.paths)
+
+    def max_bytes(self):
+        return max(self.sizes) if self.sizes else 0
+
+    def read_into(self, i, pinned):
+        """Timestep i -> the first bytes of the pinned uint8 host tensor; returns the file's size."""
+        n = self.sizes[i]
+        with open(self.paths[i], "rb") as f:
+            got = f.readinto(pinned.numpy()[:n])
+        if got != n:
+            raise RuntimeError("short read: %s" % self.paths[i])
+        return n
+
+
+class ArchivePlayer:
+    """Playback of stored timesteps: disk -> pinned host memory -> install (copies + the index rebuilt on the GPU) ->
+    decode -> frames.  TimestepStreamer's shape without the encoder: a reader thread, two pinned staging buffers, two
+    brick sets and two output volumes, the install of timestep t + 1 on a stream of its own while the decode and the
+    frames of timestep t run.  Every file must hold every brick (a brick absent from a file keeps the stream of the
+    timestep before last)."""
+
+    def __init__(self, num_bricks, brick_dims, variant=_lib.VARIANT_RECOVER):
+        self.sets = [BrickSet(num_bricks, brick_dims, variant=variant) for _ in range(2)]
+        self.n = num_bricks * brick_dims[0] * brick_dims[1] * brick_dims[2]
+        self.out = [torch.empty(self.n, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        self.install_stream = torch.cuda.Stream()
+        self.compute_stream = torch.cuda.Stream()
+        self._stage = None
+
+    def run(self, source, on_decoded=None, cut_depth=-1, cuts=None, overlap=True):
+        """source: an ArchiveSource.  on_decoded(t, volume, stream) is called with the decoded device volume while
+        `stream` is current (launch the frames there).  cuts: per-brick cut depths (decode_lod; -1 leaves a brick's
+        voxels as the timestep before last left them); else every brick at cut_depth."""
+        T = len(source)
+        need = (source.max_bytes() + 15) & ~15
+        if self._stage is None or self._stage[0].numel() < need:
+            self._stage = [torch.empty(max(need, 16), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        ready = [threading.Event() for _ in range(T)]
+        installed_host = [threading.Event() for _ in range(T)]
+        sizes = [0] * T
+        err = []
+
+        def reader():
+            try:
+                for t in range(T):
+                    if t >= 2:
+                        installed_host[t - 2].wait()       # load_set has returned: its copies out of the buffer are done
+                    sizes[t] = source.read_into(t, self._stage[t & 1])
+                    ready[t].set()
+            except Exception as ex:      # surfaces in the consumer
+                err.append(ex)
+                for e in ready:
+                    e.set()
+
+        th = threading.Thread(target=reader, daemon=True)
+        th.start()
+        installed = [torch.cuda.Event() for _ in range(T)]
+        consumed = [torch.cuda.Event() for _ in range(T)]
+
+        def install(t):
+            ready[t].wait()
+            if err:
+                raise err[0]
+            try:
+                with torch.cuda.stream(self.install_stream):
+                    if t >= 2:
+                        self.install_stream.wait_event(consumed[t - 2])       # the set's previous decode has finished
+                    self.sets[t & 1].load_set(self._stage[t & 1], nbytes=sizes[t], stream=self.install_stream)
+                    installed[t].record(self.install_stream)
+            finally:
+                installed_host[t].set()
+
+        try:
+            install(0)
+            for t in range(T):
+                bs, vol = self.sets[t & 1], self.out[t & 1]
+                with torch.cuda.stream(self.compute_stream):
+                    self.compute_stream.wait_event(installed[t])
+                    if cuts is None:
+                        bs.decode(vol, cut_depth=cut_depth, stream=self.compute_stream)
+                    else:
+                        bs.decode_lod(cuts, vol, stream=self.compute_stream)
+                    if on_decoded is not None:
+                        on_decoded(t, vol, self.compute_stream)
+                    consumed[t].record(self.compute_stream)
+                if t + 1 < T:
+                    if not overlap:
+                        self.compute_stream.synchronize()
+                    install(t + 1)
+        finally:
+            for e in installed_host:
+                e.set()
+            torch.cuda.synchronize()
+            th.join()
