@@ -237,7 +237,13 @@ vr_status vr_brickset_decode_range(vr_brickset *bs, int32_t cut_depth, uint8_t *
  * Any stream of the grammar of SURVEY.md Appendix A.4 is accepted, with any distance
  * map: not only what an encoder emits (prunes at any depth, grown branches of any
  * length 0 .. 7, distances of any byte value).  vr_brickset_decode, _decode_lod and
- * _decode_lod_pool then give the values that grammar defines, at every cut.
+ * _decode_lod_pool then give the values that grammar defines, at every cut
+ * (_decode_lod_pool at power-of-two extents only: VR_ERR_UNSUPPORTED otherwise, with
+ * nothing written, whatever installed the streams).  At extents that are not powers
+ * of two, or longer than 1024, the boxes are those of the reference's levelCut: a
+ * leaf box of several cells is halved once per node of its grown branch, the
+ * terminating 3 included, only what is left is written and the other cells are 0,
+ * at every cut (a cut stops the scalar updates, not the halvings).
  * A stream that ends early, has tokens left over or ends inside a grown branch is
  * VR_ERR_FORMAT and leaves the set as it was.
  * Extents that the tiled decoders serve: k_decode_region and k_decode_quad hold the

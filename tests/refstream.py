@@ -15,6 +15,14 @@ gen_stream / gen_levels make streams family by family, level by level in heap or
 stream has up to 18.9 M tokens); decode_levels is the vectorised reference (every cut from one pass);
 decode_recursive is the definition above written down as it reads, for small extents; write_file writes the
 reference's file layout; census says what a stream contains.
+
+General extents (any X, Y, Z; D = floor(log2 X) + floor(log2 Y) + floor(log2 Z)) keep the grammar and
+the values and change the boxes: a box [lo, hi) of more than one cell is cut at (lo + hi) / 2, a box of one cell goes to
+both children, and below a live leaf every branch node (the terminating 3 included) first halves the box like a left
+child; only the terminal node's box is written, the cells that fell out stay 0, and a progressive cut stops the scalar
+updates, never the halvings.  make_general makes such streams (a stream needs only D), decode_recursive_general is that
+definition as it reads, Decoded.at of such a stream the vectorised reference (the per-rank values of decode_levels
+through voxel_geometry and branch_nodes), census_general what the boxes make of a stream.
 """
 import functools
 import struct
@@ -37,6 +45,13 @@ def log2i(n):
 
 def depth_of(dims):
     return sum(log2i(d) for d in dims)
+
+
+def depth_general(dims):
+    """D of any extents: floor(log2 X) + floor(log2 Y) + floor(log2 Z) (depth_of where every extent is a power of two)."""
+    if min(int(d) for d in dims) < 1:
+        raise ValueError("extents %r" % (tuple(dims),))
+    return sum(int(d).bit_length() - 1 for d in dims)
 
 
 def split_axes(dims):
@@ -86,7 +101,7 @@ def write_file(path, dims, tokens, dmap):
     """The reference's file: an 88-byte header (rootMin, rootMax as int64[3], maxDepth, origDepth as int32, X, Y, Z,
     numActive as int64), then dmap[0 .. M], then the packed tokens."""
     X, Y, Z = (int(d) for d in dims)
-    D = depth_of(dims)
+    D = depth_general(dims)
     dmap = np.asarray(dmap, np.uint8)
     assert dmap.size == D + CHAIN + 1
     with open(path, "wb") as f:
@@ -133,11 +148,13 @@ class Levels:
     """A stream in heap order.  tok[d]: uint8 [2^d], the token of every node of depth d, 255 where the node does not
     exist (an ancestor was pruned).  chain_len: int8 [2^D], branch codes below each leaf (-1: the leaf is not live);
     chain_tok: uint8 [2^D][7], those codes (entries at and after chain_len unused).  A live leaf with fewer than seven
-    codes is followed by a terminating 3."""
+    codes is followed by a terminating 3.  general: the boxes are those of the general-extent walk (any X, Y, Z, with
+    D = depth_general); the stream itself knows nothing of them."""
 
-    def __init__(self, dims, tok, chain_len, chain_tok, dmap):
+    def __init__(self, dims, tok, chain_len, chain_tok, dmap, general=False):
         self.dims = tuple(int(d) for d in dims)
-        self.D = depth_of(dims)
+        self.general = bool(general)
+        self.D = depth_general(dims) if general else depth_of(dims)
         self.M = self.D + CHAIN
         self.tok, self.chain_len, self.chain_tok = tok, chain_len, chain_tok
         self.dmap = np.asarray(dmap, np.uint8)
@@ -164,10 +181,10 @@ def _profile(family, D):
     return p
 
 
-def gen_levels(rng, dims, family, law="std", dmap=None):
+def gen_levels(rng, dims, family, law="std", dmap=None, general=False):
     if family not in FAMILIES:
         raise ValueError(family)
-    D = depth_of(dims)
+    D = depth_general(dims) if general else depth_of(dims)       # all a stream needs of the extents
     if dmap is None:
         dmap = gen_dmap(rng, D, law, family)
     prob = _profile(family, D)
@@ -203,7 +220,7 @@ def gen_levels(rng, dims, family, law="std", dmap=None):
         length = rng.choice(8, nl, p=[0.16, 0.12, 0.1, 0.1, 0.1, 0.1, 0.16, 0.16])
     chain_len = np.where(live, length, -1).astype(np.int8)
     chain_tok = np.full((nl, CHAIN), fixed, np.uint8) if fixed is not None else rng.integers(0, 3, (nl, CHAIN)).astype(np.uint8)
-    return Levels(dims, tok, chain_len, chain_tok, dmap)
+    return Levels(dims, tok, chain_len, chain_tok, dmap, general)
 
 
 def assemble(lv):
@@ -267,7 +284,13 @@ class Decoded:
         return np.repeat(v, 1 << (D - cut)) if cut < D else v
 
     def at(self, cut=None):
-        """uint8 [Z][Y][X]: the decode at `cut` (None: full depth)."""
+        """uint8 [Z][Y][X]: the decode at `cut` (None: full depth).  General boxes: a voxel takes the value of the leaf
+        that owns it where that leaf's grown branch has no more nodes than halvings the voxel survives, else 0; the
+        boxes are those of the full walk whatever the cut."""
+        if self.lv.general:
+            g = voxel_geometry(tuple(self.lv.dims))
+            kept = branch_nodes(self.lv)[g.owner] <= g.surv
+            return np.where(kept, self.leaves(cut)[g.owner], 0).astype(np.uint8)
         if self._rank is None:
             self._rank = rank_of_voxels(tuple(self.lv.dims))
         return self.leaves(cut)[self._rank]
@@ -293,6 +316,106 @@ def decode_levels(lv):
         hiC, loC = hiC | hi, loC | lo
         val.append(v.astype(np.uint8))
     return Decoded(lv, val, dict(hi_interior=hiI, lo_interior=loI, hi_chain=hiC, lo_chain=loC))
+
+
+# ---- general extents: the geometry, voxel by voxel and node by node ----
+
+def _split_axis(ext, depth):
+    """ext: int64 [3][n].  (axis [n], more [n]): the axis a box at `depth` is cut on -- depth % 3, advanced cyclically
+    past axes of extent 1 -- and whether it holds more than one cell (only then is it cut)."""
+    n = ext.shape[1]
+    col = np.arange(n)
+    more = ext[0] * ext[1] * ext[2] > 1
+    a = np.full(n, depth % 3, np.int64)
+    for i in (1, 2):
+        a = np.where(more & (ext[a, col] == 1), (depth + i) % 3, a)
+    return a, more
+
+
+class VoxelGeometry:
+    """owner: int64 [Z][Y][X], the rank of the last leaf in preorder whose box of the full walk holds the voxel;
+    surv: int64 [Z][Y][X], how many halvings of that leaf's box along its grown branch the voxel survives (255: all
+    seven); single_at: int64 [Z][Y][X], the depth at which the voxel's box first held one cell (D: not above the
+    leaves)."""
+
+    def __init__(self, owner, surv, single_at):
+        self.owner, self.surv, self.single_at = owner, surv, single_at
+        for a in (owner, surv, single_at):
+            a.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=16)
+def voxel_geometry(dims):
+    """The box rules followed down from the root by every voxel at once: a box of several cells is cut at
+    (lo + hi) / 2 and the voxel goes to its side; a box of one cell goes to both children, of which the later one (bit
+    1) writes last; below depth D every branch node halves the box like a left child, and a voxel in the upper half is
+    dropped at that node."""
+    X, Y, Z = (int(d) for d in dims)
+    D = depth_general(dims)
+    V = X * Y * Z
+    v = np.arange(V, dtype=np.int64)
+    c = np.stack([v % X, (v // X) % Y, v // (X * Y)])
+    col = np.arange(V)
+    lo = np.zeros((3, V), np.int64)
+    hi = np.repeat(np.array([[X], [Y], [Z]], np.int64), V, axis=1)
+    r = np.zeros(V, np.int64)
+    single_at = np.full(V, D, np.int64)
+    for d in range(D):
+        a, more = _split_axis(hi - lo, d)
+        single_at = np.where(~more & (single_at == D), d, single_at)
+        mid = (lo[a, col] + hi[a, col]) // 2
+        up = more & (c[a, col] >= mid)
+        down = more & ~up
+        lo[a[up], col[up]] = mid[up]
+        hi[a[down], col[down]] = mid[down]
+        r = (r << 1) | np.where(more, up, True)
+    surv = np.full(V, 255, np.int64)
+    alive = np.ones(V, bool)
+    for j in range(CHAIN):
+        a, more = _split_axis(hi - lo, D + j)
+        alive = alive & more                       # one cell left: the voxel's own, at every further node
+        mid = (lo[a, col] + hi[a, col]) // 2
+        drop = alive & (c[a, col] >= mid)
+        surv[drop] = j                             # the (j + 1)-th halving drops the voxel
+        alive = alive & ~drop
+        hi[a[alive], col[alive]] = mid[alive]
+    shape = (Z, Y, X)
+    return VoxelGeometry(r.reshape(shape), surv.reshape(shape), single_at.reshape(shape))
+
+
+def branch_nodes(lv):
+    """int64 [2^D]: the nodes of the grown branch below every leaf rank -- its codes and the terminating 3, seven
+    without one -- and 0 where the leaf or an ancestor is pruned (the pruned node writes its whole box)."""
+    cl = lv.chain_len.astype(np.int64)
+    return np.where(cl >= 0, np.minimum(cl + 1, CHAIN), 0)
+
+
+@functools.lru_cache(maxsize=16)
+def node_boxes(dims):
+    """Per depth 0 .. D, in heap order: (lo, hi, cuts), each int64 [3][2^d] -- every node's box [lo, hi) and how often
+    the path to it cut each axis.  Children 2 i and 2 i + 1 are the lower and upper half; a box of one cell is handed to
+    both."""
+    D = depth_general(dims)
+    lo = np.zeros((3, 1), np.int64)
+    hi = np.array([[int(d)] for d in dims], np.int64)
+    cuts = np.zeros((3, 1), np.int64)
+    out = [(lo, hi, cuts)]
+    for d in range(D):
+        n = 1 << d
+        col = np.arange(n)
+        a, more = _split_axis(hi - lo, d)
+        mid = (lo[a, col] + hi[a, col]) // 2
+        lo2, hi2, cuts2 = (np.repeat(t, 2, axis=1) for t in (lo, hi, cuts))
+        hi2[a[more], 2 * col[more]] = mid[more]
+        lo2[a[more], 2 * col[more] + 1] = mid[more]
+        cuts2[a[more], 2 * col[more]] += 1
+        cuts2[a[more], 2 * col[more] + 1] += 1
+        lo, hi, cuts = lo2, hi2, cuts2
+        out.append((lo, hi, cuts))
+    for t in out:
+        for arr in t:
+            arr.setflags(write=False)
+    return out
 
 
 # ---- the definition, as it reads ----
@@ -357,6 +480,92 @@ def decode_recursive(dims, tokens, dmap, cut=None):
     return out
 
 
+def decode_recursive_general(dims, tokens, dmap, cut=None, writes=None):
+    """The same walker over boxes [lo, hi) of any extents, D = depth_general(dims): uint8 [Z][Y][X].  A box of more
+    than one cell is cut at (lo + hi) / 2 on axis depth % 3, advanced cyclically past axes of extent 1; a box of one
+    cell goes to both children unsplit (the later leaf wins); below a live leaf every branch node, the terminating 3
+    included, first halves the box like a left child, and only the terminal node's box is written: the cells that fell
+    out stay 0.  A cut stops the scalar updates, never the halvings.  writes (a list): every write as (lo, hi, value),
+    in order.  Raises ValueError on a stream the grammar does not produce."""
+    import sys
+    X, Y, Z = (int(d) for d in dims)
+    D = depth_general(dims)
+    cut = D + CHAIN if cut is None else int(cut)
+    tokens = [int(t) for t in np.asarray(tokens).reshape(-1)]
+    dmap = [int(t) for t in dmap]
+    out = np.zeros((Z, Y, X), np.uint8)
+    pos = [0]
+
+    def step(v, tok, j):
+        if j > cut or j == 0:
+            return v
+        if tok == 1:
+            return min(v + dmap[j], 255)
+        if tok == 2:
+            return max(v - dmap[j], 0)
+        return v
+
+    def take():
+        if pos[0] >= len(tokens):
+            raise ValueError("the stream ends early")
+        pos[0] += 1
+        return tokens[pos[0] - 1]
+
+    def axis(lo, hi, depth):
+        ext = [hi[k] - lo[k] for k in range(3)]
+        if ext[0] * ext[1] * ext[2] <= 1:
+            return None
+        a, i = depth % 3, 0
+        while ext[a] == 1:
+            i += 1
+            a = (depth + i) % 3
+        return a
+
+    def write(lo, hi, v):
+        out[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]] = v
+        if writes is not None:
+            writes.append((tuple(lo), tuple(hi), v))
+
+    def node(lo, hi, j, parent):
+        tok = take()
+        v = step(parent, tok, j)
+        if tok == 3:
+            write(lo, hi, v)
+            return
+        if j < D:
+            a = axis(lo, hi, j)
+            if a is None:
+                node(lo, hi, j + 1, v)
+                node(lo, hi, j + 1, v)
+                return
+            mid = (lo[a] + hi[a]) // 2
+            left_hi, right_lo = list(hi), list(lo)
+            left_hi[a] = right_lo[a] = mid
+            node(lo, left_hi, j + 1, v)
+            node(right_lo, hi, j + 1, v)
+            return
+        hi = list(hi)
+        for c in range(1, CHAIN + 1):
+            a = axis(lo, hi, D + c - 1)
+            if a is not None:
+                hi[a] = (lo[a] + hi[a]) // 2
+            t = take()
+            if t == 3:
+                break
+            v = step(v, t, D + c)
+        write(lo, hi, v)
+
+    old = sys.getrecursionlimit()
+    sys.setrecursionlimit(max(old, 200 + 4 * D))
+    try:
+        node([0, 0, 0], [X, Y, Z], 0, dmap[0])
+    finally:
+        sys.setrecursionlimit(old)
+    if pos[0] != len(tokens):
+        raise ValueError("tokens left over")
+    return out
+
+
 # ---- what a stream contains ----
 
 def census(lv, dec=None):
@@ -378,7 +587,7 @@ def census(lv, dec=None):
         for d in range(D - 1, D - 13, -1):
             size = np.where(lv.tok[d] == 255, 0, 1 + size[0::2] + size[1::2])
         c["block_tokens"] = size
-        if X >= 128 and Y >= 16 and Z >= 16 and _blocks_are_cubes(lv.dims):
+        if not lv.general and X >= 128 and Y >= 16 and Z >= 16 and _blocks_are_cubes(lv.dims):
             t = lv.tok[D - 12]
             dead = (t == 255) | (t == 3)
             rank = rank_of_voxels(tuple(lv.dims))[::16, ::16, ::16] >> 12
@@ -393,6 +602,37 @@ def census(lv, dec=None):
         for name, a in k.items():
             c["clamp_" + name] = int(a.sum())
     return c
+
+
+def census_general(lv, dec, cut=None):
+    """What the general boxes make of a stream, at one cut of its decode (None: full depth).  dropped: voxels left 0
+    because a halving along their owner's grown branch dropped them (a count of the geometry and the branch lengths:
+    the same at every cut); kept_at_edge / dropped_at_edge: voxels whose owner's branch has exactly as many nodes as
+    halvings they survive (written) / one more (0); multi_writer_cells: cells whose box held one cell above depth D, so that every leaf below
+    that node writes them; overwritten_differently: those of them where some earlier writer's value is not the last
+    one's; pruned_multicell_off_grid: pruned nodes (depth 0 .. D) whose box has several cells and, on some axis cut n
+    times on the way, another extent than X >> n -- boxes no power-of-two brick holds."""
+    D = lv.D
+    g = voxel_geometry(lv.dims)
+    nb = branch_nodes(lv)[g.owner]
+    out = {"voxels": int(g.owner.size), "dropped": int((nb > g.surv).sum()),
+           "kept_at_edge": int((nb == g.surv).sum()), "dropped_at_edge": int((nb == g.surv + 1).sum())}
+    multi = g.single_at < D
+    out["multi_writer_cells"] = int(multi.sum())
+    vals = dec.leaves(cut)
+    differs = 0
+    for d in np.unique(g.single_at[multi]):
+        below = vals.reshape(-1, 1 << (D - int(d)))            # the ranks below every depth-d node, in write order
+        changed = (below != below[:, -1:]).any(axis=1)
+        differs += int(changed[g.owner[multi & (g.single_at == d)] >> (D - int(d))].sum())
+    out["overwritten_differently"] = differs
+    dims = np.array(lv.dims, np.int64)[:, None]
+    n = 0
+    for d, (lo, hi, cuts) in enumerate(node_boxes(lv.dims)):
+        ext = hi - lo
+        n += int(((lv.tok[d] == 3) & (ext.prod(axis=0) > 1) & (ext != (dims >> cuts)).any(axis=0)).sum())
+    out["pruned_multicell_off_grid"] = n
+    return out
 
 
 def _blocks_are_cubes(dims):
@@ -414,3 +654,17 @@ def make(dims, family, law="std"):
     key = (tuple(int(d) for d in dims), family, law)
     seed = zlib.crc32(repr(key + ((SALT[key],) if key in SALT else ())).encode())
     return gen_levels(np.random.default_rng(seed), dims, family, law)
+
+
+# the same for make_general and the census conditions of tests/test_stream_grammar_general_cpu.py
+SALT_GENERAL = {}                                                   # (no draw misses one so far)
+
+
+def make_general(dims, family, law="std"):
+    """The stream of (general dims, family, law) that tests/test_stream_grammar_general_cpu.py and
+    tests/test_gpu_foreign_general.py share: D = depth_general(dims), boxes of the general walk.  Seeded by its own
+    name, apart from make's (a power-of-two extent on the general path, 2048 x 2 x 2, is another stream here)."""
+    import zlib
+    key = ("general", tuple(int(d) for d in dims), family, law)
+    seed = zlib.crc32(repr(key + ((SALT_GENERAL[key],) if key in SALT_GENERAL else ())).encode())
+    return gen_levels(np.random.default_rng(seed), dims, family, law, general=True)
