@@ -184,6 +184,17 @@ typedef struct vr_pool_entry {
     uint8_t shift[3];    /* log2 of the box one stored voxel stands for, per axis (0 = full resolution) */
     uint8_t pad[5];      /* 0 */
 } vr_pool_entry;
+/* The table contract of every pool reader (vr_raycast_pool and its _tf, _tf_shaded, _tf_partial, _tf2d, _tf2d_partial,
+ * _projection and _projection_partial variants, vr_skip_grid_build_pool, vr_histogram_pool).  The pool and the table are
+ * the caller's buffers and need not come from vr_brickset_decode_lod_pool:
+ *  - table_dev 16-byte aligned, else VR_ERR_INVALID, nothing launched (the kernels load an entry as one 16-byte word;
+ *    the struct's own alignment is only 8);
+ *  - pool_dev at any byte, slots at any byte offset, in any order, back to back or apart; several cells may name one slot;
+ *  - an entry with offset >= 0 has shift_k <= log2(brick_dims_k) on every axis and its slot, prod_k(brick_dims_k >>
+ *    shift_k) bytes from pool_dev + offset, lies inside the pool; offset is a full 64-bit byte offset;
+ *  - every negative offset reads as absent (the layout writes -1); an absent entry's shift and every pad are not read.
+ * The entries live on the device and no entry point reads them on the host: the third point is the caller's to keep,
+ * and a table that breaks it makes the kernels read outside the pool. */
 
 /* Host-only: the pool layout of vr_brickset_decode_lod_pool.  Bricks as in vr_assemble_bricks (brick b of brick_dims
  * voxels at cell brick_ijk[3b..3b+2] of `grid`), cuts as in vr_brickset_decode_lod.  The rule:
@@ -410,7 +421,8 @@ vr_status vr_lod_select_error(const vr_brick_error *table, int32_t num_bricks, i
  * X*Y*Z in bin 0, for the pool reads as 0 there, and its pool bytes are not touched.  Per cell and in total the result
  * equals vr_histogram_bricks of that volume laid out brick by brick.  The table is read on the device.  Restrictions:
  * vr_raycast_pool's (power-of-two brick_dims, virtual extents below 2^31), X*Y*Z <= 2^32 - 1 and fewer than 2^31 cells;
- * VR_ERR_INVALID otherwise, for a null pointer, or with both outputs null.  pool_dev at any byte.  Synchronises `stream`.
+ * VR_ERR_INVALID otherwise, for a null pointer, or with both outputs null.  pool_dev at any byte; table_dev 16-byte
+ * aligned, else VR_ERR_INVALID, nothing launched (the table contract, at vr_pool_entry).  Synchronises `stream`.
  *
  * vr_histogram2d: the joint histogram of value and gradient magnitude of a dense volume, the design space of a
  * two-dimensional transfer function.  volume_dev holds the voxels [vol_origin, vol_origin + dims) of a global volume of
@@ -550,7 +562,8 @@ vr_status vr_skip_grid_build(const uint8_t *volume_dev, const int64_t dims[3], i
  * in every mode, with or without a skip grid (one built by vr_skip_grid_build_pool from the same pool and table, or by
  * vr_skip_grid_build from the dense volume: they are byte-identical).  brick_dims must be powers of two and the
  * virtual extents below 2^31; params->vol_origin must be 0 and params->global_dims 0 or the virtual extents, else
- * VR_ERR_INVALID. */
+ * VR_ERR_INVALID.  table_dev 16-byte aligned, else VR_ERR_INVALID, nothing launched -- here and in every vr_raycast_pool_*
+ * call below (the table contract, at vr_pool_entry); pool_dev at any byte. */
 vr_status vr_raycast_pool(const uint8_t *pool_dev, const vr_pool_entry *table_dev, const int64_t brick_dims[3],
                           const int64_t grid[3], const vr_camera *cam, const vr_render_params *params, float *rgba_dev,
                           void *stream);

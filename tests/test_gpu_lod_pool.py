@@ -2,9 +2,13 @@
 (checked against vr_brickset_decode_lod over whole bricks), and vr_raycast_pool / vr_skip_grid_build_pool render and
 bound the pool's virtual volume bit-identically to vr_raycast / vr_skip_grid_build of the dense LOD volume."""
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import refpool  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +55,8 @@ def dense_lod(bs, cuts):
 
 def check_pool(vr, bs, cuts, ijk, grid, pool, table):
     """Every decoded brick's slot holds the min corner of every box of the dense decode, and the dense decode is
-    constant on the boxes; bytes outside the slots keep FILL; the uploaded table is the layout's."""
+    constant on the boxes; bytes outside the slots keep FILL; the uploaded table is the layout's; and the pool read by
+    the header's address formula (refpool.expand) is the dense decode assembled on the grid, 0 where no brick is."""
     from volumerenderer_amd.render import POOL_ENTRY
     info = bs.info(0)
     want_t, nbytes = vr.lod_pool_layout(bs.dims, ijk, grid, cuts, info["orig_tree_depth"], info["max_tree_depth"])
@@ -76,6 +81,12 @@ def check_pool(vr, bs, cuts, ijk, grid, pool, table):
         up = np.repeat(np.repeat(np.repeat(stored, 1 << sz, 0), 1 << sy, 1), 1 << sx, 2)
         assert np.array_equal(up, dense[b]), (b, c, (sx, sy, sz))
     assert np.all(p[~used] == FILL)
+    virtual = np.zeros((grid[2] * Z, grid[1] * Y, grid[0] * X), np.uint8)
+    for b, c in enumerate(cuts):
+        i, j, k = (int(v) for v in ijk[b])
+        if c >= 0:
+            virtual[k * Z:(k + 1) * Z, j * Y:(j + 1) * Y, i * X:(i + 1) * X] = dense[b]
+    assert np.array_equal(refpool.expand(p, got_t, (X, Y, Z), grid), virtual)
 
 
 def run_pool(vr, bs, cuts, ijk, grid, extra=4096, stream=None):
@@ -143,6 +154,39 @@ def test_pool_midrange(vr):
 def test_pool_opened_golden_file(vr):
     bs = vr.BrickSet.open(os.path.join(GOLD, "ref_sphere_n3_16_tol1_ep2.tree.bin"))
     check_all_cuts(vr, bs)
+
+
+# (dims, bricks, grid, their cells): extents that decode through k_decode_lane, down to an extent of 1; a (1, B, 1) grid;
+# a grid with a cell no brick sits on
+SMALL_SETS = [((4, 1, 2), 3, (3, 1, 1), [(0, 0, 0), (1, 0, 0), (2, 0, 0)]),
+              ((8, 8, 8), 4, (1, 4, 1), [(0, 3, 0), (0, 1, 0), (0, 0, 0), (0, 2, 0)]),
+              ((16, 8, 4), 3, (2, 2, 1), [(1, 1, 0), (0, 0, 0), (1, 0, 0)]),
+              ((128, 8, 4), 5, (5, 1, 1), [(b, 0, 0) for b in range(5)])]
+
+
+@pytest.mark.parametrize("dims,B,grid,cells", SMALL_SETS)
+def test_pool_small_extents(vr, dims, B, grid, cells):
+    """Sets of 3 to 5 encoder-built bricks (noise, rm_like, one constant) at every cut 0 .. M and -1, rotating per brick:
+    k_pool_pack's scalar branch (stored rows of 1 and 2 bytes) and its first vector widths (4 and 8)."""
+    X, Y, Z = dims
+    rng = np.random.default_rng(31 + X)
+    vols = [rng.integers(0, 256, (Z, Y, X), dtype=np.uint8), rm_like((Z, Y, X), 5), np.full((Z, Y, X), 77, np.uint8)]
+    vols += [rm_like((Z, Y, X), 6 + b)[::-1].copy() for b in range(B - 3)]
+    bs = vr.BrickSet(B, dims, 1, 2)
+    bs.build(np.stack(vols))
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    choices = [-1] + list(range(M + 1))
+    ijk = np.array(cells, np.int64)
+    rows = set()
+    for r in range(len(choices)):
+        cuts = np.array([choices[(r + 3 * b) % len(choices)] for b in range(B)], np.int32)
+        p, t = run_pool(vr, bs, cuts, ijk, grid, extra=64)
+        check_pool(vr, bs, cuts, ijk, grid, p, t)
+        want_t, _ = vr.lod_pool_layout(dims, ijk, grid, cuts, D, M)
+        rows |= {X >> int(e["shift"][0]) for e in want_t if e["offset"] >= 0}
+    assert rows == {X >> s for s in range(X.bit_length())}, rows       # every stored row length the extent has
+    assert rows >= {1, 2, 4, 8} & {X >> s for s in range(X.bit_length())}
 
 
 def test_pool_general_extents_unsupported(vr):

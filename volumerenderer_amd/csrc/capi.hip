@@ -1326,10 +1326,12 @@ static bool dense_ok(const uint8_t *vol, const int64_t dims[3])
     return true;
 }
 
-// the virtual volume of a pool: power-of-two bricks, extents below 2^31 (tex3d's int indices)
+// the virtual volume of a pool: power-of-two bricks, extents below 2^31 (tex3d's int indices); the table 16-byte
+// aligned (pool_cell loads an entry as one uint4)
 static bool pool_ok(const uint8_t *pool, const vr_pool_entry *table, const int64_t bd[3], const int64_t grid[3])
 {
     if (!pool || !table || !bd || !grid) return false;
+    if (((uintptr_t)table & 15u) != 0) return false;
     for (int k = 0; k < 3; ++k) {
         if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || grid[k] <= 0) return false;
         if (grid[k] >= (1ll << 31) / bd[k]) return false;

@@ -459,6 +459,7 @@ vr_status vr_histogram_pool(const uint8_t *pool, const vr_pool_entry *table, con
                             uint32_t *cells_host, uint64_t *total_host, void *stream)
 {
     if (!pool || !table || !bd || !grid || (!cells_host && !total_host)) return VR_ERR_INVALID;
+    if (((uintptr_t)table & 15u) != 0) return VR_ERR_INVALID;      // the table contract of every pool reader (vrhip.h)
     int64_t V = 1, cells = 1;
     for (int k = 0; k < 3; ++k) {              // vr_raycast_pool's restrictions
         if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || grid[k] <= 0) return VR_ERR_INVALID;

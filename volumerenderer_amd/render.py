@@ -303,7 +303,9 @@ def _check_pool(pool, table, grid, device):
 
 
 def _pool_source(pool, table, brick_dims, grid):
-    """A pool and its table, checked; the source's extents are the virtual volume's."""
+    """A pool and its table, checked; the source's extents are the virtual volume's.  The table contract is vrhip.h's (at
+    vr_pool_entry): any pool and table that keep it, not only decode_lod_pool's; a table that is not 16-byte aligned is
+    refused by the C entry points (VrError, VR_ERR_INVALID)."""
     if not isinstance(pool, torch.Tensor):
         raise ValueError("pool must be a torch tensor")
     _check_pool(pool, table, grid, pool.device)
