@@ -848,7 +848,9 @@ typedef struct vr_slice_plane {
 /* VR_ERR_INVALID (nothing launched) for a null pointer; width, height < 1; layers outside 1 .. 2^24; a filter that is
  * neither value; a non-finite origin, du, dv, dw or box; dims as vr_raycast refuses them; a proj that
  * vr_raycast_projection would refuse.  Then VR_ERR_NO_DEVICE: there is no CPU fallback.  volume_dev may start at any
- * byte.  The _partial call writes the partial instead of the frame: of proj it uses the op. */
+ * byte; rgba_dev / partial_dev at any 4-byte-aligned address (a frame may be a view at any float of an allocation: no
+ * 16-byte alignment is asked for, and nothing outside the width * height * 4 floats is written).  The _partial call writes
+ * the partial instead of the frame: of proj it uses the op. */
 vr_status vr_reslice(const uint8_t *volume_dev, const int64_t dims[3], const vr_slice_plane *plane, const vr_projection *proj,
                      float *rgba_dev, void *stream);
 vr_status vr_reslice_partial(const uint8_t *volume_dev, const int64_t dims[3], const vr_slice_plane *plane,
