@@ -1861,6 +1861,13 @@ __device__ __forceinline__ uint32_t block4_excl_scan_u32(uint32_t v, uint32_t *s
     return woff + incl - v;
 }
 
+// 1: k_prune_emit12 prunes depths D-5 .. D-12 by wave 0 in registers, behind one batch of LDS reads and in front of one
+// workgroup barrier, while waves 1 .. 3 clear the string buffer.  0: the code as it was -- an eight-level LDS loop with
+// a barrier per level that all four waves run -- for a trace of the old behaviour.
+#ifndef VR_PRUNE_CHAIN
+#define VR_PRUNE_CHAIN 1
+#endif
+
 // ---- prune + block-local emit (VolumeKdtree streams with D >= 12: K = 6, Ds = D-6) --------------
 // One block owns a depth-(D-12) subtree: 4096 leaves, 16 per thread.  It prunes the twelve levels
 // bottom-up (the four above the leaves in registers, the other eight in LDS), and then,
@@ -1973,10 +1980,17 @@ __global__ void __launch_bounds__(256, RANGE ? 4 : 6)
 k_prune_emit12(PruneEmitArgs a)
 {
     __shared__ uint32_t lutS[512];                   // grown branch by signed initial error (k_chain_lut)
+#if VR_PRUNE_CHAIN
+    __shared__ __attribute__((aligned(16))) uint32_t W[PE_WORDS];
+    __shared__ __attribute__((aligned(4))) uint8_t codeH[256], codeOldH[256];    // the block's nodes of depths D-12 .. D-5, heap order (1 .. 255)
+    __shared__ __attribute__((aligned(4))) uint8_t fl4H[256];                    // "subtree is a single pruned token" flags of the depth-(D-4) nodes
+    __shared__ __attribute__((aligned(8))) uint16_t cnt4H[256];                  // tokens their subtrees emit when live
+#else
     __shared__ uint32_t W[PE_WORDS];
     __shared__ uint8_t codeH[256], codeOldH[256];    // the block's nodes of depths D-12 .. D-5, heap order (1 .. 255)
     __shared__ uint8_t flH[512];                     // "subtree is a single pruned token" flags; 256 + t = the depth-(D-4) nodes
     __shared__ uint16_t cntH[512];                   // tokens a live subtree emits
+#endif
     __shared__ uint32_t shw[4];
     const int brick = blockIdx.y, t = threadIdx.x, D = a.D, tol = a.tol;
     Ctrl &c = a.ctrls[brick];
@@ -2072,10 +2086,14 @@ k_prune_emit12(PruneEmitArgs a)
         if (t < 64) a.idxOff[(int64_t)brick * a.nIdx + (base >> 6) + t] = VR_IDX_DEAD;
         return;
     }
-    // (the string buffer and the upper codes: only blocks that get here need them -- two thirds leave above -- and
-    // barriers lie between these stores and their first readers)
+    // (the string buffer and the upper codes: only blocks that get here need them.  In a build without
+    // k_prune_emit12_const the exact all-"keep" boxes leave above, two thirds of the bench volume's; in the default
+    // build the constant ones among them have returned before the loads, so a box that loads usually gets here.
+    // Barriers lie between these stores and their first readers)
     { const uint8_t cu = (uint8_t)((upB >> ((int)(niU & 3) * 2)) & 3u); codeH[t] = cu; codeOldH[t] = cu; }
+#if !VR_PRUNE_CHAIN      // (otherwise waves 1 .. 3 clear it while wave 0 prunes the upper levels)
     for (int i = t; i < PE_WORDS; i += 256) W[i] = 0;
+#endif
     // ---- leaves: prune (R.cpp:618-626), grown branches (R.cpp:655-704); sibling leaves share packed 16-bit lanes
     const uint32_t tw[4] = {tv.x, tv.y, tv.z, tv.w}, rw[4] = {rv.x, rv.y, rv.z, rv.w}, pwL[2] = {pv.x, pv.y};
     const uint32_t dR2 = (uint32_t)cDistR * 0x10001u, dC2 = (uint32_t)cDistC * 0x10001u;
@@ -2212,6 +2230,65 @@ k_prune_emit12(PruneEmitArgs a)
 #pragma unroll
     for (int r = 0; r < 2; ++r) cnt3[r] = 1 + ((cnt2[2 * r] + cnt2[2 * r + 1]) & ~__builtin_amdgcn_sbfe((int)F3, 8 * r, 1));
     const int cnt4 = 1 + ((cnt3[0] + cnt3[1]) & ~__builtin_amdgcn_sbfe((int)F4, 0, 1));
+#if VR_PRUNE_CHAIN
+    fl4H[t] = (uint8_t)F4;
+    cnt4H[t] = (uint16_t)cnt4;
+    __syncthreads();
+    // ---- depths D-5 .. D-12 by wave 0 in registers: 255 nodes need no workgroup barrier between their levels.  Lane l
+    // reads everything it will look at in one batch -- flags and counts of the four depth-(D-4) nodes below its two
+    // level-7 nodes, those two codes, and the code of its ancestor at every level above -- computes levels 7 and 6 from
+    // its own registers, and from level 5 up meets its sibling subtree's (flag, count) in the lane at distance 1, 2,
+    // 4, 8 (DPP; all lanes below a node hold the node's result, so any lane of the sibling's group is a partner), the
+    // last two levels from the four rows' values as scalars.  Waves 1 .. 3 clear the string buffer meanwhile; the
+    // barrier behind publishes both.
+    if (t < 64) {
+        const uint32_t fl = *(const uint32_t *)&fl4H[4 * t];
+        const uint2 cn = *(const uint2 *)&cnt4H[4 * t];
+        const uint32_t c7 = *(const uint16_t *)&codeH[128 + 2 * t];
+        uint32_t cA[7];
+#pragma unroll
+        for (int lq = 0; lq < 7; ++lq) cA[lq] = codeH[(1 << lq) + (t >> (6 - lq))];
+        // a node from its code and its children's (pruned flag, count): R.cpp:596-629
+        const auto node = [](uint32_t code, uint32_t fL, uint32_t fR, uint32_t cL, uint32_t cR, uint32_t &f, uint32_t &cnt) -> uint32_t {
+            const uint32_t nc = (fL & fR & (code == 0u ? 1u : 0u)) ? 3u : code;
+            f = nc == 3u ? 1u : 0u;
+            cnt = f ? 1u : 1u + cL + cR;
+            return nc;
+        };
+        uint32_t fA, nA, fB, nB, f, n;
+        const uint32_t cdA = node(c7 & 0xFFu, fl & 1u, (fl >> 8) & 1u, cn.x & 0xFFFFu, cn.x >> 16, fA, nA);
+        const uint32_t cdB = node(c7 >> 8, (fl >> 16) & 1u, fl >> 24, cn.y & 0xFFFFu, cn.y >> 16, fB, nB);
+        *(uint16_t *)&codeH[128 + 2 * t] = (uint16_t)(cdA | (cdB << 8));
+        codeH[64 + t] = (uint8_t)node(cA[6], fA, fB, nA, nB, f, n);
+        uint32_t v = n | (f << 16);              // a count is at most 36863
+#pragma unroll
+        for (int lq = 5; lq >= 2; --lq) {
+            const uint32_t pv = lq == 5 ? dpp_u32<0xB1, 0xf>(v, v)        // quad_perm [1,0,3,2]
+                              : lq == 4 ? dpp_u32<0x4E, 0xf>(v, v)        // quad_perm [2,3,0,1]
+                              : lq == 3 ? dpp_u32<0x141, 0xf>(v, v)       // row_half_mirror: the other quad of my eight
+                                        : dpp_u32<0x140, 0xf>(v, v);      // row_mirror: the other eight of my row
+            const uint32_t nc = node(cA[lq], v >> 16, pv >> 16, v & 0xFFFFu, pv & 0xFFFFu, f, n);
+            v = n | (f << 16);
+            if (nc != cA[lq] && (t & ((2 << (5 - lq)) - 1)) == 0) codeH[(1 << lq) + (t >> (6 - lq))] = 3;
+        }
+        // levels 1 and 0: the four rows' results and the three codes are wave-uniform
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+        const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+        const uint32_t k2 = (uint32_t)__builtin_amdgcn_readlane((int)cA[1], 0), k3 = (uint32_t)__builtin_amdgcn_readlane((int)cA[1], 32);
+        const uint32_t k1 = (uint32_t)__builtin_amdgcn_readlane((int)cA[0], 0);
+        uint32_t f2, n2h, f3, n3h, f1, n1h;
+        const uint32_t cd2 = node(k2, r0 >> 16, r1 >> 16, r0 & 0xFFFFu, r1 & 0xFFFFu, f2, n2h);
+        const uint32_t cd3 = node(k3, r2 >> 16, r3 >> 16, r2 & 0xFFFFu, r3 & 0xFFFFu, f3, n3h);
+        const uint32_t cd1 = node(k1, f2, f3, n2h, n3h, f1, n1h);
+        if (t == 0) {
+            codeH[1] = (uint8_t)cd1; codeH[2] = (uint8_t)cd2; codeH[3] = (uint8_t)cd3;
+            if (!RANGE) a.subTok[(int64_t)brick * a.nEmitBlk + blk] = n1h;
+        }
+    } else {
+        for (int i = t - 64; i < PE_WORDS / 4; i += 192) ((uint4 *)W)[i] = make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+#else
     flH[256 + t] = (uint8_t)F4;
     cntH[256 + t] = (uint16_t)cnt4;
     __syncthreads();
@@ -2228,6 +2305,7 @@ k_prune_emit12(PruneEmitArgs a)
         }
         __syncthreads();
     }
+#endif
     // RANGE: from here on the token VALUES are the range stream's: its own codes, 3 wherever the mid stream pruned
     // (M.cpp:864-865); the shape (which tokens exist) is unchanged because a token is 3 in both streams or in neither
     if (RANGE) {
@@ -2260,7 +2338,9 @@ k_prune_emit12(PruneEmitArgs a)
         const int lq = 31 - __clz(t);
         cset3(Cw, ((int64_t)1 << (D - 12 + lq)) + ((int64_t)blk << lq) + (t - (1 << lq)));
     }
+#if !VR_PRUNE_CHAIN      // (otherwise wave 0 wrote it from its register)
     if (!RANGE && t == 0) a.subTok[(int64_t)brick * a.nEmitBlk + blk] = cntH[1];
+#endif
     // ---- top-down: the block's own token string, root assumed live.  Thread t owns the live nodes whose
     // first leaf is its first leaf: ancestors at in-block level lq (depth D-12+lq) when t % 2^(8-lq) == 0
     const int jmin = t ? 8 - (__ffs(t) - 1) : 0;
