@@ -124,8 +124,12 @@ vr_status vr_download(void *dst_host, const void *src_dev, int64_t bytes, void *
  * max_epochs: 0 .. VR_MAX_EPOCHS.  A build issues max_epochs x origTreeDepth x (3 to 4) launches whatever the data
  * does (no level used more than 13 epochs on the volumes measured), so a larger value is refused
  * with VR_ERR_UNSUPPORTED by vr_brickset_create and vr_brickset_set_max_epochs (the set then keeps its setting),
- * before anything is launched. */
+ * before anything is launched.
+ * num_bricks: 1 .. VR_MAX_BRICKS.  The batched launches carry the brick index on the grid's second axis, which the
+ * device limits (an MI355X reports 65536); a larger set is refused with VR_ERR_UNSUPPORTED here, before the device is
+ * touched, and nothing is ever launched past that limit. */
 #define VR_MAX_EPOCHS 1024
+#define VR_MAX_BRICKS 65535
 vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_t dims[3],
                              int32_t tolerance, int32_t max_epochs, int32_t variant);
 vr_status vr_brickset_destroy(vr_brickset *bs);
@@ -470,7 +474,8 @@ vr_status vr_window_from_histogram(const uint64_t *hist /* 256 */, int32_t first
  * 2^32 voxels, VolumeReader.h:171).  vr_disassemble_bricks is the inverse (global
  * volume -> contiguous bricks), used to feed per-brick trees.  Either buffer may start at any byte (16-byte vector
  * copies where both are 16-byte aligned, byte copies otherwise: no reliance on the hardware's tolerance of misaligned
- * vector loads). */
+ * vector loads).  num_bricks above VR_MAX_BRICKS is VR_ERR_UNSUPPORTED, as for vr_brickset_create and for the same
+ * reason, before the device is touched (a longer brick list goes in several calls). */
 vr_status vr_assemble_bricks(const uint8_t *bricks_dev, int32_t num_bricks, const int64_t brick_dims[3],
                              const int64_t *brick_ijk, const int64_t grid[3], uint8_t *volume_dev, void *stream);
 vr_status vr_disassemble_bricks(const uint8_t *volume_dev, int32_t num_bricks, const int64_t brick_dims[3],

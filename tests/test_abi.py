@@ -35,6 +35,16 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.RenderParams) == 32 + 24 + 48 + 8 + 8
 
 
+def test_header_limits():
+    """The limits a caller may build on: VR_MAX_BRICKS is the largest brick count every batched launch accepts (the brick
+    index is the grid's second axis, of which an MI355X allows 65536)."""
+    hdr = open(os.path.join(ROOT, "include", "vrhip.h")).read()
+    limits = {k: int(v) for k, v in re.findall(r"#define\s+(VR_MAX_\w+|VR_POOL_STAGE_BRICKS)\s+(\d+)", hdr)}
+    assert limits["VR_MAX_BRICKS"] == 65535
+    assert limits["VR_MAX_EPOCHS"] == 1024
+    assert limits["VR_POOL_STAGE_BRICKS"] == 32
+
+
 def test_status_strings(L):
     assert L.vr_status_string(0) == b"ok"
     assert b"no CPU fallback" in L.vr_status_string(-2)
@@ -50,6 +60,7 @@ def test_argument_validation_and_no_cpu_fallback(L):
     assert L.vr_brickset_create(None, 1, dims, 1, 2, 0) == -1           # VR_ERR_INVALID
     assert L.vr_brickset_create(C.byref(h), 1, dims, -1, 2, 0) == -1    # negative tolerance
     assert L.vr_brickset_create(C.byref(h), 1, bad, 1, 2, 0) == -7      # VR_ERR_UNSUPPORTED
+    assert L.vr_brickset_create(C.byref(h), 65536, dims, 1, 2, 0) == -7 and not h   # more than VR_MAX_BRICKS bricks
     # vr_compositor_create_with_transport: argument checks first, whatever the device
     noop = C.CFUNCTYPE(C.c_int32, C.c_void_p)(lambda ctx: 0)
     xfer = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)(lambda *a: 0)

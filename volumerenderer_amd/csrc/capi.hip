@@ -237,6 +237,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
     bool general = !pow2(dims[0]) || !pow2(dims[1]) || !pow2(dims[2]) || dims[0] > 1024 || dims[1] > 1024 || dims[2] > 1024;
     if (dims[0] > (1ll << 20) || dims[1] > (1ll << 20) || dims[2] > (1ll << 20) || dims[0] * dims[1] * dims[2] >= (1ll << 32))
         return VR_ERR_UNSUPPORTED;
+    if (num_bricks > VR_MAX_BRICKS) return VR_ERR_UNSUPPORTED;   // the brick index rides on gridDim.y
     if (!device_ok()) return VR_ERR_NO_DEVICE;
     vr_brickset *h = new (std::nothrow) vr_brickset();
     if (!h) return VR_ERR_OOM;
@@ -1269,6 +1270,7 @@ static vr_status assemble_common(bool toVolume, const uint8_t *src, int32_t nb, 
 {
     if (!src || !dst || !bd || !ijk || !grid || nb <= 0) return VR_ERR_INVALID;
     if (bd[0] % 16 != 0) return VR_ERR_UNSUPPORTED;
+    if (nb > VR_MAX_BRICKS) return VR_ERR_UNSUPPORTED;   // k_assemble has the brick on gridDim.y
     for (int b = 0; b < nb; ++b)
         for (int k = 0; k < 3; ++k)
             if (ijk[3 * b + k] < 0 || ijk[3 * b + k] >= grid[k]) return VR_ERR_INVALID;
