@@ -966,11 +966,13 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
 /* ---- debugging switches (new) ----------------------------------------------------------------------------------
  * Which kernel serves a call is decided by the set's geometry and by a few switches kept IN THE HANDLE: they are
  * initialised from the environment (VRHIP_DECODE_WALK, VRHIP_DECODE_FINE_V1, VRHIP_DECODE_QUAD, VRHIP_NO_SKIP_BLOCKS,
- * VRHIP_NO_UNIFORM_BLOCKS, VRHIP_NO_UNIFORM_DECODE, VRHIP_EST_EXACT_BOUNDS, VRHIP_PYRAMID_BOXES)
+ * VRHIP_NO_UNIFORM_BLOCKS, VRHIP_NO_UNIFORM_DECODE, VRHIP_EST_EXACT_BOUNDS, VRHIP_EST_OLD_SCHEDULE, VRHIP_PYRAMID_BOXES)
  * once, when the set is created, and changed afterwards only through this call -- never by the environment at launch
  * time.  Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks", "no_uniform_blocks",
- * "no_uniform_decode", "est_exact_bounds" (the distance estimator's first round computes exact bounds per node instead
- * of sufficient ones per quad of nodes, and has no fallback budget), "pyramid_boxes" (the pyramid's bottom twelve levels
+ * "no_uniform_decode", "est_exact_bounds" (the distance estimator's quad rounds compute exact bounds per node instead
+ * of sufficient ones per quad of nodes, and have no fallback budget), "est_old_schedule" (every round of the distance
+ * estimator summarises a level to its end, under four candidate thresholds first, instead of a four-candidate round over
+ * the level's first sixteenth, a two-candidate one up to a quarter and a one-candidate round over the bulk), "pyramid_boxes" (the pyramid's bottom twelve levels
  * by one 16^3 box per workgroup also where eight boxes per workgroup apply), "index_per_block" (the decode index of a
  * build by one wave per 4096-leaf block, not 32 blocks per workgroup); any other name is VR_ERR_INVALID.
  * Results never depend on a switch; the tests use them to check the kernels against each other.

@@ -72,7 +72,7 @@ class BrickSet:
         """Debugging switch of this set (vr_brickset_set_switch): which kernel serves the next calls.
 
         Names: "decode_walk", "decode_fine_v1", "decode_quad", "no_skip_blocks", "no_uniform_blocks",
-        "no_uniform_decode", "est_exact_bounds", "pyramid_boxes", "index_per_block" (include/vrhip.h)."""
+        "no_uniform_decode", "est_exact_bounds", "est_old_schedule", "pyramid_boxes", "index_per_block" (include/vrhip.h)."""
         check(self._L.vr_brickset_set_switch(self._h, name.encode(), int(value)), "vr_brickset_set_switch(%s)" % name)
 
     def build(self, voxels, stream=None):

@@ -22,15 +22,16 @@ struct Stream2 {              // one 2-bit stream (mid, or MidRangeTree's half-r
 // Debugging switches: each runs one kernel in place of another on the same data, for the tests to compare.  Read from
 // the environment (VRHIP_<NAME>) ONCE, when a set is created, or set explicitly with vr_brickset_set_switch -- never
 // in a launch path: the kernels a handle uses do not change behind the caller's back.
-#define EST_R0_BUDGET 8          // 8, 16 and 32 measured, 8 kept
+#define EST_QUAD_BUDGET 8        // per brick and level, over its quad rounds (once round 0's: EST_R0_BUDGET).  DESIGN.md 3.2: 8, 16 and 32 measured, 8 kept
 struct Switches {
     bool decodeWalk = false;     // VRHIP_DECODE_WALK: k_decode_tile (no per-4-leaf counts)
     bool decodeFineV1 = false;   // VRHIP_DECODE_FINE_V1: round 1's k_decode_fine
     bool decodeQuad = false;     // VRHIP_DECODE_QUAD: round 2's k_decode_quad instead of k_decode_region
     bool noSkipBlocks = false;   // VRHIP_NO_SKIP_BLOCKS
     bool noUniformBlocks = false; // VRHIP_NO_UNIFORM_BLOCKS: constant 4096-leaf blocks go through k_prune_emit12, not k_prune_emit12_const
-    bool estExactBounds = false; // VRHIP_EST_EXACT_BOUNDS: the estimator's first round runs the exact k_est_summ<false>, with no fallback budget
-    int estBudget = EST_R0_BUDGET; // VRHIP_EST_BUDGET=<n>: node-by-node segments a brick may walk in the estimator's first round (measurement aid)
+    bool estExactBounds = false; // VRHIP_EST_EXACT_BOUNDS: the estimator's quad rounds run the exact k_est_summ<false>, with no fallback budget
+    bool estOldSchedule = false; // VRHIP_EST_OLD_SCHEDULE: every estimator round over the whole level, 4-wide quads first (est_round_plan)
+    int estBudget = EST_QUAD_BUDGET; // VRHIP_EST_BUDGET=<n>: node-by-node segments a brick may walk in a level's quad rounds (measurement aid)
     bool pyramidBoxes = false;   // VRHIP_PYRAMID_BOXES: k_pyramid12 (one box per workgroup) where k_pyramid12_lines applies
     bool indexPerBlock = false;  // VRHIP_INDEX_PER_BLOCK: k_index12_block (a wave per 4096-leaf block) + k_const_finish over every index entry, not k_index12
     bool noUniformDecode = false; // VRHIP_NO_UNIFORM_DECODE: k_decode_region ignores BrickSet::boxUniform (every live box is parsed).  Read per call

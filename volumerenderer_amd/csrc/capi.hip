@@ -254,6 +254,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         w.pyramidBoxes = getenv("VRHIP_PYRAMID_BOXES") != nullptr;
         w.indexPerBlock = getenv("VRHIP_INDEX_PER_BLOCK") != nullptr;
         w.estExactBounds = getenv("VRHIP_EST_EXACT_BOUNDS") != nullptr;
+        w.estOldSchedule = getenv("VRHIP_EST_OLD_SCHEDULE") != nullptr;
         if (const char *eb = getenv("VRHIP_EST_BUDGET")) { const int v = atoi(eb); if (v >= 0) w.estBudget = v; }
     }
     make_geom(b.g, dims);
@@ -322,6 +323,7 @@ vr_status vr_brickset_set_switch(vr_brickset *h, const char *name, int32_t value
     else if (!strcmp(name, "pyramid_boxes")) w.pyramidBoxes = on;
     else if (!strcmp(name, "index_per_block")) w.indexPerBlock = on;
     else if (!strcmp(name, "est_exact_bounds")) w.estExactBounds = on;
+    else if (!strcmp(name, "est_old_schedule")) w.estOldSchedule = on;
     else return VR_ERR_INVALID;
     return VR_OK;
 }

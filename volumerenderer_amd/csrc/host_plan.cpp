@@ -421,6 +421,35 @@ bool read_header(FILE *f, Header &h)
 
 bool write_header(FILE *f, const Header &h) { return fwrite(&h, VR_HEADER_BYTES, 1, f) == 1; }
 
+// ---- the estimator's round plan (the census of threshold trajectories it was chosen from) ----
+// On the bench volume half of the walks never change their threshold and a third of all changes fall into the first
+// sixteenth of a level: a 4-wide prefix round over that sixteenth and a 2-wide one (oriented by the half of its interval
+// the mean sits in) up to a quarter absorb them for a fraction of the level's segments, the bulk gets ONE candidate, a
+// 4-wide quad round picks up the bricks that left it, and 8-wide exact rounds finish what is left.  A prefix shorter than
+// EST_MIN_PREFIX segments is not worth its launches.
+EstPlan est_round_plan(uint32_t nseg, bool oldSchedule)
+{
+    constexpr uint32_t first = VR_EST_HEAD / VR_EST_SEG, EST_MIN_PREFIX = 8;
+    EstPlan p{};
+    const auto add = [&](uint32_t end, int nc, bool quads, int sweeps = 4) { p.r[p.rounds++] = EstRound{end, nc, quads, sweeps}; };
+    if (nseg <= first) return p;
+    if (oldSchedule) {
+        add(nseg, 4, true);
+        add(nseg, 4, false);
+    } else {
+        const uint32_t len = nseg - first;
+        uint32_t at = first;
+        for (const int shift : {4, 2}) {
+            const uint32_t pre = len >> shift;
+            if (pre >= EST_MIN_PREFIX && first + pre > at) { at = first + pre; add(at, shift == 4 ? 4 : 2, true); }
+        }
+        add(nseg, 1, true);
+        add(nseg, 4, true, 16);     // (4 and 8 sweeps measured: DESIGN.md 3.2)
+    }
+    for (int i = 0; i < 3; ++i) add(nseg, VR_EST_CAND, false);
+    return p;
+}
+
 } // namespace vr
 
 // ---- error-bounded selection of cuts: the rule is stated in vrhip.h ("error-bounded level of detail") ----

@@ -90,6 +90,30 @@ struct Pyr12Plan {              // k_pyramid12: the geometry fields of Pyr12Geom
 void make_plans(const Geom &g, int K, bool generalGeom, bool idx64, int64_t treeCap, TilePlan &tile, RegionPlan &region,
                 Pyr12Plan &pyr12);
 
+// ---- the start-distance estimator's rounds (kd_encode.hip "running-mean start distance") ----
+// A level of n > VR_EST_HEAD nodes is nseg = n / VR_EST_SEG segments; the head walk covers the first four.  Round r
+// summarises the segments from where a brick's walk stands up to segEnd under nc candidate thresholds around the
+// brick's current one, and the walk then carries the exact state to segEnd, or to where the threshold leaves the
+// window.  nseg is the same for every brick of a level, so the plan is a host constant per level.  quads: the round may
+// run the byte-quad kernel with sufficient bounds (and counts against the brick's budget of node-by-node segments);
+// the last round never does: it finishes the level whatever happens.  sweeps: segments a workgroup of the summary kernel
+// takes, in eights -- few where most bricks take part, many in a round that picks up the few bricks that left an earlier one
+// (its other workgroups only return).
+constexpr int VR_EST_SEG = 1024, VR_EST_HEAD = 4096, VR_EST_CAND = 8, VR_EST_MAX_ROUNDS = 8;
+struct EstRound { uint32_t segEnd; int32_t nc; bool quads; int32_t sweeps; };
+struct EstPlan { int32_t rounds; EstRound r[VR_EST_MAX_ROUNDS]; };
+// oldSchedule: every round over the whole level, 4-wide quads, 4-wide exact, then 8-wide exact ones
+EstPlan est_round_plan(uint32_t nseg, bool oldSchedule);
+// first threshold of a window of nc candidates around threshold T; `up`: the running mean S / (2C + 1) sits in the
+// upper half of [T, T + 1), which orients a window that has no room for both neighbours
+VR_HD inline int est_window_base(long long T, int up, int nc)
+{
+    long long b = T - (nc >= 8 ? 2 : (nc >= 3 ? 1 : (nc == 2 && !up ? 1 : 0)));
+    if (b < 0) b = 0;
+    if (b > 256 - nc) b = 256 - nc;
+    return (int)b;
+}
+
 // ---- foreign streams (host): one preorder walk over the 2-bit tokens, grammar checked ----
 // Per tree token node(depth, path, pos, tok, val): val is the node's decoded scalar, refined down to depth `cut` only; then
 // pruned(depth, path, val) if the token ends the subtree (a 3), and chain(path) per token of the grown branch below

@@ -28,8 +28,10 @@ struct Ctrl {
     int32_t par, ra, rb;     // physical recon buffer indices: parents, level buffers
     int32_t numReverts;
     int32_t maxErrBefore, maxErrAfter;
-    int32_t estTbase;        // estimator: first candidate threshold of the current level
-    unsigned long long estS; // estimator: exact state after the head segment
+    int32_t estT;            // estimator: the threshold floor(S / (2C + 1)) where the walk stands; the next round's window lies around it
+    int32_t estUp;           // estimator: S / (2C + 1) is in the upper half of [estT, estT + 1) (est_window_base)
+    int32_t estQuadFb;       // estimator: segments of this level walked node by node in quad rounds, against the level's budget
+    unsigned long long estS; // estimator: exact state where the walk stands
     uint32_t estC;
     int32_t estFallbacks;    // segments the estimator had to walk node by node (diagnostic)
     int32_t estSeg;          // estimator: next segment to verify

@@ -493,7 +493,7 @@ __global__ void k_ctrl_init(Ctrl *ctrls, const uint8_t *rootMin, const uint8_t *
     c.par = 0; c.ra = 1; c.rb = 2;
     c.altValid = 0; c.altSel = 0; c.altDist = 0;
     c.numReverts = 0; c.maxErrBefore = 0; c.maxErrAfter = 0;
-    c.estS = 0; c.estC = 0; c.estTbase = 0; c.estFallbacks = 0; c.estSeg = 0; c.estDone = 0; c.emitOverflow = 0;
+    c.estS = 0; c.estC = 0; c.estT = 0; c.estUp = 0; c.estQuadFb = 0; c.estFallbacks = 0; c.estSeg = 0; c.estDone = 0; c.emitOverflow = 0;
     for (int i = 0; i < VR_MAX_DEPTH + 8; ++i) c.distanceMap[i] = 0;
 }
 
@@ -516,10 +516,12 @@ __global__ void k_ctrl_init(Ctrl *ctrls, const uint8_t *rootMin, const uint8_t *
 //               prefix-sums the hypothesised sums, checks A/B for every segment with
 //               its exact start state, commits up to the first failure and walks only
 //               that segment node by node.
-#define EST_SEG 1024
-#define EST_CAND 8          // widest candidate window (records hold EST_CAND entries)
-#define EST_ROUNDS 5        // rounds 0,1 use a 4-wide window, later rounds EST_CAND-wide recentred ones; the last one walks exactly if it must
-#define EST_HEAD 4096
+// The rounds of a level -- which segments, how wide a window, which kernel -- are est_round_plan's (host_plan.cpp):
+// a 4-wide and a 2-wide prefix round, a 1-wide bulk round, a 4-wide one for the bricks that left it, then EST_CAND-wide
+// exact rounds; the last round walks exactly if it must.
+#define EST_SEG VR_EST_SEG
+#define EST_CAND VR_EST_CAND    // widest candidate window (records hold EST_CAND entries)
+#define EST_HEAD VR_EST_HEAD
 
 // Segment summaries of one brick: one plane per candidate, 16 bytes (sumS, sumC, A, B) per segment in it.
 // k_est_summ writes a candidate's record with one 16-byte store (a segment's last lane); the walking wave reads 64
@@ -602,13 +604,13 @@ __device__ inline void est_exact_chain(const uint8_t *__restrict__ T, const uint
     }
 }
 
-// candidate window [base, base+nc) around the current threshold
-__device__ inline int est_window_base(long long T, int nc)
+// where a walk stands, for the next round: the exact state, the threshold and the half of its interval the mean is in
+__device__ inline void est_park(Ctrl &c, unsigned long long S, uint32_t C, uint32_t seg)
 {
-    long long b = T - (nc <= 4 ? 1 : 2);
-    if (b < 0) b = 0;
-    if (b > 256 - nc) b = 256 - nc;
-    return (int)b;
+    const unsigned long long q = 2ull * C + 1ull, T = S / q;
+    c.estS = S; c.estC = C; c.estSeg = (int)seg;
+    c.estT = (int)T;
+    c.estUp = 2ull * (S - T * q) >= q ? 1 : 0;
 }
 
 __device__ inline void est_finish(Ctrl &c, unsigned long long S, uint32_t C, int maxEpochs)
@@ -641,10 +643,9 @@ k_est_head(int d, int maxEpochs, Ctrl *ctrls, const uint8_t *__restrict__ temp, 
     if (lane == 0) {
         if (n <= EST_HEAD) est_finish(c, S, C, maxEpochs);
         else {
-            c.estS = S; c.estC = C;
-            c.estSeg = EST_HEAD / EST_SEG;
+            est_park(c, S, C, EST_HEAD / EST_SEG);
             c.estDone = 0;
-            c.estTbase = est_window_base((long long)(S / (2ull * C + 1ull)), 4);
+            c.estQuadFb = 0;
         }
     }
 }
@@ -703,23 +704,26 @@ __device__ __forceinline__ int seg_min_i32_dpp(int v)
 // is exact.  8 instructions per quad and candidate instead of 9 per node pair.
 template <bool QUADS>
 __global__ void __launch_bounds__(256)
-k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
+k_est_summ(int d, int nc, uint32_t segEnd, int budget, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
            int64_t leafStride, uint32_t *__restrict__ summ, int64_t summStride, SkipBlocks sk)
 {
     constexpr int L = 32, SPW = 64 / L, NP = EST_SEG / 2 / L, TW = NP / 2, PW = NP / 4;   // lanes and pairs per segment, words per lane
     const int brick = blockIdx.y, lane = threadIdx.x & 63, row = lane / L, rl = lane % L;
     const Ctrl &c = ctrls[brick];
-    const uint32_t n = 1u << d;
     // one scalar round trip for the control-block fields, in front of the first branch
-    const int cConst = c.constBrick, cDone = c.estDone, cSeg = c.estSeg, cPar = c.par, cTbase = c.estTbase;
-    if (cConst || cDone) return;
+    const int cConst = c.constBrick, cDone = c.estDone, cSeg = c.estSeg, cPar = c.par, cT = c.estT, cUp = c.estUp, cFb = c.estQuadFb;
+    // (budget >= 0, a quad round: a brick that has spent its level's budget waits for the exact rounds, as k_est_walk does)
+    if (cConst || cDone || (budget >= 0 && cFb > budget)) return;
+    // this round's segments end at segEnd (the level's end or before it): the records behind it are not written, and
+    // k_est_walk reads none of them.  Below, `nseg` is that end
+    const uint32_t nseg = segEnd;
     // segments from where the walk stands (any start, not a multiple of SPW); later rounds run on a small grid
     const uint8_t *Tl = temp + (int64_t)brick * heapStride + ((int64_t)1 << d) + rl * (4 * TW);
     const uint8_t *Pl = (cPar == 0 ? rb.b[0] : (cPar == 1 ? rb.b[1] : rb.b[2])) + (int64_t)brick * leafStride + rl * (4 * PW);
-    const uint32_t nseg = n / EST_SEG, step = gridDim.x * (4u * SPW);
+    const uint32_t step = gridDim.x * (4u * SPW);
     const uint32_t g0 = (uint32_t)cSeg + (blockIdx.x * 4u + (threadIdx.x >> 6)) * SPW;
     // the next segments' bytes are in flight while these are summarised (a wave's load round trip is what bounds
-    // this kernel otherwise).  A segment past the level's end or inside a skipped block (SkipBlocks) loads nothing:
+    // this kernel otherwise).  A segment past the round's end or inside a skipped block (SkipBlocks) loads nothing:
     // its zero bytes are pd = 0 everywhere, which never counts and yields the all-zero record by itself.
     uint4 tN[TW / 4], pN[PW / 4];
     auto fetch = [&](uint32_t g) {
@@ -737,7 +741,7 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
         }
     };
     fetch(g0);
-    const int Tbase = cTbase;
+    const int Tbase = est_window_base(cT, cUp, nc);
     uint32_t *out = summ + (int64_t)brick * summStride * (4 * EST_CAND);
     for (uint32_t g = g0; g < nseg; g += step) {
     uint32_t tw[TW], pw[PW];
@@ -746,7 +750,7 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
 #pragma unroll
     for (int j = 0; j < PW / 4; ++j) { pw[4 * j] = pN[j].x; pw[4 * j + 1] = pN[j].y; pw[4 * j + 2] = pN[j].z; pw[4 * j + 3] = pN[j].w; }
     const uint32_t seg = g + (uint32_t)row;
-    const bool segLive = seg < nseg;         // segments past the level's end store nothing
+    const bool segLive = seg < nseg;         // segments past the round's end store nothing
     // Lane-uniform waves (both segments): every lane's 32 truths are one value and its 16 parents' reconstructions one
     // value -- constant 4096-leaf blocks below their root, see k_fill16.  All pairs of the lane are pair 0 then, and the
     // candidate loop below has a closed form.
@@ -892,8 +896,36 @@ k_est_summ(int d, int nc, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t
     }
 }
 
+// VR_EST_CENSUS (a build of its own, never the library's): k_est_walk logs every segment it walks node by node and
+// where and why every round of every brick ends, for profiles/tools/est_census.py to replay against round plans.
+#ifdef VR_EST_CENSUS
+#define EST_CENSUS_CAP (1u << 22)
+__device__ uint32_t g_estCensusN;
+__device__ uint4 g_estCensus[EST_CENSUS_CAP];
+enum { EC_WALKED = 1, EC_WINDOW = 2, EC_BUDGET = 3, EC_LIMIT = 4, EC_DONE = 5, EC_LAST_RESORT = 6, EC_START = 7 };    // | 256: the mean is in its interval's upper half
+#define EST_UP(S_, C_, T_) (2ull * ((S_) - (unsigned long long)(T_) * (2ull * (C_) + 1ull)) >= 2ull * (C_) + 1ull ? 256u : 0u)
+#define EST_LOG(kind, seg_, T_) do { if (lane == 0) { const uint32_t i_ = atomicAdd(&g_estCensusN, 1u); \
+    if (i_ < EST_CENSUS_CAP) g_estCensus[i_] = make_uint4((uint32_t)brick | ((uint32_t)d << 16) | ((uint32_t)round << 24), (seg_), (uint32_t)(T_), (kind)); } } while (0)
+extern "C" int64_t vr_debug_est_census(uint32_t *out, int64_t capRecords)
+{
+    uint32_t n = 0, zero = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_estCensusN), 4) != hipSuccess) return -1;
+    const int64_t m = n < EST_CENSUS_CAP ? n : EST_CENSUS_CAP;
+    if (m > capRecords) return -2;
+    if (m && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_estCensus), (size_t)m * 16) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_estCensusN), &zero, 4) != hipSuccess) return -1;
+    return n;
+}
+#else
+#define EST_LOG(kind, seg_, T_) do { } while (0)
+#endif
+
+// One wave per brick.  This round's records cover the segments [c.estSeg, segEnd) under the nc thresholds from
+// est_window_base(c.estT, c.estUp, nc) -- k_est_summ derives the same window from the same fields.  The walk stops where
+// the threshold leaves the window, where a quad round's budget is spent, or at segEnd; short of the level's end it
+// parks its state for the next round.  Records at or behind segEnd are stale: no guard below may look past it.
 __global__ void __launch_bounds__(64)
-k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
+k_est_walk(int d, int maxEpochs, int nc, uint32_t segEnd, int round, int lastRound, int budget, Ctrl *ctrls, const uint8_t *__restrict__ temp, int64_t heapStride, ReconBufs rb,
            int64_t leafStride, const uint32_t *__restrict__ summ, int64_t summStride, SkipBlocks sk)
 {
     const int brick = blockIdx.x, lane = threadIdx.x;
@@ -903,13 +935,18 @@ k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, 
     const uint32_t n = 1u << d, nseg = n / EST_SEG;
     const uint32_t *sm = summ + (int64_t)brick * summStride * (4 * EST_CAND);
     if (c.constBrick || c.estDone) return;
+    // budget >= 0 (a quad round, whose records carry sufficient bounds only): the brick's budget of node-by-node
+    // segments is one per level, carried across the quad rounds; once spent, the exact rounds finish the brick
+    const int fb0 = c.estQuadFb;
+    if (budget >= 0 && fb0 > budget) return;
     __shared__ __attribute__((aligned(16))) uint8_t stage[EST_STAGE_NODES + EST_STAGE_NODES / 2];    // est_exact_chain's (a failed segment)
     unsigned long long S = c.estS;
     uint32_t C = c.estC;
-    const int Tbase = c.estTbase;
+    const int Tbase = est_window_base(c.estT, c.estUp, nc);
     long long Tc = (long long)(S / (2ull * C + 1ull));
     uint32_t seg = (uint32_t)c.estSeg;
     int fallbacks = 0;
+    EST_LOG(EC_START | EST_UP(S, C, Tc), seg, Tc);
     // 256 segments per step, four consecutive ones per lane (64 contiguous bytes of its candidate's plane), the next
     // step's records in flight while these are checked (same candidate: the common case).  (64 per step, one per lane:
     // 128 steps of one memory round trip each on the leaf level, 220 us.)
@@ -923,25 +960,32 @@ k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             r[j] = make_uint4(0, 0, 0x80000000u, 0x7FFFFFFFu);          // (sums 0, A = INT_MIN, B = INT_MAX: always true)
-            if (k0 + (uint32_t)j < nseg) r[j] = *(const uint4 *)(sm + est_at((int)ci_, k0 + (uint32_t)j));
+            if (k0 + (uint32_t)j < segEnd) r[j] = *(const uint4 *)(sm + est_at((int)ci_, k0 + (uint32_t)j));
         }
     };
-    while (seg < nseg) {
+    // the next round: new summaries around the threshold of where the walk stands
+    const auto park = [&]() {
+        if (lane == 0) {
+            est_park(c, S, C, seg);
+            c.estFallbacks += fallbacks;
+            if (budget >= 0) c.estQuadFb = fb0 + fallbacks;
+        }
+    };
+    while (seg < segEnd) {
         const long long ci = Tc - Tbase;
-        // budget >= 0 (the first round, whose records carry sufficient bounds only): a brick that has walked more than
-        // `budget` segments node by node leaves the round as if the threshold had left the window, and the next round
-        // continues from here with exact records -- no launch lasts as long as its unluckiest brick
-        if (ci < 0 || ci >= nc || (budget >= 0 && !lastRound && fallbacks > budget)) {   // threshold left the candidate window
-            if (!lastRound) {                // next round: new summaries around the new threshold
-                if (lane == 0) {
-                    c.estS = S; c.estC = C; c.estSeg = (int)seg;
-                    c.estTbase = est_window_base(Tc, ncNext);
-                    c.estFallbacks += fallbacks;
-                }
+        // a brick that has walked more than `budget` segments of the level node by node leaves the quad rounds as if
+        // the threshold had left the window -- no launch lasts as long as its unluckiest brick
+        const bool spent = budget >= 0 && !lastRound && fb0 + fallbacks > budget;
+        if (ci < 0 || ci >= nc || spent) {   // threshold left the candidate window
+            if (!lastRound) {
+                EST_LOG(spent ? EC_BUDGET : EC_WINDOW, seg, Tc);
+                park();
                 return;
             }
+            EST_LOG(EC_LAST_RESORT, seg, Tc);
             est_exact_chain(T, P, d, seg * EST_SEG, n, S, C, lane, sk, brick);   // last resort: walk the rest in order
             fallbacks += (int)(nseg - seg);
+            seg = nseg;
             break;
         }
         uint4 r[4];
@@ -961,7 +1005,7 @@ k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, 
         for (int j = 0; j < 4; ++j) {
             const long long S0 = (long long)S + (long long)eS;
             const long long q = 2ll * ((long long)C + (long long)eC) + 1ll;
-            const bool ok = k0 + (uint32_t)j >= nseg || (S0 - Tc * q >= (long long)(int)r[j].z && S0 - (Tc + 1) * q < (long long)(int)r[j].w);
+            const bool ok = k0 + (uint32_t)j >= segEnd || (S0 - Tc * q >= (long long)(int)r[j].z && S0 - (Tc + 1) * q < (long long)(int)r[j].w);
             if (!ok && failJ == 4) { failJ = j; fS = eS; fC = eC; }
             eS += r[j].x; eC += r[j].y;
         }
@@ -969,7 +1013,7 @@ k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, 
         if (bad == 0ull) {
             S += lane_u32(si, 63);
             C += lane_u32(sci, 63);
-            seg += 256u;
+            seg = seg + 256u < segEnd ? seg + 256u : segEnd;
             continue;
         }
         const int f = __ffsll((long long)bad) - 1;            // the lane of the first segment whose hypothesis fails
@@ -980,7 +1024,14 @@ k_est_walk(int d, int maxEpochs, int nc, int ncNext, int lastRound, int budget, 
         Tc = (long long)(S / (2ull * C + 1ull));
         seg += 1;
         ++fallbacks;
+        EST_LOG(EC_WALKED | EST_UP(S, C, Tc), seg - 1u, Tc);
     }
+    if (seg < nseg) {                        // this round's limit (the host's last round ends at the level's end)
+        EST_LOG(EC_LIMIT, seg, Tc);
+        park();
+        return;
+    }
+    EST_LOG(EC_DONE, seg, Tc);
     if (lane == 0) { est_finish(c, S, C, maxEpochs); c.estFallbacks += fallbacks; c.estDone = 1; }
 }
 
@@ -3367,18 +3418,21 @@ static void compress_stream(BrickSet *bs, Stream2 &s0, hipStream_t st, const uin
         hipLaunchKernelGGL(k_est_head, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, s.ctrl, s.temp, bs->heapStride, rb,
                            bs->reconStride, sk);
         if (n > EST_HEAD) {
-            const int64_t nseg = n / EST_SEG - EST_HEAD / EST_SEG;
-            for (int r = 0; r < EST_ROUNDS; ++r) {
-                const int nc = r < 2 ? 4 : EST_CAND, ncNext = r + 1 < 2 ? 4 : EST_CAND;   // two 4-wide windows, then 8-wide ones
-                // eight segments per workgroup and sweep (two per wave); the first round makes four sweeps
-                const unsigned gx = r == 0 ? cdiv(nseg, 32) : (cdiv(nseg, 8) < 64 ? cdiv(nseg, 8) : 64);
-                // the first round: byte-packed quads with sufficient bounds, and a budget of node-by-node segments per
-                // brick (est_exact_bounds: the exact kernel, no budget); later rounds: exact records
-                const bool quads = r == 0 && !bs->sw.estExactBounds;
-                hipLaunchKernelGGL(quads ? k_est_summ<true> : k_est_summ<false>, dim3(gx, B), dim3(256), 0, st, d, nc, s.ctrl, s.temp,
-                                   bs->heapStride, rb, bs->reconStride, (uint32_t *)estSumm, bs->estSummStride, sk);
-                hipLaunchKernelGGL(k_est_walk, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, nc, ncNext,
-                                   r == EST_ROUNDS - 1 ? 1 : 0, quads ? bs->sw.estBudget : -1, s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride,
+            const vr::EstPlan plan = vr::est_round_plan((uint32_t)(n / EST_SEG), bs->sw.estOldSchedule);
+            for (int r = 0; r < plan.rounds; ++r) {
+                const vr::EstRound &R = plan.r[r];
+                // eight segments per workgroup and sweep (two per wave).  A quad round makes R.sweeps sweeps over the
+                // segments a brick can still have in front of it; the exact rounds behind them run on a small grid
+                const int64_t len = (int64_t)R.segEnd - EST_HEAD / EST_SEG;
+                const unsigned gx = R.quads ? cdiv(len, 8 * R.sweeps) : (cdiv(len, 8) < 64 ? cdiv(len, 8) : 64);
+                // quad rounds: byte-packed quads with sufficient bounds, and the level's budget of node-by-node segments
+                // per brick (est_exact_bounds: the exact kernel, no budget); the rounds behind them: exact records
+                const bool quads = R.quads && !bs->sw.estExactBounds;
+                const int budget = quads ? bs->sw.estBudget : -1;
+                hipLaunchKernelGGL(quads ? k_est_summ<true> : k_est_summ<false>, dim3(gx, B), dim3(256), 0, st, d, R.nc, R.segEnd, budget,
+                                   s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride, (uint32_t *)estSumm, bs->estSummStride, sk);
+                hipLaunchKernelGGL(k_est_walk, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, R.nc, R.segEnd, r,
+                                   r == plan.rounds - 1 ? 1 : 0, budget, s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride,
                                    (const uint32_t *)estSumm, bs->estSummStride, sk);
             }
         }
