@@ -465,6 +465,92 @@ vr_status vr_histogram2d(const uint8_t *volume_dev, const int64_t dims[3], const
 vr_status vr_window_from_histogram(const uint64_t *hist /* 256 */, int32_t first_bin, double lo_fraction,
                                    double hi_fraction, float *window_lo, float *window_hi);
 
+/* ---- iso-surface meshes (new): the surface itself, as indexed watertight triangles -------------------------------------
+ * The mesh of the iso-surface of a dense volume, by one exact rule: counts and indices are integers, a vertex depends
+ * on two voxels alone, and the meshes of disjoint cell boxes concatenate to the mesh of the whole.  Nothing below
+ * depends on the launch shape; two calls on the same input write the same bytes.
+ *
+ * Lattice.  The lattice points are the voxel centres of the global volume of G = global_dims voxels (an extent of 0
+ * means dims' own); v(q) is the voxel at q.  With cap == 0 the lattice is 0 .. G_k - 1 per axis.  With cap == 1 it is
+ * -1 .. G_k, and v(q) = 0 wherever a coordinate is -1 or G_k: capping closes every surface at the volume's faces.
+ *
+ * Inside test.  level = iso_value * 255.0f, a float32 product (iso_value as in vr_render_params);
+ * inside(q) = (float)v(q) >= level, the side the iso-surface marcher calls ">= iso".
+ *
+ * Cells.  A cell is the cube with low corner c; cells exist for 0 <= c_k <= G_k - 2 without cap and for
+ * -1 <= c_k <= G_k - 1 with it.  Every cell is split into the six Kuhn tetrahedra around its main diagonal: for each
+ * permutation pi of the axes in lexicographic order (xyz, xzy, yxz, yzx, zxy, zyx) the tetrahedron
+ * a0 = c, a1 = a0 + e_pi1, a2 = a1 + e_pi2, a3 = c + (1,1,1).  The split is translation invariant, so neighbouring cells
+ * agree on their shared faces: there are no ambiguous cases.
+ *
+ * Edge vertices.  A lattice edge is (p, d), d in {0,1}^3 \ 0, owned by its low endpoint p; its type is
+ * e = d_x + 2 d_y + 4 d_z - 1, in 0 .. 6.  It carries a vertex iff inside(p) != inside(p + d).  The vertex is
+ * pos_k = (float)p_k + (d_k ? t : 0.0f) with t = (level - (float)v(p)) / ((float)v(p + d) - (float)v(p)), one correctly
+ * rounded float32 division.  Positions are in voxel-centre index coordinates: texture space is (pos + 0.5) / G, and the
+ * renderer's world cube is that minus 0.5.
+ *
+ * Triangles of one tetrahedron.  m_i = inside(a_i); (i, j) with i < j names the edge (a_i, a_j - a_i).
+ *   all four corners equal: no triangle;
+ *   one corner i differs from the other three: one triangle with the corners (i, j), j != i ascending;
+ *   two inside i < j and two outside k < l: the quad q = (i,k), (i,l), (j,l), (j,k) gives (q0,q1,q2) and (q0,q2,q3).
+ * A triangle winds counter-clockwise seen from the outside (the lower-value side).  Where the order above winds the
+ * other way the single triangle swaps its last two corners, and the quad becomes (q0,q3,q2), (q0,q2,q1).  The winding
+ * depends on (pi, m) alone, not on t.
+ *
+ * Ownership and order.  The call owns the cells own_lo <= c < own_hi (global cell coordinates); a box that is empty on
+ * some axis is allowed and gives an empty mesh.
+ *   triangles: those of the owned cells, ordered by cell (x fastest), then tetrahedron, then the order above;
+ *   vertices: every crossing edge whose two endpoints lie in the closed point box [own_lo, own_hi] -- exactly the edges
+ *     of the owned cells -- ordered by owner point (x fastest over that point box), then type e.  Indices are uint32
+ *     into this list: a vertex shared by up to six triangles is stored once.
+ *
+ * Gradients (optional).  One float3 per vertex, g = ga + t * (gb - ga) per component in that operation order, ga and gb
+ * the integer central differences v^(q + e_k) - v^(q - e_k) at the edge's two endpoints; v^ = v with the indices clamped
+ * to [0, G - 1] when cap == 0, zero-extended outside the volume when cap == 1.  The same integers as the lit marcher's
+ * and the joint histogram's.  Unnormalised and exact; -g is the outward normal.
+ *
+ * Workspace.  N = the number of points of the own point box, the product of own_hi_k - own_lo_k + 1 (0 for a box empty
+ * on some axis); R = ceil(N / 64) runs of 64 points; B = ceil(R / 1024).  With up16 rounding up to a multiple of 16,
+ *   bytes = up16(2 N) + 2 up16(4 R) + 16 B + 16:
+ * per point a 16-bit word (the 7-bit mask of its crossing edges and the 9-bit count of the vertices before it in its
+ * run), per run a 32-bit first vertex and first triangle, per 1024 runs two 64-bit sums, and the two totals.  About
+ * 2.13 bytes per point.  workspace_dev must be 16-byte aligned.
+ *
+ * vr_isomesh_workspace_bytes is host-only.  vr_isomesh_count fills the workspace and reports {vertices, triangles} as
+ * 64-bit counts; it synchronises `stream`.  More than VR_ISOMESH_MAX_VERTICES vertices or VR_ISOMESH_MAX_TRIANGLES
+ * triangles: VR_ERR_UNSUPPORTED, with the counts still reported.  A box of more than 2^36 points: VR_ERR_UNSUPPORTED.
+ * vr_isomesh_emit takes the same volume and desc as the count, and the counts it reported: positions_dev 3 floats per
+ * vertex, gradients_dev likewise or NULL, indices_dev 3 uint32 per triangle; asynchronous on `stream`.  Every store is
+ * guarded by the two counts passed in: a stale or foreign workspace can produce a wrong mesh, never a write outside
+ * the three outputs.  The three outputs may be 4-byte aligned; volume_dev may start at any byte.  Zero counts launch
+ * nothing and return VR_OK; positions_dev may be NULL where num_vertices is 0, indices_dev where num_triangles is 0.
+ *
+ * VR_ERR_INVALID, nothing launched, before VR_ERR_NO_DEVICE: a null pointer; a workspace that is not 16-byte or an
+ * output that is not 4-byte aligned; dims or global_dims as vr_raycast refuses them; a local volume that leaves the
+ * global one; cap not 0 or 1; iso_value not finite; per axis an own box outside the cell range of its cap setting
+ * (own_lo < 0 or own_hi > G - 1 without cap, own_lo < -1 or own_hi > G with it) or with own_lo > own_hi; a held volume
+ * that does not contain every in-volume point of [own_lo, own_hi]: max(own_lo, 0) < vol_origin or
+ * min(own_hi, G - 1) > vol_origin + dims - 1; with gradients_dev, the same with the box grown by one point on both
+ * sides; counts that are negative or beyond the two limits.  With these checks no kernel can form an address outside
+ * volume_dev.  A slab of several GPUs holds the points of its own box, and one layer more for gradients; the ranks'
+ * meshes concatenate (seam vertices are stored by both neighbours, bit for bit equal). */
+#define VR_ISOMESH_MAX_VERTICES  4294967295ull     /* 2^32 - 1 */
+#define VR_ISOMESH_MAX_TRIANGLES 1431655765ull     /* 2^32 / 3 */
+typedef struct vr_isomesh_desc {
+    float   iso_value;
+    int32_t cap;                /* 0 or 1 */
+    int64_t global_dims[3];     /* 0 = dims */
+    int64_t vol_origin[3];
+    int64_t own_lo[3];          /* owned cells, global cell coordinates: own_lo <= c < own_hi */
+    int64_t own_hi[3];
+} vr_isomesh_desc;              /* 104 bytes */
+vr_status vr_isomesh_workspace_bytes(const int64_t dims[3], const vr_isomesh_desc *desc, int64_t *bytes);
+vr_status vr_isomesh_count(const uint8_t *volume_dev, const int64_t dims[3], const vr_isomesh_desc *desc,
+                           void *workspace_dev, uint64_t counts_host[2], void *stream);
+vr_status vr_isomesh_emit(const uint8_t *volume_dev, const int64_t dims[3], const vr_isomesh_desc *desc,
+                          const void *workspace_dev, int64_t num_vertices, int64_t num_triangles, float *positions_dev,
+                          float *gradients_dev /* or NULL */, uint32_t *indices_dev, void *stream);
+
 /* ---- ingest: VolumeReader<T>::LoadBricksToTexture (VolumeReader.h:151-223) ------
  * Places brick b (brick_dims, x-fastest, contiguous at bricks_dev + b*brick_voxels)
  * at grid cell brick_ijk[3*b..3*b+2] of a global x-fastest volume of
@@ -978,7 +1064,9 @@ vr_status vr_brickset_set_compaction(vr_brickset *bs, int32_t on_build);
  * Results never depend on a switch; the tests use them to check the kernels against each other.
  * vr_debug_set: process-wide switches that belong to no set: "skip_grid_v1"; "reslice_tile_w" = 8, 16 or 64, the width of
  * the 64-pixel tile a wave of vr_reslice covers (16 is the default, chosen by measurement: DESIGN.md 3.5g); "hist_plain" = 1
- * runs the histogram kernels without their data-aware paths (the same counts; DESIGN.md 3.5i prices them with it). */
+ * runs the histogram kernels without their data-aware paths (the same counts; DESIGN.md 3.5i prices them with it);
+ * "mesh_count_only" = 1 makes vr_isomesh_count stop after its per-point pass -- it reports zero counts and leaves the
+ * workspace unscanned -- so that profiles/tools/mesh_bench.py can price the scans. */
 vr_status vr_brickset_set_switch(vr_brickset *bs, const char *name, int32_t value);
 vr_status vr_debug_set(const char *name, int32_t value);
 

@@ -25,7 +25,8 @@ def __getattr__(name):  # torch is imported lazily so that `import volumerendere
                 "composite_finish_proj", "SlicePlane", "reslice", "reslice_partial", "select_lod_error", "rate_distortion",
                 "histogram_bricks", "histogram", "histogram_pool", "histogram2d", "window_from_histogram",
                 "projection_from_histogram", "TransferFunction2D", "tf2d_separable_table", "raycast_tf2d",
-                "raycast_pool_tf2d", "raycast_tf2d_partial", "raycast_pool_tf2d_partial"):
+                "raycast_pool_tf2d", "raycast_tf2d_partial", "raycast_pool_tf2d_partial", "IsoMesh", "isosurface_mesh",
+                "write_ply", "read_ply"):
         from . import render
         return getattr(render, name)
     raise AttributeError(name)

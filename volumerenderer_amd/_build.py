@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvrhip.so")
 SOURCES = ["kd_encode.hip", "kd_decode.hip", "raymarch.hip", "capi.hip", "compositor.hip", "error_table.hip", "histogram.hip",
-           "kd_index.hip", "host_plan.cpp"]
+           "kd_index.hip", "isomesh.hip", "host_plan.cpp"]
 HEADERS = ["kd_common.h", "brickset.h", "host_plan.h", "raymarch.h", os.path.join("..", "..", "include", "vrhip.h")]
 # -ffp-contract=off: the gradient-descent control kernel and the ray marcher must round
 # exactly like the reference's scalar code (no FMA contraction).

@@ -92,6 +92,12 @@ class BrickError(C.Structure):
     _fields_ = [("sum_abs", C.c_uint64), ("sum_sq", C.c_uint64), ("max_abs", C.c_uint32), ("num_diff", C.c_uint32)]
 
 
+class IsoMeshDesc(C.Structure):
+    """vr_isomesh_desc (104 bytes)."""
+    _fields_ = [("iso_value", C.c_float), ("cap", C.c_int32), ("global_dims", C.c_int64 * 3), ("vol_origin", C.c_int64 * 3),
+                ("own_lo", C.c_int64 * 3), ("own_hi", C.c_int64 * 3)]
+
+
 # every symbol include/vrhip.h declares, with its signature
 _P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -143,6 +149,9 @@ SIGNATURES = {
     "vr_histogram_pool": (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), _P, _P, _P]),
     "vr_histogram2d": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_window_from_histogram": (_I32, [_P, _I32, C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "vr_isomesh_workspace_bytes": (_I32, [C.POINTER(_I64), C.POINTER(IsoMeshDesc), C.POINTER(_I64)]),
+    "vr_isomesh_count": (_I32, [_P, C.POINTER(_I64), C.POINTER(IsoMeshDesc), _P, C.POINTER(C.c_uint64), _P]),
+    "vr_isomesh_emit": (_I32, [_P, C.POINTER(_I64), C.POINTER(IsoMeshDesc), _P, _I64, _I64, _P, _P, _P, _P]),
     "vr_assemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_disassemble_bricks": (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "vr_raycast": (_I32, [_P, C.POINTER(_I64), C.POINTER(Camera), C.POINTER(RenderParams), _P, _P]),

@@ -345,6 +345,7 @@ vr_status vr_debug_set(const char *name, int32_t value)
         return VR_OK;
     }
     if (!strcmp(name, "hist_plain")) { vr::g_histPlain.store(value ? 1 : 0); return VR_OK; }
+    if (!strcmp(name, "mesh_count_only")) { vr::g_meshCountOnly.store(value ? 1 : 0); return VR_OK; }
     return VR_ERR_INVALID;
 }
 

@@ -65,5 +65,6 @@ bool projection_ok(const vr_projection *);
 extern std::atomic<int> g_skipGridV1;
 extern std::atomic<int> g_resliceTileLog2;
 extern std::atomic<int> g_histPlain;          // histogram.hip: the kernels without their data-aware paths
+extern std::atomic<int> g_meshCountOnly;      // isomesh.hip: vr_isomesh_count without its scans (for measurements)
 
 } // namespace vr

@@ -131,6 +131,30 @@ def slab_voxels(dims, axis, rank, world, halo=1):
     return tuple(org), tuple(lo), tuple(hi), local, held
 
 
+def slab_cells(dims, axis, rank, world, cap=False, gradients=False):
+    """slab_voxels' twin for the cell-space call (render.isosurface_mesh): rank `rank`'s slab when the CELLS of a volume
+    of `dims` voxels are cut into `world` slabs along `axis`.  Along an axis of G voxels there are G - 1 cells from 0
+    without cap and G + 1 cells from -1 with it; shard_range cuts them.  Returns (vol_origin, own_lo, own_hi,
+    local_dims, (a0, a1)): the rank owns the cells own_lo <= c < own_hi (global cell coordinates) and holds the voxels
+    [a0, a1) along `axis` -- every in-volume point of the closed point box [own_lo, own_hi], and one layer more on both
+    sides with `gradients` (vrhip.h).  The own boxes of the ranks tile the cell range, so the ranks' meshes
+    concatenate with no exchange (render.IsoMesh.concat); a rank beyond the number of cells owns an empty box."""
+    dims = [int(q) for q in dims]
+    if len(dims) != 3 or any(q < 1 for q in dims) or axis not in (0, 1, 2) or world < 1 or not 0 <= rank < world:
+        raise ValueError("slab_cells: axis %r, rank %r of %r, extents %r" % (axis, rank, world, dims))
+    n, grow = dims[axis], 1 if gradients else 0
+    first, cells = (-1, n + 1) if cap else (0, n - 1)
+    s0, s1 = shard_range(cells, rank, world)
+    lo = [-1, -1, -1] if cap else [0, 0, 0]
+    hi = list(dims) if cap else [q - 1 for q in dims]
+    lo[axis], hi[axis] = first + s0, first + s1
+    a0 = min(max(lo[axis] - grow, 0), n - 1)
+    a1 = max(min(hi[axis] + grow, n - 1), a0) + 1
+    org, local = [0, 0, 0], list(dims)
+    org[axis], local[axis] = a0, a1 - a0
+    return tuple(org), tuple(lo), tuple(hi), tuple(local), (a0, a1)
+
+
 def histogram_all_reduce(hist, group=None):
     """The sum of every rank's histogram (any of render's tables: counts add exactly): an int64 all-reduce over `group`
     (None: the default group).  Without a process group -- torch.distributed not initialised -- it is the identity.

@@ -986,6 +986,156 @@ def projection_from_histogram(hist, op="max", first_bin=0, lo_fraction=0.01, hi_
     return Projection(op, window_from_histogram(hist, first_bin, lo_fraction, hi_fraction), background, lut, device)
 
 
+class IsoMesh:
+    """An indexed triangle mesh of an iso-surface (vrhip.h "iso-surface meshes"), device tensors: `positions` (V, 3)
+    float32 in voxel-centre index coordinates, `gradients` (V, 3) float32 or None (unnormalised, exact; -g points
+    outwards), `triangles` (T, 3) int32 holding the uint32 indices' bits (torch has no arithmetic on uint32 here; an index
+    below 2^31 reads as itself, `triangles.to(torch.int64) & 0xFFFFFFFF` is exact for all)."""
+
+    def __init__(self, positions, gradients, triangles):
+        self.positions, self.gradients, self.triangles = positions, gradients, triangles
+
+    @property
+    def num_vertices(self):
+        return int(self.positions.shape[0])
+
+    @property
+    def num_triangles(self):
+        return int(self.triangles.shape[0])
+
+    def world_positions(self, global_dims):
+        """The positions in the renderer's world cube: (pos + 0.5) / G - 0.5."""
+        G = torch.tensor(_int3(global_dims, "global_dims"), dtype=torch.float32, device=self.positions.device)
+        return (self.positions + 0.5) / G - 0.5
+
+    def normals(self):
+        """Unit outward normals, -g / |g|; zero where g is zero.  ValueError for a mesh made without gradients."""
+        if self.gradients is None:
+            raise ValueError("IsoMesh.normals: the mesh has no gradients (isosurface_mesh(..., gradients=True))")
+        n = torch.linalg.vector_norm(self.gradients, dim=1, keepdim=True)
+        return torch.where(n > 0, -self.gradients / torch.where(n > 0, n, torch.ones_like(n)), torch.zeros_like(self.gradients))
+
+    @staticmethod
+    def concat(meshes):
+        """One mesh of several (the meshes of disjoint cell boxes, e.g. of the ranks' slabs): vertices and triangles
+        appended in order, the indices rebased.  Seam vertices stay duplicated."""
+        meshes = list(meshes)
+        if not meshes:
+            raise ValueError("IsoMesh.concat: no meshes")
+        with_g = [m.gradients is not None for m in meshes]
+        if any(with_g) != all(with_g):
+            raise ValueError("IsoMesh.concat: some meshes have gradients and some have none")
+        if sum(m.num_vertices for m in meshes) > 0xFFFFFFFF:
+            raise ValueError("IsoMesh.concat: more than 2^32 - 1 vertices")
+        tris, base = [], 0
+        for m in meshes:
+            off = base - (1 << 32) if base >= 1 << 31 else base          # the same bits as an int32
+            tris.append(m.triangles + off)
+            base += m.num_vertices
+        return IsoMesh(torch.cat([m.positions for m in meshes]),
+                       torch.cat([m.gradients for m in meshes]) if all(with_g) else None, torch.cat(tris))
+
+
+def isomesh_desc(dims, iso_value, cap=False, gradients=False, global_dims=None, vol_origin=(0, 0, 0), own_lo=None, own_hi=None):
+    """The checked vr_isomesh_desc of isosurface_mesh's arguments (ValueError for what the C call would refuse)."""
+    d = _int3(dims, "dims")
+    G = d if global_dims is None else tuple(g or q for g, q in zip(_int3(global_dims, "global_dims"), d))
+    org = _int3(vol_origin, "vol_origin")
+    cap = bool(cap)
+    lo = ((-1,) * 3 if cap else (0,) * 3) if own_lo is None else _int3(own_lo, "own_lo")
+    hi = (G if cap else tuple(g - 1 for g in G)) if own_hi is None else _int3(own_hi, "own_hi")
+    iso = float(iso_value)
+    if not math.isfinite(iso) or abs(iso) > 3.4028234663852886e38:      # (the desc carries it as a float32)
+        raise ValueError("isosurface_mesh: iso_value %r is not finite" % (iso_value,))
+    grow = 1 if gradients else 0
+    for k in range(3):
+        end = org[k] + d[k]
+        if not (0 < d[k] < 1 << 31 and 0 < G[k] < 1 << 31 and 0 <= org[k] and end <= G[k]):
+            raise ValueError("isosurface_mesh: axis %d: %d voxels at %d of %d" % (k, d[k], org[k], G[k]))
+        if not ((-1 if cap else 0) <= lo[k] <= hi[k] <= (G[k] if cap else G[k] - 1)):
+            raise ValueError("isosurface_mesh: axis %d: own cells [%d, %d) of the cells [%d, %d)"
+                             % (k, lo[k], hi[k], -1 if cap else 0, G[k] if cap else G[k] - 1))
+        if max(lo[k] - grow, 0) < org[k] or min(hi[k] + grow, G[k] - 1) > end - 1:
+            raise ValueError("isosurface_mesh: axis %d: the volume holds [%d, %d), not every point of [%d, %d]%s"
+                             % (k, org[k], end, lo[k], hi[k], " grown by one for the gradients" if grow else ""))
+    desc = _lib.IsoMeshDesc()
+    desc.iso_value, desc.cap = iso, int(cap)
+    desc.global_dims[:], desc.vol_origin[:], desc.own_lo[:], desc.own_hi[:] = G, org, lo, hi
+    return desc
+
+
+def isosurface_mesh(volume, dims, iso_value, cap=False, gradients=False, global_dims=None, vol_origin=(0, 0, 0), own_lo=None,
+                    own_hi=None, stream=None):
+    """The iso-surface of a dense device volume as an IsoMesh (vr_isomesh_count + vr_isomesh_emit; the rule is in
+    vrhip.h).  `volume` holds the voxels [vol_origin, vol_origin + dims) of a volume of `global_dims` (default: dims);
+    the call owns the cells own_lo <= c < own_hi in global cell coordinates (default: every cell; with cap=True the
+    cells from -1 to G, which close the surface at the volume's faces).  iso_value as in RenderParams: the surface is
+    at iso_value * 255.  The meshes of disjoint own boxes (distributed.slab_cells) concatenate to the whole mesh
+    (IsoMesh.concat).  ValueError before any C call for arguments the library would refuse."""
+    desc = isomesh_desc(dims, iso_value, cap, gradients, global_dims, vol_origin, own_lo, own_hi)
+    held = volume.numel() if isinstance(volume, torch.Tensor) else np.size(volume)
+    if held != math.prod(_int3(dims, "dims")):
+        raise ValueError("isosurface_mesh: %d voxels do not fill dims %r" % (held, tuple(dims)))
+    src = _dense_source(volume, _int3(dims, "dims"))
+    L, st = _lib.lib(), _stream_ptr(stream)
+    nbytes = C.c_int64()
+    check(L.vr_isomesh_workspace_bytes(src.args[1], C.byref(desc), C.byref(nbytes)), "vr_isomesh_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=src.device)
+    counts = (C.c_uint64 * 2)()
+    check(L.vr_isomesh_count(src.args[0], src.args[1], C.byref(desc), _ptr(ws), counts, st), "vr_isomesh_count")
+    V, T = int(counts[0]), int(counts[1])
+    pos = torch.empty((V, 3), dtype=torch.float32, device=src.device)
+    grad = torch.empty((V, 3), dtype=torch.float32, device=src.device) if gradients else None
+    tri = torch.empty((T, 3), dtype=torch.int32, device=src.device)
+    if V or T:
+        check(L.vr_isomesh_emit(src.args[0], src.args[1], C.byref(desc), _ptr(ws), V, T, _ptr(pos),
+                                _ptr(grad) if gradients else None, _ptr(tri), st), "vr_isomesh_emit")
+        if stream is not None:
+            ws.record_stream(stream)                   # (emit is asynchronous: the workspace outlives this call)
+    return IsoMesh(pos, grad, tri)
+
+
+def write_ply(path, mesh):
+    """Writes an IsoMesh as a binary little-endian PLY: x y z (and nx ny nz, the unit outward normals, where the mesh has
+    gradients) as float32 per vertex, then every face as a uchar 3 and three uint32 indices.  Host side."""
+    pos = mesh.positions.detach().cpu().numpy().astype("<f4")
+    tri = (mesh.triangles.detach().cpu().numpy().astype(np.int64) & 0xFFFFFFFF).astype("<u4")
+    cols = [pos]
+    head = ["ply", "format binary_little_endian 1.0", "comment volumerenderer_amd iso-surface mesh",
+            "element vertex %d" % len(pos), "property float x", "property float y", "property float z"]
+    if mesh.gradients is not None:
+        cols.append(mesh.normals().detach().cpu().numpy().astype("<f4"))
+        head += ["property float nx", "property float ny", "property float nz"]
+    head += ["element face %d" % len(tri), "property list uchar uint vertex_indices", "end_header"]
+    faces = np.empty(len(tri), dtype=[("n", "u1"), ("v", "<u4", (3,))])
+    faces["n"], faces["v"] = 3, tri
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(np.ascontiguousarray(np.concatenate(cols, axis=1)).tobytes())
+        f.write(faces.tobytes())
+
+
+def read_ply(path):
+    """What write_ply wrote, back as numpy arrays: (positions (V, 3) float32, normals (V, 3) float32 or None,
+    triangles (T, 3) uint32).  Reads only files of write_ply's own layout."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii").split("\n")
+    if head[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError("read_ply: %s is not a binary little-endian PLY" % path)
+    nv = next(int(h.split()[2]) for h in head if h.startswith("element vertex"))
+    nf = next(int(h.split()[2]) for h in head if h.startswith("element face"))
+    ncol = sum(1 for h in head if h.startswith("property float"))
+    if ncol not in (3, 6) or len(raw) != end + nv * ncol * 4 + nf * 13:
+        raise ValueError("read_ply: %s does not have write_ply's layout" % path)
+    v = np.frombuffer(raw, "<f4", nv * ncol, end).reshape(nv, ncol)
+    faces = np.frombuffer(raw, np.dtype([("n", "u1"), ("v", "<u4", (3,))]), nf, end + nv * ncol * 4)
+    if nf and (faces["n"] != 3).any():
+        raise ValueError("read_ply: %s has faces that are not triangles" % path)
+    return v[:, :3].copy(), (v[:, 3:].copy() if ncol == 6 else None), faces["v"].astype(np.uint32)
+
+
 def fill_volume_brick_map(ni=8, nj=8, nk=15):
     """fillVolumeBrickMap (main.cpp:599-619): brick b -> (i, j, k), i fastest."""
     m = {}
