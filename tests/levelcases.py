@@ -106,7 +106,7 @@ def decisions(tree, max_epochs=None, stream=0):
 def alt_epoch(tree, max_epochs=None):
     """Which of k_control's three selections the LAST epoch of the leaf level falls under: "alt_minus", "alt_plus",
     "alt_neither", or None where the leaf level never reaches its last epoch with a fill.  Meaningful for leafless
-    builds (D >= 12, max_epochs >= 1: brickset.h leafless_build).
+    builds (D >= 12, max_epochs >= 1: host_plan.cpp BuildPlan::leafless).
 
     Reads: the kind-1 (fill) records of depth D, their `epoch` and `distance`.  Every epoch that is entered and does
     not stop at "same distance" runs a fill, so the fill of epoch max_epochs-1 is the last epoch's and the fill of
@@ -167,7 +167,7 @@ SMALLEST = {"wave": (1, 1, 1), "mem": (32, 16, 16), "staged": (64, 64, 64), "sta
 
 
 def level_class(D, d, nblocks_skipped=0, general=False, max_epochs=1):
-    """The classes of level d of a depth-D brick, as compress_stream / encode_launch (kd_encode.hip) launch it; a
+    """The classes of level d of a depth-D brick, as compress_stream / encode_launch (kd_encode.hip) launch it from build_level (host_plan.cpp); a
     tuple, the size class first.
 
     By the level's size n = 2^d (exactly one):
@@ -209,7 +209,7 @@ def is_general(shape):
 
 
 def skipped_blocks(tree, vol, tolerance, max_epochs, variant=PLAIN):
-    """How many 4096-leaf blocks the level loop skips (encode_launch's skipOn and k_fill16's level D-2 test): the
+    """How many 4096-leaf blocks the level loop skips (BuildPlan::skipBlocks and k_fill16's level D-2 test): the
     block is one value and every depth-(D-3) node above it is reconstructed to exactly that value."""
     D = tree.origTreeDepth
     if D < 14 or tolerance < 1 or max_epochs < 1 or is_general(vol.shape) or int(vol.min()) == int(vol.max()):

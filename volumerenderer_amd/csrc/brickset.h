@@ -19,24 +19,6 @@ struct Stream2 {              // one 2-bit stream (mid, or MidRangeTree's half-r
                                     // BrickSet::brickOff[b] (compact_launch; at the end of build() unless compaction was turned off)
 };
 
-// Debugging switches: each runs one kernel in place of another on the same data, for the tests to compare.  Read from
-// the environment (VRHIP_<NAME>) ONCE, when a set is created, or set explicitly with vr_brickset_set_switch -- never
-// in a launch path: the kernels a handle uses do not change behind the caller's back.
-#define EST_QUAD_BUDGET 8        // per brick and level, over its quad rounds (once round 0's: EST_R0_BUDGET).  DESIGN.md 3.2: 8, 16 and 32 measured, 8 kept
-struct Switches {
-    bool decodeWalk = false;     // VRHIP_DECODE_WALK: k_decode_tile (no per-4-leaf counts)
-    bool decodeFineV1 = false;   // VRHIP_DECODE_FINE_V1: round 1's k_decode_fine
-    bool decodeQuad = false;     // VRHIP_DECODE_QUAD: round 2's k_decode_quad instead of k_decode_region
-    bool noSkipBlocks = false;   // VRHIP_NO_SKIP_BLOCKS
-    bool noUniformBlocks = false; // VRHIP_NO_UNIFORM_BLOCKS: constant 4096-leaf blocks go through k_prune_emit12, not k_prune_emit12_const
-    bool estExactBounds = false; // VRHIP_EST_EXACT_BOUNDS: the estimator's quad rounds run the exact k_est_summ<false>, with no fallback budget
-    bool estOldSchedule = false; // VRHIP_EST_OLD_SCHEDULE: every estimator round over the whole level, 4-wide quads first (est_round_plan)
-    int estBudget = EST_QUAD_BUDGET; // VRHIP_EST_BUDGET=<n>: node-by-node segments a brick may walk in a level's quad rounds (measurement aid)
-    bool pyramidBoxes = false;   // VRHIP_PYRAMID_BOXES: k_pyramid12 (one box per workgroup) where k_pyramid12_lines applies
-    bool indexPerBlock = false;  // VRHIP_INDEX_PER_BLOCK: k_index12_block (a wave per 4096-leaf block) + k_const_finish over every index entry, not k_index12
-    bool noUniformDecode = false; // VRHIP_NO_UNIFORM_DECODE: k_decode_region ignores BrickSet::boxUniform (every live box is parsed).  Read per call
-};
-
 // vr_brickset_decode_lod: the device state of one call.  Calls take the slots of a ring in turn; a call waits on the
 // host for its slot's previous call (its event) before rewriting anything in it, so up to VR_LOD_SLOTS calls of a set
 // may be queued, on one stream or several, without a host synchronisation, and none overwrites what another still reads.
@@ -57,7 +39,8 @@ struct LodSlot {
 
 struct BrickSet {
     int32_t B = 0;
-    Switches sw;
+    Switches sw;              // host_plan.h: one table, read from the environment once, at vr_brickset_create
+    BuildPlan plan{};         // of the current build (vr_brickset_build, before its first launch): host_plan.h
     Geom g{};
     TilePlan tile{};          // launch geometry (host_plan.h), made once by vr_brickset_create: nothing in it depends on
     RegionPlan region{};      // the switches or on anything else that can change afterwards
@@ -76,7 +59,7 @@ struct BrickSet {
     int64_t reconStride = 0;  // bytes per brick of a reconstruction buffer: 2^D, or 2^(D-1) in a leafless build
     // A fused build (k_prune_emit12) never stores the leaf level's codes and reconstruction: its leaf-level fills only
     // sum errors, and the prune recomputes both from (truth, parent's reconstruction, the distances the level loop ended
-    // with: Ctrl::finalReconDist / finalCodesDist).  Set from leafless_build() when the encoder's buffers are allocated.
+    // with: Ctrl::finalReconDist / finalCodesDist).  Set from BuildPlan::leafless when the encoder's buffers are allocated.
     bool leafless = false;
     int64_t treeCap = 0;      // bytes per brick reserved for the preorder stream
     int64_t nIdx = 0;         // 2^Ds index entries per brick
@@ -178,10 +161,6 @@ struct PoolDest {
     int64_t cells = 0;
 };
 
-// Every D >= 12 brick is built by k_prune_emit12; with a level loop that runs, such a build keeps nothing of the leaf
-// level (BrickSet::leafless).
-inline bool leafless_build(const BrickSet &b) { return b.D >= 12 && b.maxEpochs >= 1; }
-
 // The tolerance the kernels get.  A leaf error never exceeds 255, so every tolerance >= 256 means the same thing; the
 // fused prune kernels carry it in two signed 16-bit lanes (kd_encode.hip pe_leaf_table), which the caller's value
 // (any non-negative int32) would overflow from 32769 up.
@@ -190,9 +169,10 @@ inline int kernel_tolerance(const BrickSet &b) { return b.tolerance < 256 ? b.to
 inline void fine_has_changed(BrickSet &b) { b.fineAll = (int)b.fineHas.size() == b.B && std::find(b.fineHas.begin(), b.fineHas.end(), 0) == b.fineHas.end(); }
 
 // kd_encode.hip
-int encode_launch(BrickSet *bs, const uint8_t *voxDev, hipStream_t st);
-int compact_launch(BrickSet *bs, hipStream_t st);   // fused builds: contiguous stream(s) into Stream2::treeCompact
-inline bool build_loads_vectors(const BrickSet *bs) { return bs->pyr12.use12; }   // k_pyramid12 serves the set: 16-byte loads from the caller's voxels
+// executes the plan: allocates nothing, creates no stream or event (capi.hip vr_brickset_build has made whatever the plan touches)
+int encode_launch(BrickSet *bs, const BuildPlan &plan, const uint8_t *voxDev, hipStream_t st);
+// fused builds: contiguous stream(s) into Stream2::treeCompact; -1 without its buffers (capi.hip ensure_compact_buffers)
+int compact_launch(BrickSet *bs, hipStream_t st);
 // kd_decode.hip
 // would the call store vectors to the caller's buffer (the tiled kernels, k_pool_pack)?  capi.hip asks before it launches
 bool decode_stores_vectors(const BrickSet *bs, int cutDepth, bool rangeStream);

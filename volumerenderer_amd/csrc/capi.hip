@@ -139,11 +139,11 @@ static void free_encoder_buffers(BrickSet &b)
     b.encoderReady = false;
 }
 
-static vr_status alloc_encoder_buffers(BrickSet &b)
+static vr_status alloc_encoder_buffers(BrickSet &b, const BuildPlan &plan)
 {
     const size_t B = (size_t)b.B;
     // a leafless build's codes and reconstruction arrays end one level above the leaves
-    b.leafless = leafless_build(b);
+    b.leafless = plan.leafless;
     b.reconStride = b.leafless ? b.leafStride / 2 : b.leafStride;
     b.codeStride = b.leafless ? b.leafStride / 4 + 16 : ((b.heapStride + 15) / 16) * 4;
     HIPCHK(hipMalloc(&b.mid.temp, B * (size_t)b.heapStride));
@@ -156,10 +156,9 @@ static vr_status alloc_encoder_buffers(BrickSet &b)
         HIPCHK(hipMalloc(&b.rng.codes, B * (size_t)b.codeStride));
         for (int i = 0; i < 3; ++i) HIPCHK(hipMalloc(&b.rng.recon[i], B * (size_t)b.reconStride));
     }
-    const int64_t mm = (int64_t)1 << (b.D > 10 ? b.D - 10 : 0);
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipMalloc(&b.mmMin[i], B * (size_t)mm));
-        HIPCHK(hipMalloc(&b.mmMax[i], B * (size_t)mm));
+        HIPCHK(hipMalloc(&b.mmMin[i], B * (size_t)plan.rootStride));
+        HIPCHK(hipMalloc(&b.mmMax[i], B * (size_t)plan.rootStride));
     }
     b.nErrBlk = ((int64_t)1 << b.D) / 1024 > 0 ? ((int64_t)1 << b.D) / 1024 : 1;
     HIPCHK(hipMalloc(&b.blockErr, 3 * B * (size_t)b.nErrBlk * sizeof(unsigned long long)));     // + the central difference's two planes (Ctrl::altSel)
@@ -171,8 +170,9 @@ static vr_status alloc_encoder_buffers(BrickSet &b)
     }
     b.nEmitBlk = (((int64_t)1 << b.D) + 255) / 256;
     HIPCHK(hipMalloc(&b.blockL1, B * (size_t)b.nEmitBlk * sizeof(unsigned long long)));
-    if (b.D >= 12) HIPCHK(hipMalloc(&b.blockFlag, B * ((size_t)1 << (b.D - 12))));
-    if (b.D >= 12 && b.variant == VR_VARIANT_MIDRANGE) HIPCHK(hipMalloc(&b.blockFlagR, B * ((size_t)1 << (b.D - 12))));
+    // (BuildPlan's contract: the flags exist exactly when the build is fused, the range stream's for a MidRangeTree)
+    if (plan.fused) HIPCHK(hipMalloc(&b.blockFlag, B * (size_t)plan.boxes));
+    if (plan.fused && plan.midRange) HIPCHK(hipMalloc(&b.blockFlagR, B * (size_t)plan.boxes));
     HIPCHK(hipMalloc(&b.blockAlive, B * (size_t)b.nEmitBlk));
     HIPCHK(hipMalloc(&b.blockVal, B * (size_t)b.nEmitBlk));
     HIPCHK(hipMalloc(&b.blockSpine, B * (size_t)b.nEmitBlk * sizeof(unsigned long long)));
@@ -190,13 +190,71 @@ static vr_status alloc_encoder_buffers(BrickSet &b)
 // "ready" is a flag of its own, set after the last allocation: a failure part-way (out of memory) releases what
 // was taken, so the next build retries from scratch and reports the same error instead of launching kernels on
 // null side buffers.
-static vr_status ensure_encoder_buffers(BrickSet &b)
+static vr_status ensure_encoder_buffers(BrickSet &b, const BuildPlan &plan)
 {
     if (b.encoderReady) return VR_OK;
-    const vr_status rc = alloc_encoder_buffers(b);
+    const vr_status rc = alloc_encoder_buffers(b, plan);
     if (rc != VR_OK) { (void)hipGetLastError(); free_encoder_buffers(b); return rc; }
     b.encoderReady = true;
     return VR_OK;
+}
+
+// What a fused build writes beside the encoder's arrays: the fine index, the depth-(D-3) scalars and the uniform hint
+static vr_status ensure_fused_buffers(BrickSet &b, const BuildPlan &plan)
+{
+    const size_t B = (size_t)b.B;
+    if (!b.fineIdx) HIPCHK(hipMalloc(&b.fineIdx, B * (size_t)b.nIdx * 16));
+    if (!b.idxVal3) HIPCHK(hipMalloc(&b.idxVal3, B * (size_t)b.nIdx * 8));
+    if (!b.boxUniform) HIPCHK(hipMalloc(&b.boxUniform, B * (size_t)plan.boxes * sizeof(uint32_t)));
+    return VR_OK;
+}
+
+// The buffers of compact_launch (kd_encode.hip): brickOff, compactOverflow and a treeCompact of at least minCap bytes
+// per stream the variant has (0: whatever there is, or the first guess), for the build and for contiguous_stream's
+// regrow.  compactCap is non-zero only while every treeCompact the variant needs exists: it is cleared before anything
+// is freed and assigned after the last allocation.
+static vr_status ensure_compact_buffers(BrickSet &b, int64_t minCap)
+{
+    if (!b.brickOff) HIPCHK(hipMalloc(&b.brickOff, (size_t)(b.B + 1) * sizeof(unsigned long long)));
+    if (!b.compactOverflow) HIPCHK(hipMalloc(&b.compactOverflow, sizeof(int32_t)));
+    if (b.compactCap != 0 && b.compactCap >= minCap) return VR_OK;
+    int64_t cap = minCap;
+    if (cap == 0) {
+        // first time: 5/8 byte per voxel (the bench volume takes 0.56; noise takes up to 2.3) -- a guess, corrected on demand
+        cap = (int64_t)b.B * b.g.voxels / 8 * 5 + (int64_t)b.B * 64 + 4096;
+        cap = std::min(cap, (int64_t)b.B * b.treeCap);
+    }
+    b.compactCap = 0;
+    b.compactValid = false;
+    hipFree(b.mid.treeCompact); b.mid.treeCompact = nullptr;
+    hipFree(b.rng.treeCompact); b.rng.treeCompact = nullptr;
+    HIPCHK(hipMalloc(&b.mid.treeCompact, (size_t)cap));
+    if (b.variant == VR_VARIANT_MIDRANGE && hipMalloc(&b.rng.treeCompact, (size_t)cap) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(b.mid.treeCompact); b.mid.treeCompact = nullptr;
+        return VR_ERR_OOM;
+    }
+    b.compactCap = cap;
+    return VR_OK;
+}
+
+// Internal streams for the forks of a build (kd_encode.hip encode_launch), created on first need and only as many as are
+// used: a process has few hardware queues (4 by default), streams beyond them share one, and a kernel queued behind
+// another stream's long copy on a shared queue waits for it (a MidRangeTree build inside the timestep streamer took 236
+// instead of 68 ms with three idle extra streams per handle).  Returns how many of the n the handle has.
+static int ensure_aux(BrickSet &b, int n)
+{
+    if (n > 3) n = 3;
+    if (n <= 0) return 0;
+    if (!b.evFork && hipEventCreateWithFlags(&b.evFork, hipEventDisableTiming) != hipSuccess) return 0;
+    int have = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!b.auxN[i] && hipStreamCreateWithFlags(&b.auxN[i], hipStreamNonBlocking) != hipSuccess) break;
+        if (!b.evJoinN[i] && hipEventCreateWithFlags(&b.evJoinN[i], hipEventDisableTiming) != hipSuccess) break;
+        ++have;
+    }
+    b.aux = b.auxN[0]; b.evJoin = b.evJoinN[0];
+    return have;
 }
 
 vr_status vr_brickset_destroy(vr_brickset *h)
@@ -243,20 +301,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
     if (!h) return VR_ERR_OOM;
     BrickSet &b = h->s;
     b.B = num_bricks;
-    {   // the VRHIP_* debugging switches are read here, once per set (brickset.h Switches)
-        Switches &w = b.sw;
-        w.decodeWalk = getenv("VRHIP_DECODE_WALK") != nullptr;
-        w.decodeFineV1 = getenv("VRHIP_DECODE_FINE_V1") != nullptr;
-        w.decodeQuad = getenv("VRHIP_DECODE_QUAD") != nullptr;
-        w.noSkipBlocks = getenv("VRHIP_NO_SKIP_BLOCKS") != nullptr;
-        w.noUniformBlocks = getenv("VRHIP_NO_UNIFORM_BLOCKS") != nullptr;
-        w.noUniformDecode = getenv("VRHIP_NO_UNIFORM_DECODE") != nullptr;
-        w.pyramidBoxes = getenv("VRHIP_PYRAMID_BOXES") != nullptr;
-        w.indexPerBlock = getenv("VRHIP_INDEX_PER_BLOCK") != nullptr;
-        w.estExactBounds = getenv("VRHIP_EST_EXACT_BOUNDS") != nullptr;
-        w.estOldSchedule = getenv("VRHIP_EST_OLD_SCHEDULE") != nullptr;
-        if (const char *eb = getenv("VRHIP_EST_BUDGET")) { const int v = atoi(eb); if (v >= 0) w.estBudget = v; }
-    }
+    b.sw = switches_from_env();      // the VRHIP_* debugging switches are read here, once per set (host_plan.h Switches)
     make_geom(b.g, dims);
     b.D = b.g.D;
     if (b.D > 31) { delete h; return VR_ERR_UNSUPPORTED; }
@@ -276,7 +321,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
     b.reconStride = b.leafStride;
     const int64_t numMax = b.heapStride - 1 + VR_CHAIN_LEVELS * b.leafStride; // numMaxNodes R.cpp:35
     b.treeCap = ((numMax + 15) / 16 + 2) * 4 + 256;   // slack: the decoder stages whole words past a run's end
-    if (b.D >= 12) {   // a fused build keeps every 4096-leaf block's string in a fixed slot of 2320 words (kd_encode.hip PE_WORDS)
+    if (build_fused(b.D)) {   // a fused build keeps every 4096-leaf block's string in a fixed slot of 2320 words (kd_encode.hip PE_WORDS)
         const int64_t gappedBytes = ((int64_t)1 << (b.D - 12)) * 2320 * 4 + 256;
         if (gappedBytes > b.treeCap) b.treeCap = gappedBytes;
     }
@@ -299,7 +344,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         if (e == hipSuccess && !general) e = hipMalloc(&b.spread, (size_t)(b.g.X + b.g.Y + b.g.Z) * sizeof(uint32_t));
         if (e == hipSuccess && !general) e = upload(b.spread, make_spread(b.g));
         for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&b.ev[i]);
-        // (the internal streams of a build are created when a build first needs them: kd_encode.hip ensure_aux)
+        // (the internal streams of a build are created when a build first needs them: ensure_aux)
         if (e != hipSuccess) rc = e == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_NO_DEVICE;
     }
     if (rc != VR_OK) { vr_brickset_destroy(h); return rc; }
@@ -312,19 +357,9 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
 vr_status vr_brickset_set_switch(vr_brickset *h, const char *name, int32_t value)
 {
     if (!h || !name) return VR_ERR_INVALID;
-    Switches &w = h->s.sw;
-    const bool on = value != 0;
-    if (!strcmp(name, "decode_walk")) w.decodeWalk = on;
-    else if (!strcmp(name, "decode_fine_v1")) w.decodeFineV1 = on;
-    else if (!strcmp(name, "decode_quad")) w.decodeQuad = on;
-    else if (!strcmp(name, "no_skip_blocks")) w.noSkipBlocks = on;
-    else if (!strcmp(name, "no_uniform_blocks")) w.noUniformBlocks = on;
-    else if (!strcmp(name, "no_uniform_decode")) w.noUniformDecode = on;
-    else if (!strcmp(name, "pyramid_boxes")) w.pyramidBoxes = on;
-    else if (!strcmp(name, "index_per_block")) w.indexPerBlock = on;
-    else if (!strcmp(name, "est_exact_bounds")) w.estExactBounds = on;
-    else if (!strcmp(name, "est_old_schedule")) w.estOldSchedule = on;
-    else return VR_ERR_INVALID;
+    bool Switches::*const m = find_switch(name);
+    if (!m) return VR_ERR_INVALID;
+    h->s.sw.*m = value != 0;
     return VR_OK;
 }
 
@@ -367,23 +402,39 @@ vr_status vr_brickset_build(vr_brickset *h, const uint8_t *vox, void *stream)
 {
     if (!h || !vox) return VR_ERR_INVALID;
     BrickSet &b = h->s;
-    if (build_loads_vectors(&b) && misaligned16(vox)) return VR_ERR_INVALID;
+    // k_pyramid12 serves the set: 16-byte loads from the caller's voxels
+    if (b.pyr12.use12 && misaligned16(vox)) return VR_ERR_INVALID;
+    // the side streams, then the plan (it takes how many there are), then every buffer its launches touch: a failure up
+    // to here has enqueued nothing and changed nothing the previous build's readers use
+    BuildInputs in{};
+    in.D = b.D; in.B = b.B; in.variant = b.variant; in.tolerance = b.tolerance; in.maxEpochs = b.maxEpochs;
+    in.use12 = b.pyr12.use12; in.lines = b.pyr12.lines; in.generalGeom = b.generalGeom;
+    in.sw = b.sw; in.levelLoopStreams = b.levelLoopStreams; in.compactOnBuild = b.compactOnBuild;
+    in.sideStreams = ensure_aux(b, build_side_streams(b.variant, b.B, b.levelLoopStreams));
+    const BuildPlan plan = make_build_plan(in);
+    vr_status rc = plan.fused ? ensure_fused_buffers(b, plan) : VR_OK;
+    if (rc == VR_OK && plan.compact) rc = ensure_compact_buffers(b, 0);
+    if (rc != VR_OK) { (void)hipGetLastError(); return rc; }
     // (vr_brickset_set_max_epochs(0) <-> >= 1 between two builds changes what the level loop keeps of the leaf level:
-    // the encoder's arrays are made again for the other mode)
-    if (b.encoderReady && b.leafless != leafless_build(b)) {
+    // the encoder's arrays are made again for the other mode.  They are released first -- both sizes at once may not
+    // fit -- and last of all buffers: if they cannot be made again the set has no build any more, VR_ERR_STATE from
+    // then on, not kernels on null arrays)
+    const bool resize = b.encoderReady && b.leafless != plan.leafless;
+    if (resize) {
         HIPCHK(hipDeviceSynchronize());
         free_encoder_buffers(b);
     }
-    vr_status rc = ensure_encoder_buffers(b);
-    if (rc != VR_OK) return rc;
+    rc = ensure_encoder_buffers(b, plan);
+    if (rc != VR_OK) {
+        if (resize) b.built = false;
+        return rc;
+    }
     b.hostCtrlValid = false;
     b.hostBrickOff.clear();
     b.foreign = false;
     std::fill(b.openTreeBytes.begin(), b.openTreeBytes.end(), -1);
-    {   // -3: a lazily allocated side buffer did not fit
-        const int rc = encode_launch(&b, vox, (hipStream_t)stream);
-        if (rc != 0) return rc == -3 ? VR_ERR_OOM : VR_ERR_NO_DEVICE;
-    }
+    b.plan = plan;
+    if (encode_launch(&b, b.plan, vox, (hipStream_t)stream) != 0) return VR_ERR_NO_DEVICE;
     b.built = true;
     b.timingsPending = true;
     b.lastStream = stream;
@@ -441,12 +492,12 @@ static vr_status contiguous_stream(BrickSet &b, Stream2 &s, int brick, const uin
 {
     if (!s.tree) return VR_ERR_STATE;
     if (!b.gapped) { *ptr = s.tree + (size_t)brick * b.treeCap; return VR_OK; }
-    const bool mr = b.variant == VR_VARIANT_MIDRANGE;
     for (int attempt = 0; attempt < 2; ++attempt) {
         HIPCHK(hipStreamSynchronize((hipStream_t)b.lastStream));
         if (!b.compactValid) {
-            const int rc = compact_launch(&b, (hipStream_t)b.lastStream);
-            if (rc != 0) return rc == -3 ? VR_ERR_OOM : VR_ERR_NO_DEVICE;
+            const vr_status brc = ensure_compact_buffers(b, 0);
+            if (brc != VR_OK) return brc;
+            if (compact_launch(&b, (hipStream_t)b.lastStream) != 0) return VR_ERR_NO_DEVICE;
             HIPCHK(hipStreamSynchronize((hipStream_t)b.lastStream));
             b.hostBrickOff.clear();
         }
@@ -460,13 +511,8 @@ static vr_status contiguous_stream(BrickSet &b, Stream2 &s, int brick, const uin
         const int64_t total = (int64_t)b.hostBrickOff[(size_t)b.B];
         if (total <= b.compactCap) break;
         // did not fit: nothing was written.  Regrow (some headroom: the next timestep's streams differ) and repeat
-        hipFree(b.mid.treeCompact); b.mid.treeCompact = nullptr;
-        hipFree(b.rng.treeCompact); b.rng.treeCompact = nullptr;
-        const int64_t cap = total + total / 8 + 4096;
-        HIPCHK(hipMalloc(&b.mid.treeCompact, (size_t)cap));
-        if (mr) HIPCHK(hipMalloc(&b.rng.treeCompact, (size_t)cap));
-        b.compactCap = cap;
-        b.compactValid = false;
+        const vr_status brc = ensure_compact_buffers(b, total + total / 8 + 4096);
+        if (brc != VR_OK) return brc;
         if (attempt == 1) return VR_ERR_STATE;
     }
     *ptr = s.treeCompact + (size_t)b.hostBrickOff[(size_t)brick];

@@ -1,6 +1,7 @@
 // host_plan.cpp -- see host_plan.h.  Plain C++: nothing here touches a device.
 #include "host_plan.h"
 #include "../../include/vrhip.h"
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <atomic>
@@ -448,6 +449,138 @@ EstPlan est_round_plan(uint32_t nseg, bool oldSchedule)
     }
     for (int i = 0; i < 3; ++i) add(nseg, VR_EST_CAND, false);
     return p;
+}
+
+static uint32_t cdiv(int64_t a, int64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+EstLaunch est_launch(const EstRound &R, bool exactBounds, int32_t budget)
+{
+    const int64_t len = (int64_t)R.segEnd - VR_EST_HEAD / VR_EST_SEG;
+    EstLaunch l{};
+    l.gx = R.quads ? cdiv(len, 8 * R.sweeps) : std::min(cdiv(len, 8), 64u);
+    l.quads = R.quads && !exactBounds;
+    l.budget = l.quads ? budget : -1;
+    return l;
+}
+
+// ---- the debugging switches ----
+const SwitchRow VR_SWITCHES[] = {
+    {"decode_walk", &Switches::decodeWalk},
+    {"decode_fine_v1", &Switches::decodeFineV1},
+    {"decode_quad", &Switches::decodeQuad},
+    {"no_skip_blocks", &Switches::noSkipBlocks},
+    {"no_uniform_blocks", &Switches::noUniformBlocks},
+    {"no_uniform_decode", &Switches::noUniformDecode},
+    {"pyramid_boxes", &Switches::pyramidBoxes},
+    {"index_per_block", &Switches::indexPerBlock},
+    {"est_exact_bounds", &Switches::estExactBounds},
+    {"est_old_schedule", &Switches::estOldSchedule},
+};
+const int VR_NUM_SWITCHES = (int)(sizeof(VR_SWITCHES) / sizeof(VR_SWITCHES[0]));
+
+bool Switches::*find_switch(const char *name)
+{
+    for (int i = 0; name && i < VR_NUM_SWITCHES; ++i)
+        if (!strcmp(name, VR_SWITCHES[i].name)) return VR_SWITCHES[i].member;
+    return nullptr;
+}
+
+void switch_env_name(const char *name, char *out, size_t cap)
+{
+    snprintf(out, cap, "VRHIP_%s", name);
+    for (char *c = out; *c; ++c) if (*c >= 'a' && *c <= 'z') *c = (char)(*c - 'a' + 'A');
+}
+
+Switches switches_from_env()
+{
+    Switches w;
+    char env[64];
+    for (int i = 0; i < VR_NUM_SWITCHES; ++i) {
+        switch_env_name(VR_SWITCHES[i].name, env, sizeof(env));
+        w.*VR_SWITCHES[i].member = getenv(env) != nullptr;
+    }
+    if (const char *eb = getenv("VRHIP_EST_BUDGET")) { const int v = atoi(eb); if (v >= 0) w.estBudget = v; }
+    return w;
+}
+
+// ---- the build ----
+int build_side_streams(int variant, int B, int levelLoopStreams)
+{
+    if (variant == VR_VARIANT_MIDRANGE) return 1;
+    const int p = std::min(levelLoopStreams, VR_MAX_PARTS);
+    return (B < 16 * p || p < 2) ? 0 : p - 1;
+}
+
+BuildPlan make_build_plan(const BuildInputs &in)
+{
+    BuildPlan p{};
+    const int D = in.D, B = in.B;
+    const int64_t leaves = (int64_t)1 << D;
+    p.D = D; p.B = B; p.maxEpochs = in.maxEpochs;
+    p.midRange = in.variant == VR_VARIANT_MIDRANGE;
+    p.guarded = in.variant != VR_VARIANT_RECOVER;
+    p.fused = build_fused(D);
+    p.leafless = p.fused && in.maxEpochs >= 1;
+    // SkipBlocks needs k_pyramid12's constant bit in front and k_prune_emit12 behind, a prune that makes such blocks
+    // one token (tolerance >= 1) and a level loop that runs
+    p.skipBlocks = p.fused && in.use12 && in.tolerance >= 1 && in.maxEpochs >= 1 && D >= 14 && !in.sw.noSkipBlocks;
+    // (both streams of a MidRangeTree too; needs the leaf prune and an epoch to exist)
+    p.constClosedForm = in.maxEpochs >= 1 && in.tolerance >= 1 && D >= 1;
+    p.zeroFill = in.maxEpochs <= 0;
+    p.boxes = (int64_t)1 << block_depth(D);
+    // pyramid: bottom 12 levels by k_pyramid12 when x-runs of 16 voxels exist (eight boxes per workgroup where they
+    // share their 128-byte lines), the rest (and small / thin bricks) in rounds of <= 10 levels
+    p.pyr12 = in.use12;
+    p.pyr12Lines = in.use12 && in.lines && !in.sw.pyramidBoxes;
+    p.pyr12Grid = !p.pyr12 ? 0u : (uint32_t)((int64_t)1 << (p.pyr12Lines ? D - 15 : D - 12));
+    p.pyrSrcIdx = !p.pyr12 && in.generalGeom;
+    for (int dLeaf = p.pyr12 ? D - 12 : D; dLeaf > 0 || (!p.pyr12 && p.pyrRounds == 0); ) {
+        const int L = std::min(dLeaf, 10);
+        p.pyr[p.pyrRounds++] = PyrRound{dLeaf, L, (uint32_t)((int64_t)1 << (dLeaf - L))};
+        dLeaf -= L;
+    }
+    p.rootStride = (int64_t)1 << std::max(D - 10, 0);
+    // level loop: a MidRangeTree's two streams do not depend on each other, nor do the bricks of a VolumeKdtree
+    const int want = std::min(in.levelLoopStreams, VR_MAX_PARTS);
+    p.parts = (p.midRange || B < 16 * want || want < 2) ? 1 : std::min(want, 1 + in.sideStreams);
+    for (int i = 0; i <= p.parts; ++i) p.range[i] = (int32_t)((int64_t)B * i / p.parts);
+    p.forkRange = p.midRange && in.sideStreams >= 1;
+    p.estOldSchedule = in.sw.estOldSchedule; p.estExactBounds = in.sw.estExactBounds; p.estBudget = in.sw.estBudget;
+    // prune: constant blocks of a leafless SkipBlocks build have a closed form (k_prune_emit12_const)
+    p.uniformBlocks = p.skipBlocks && p.leafless && !p.midRange && !in.sw.noUniformBlocks;
+    p.uniformGrid = cdiv(p.boxes, VR_PEC_BOXES);
+    p.pruneGrid = p.fused ? (uint32_t)p.boxes : cdiv(leaves, 256);
+    p.pruneFrom = p.fused ? D - 13 : D - 1;
+    // convert
+    p.emitLeaves = p.fused ? 4096 : VR_EMIT_RANKS;
+    p.nblk = cdiv(leaves, p.emitLeaves);
+    p.index = !p.fused ? VR_EMIT_WRITE : (in.sw.indexPerBlock ? VR_INDEX12_BLOCK : VR_INDEX12);
+    p.indexGrid = p.index == VR_INDEX12 ? cdiv(p.nblk, VR_IDX_BLOCKS) : (p.index == VR_INDEX12_BLOCK ? cdiv(p.nblk, 4) : (uint32_t)p.nblk);
+    // (k_index12 writes the index entries of constant bricks too; the other two leave them to k_const_finish)
+    p.constFinishIdx = p.index == VR_INDEX12 ? 0 : (int64_t)1 << (D - std::min(D, 6));
+    p.constFinishGrid = p.index == VR_INDEX12 ? 1u : cdiv(p.constFinishIdx, 256);
+    p.constFinishThreads = p.index == VR_INDEX12 ? 64u : 256u;
+    // statistics records: one per 1024 leaves from k_prune_emit12, one per 256 from k_prune_leaf
+    p.statRecords = cdiv(leaves, p.fused ? 1024 : 256);
+    p.gapped = p.fused;
+    p.compact = p.fused && in.compactOnBuild;
+    return p;
+}
+
+BuildLevel build_level(const BuildPlan &p, int d)
+{
+    BuildLevel l{};
+    const int64_t n = (int64_t)1 << d;
+    l.constLeaves = p.skipBlocks && d == p.D - 1;
+    if (n > VR_EST_HEAD) {
+        l.est = est_round_plan((uint32_t)(n / VR_EST_SEG), p.estOldSchedule);
+        for (int r = 0; r < l.est.rounds; ++r) l.estL[r] = est_launch(l.est.r[r], p.estExactBounds, p.estBudget);
+    }
+    l.fill16 = n >= 4096;
+    l.sumsOnly = p.leafless && d == p.D;
+    l.iters = !l.fill16 ? 0 : (n / 4096 >= 512 ? FILL_ITERS : (n / 4096 >= 64 ? std::min(FILL_ITERS, 4) : 1));
+    l.fillGrid = l.fill16 ? cdiv(n / 4096, l.iters) : cdiv(n, FILL_NODES_PER_BLOCK);
+    return l;
 }
 
 } // namespace vr

@@ -1,5 +1,6 @@
 // host_plan.h -- the codec's host logic that needs no device: the split rule and what follows from it, the launch
-// geometry of the tiled kernels (planned once per set, at vr_brickset_create), the walker of foreign streams and the
+// geometry of the tiled kernels (planned once per set, at vr_brickset_create), the debugging switches' one table, the
+// plan of a build (BuildPlan: every kernel, grid and brick range of vr_brickset_build), the walker of foreign streams and the
 // file header, the block tables and per-block index walker of installed streams (shared with kd_index.hip's kernel) and the
 // brick-set archive's parser and writer; and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
 // host_plan.cpp: a rule on a host table).  Includes no HIP header: compiles with a plain C++17 compiler (tests/host_plan_main.cpp links it
@@ -113,6 +114,113 @@ VR_HD inline int est_window_base(long long T, int up, int nc)
     if (b > 256 - nc) b = 256 - nc;
     return (int)b;
 }
+
+// ---- debugging switches ----
+// Each runs one kernel in place of another on the same data, for the tests to compare.  ONE table (VR_SWITCHES) names
+// them: vr_brickset_set_switch looks its argument up there, and vr_brickset_create reads VRHIP_<NAME in capitals> of
+// the same rows from the environment, ONCE -- never in a launch path: the kernels a handle uses do not change behind
+// the caller's back.  A switch is a member here and a row there; vrhip.h documents the names (tests/test_build_plan.py
+// compares its list with the table).
+constexpr int EST_QUAD_BUDGET = 8;  // per brick and level, over its quad rounds (once round 0's: EST_R0_BUDGET).  DESIGN.md 3.2: 8, 16 and 32 measured, 8 kept
+struct Switches {
+    bool decodeWalk = false;     // decode_walk: k_decode_tile (no per-4-leaf counts)
+    bool decodeFineV1 = false;   // decode_fine_v1: round 1's k_decode_fine
+    bool decodeQuad = false;     // decode_quad: round 2's k_decode_quad instead of k_decode_region
+    bool noSkipBlocks = false;   // no_skip_blocks
+    bool noUniformBlocks = false; // no_uniform_blocks: constant 4096-leaf blocks go through k_prune_emit12, not k_prune_emit12_const
+    bool estExactBounds = false; // est_exact_bounds: the estimator's quad rounds run the exact k_est_summ<false>, with no fallback budget
+    bool estOldSchedule = false; // est_old_schedule: every estimator round over the whole level, 4-wide quads first (est_round_plan)
+    int estBudget = EST_QUAD_BUDGET; // VRHIP_EST_BUDGET=<n> only: node-by-node segments a brick may walk in a level's quad rounds (measurement aid)
+    bool pyramidBoxes = false;   // pyramid_boxes: k_pyramid12 (one box per workgroup) where k_pyramid12_lines applies
+    bool indexPerBlock = false;  // index_per_block: k_index12_block (a wave per 4096-leaf block) + k_const_finish over every index entry, not k_index12
+    bool noUniformDecode = false; // no_uniform_decode: k_decode_region ignores BrickSet::boxUniform (every live box is parsed).  Read per call
+};
+struct SwitchRow { const char *name; bool Switches::*member; };
+extern const SwitchRow VR_SWITCHES[];
+extern const int VR_NUM_SWITCHES;
+bool Switches::*find_switch(const char *name);      // nullptr: no row of that name
+void switch_env_name(const char *name, char *out, size_t cap);   // "VRHIP_" + the name in capitals
+Switches switches_from_env();
+
+// ---- the build (kd_encode.hip encode_launch / compress_stream execute it; they decide nothing) ----
+// Every decision of a build from plain inputs: which kernels, on which grids, over which brick ranges.  Contract with
+// the allocator (capi.hip): blockFlag exists exactly when fused, blockFlagR when fused and MidRange; fineIdx, idxVal3 and
+// boxUniform exist when fused; brickOff, compactOverflow and treeCompact when compact -- all before the first launch.
+constexpr int FILL_ITERS = 8;                // chunks of 4096 nodes per workgroup of k_fill16 (large levels)
+constexpr int FILL_NODES_PER_BLOCK = 1024;   // nodes per workgroup of k_fill (levels below 4096 nodes)
+constexpr int VR_PEC_BOXES = 16, VR_IDX_BLOCKS = 32, VR_EMIT_RANKS = 256;    // kd_encode.hip PEC_BOXES, IDX_BLOCKS, EMIT_RANKS_PER_BLOCK
+constexpr int VR_PYR_MAX_ROUNDS = 4, VR_MAX_PARTS = 4;
+
+inline bool build_fused(int D) { return D >= 12; }     // BuildPlan::fused: also sizes a set's stream slots (vr_brickset_create)
+struct BuildInputs {
+    int32_t D, B, variant, tolerance, maxEpochs;
+    bool use12, lines;          // Pyr12Plan
+    bool generalGeom;
+    Switches sw;
+    int32_t levelLoopStreams;
+    bool compactOnBuild;
+    int32_t sideStreams;        // internal streams the handle has (at least build_side_streams() were asked for)
+};
+// internal streams a build would use beside the caller's: one for a MidRangeTree's half-range stream, one per further
+// brick range of a VolumeKdtree
+int build_side_streams(int variant, int B, int levelLoopStreams);
+
+struct PyrRound { int32_t dLeaf, L; uint32_t blocks; };      // k_pyramid: L <= 10 levels from depth dLeaf up
+enum IndexKernel { VR_INDEX12, VR_INDEX12_BLOCK, VR_EMIT_WRITE };
+struct BuildPlan {
+    int32_t D, B, maxEpochs;
+    bool midRange, guarded;     // guarded: GUARDED and MIDRANGE both carry the R.cpp:333/:340 guard
+    bool fused;                 // k_prune_emit12: prune + block-local emit in one kernel, 4096-leaf blocks
+    bool leafless;              // the level loop keeps nothing of the leaf level (sizes the encoder's arrays)
+    bool skipBlocks;            // kd_encode.hip SkipBlocks
+    bool constClosedForm;       // constant bricks take k_const_finish's closed form
+    bool zeroFill;              // no epoch runs: codes and reconstructions are zero-filled
+    int64_t boxes;              // 4096-leaf boxes per brick, 2^max(D-12, 0): blockFlag, boxUniform, SkipBlocks::nBlk
+    // pyramid: the bottom twelve levels by one of the k_pyramid12 kernels, the rest in rounds of k_pyramid; round 0
+    // reads voxels (exactly when !pyr12), through srcIdx when pyrSrcIdx
+    bool pyr12, pyr12Lines, pyrSrcIdx;
+    uint32_t pyr12Grid;
+    int32_t pyrRounds;
+    PyrRound pyr[VR_PYR_MAX_ROUNDS];
+    int64_t rootStride;         // bytes per brick of a carry array (mmMin / mmMax): 2^max(D-10, 0)
+    // level loop: brick range i is [range[i], range[i+1]); range 0 on the caller's stream, range i on side stream i-1
+    int32_t parts, range[VR_MAX_PARTS + 1];
+    bool forkRange;             // the half-range stream's level loop on side stream 0
+    bool estOldSchedule, estExactBounds;
+    int32_t estBudget;
+    // prune
+    bool uniformBlocks;         // k_prune_emit12_const in front
+    uint32_t uniformGrid, pruneGrid;     // pruneGrid: k_prune_emit12<RANGE, leafless> when fused, k_prune_leaf otherwise
+    int32_t pruneFrom;          // k_prune_level from this depth up to 0
+    // convert
+    int32_t emitLeaves;         // leaves per emit block
+    int64_t nblk;               // emit blocks per brick
+    IndexKernel index;
+    uint32_t indexGrid;
+    uint32_t constFinishGrid, constFinishThreads;
+    int64_t constFinishIdx;     // index entries per brick k_const_finish writes (0: k_index12 wrote them)
+    int64_t statRecords;        // k_emit_stats: records per brick
+    bool gapped, compact;
+};
+BuildPlan make_build_plan(const BuildInputs &in);
+
+// one level (n = 2^d nodes) of the level loop
+struct EstLaunch { uint32_t gx; bool quads; int32_t budget; };      // k_est_summ<quads> on gx workgroups per brick
+// eight segments per workgroup and sweep (two per wave).  A quad round makes R.sweeps sweeps over the segments a brick
+// can still have in front of it; the exact rounds behind them run on a small grid.  Quad rounds: byte-packed quads with
+// sufficient bounds, and the level's budget of node-by-node segments per brick (exactBounds: the exact kernel, no
+// budget, -1); the rounds behind them: exact records
+EstLaunch est_launch(const EstRound &R, bool exactBounds, int32_t budget);
+struct BuildLevel {
+    bool constLeaves;           // k_fill_const_leaves in front: the skip bits are final (level D-2 has ended)
+    EstPlan est;                // rounds == 0: k_est_head covers the level
+    EstLaunch estL[VR_EST_MAX_ROUNDS];
+    bool fill16;                // k_fill16<!sumsOnly> with iters chunks per workgroup; else k_fill
+    bool sumsOnly;              // the leaf level of a leafless build: errors only
+    int32_t iters;
+    uint32_t fillGrid;
+};
+BuildLevel build_level(const BuildPlan &p, int d);
 
 // ---- foreign streams (host): one preorder walk over the 2-bit tokens, grammar checked ----
 // Per tree token node(depth, path, pos, tok, val): val is the node's decoded scalar, refined down to depth `cut` only; then

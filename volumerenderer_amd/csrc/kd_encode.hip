@@ -23,8 +23,7 @@
 
 namespace vr {
 
-#define FILL_NODES_PER_BLOCK 1024
-#define EMIT_RANKS_PER_BLOCK 256
+#define EMIT_RANKS_PER_BLOCK 256     // (FILL_NODES_PER_BLOCK, FILL_ITERS: host_plan.h)
 
 // ---------------------------------------------------------------- pyramid ----
 // One block reduces 2^L inputs (L <= 10) at depth dLeaf and writes the midranges of
@@ -1128,7 +1127,6 @@ __device__ __forceinline__ void leaf_pair_encode(uint32_t tword, int tsel, uint3
     codes2 = take & pk_u(pk_s(c.up) + pk_s(0x00020002u));                   // up ? 1 : 2 (per-lane wrap)
 }
 
-#define FILL_ITERS 8        // chunks of 4096 nodes per workgroup of k_fill16 (large levels)
 static_assert(FILL_ITERS < 32, "k_fill16 keeps a workgroup's chunks as the bits of a 32-bit mask and the lanes of a wave");
 template <bool STORE>     // false (the leaf level of a leafless build): errors only -- k_prune_emit12 recomputes codes and reconstruction
 __global__ void __launch_bounds__(256)
@@ -3386,69 +3384,56 @@ __global__ void k_const_finish_range(int D, Ctrl *ctrlsR, uint8_t *treeR, int64_
 // ------------------------------------------------------------ host driver ----
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
+static_assert(PEC_BOXES == VR_PEC_BOXES && IDX_BLOCKS == VR_IDX_BLOCKS && EMIT_RANKS_PER_BLOCK == VR_EMIT_RANKS, "host_plan.cpp sizes the grids");
+
 // The level loop of the bricks [b0, b0 + nb) of a stream (every array of a set is per brick: a sub-range is the same
-// launches on offset pointers)
-static void compress_stream(BrickSet *bs, Stream2 &s0, hipStream_t st, const uint8_t *rootMin, const uint8_t *rootMax,
-                            int64_t mmStride, SkipBlocks sk, unsigned long long *blockErr, void *estSumm0,
-                            int b0 = 0, int nb = -1)
+// launches on offset pointers).  Executes plan and build_level(plan, d): nothing is decided here.
+static void compress_stream(BrickSet *bs, const BuildPlan &plan, Stream2 &s0, hipStream_t st, const uint8_t *rootMin,
+                            const uint8_t *rootMax, SkipBlocks sk, unsigned long long *blockErr, void *estSumm0, int b0, int nb)
 {
-    const int D = bs->D, B = nb < 0 ? bs->B : nb;
+    const int D = plan.D, B = nb;
+    const int64_t mmStride = plan.rootStride;
     struct { Ctrl *ctrl; uint8_t *temp, *codes; uint8_t *recon[3]; } s;
     s.ctrl = s0.ctrl + b0; s.temp = s0.temp + (int64_t)b0 * bs->heapStride; s.codes = s0.codes + (int64_t)b0 * bs->codeStride;
     for (int i = 0; i < 3; ++i) s.recon[i] = s0.recon[i] + (int64_t)b0 * bs->reconStride;
     blockErr += (int64_t)b0 * bs->nErrBlk;
     const int64_t errPlane = (int64_t)bs->B * bs->nErrBlk;     // the minus / plus planes of the partials (leafless leaf level) lie behind the first
     void *estSumm = (uint32_t *)estSumm0 + (int64_t)b0 * bs->estSummStride * (4 * EST_CAND);
-    if (sk.flag) sk.flag += (int64_t)b0 * sk.nBlk;
-    if (rootMin) { rootMin += (int64_t)b0 * mmStride; rootMax += (int64_t)b0 * mmStride; }
+    if (plan.skipBlocks) sk.flag += (int64_t)b0 * sk.nBlk;
+    if (plan.constClosedForm) { rootMin += (int64_t)b0 * mmStride; rootMax += (int64_t)b0 * mmStride; }
     ReconBufs rb{{s.recon[0], s.recon[1], s.recon[2]}};
-    const int guarded = bs->variant != 0; // GUARDED and MIDRANGE both carry the :333/:340 guard
     hipLaunchKernelGGL(k_ctrl_init, dim3(B), dim3(64), 0, st, s.ctrl, rootMin, rootMax, mmStride);
-    if (bs->maxEpochs <= 0) { // the loop never runs: tree.resize() / recon.resize() zero-fill is the result
+    if (plan.zeroFill) { // the loop never runs: tree.resize() / recon.resize() zero-fill is the result
         for (int i = 0; i < 3; ++i) hipMemsetAsync(s.recon[i], 0, (size_t)B * bs->reconStride, st);
         hipMemsetAsync(s.codes, 0, (size_t)B * bs->codeStride, st);
     }
     for (int d = 0; d <= D; ++d) {
-        const int64_t n = (int64_t)1 << d;
-        // the skip bits are final (level D-2 has ended): the constant blocks that are not skipped get the two levels
-        // k_pyramid12 did not write, in front of their first reader
-        if (sk.flag && d == D - 1)
+        const BuildLevel L = build_level(plan, d);
+        // the constant blocks that are not skipped get the two levels k_pyramid12 did not write, in front of their first reader
+        if (L.constLeaves)
             hipLaunchKernelGGL(k_fill_const_leaves, dim3(cdiv(sk.nBlk, 256), B), dim3(256), 0, st, D, s.ctrl, s.temp,
                                bs->heapStride, sk);
-        hipLaunchKernelGGL(k_est_head, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, s.ctrl, s.temp, bs->heapStride, rb,
+        hipLaunchKernelGGL(k_est_head, dim3(B), dim3(64), 0, st, d, plan.maxEpochs, s.ctrl, s.temp, bs->heapStride, rb,
                            bs->reconStride, sk);
-        if (n > EST_HEAD) {
-            const vr::EstPlan plan = vr::est_round_plan((uint32_t)(n / EST_SEG), bs->sw.estOldSchedule);
-            for (int r = 0; r < plan.rounds; ++r) {
-                const vr::EstRound &R = plan.r[r];
-                // eight segments per workgroup and sweep (two per wave).  A quad round makes R.sweeps sweeps over the
-                // segments a brick can still have in front of it; the exact rounds behind them run on a small grid
-                const int64_t len = (int64_t)R.segEnd - EST_HEAD / EST_SEG;
-                const unsigned gx = R.quads ? cdiv(len, 8 * R.sweeps) : (cdiv(len, 8) < 64 ? cdiv(len, 8) : 64);
-                // quad rounds: byte-packed quads with sufficient bounds, and the level's budget of node-by-node segments
-                // per brick (est_exact_bounds: the exact kernel, no budget); the rounds behind them: exact records
-                const bool quads = R.quads && !bs->sw.estExactBounds;
-                const int budget = quads ? bs->sw.estBudget : -1;
-                hipLaunchKernelGGL(quads ? k_est_summ<true> : k_est_summ<false>, dim3(gx, B), dim3(256), 0, st, d, R.nc, R.segEnd, budget,
-                                   s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride, (uint32_t *)estSumm, bs->estSummStride, sk);
-                hipLaunchKernelGGL(k_est_walk, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, R.nc, R.segEnd, r,
-                                   r == plan.rounds - 1 ? 1 : 0, budget, s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride,
-                                   (const uint32_t *)estSumm, bs->estSummStride, sk);
-            }
+        for (int r = 0; r < L.est.rounds; ++r) {
+            const EstRound &R = L.est.r[r];
+            const EstLaunch &E = L.estL[r];
+            hipLaunchKernelGGL(E.quads ? k_est_summ<true> : k_est_summ<false>, dim3(E.gx, B), dim3(256), 0, st, d, R.nc, R.segEnd, E.budget,
+                               s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride, (uint32_t *)estSumm, bs->estSummStride, sk);
+            hipLaunchKernelGGL(k_est_walk, dim3(B), dim3(64), 0, st, d, plan.maxEpochs, R.nc, R.segEnd, r,
+                               r == L.est.rounds - 1 ? 1 : 0, E.budget, s.ctrl, s.temp, bs->heapStride, rb, bs->reconStride,
+                               (const uint32_t *)estSumm, bs->estSummStride, sk);
         }
-        for (int e = 0; e < bs->maxEpochs; ++e) {
-            if (n >= 4096)
-            {
-                const int iters = n / 4096 >= 512 ? FILL_ITERS : (n / 4096 >= 64 ? (FILL_ITERS < 4 ? FILL_ITERS : 4) : 1);
-                hipLaunchKernelGGL((bs->leafless && d == D) ? k_fill16<false> : k_fill16<true>, dim3(cdiv(n / 4096, iters), B), dim3(256), 0, st,
-                                   d, bs->maxEpochs, s.ctrl, s.temp, s.codes, bs->heapStride, bs->codeStride, rb, bs->reconStride, blockErr,
-                                   bs->nErrBlk, sk, errPlane, iters);
-            }
+        for (int e = 0; e < plan.maxEpochs; ++e) {
+            if (L.fill16)
+                hipLaunchKernelGGL(L.sumsOnly ? k_fill16<false> : k_fill16<true>, dim3(L.fillGrid, B), dim3(256), 0, st,
+                                   d, plan.maxEpochs, s.ctrl, s.temp, s.codes, bs->heapStride, bs->codeStride, rb, bs->reconStride, blockErr,
+                                   bs->nErrBlk, sk, errPlane, L.iters);
             else
-                hipLaunchKernelGGL(k_fill, dim3(cdiv(n, FILL_NODES_PER_BLOCK), B), dim3(256), 0, st, d, s.ctrl, s.temp,
+                hipLaunchKernelGGL(k_fill, dim3(L.fillGrid, B), dim3(256), 0, st, d, s.ctrl, s.temp,
                                    s.codes, bs->heapStride, bs->codeStride, rb, bs->reconStride, blockErr, bs->nErrBlk);
-            hipLaunchKernelGGL(k_control, dim3(B), dim3(64), 0, st, d, bs->maxEpochs, guarded, s.ctrl, s.temp,
-                               bs->heapStride, rb, bs->reconStride, blockErr, bs->nErrBlk, errPlane, (bs->leafless && d == D) ? 1 : 0);
+            hipLaunchKernelGGL(k_control, dim3(B), dim3(64), 0, st, d, plan.maxEpochs, plan.guarded ? 1 : 0, s.ctrl, s.temp,
+                               bs->heapStride, rb, bs->reconStride, blockErr, bs->nErrBlk, errPlane, L.sumsOnly ? 1 : 0);
         }
         hipLaunchKernelGGL(k_level_end, dim3(B), dim3(64), 0, st, d, s.ctrl);
     }
@@ -3476,7 +3461,7 @@ static bool dbg_sync(hipStream_t st, const char *phase)
 
 static void fill_emit_args(BrickSet *bs, EmitArgs &a)
 {
-    const bool mr = bs->variant == 2;
+    const bool mr = bs->plan.midRange;
     a.codes = bs->mid.codes; a.codesR = mr ? bs->rng.codes : nullptr;
     a.temp = bs->mid.temp; a.tempR = mr ? bs->rng.temp : nullptr;
     a.rb = ReconBufs{{bs->mid.recon[0], bs->mid.recon[1], bs->mid.recon[2]}};
@@ -3496,29 +3481,21 @@ static void fill_emit_args(BrickSet *bs, EmitArgs &a)
 
 // The reference's contiguous stream(s) of a fused build, into bs->mid.treeCompact (and rng.treeCompact): the bricks'
 // byte offsets (their streams back to back), the words two blocks share zeroed, then spine + string of every block to
-// its place.  At the end of build() (BrickSet::compactOnBuild) or when the host first asks for bytes.  The buffers are
+// its place.  At the end of build() (BuildPlan::compact) or when the host first asks for bytes.  The buffers are
 // sized from the streams' real lengths: the first build of a set guesses, a stream that does not fit raises
 // compactOverflow and writes nothing, and the host (capi.hip contiguous_stream) regrows the buffers and repeats.
+// Allocates nothing: capi.hip ensure_compact_buffers comes first.
 int compact_launch(BrickSet *bs, hipStream_t st)
 {
-    const int D = bs->D, B = bs->B;
-    const bool mr = bs->variant == 2;
-    if (!bs->brickOff && hipMalloc(&bs->brickOff, (size_t)(B + 1) * sizeof(unsigned long long)) != hipSuccess) return -3;
-    if (!bs->compactOverflow && hipMalloc(&bs->compactOverflow, sizeof(int32_t)) != hipSuccess) return -3;
-    if (bs->compactCap == 0) {
-        // first time: 5/8 byte per voxel (the bench volume takes 0.56; noise takes up to 2.3) -- a guess, corrected on demand
-        int64_t cap = (int64_t)B * bs->g.voxels / 8 * 5 + (int64_t)B * 64 + 4096;
-        const int64_t worst = (int64_t)B * bs->treeCap;
-        if (cap > worst) cap = worst;
-        if (hipMalloc(&bs->mid.treeCompact, (size_t)cap) != hipSuccess) return -3;
-        if (mr && hipMalloc(&bs->rng.treeCompact, (size_t)cap) != hipSuccess) { hipFree(bs->mid.treeCompact); bs->mid.treeCompact = nullptr; return -3; }
-        bs->compactCap = cap;
-    }
+    const BuildPlan &plan = bs->plan;
+    const int D = plan.D, B = plan.B;
+    const bool mr = plan.midRange;
+    if (!bs->brickOff || !bs->compactOverflow || !bs->mid.treeCompact || (mr && !bs->rng.treeCompact)) return -1;
     EmitArgs a;
     fill_emit_args(bs, a);
     a.tree = bs->mid.treeCompact; a.treeR = mr ? bs->rng.treeCompact : nullptr;
     a.brickOff = bs->brickOff; a.compactCap = bs->compactCap;
-    const int64_t nblk = cdiv((int64_t)1 << D, 4096);
+    const int64_t nblk = plan.nblk;
     // constant bricks first: their token counts (closed form) are part of the offsets
     hipLaunchKernelGGL(k_brick_offsets, dim3(1), dim3(1024), 0, st, bs->mid.ctrl, B, bs->brickOff, bs->compactCap, bs->compactOverflow);
     hipLaunchKernelGGL(k_emit_zero, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk);
@@ -3532,131 +3509,75 @@ int compact_launch(BrickSet *bs, hipStream_t st)
     return launch_status("compact");
 }
 
-// Internal streams for the forks below, created on first need and only as many as are used: a process has few hardware
-// queues (4 by default), streams beyond them share one, and a kernel queued behind another stream's long copy on a shared
-// queue waits for it (a MidRangeTree build inside the timestep streamer took 236 instead of 68 ms with three idle
-// extra streams per handle).
-static int ensure_aux(BrickSet *bs, int n)
+// Executes a BuildPlan (host_plan.cpp make_build_plan): every `if` below reads a plan field.  Every buffer, stream and
+// event it touches exists (capi.hip vr_brickset_build: the side streams, then the plan, then the buffers, then this).
+int encode_launch(BrickSet *bs, const BuildPlan &plan, const uint8_t *vox, hipStream_t st)
 {
-    if (n > 3) n = 3;
-    if (!bs->evFork && hipEventCreateWithFlags(&bs->evFork, hipEventDisableTiming) != hipSuccess) return 0;
-    int have = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!bs->auxN[i] && hipStreamCreateWithFlags(&bs->auxN[i], hipStreamNonBlocking) != hipSuccess) break;
-        if (!bs->evJoinN[i] && hipEventCreateWithFlags(&bs->evJoinN[i], hipEventDisableTiming) != hipSuccess) break;
-        ++have;
-    }
-    bs->aux = bs->auxN[0]; bs->evJoin = bs->evJoinN[0];
-    return have;
-}
-
-int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
-{
-    const int D = bs->D, B = bs->B;
-    const bool mr = bs->variant == 2;
+    const int D = plan.D, B = plan.B;
+    const bool mr = plan.midRange;
     hipEventRecord(bs->ev[0], st);
-    const uint8_t *rootMinP = nullptr, *rootMaxP = nullptr;   // where the last pyramid round leaves each brick's root (min,max)
-    const bool fused = D >= 12;      // prune + block-local emit in one kernel (K = 6 for every D >= 6)
-    if (bs->leafless != leafless_build(*bs)) return -2;      // (the arrays were sized for the other mode: capi alloc_encoder_buffers)
-    // SkipBlocks needs k_pyramid12's constant bit in front and k_prune_emit12 behind, a prune that makes such blocks
-    // one token (tolerance >= 1) and a level loop that runs
-    bool skipOn = fused && bs->blockFlag && (!mr || bs->blockFlagR) && bs->tolerance >= 1 && bs->maxEpochs >= 1 && D >= 14 && !bs->sw.noSkipBlocks;
-    const int64_t rootStride = (int64_t)1 << (D > 10 ? D - 10 : 0);
-    // ---- BUILD: pyramid.  Bottom 12 levels by k_pyramid12 when x-runs of 16 voxels exist,
-    // the rest (and small / thin bricks) in rounds of <= 10 levels.
-    {
-        int dLeaf = D, round = 0;
-        const uint8_t *inMin = nullptr, *inMax = nullptr;
-        int64_t inStride = 0;
-        const int64_t oStride = (int64_t)1 << (D > 10 ? D - 10 : 0);
+    uint8_t *const flag = plan.skipBlocks ? bs->blockFlag : nullptr, *const flagR = plan.skipBlocks && mr ? bs->blockFlagR : nullptr;
+    uint8_t *const tempR = mr ? bs->rng.temp : nullptr;
+    // ---- BUILD: pyramid.  Each round leaves the (min, max) of its block roots in one of the two carry arrays; the
+    // last one each brick's root's
+    int buf = 0;
+    if (plan.pyr12) {
         const Pyr12Plan &pp = bs->pyr12;      // (planned at create: host_plan.cpp)
-        skipOn = skipOn && pp.use12;
-        if (pp.use12) {
-            Pyr12Geom pg{};
-            pg.ax = pp.ax; pg.ay = pp.ay; pg.az = pp.az;
-            memcpy(pg.sx, pp.sx, sizeof(pg.sx));
-            pg.swz = pp.swz; pg.nbx = pp.nbx; pg.nby = pp.nby; pg.lnbx = pp.lnbx; pg.lnby = pp.lnby;
-            pg.spread = bs->spread;
-            // eight boxes per workgroup where they share their 128-byte lines (no XCD order: the sharers are one workgroup)
-            if (pp.lines && !bs->sw.pyramidBoxes)
-                hipLaunchKernelGGL(k_pyramid12_lines, dim3((unsigned)((int64_t)1 << (D - 15)), B), dim3(256), 0, st, bs->g, pg, vox,
-                                   bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr, bs->mmMin[0], bs->mmMax[0],
-                                   oStride, skipOn ? bs->blockFlag : nullptr, skipOn && mr ? bs->blockFlagR : nullptr);
-            else
-                hipLaunchKernelGGL(k_pyramid12, dim3((unsigned)((int64_t)1 << (D - 12)), B), dim3(256), 0, st, bs->g, pg, vox,
-                                   bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr, bs->mmMin[0], bs->mmMax[0],
-                                   oStride, skipOn ? bs->blockFlag : nullptr, skipOn && mr ? bs->blockFlagR : nullptr);
-            dLeaf = D - 12;
-            inMin = bs->mmMin[0]; inMax = bs->mmMax[0]; inStride = oStride;
-            rootMinP = inMin; rootMaxP = inMax;
-            round = 1;
-        }
-        while (dLeaf > 0 || round == 0) {
-            int L = dLeaf < 10 ? dLeaf : 10;
-            int64_t nblk = (int64_t)1 << (dLeaf - L);
-            uint8_t *oMin = bs->mmMin[round & 1], *oMax = bs->mmMax[round & 1];
-            if (round == 0)
-                hipLaunchKernelGGL(k_pyramid<true>, dim3((unsigned)nblk, B), dim3(256), 0, st, bs->g, dLeaf, L, vox,
-                                   inMin, inMax, inStride, bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr,
-                                   oMin, oMax, oStride, bs->generalGeom ? bs->srcIdx : nullptr);
-            else
-                hipLaunchKernelGGL(k_pyramid<false>, dim3((unsigned)nblk, B), dim3(256), 0, st, bs->g, dLeaf, L, vox,
-                                   inMin, inMax, inStride, bs->mid.temp, bs->heapStride, mr ? bs->rng.temp : nullptr,
-                                   oMin, oMax, oStride, nullptr);
-            dLeaf -= L;
-            rootMinP = oMin; rootMaxP = oMax;
-            if (dLeaf == 0) break;
-            inMin = oMin; inMax = oMax; inStride = oStride;
-            ++round;
-        }
+        Pyr12Geom pg{};
+        pg.ax = pp.ax; pg.ay = pp.ay; pg.az = pp.az;
+        memcpy(pg.sx, pp.sx, sizeof(pg.sx));
+        pg.swz = pp.swz; pg.nbx = pp.nbx; pg.nby = pp.nby; pg.lnbx = pp.lnbx; pg.lnby = pp.lnby;
+        pg.spread = bs->spread;
+        // eight boxes per workgroup where they share their 128-byte lines (no XCD order: the sharers are one workgroup)
+        hipLaunchKernelGGL(plan.pyr12Lines ? k_pyramid12_lines : k_pyramid12, dim3(plan.pyr12Grid, B), dim3(256), 0, st, bs->g, pg, vox,
+                           bs->mid.temp, bs->heapStride, tempR, bs->mmMin[0], bs->mmMax[0], plan.rootStride, flag, flagR);
+        buf = 1;
     }
+    for (int r = 0; r < plan.pyrRounds; ++r, buf ^= 1) {
+        const PyrRound &R = plan.pyr[r];
+        const bool fromVoxels = r == 0 && !plan.pyr12;
+        hipLaunchKernelGGL(fromVoxels ? k_pyramid<true> : k_pyramid<false>, dim3(R.blocks, B), dim3(256), 0, st, bs->g, R.dLeaf, R.L, vox,
+                           fromVoxels ? nullptr : bs->mmMin[buf ^ 1], fromVoxels ? nullptr : bs->mmMax[buf ^ 1],
+                           fromVoxels ? (int64_t)0 : plan.rootStride, bs->mid.temp, bs->heapStride, tempR,
+                           bs->mmMin[buf], bs->mmMax[buf], plan.rootStride, fromVoxels && plan.pyrSrcIdx ? bs->srcIdx : nullptr);
+    }
+    const uint8_t *const rootMinP = bs->mmMin[buf ^ 1], *const rootMaxP = bs->mmMax[buf ^ 1];    // the last round's
     hipEventRecord(bs->ev[1], st);
     dbg_sync(st, "pyramid");
     // ---- COMPRESS
-    // constant bricks take the closed form (both streams of a MidRangeTree too; needs the leaf prune and an epoch to exist)
-    const bool constOk = bs->maxEpochs >= 1 && bs->tolerance >= 1 && D >= 1;
-    const uint8_t *cMin = constOk ? rootMinP : nullptr, *cMax = constOk ? rootMaxP : nullptr;
-    const SkipBlocks sk{skipOn ? bs->blockFlag : nullptr, (int64_t)1 << (D >= 12 ? D - 12 : 0), D - 2};
-    const SkipBlocks skR{skipOn && mr ? bs->blockFlagR : nullptr, sk.nBlk, D - 2};
+    // constant bricks take the closed form
+    const uint8_t *cMin = plan.constClosedForm ? rootMinP : nullptr, *cMax = plan.constClosedForm ? rootMaxP : nullptr;
+    const SkipBlocks sk{flag, plan.boxes, D - 2};
+    const SkipBlocks skR{flagR, plan.boxes, D - 2};
     // MidRangeTree: the two streams' level loops do not depend on each other (M.cpp:399-544 runs them one after the
     // other): the half-range stream's goes to the set's second stream, so its one-wave-per-brick walkers run beside
     // the mid stream's wide kernels and the other way round
-    const bool forkR = mr && bs->blockErrR && bs->estSummR && ensure_aux(bs, 1) == 1;
-    if (forkR) {
+    if (plan.forkRange) {
         hipEventRecord(bs->evFork, st);
         hipStreamWaitEvent(bs->aux, bs->evFork, 0);
-        compress_stream(bs, bs->rng, bs->aux, cMin, cMax, rootStride, skR, bs->blockErrR, bs->estSummR);
+        compress_stream(bs, plan, bs->rng, bs->aux, cMin, cMax, skR, bs->blockErrR, bs->estSummR, 0, B);
         hipEventRecord(bs->evJoin, bs->aux);
     }
     // VolumeKdtree: the same trick over ranges of the bricks (vr_brickset_set_concurrency; 2 by default)
-    int parts = bs->levelLoopStreams;
-    if (parts > 4) parts = 4;
-    if (mr || B < 16 * parts || parts < 2) parts = 1;
-    if (parts > 1) parts = 1 + ensure_aux(bs, parts - 1);
-    if (parts > 1) {
-        hipEventRecord(bs->evFork, st);
-        for (int p = 1; p < parts; ++p) {
-            const int b0 = (int)((int64_t)B * p / parts), b1 = (int)((int64_t)B * (p + 1) / parts);
-            hipStreamWaitEvent(bs->auxN[p - 1], bs->evFork, 0);
-            compress_stream(bs, bs->mid, bs->auxN[p - 1], cMin, cMax, rootStride, sk, bs->blockErr, bs->estSumm, b0, b1 - b0);
-            hipEventRecord(bs->evJoinN[p - 1], bs->auxN[p - 1]);
-        }
-        compress_stream(bs, bs->mid, st, cMin, cMax, rootStride, sk, bs->blockErr, bs->estSumm, 0, (int)((int64_t)B / parts));
-        for (int p = 1; p < parts; ++p) hipStreamWaitEvent(st, bs->evJoinN[p - 1], 0);
-    } else
-    compress_stream(bs, bs->mid, st, cMin, cMax, rootStride, sk, bs->blockErr, bs->estSumm);
-    if (forkR) hipStreamWaitEvent(st, bs->evJoin, 0);
-    else if (mr) compress_stream(bs, bs->rng, st, cMin, cMax, rootStride, skR, bs->blockErr, bs->estSumm);
+    if (plan.parts > 1) hipEventRecord(bs->evFork, st);
+    for (int p = 1; p < plan.parts; ++p) {
+        hipStreamWaitEvent(bs->auxN[p - 1], bs->evFork, 0);
+        compress_stream(bs, plan, bs->mid, bs->auxN[p - 1], cMin, cMax, sk, bs->blockErr, bs->estSumm, plan.range[p], plan.range[p + 1] - plan.range[p]);
+        hipEventRecord(bs->evJoinN[p - 1], bs->auxN[p - 1]);
+    }
+    compress_stream(bs, plan, bs->mid, st, cMin, cMax, sk, bs->blockErr, bs->estSumm, 0, plan.range[1]);
+    for (int p = 1; p < plan.parts; ++p) hipStreamWaitEvent(st, bs->evJoinN[p - 1], 0);
+    if (plan.forkRange) hipStreamWaitEvent(st, bs->evJoin, 0);
+    else if (mr) compress_stream(bs, plan, bs->rng, st, cMin, cMax, skR, bs->blockErr, bs->estSumm, 0, B);
     hipEventRecord(bs->ev[2], st);
     dbg_sync(st, "compress");
     // ---- PRUNE
     hipLaunchKernelGGL(k_chain_lut, dim3(1), dim3(256), 0, st, kernel_tolerance(*bs), bs->maxDepth - D, bs->chainLut);
     ReconBufs rb{{bs->mid.recon[0], bs->mid.recon[1], bs->mid.recon[2]}};
     ReconBufs rbR{{bs->rng.recon[0], bs->rng.recon[1], bs->rng.recon[2]}};
-    int pruneFrom = D - 1;
     bs->fineHas.assign((size_t)B, 0);
     fine_has_changed(*bs);
-    if (fused) {
+    if (plan.fused) {
         PruneEmitArgs pa;
         pa.sk = sk; pa.skR = skR;
         pa.D = D; pa.tol = kernel_tolerance(*bs); pa.maxDepth = bs->maxDepth; pa.ctrls = bs->mid.ctrl;
@@ -3664,37 +3585,27 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
         pa.heapStride = bs->heapStride; pa.codeStride = bs->codeStride; pa.leafStride = bs->reconStride;
         pa.rb = rb; pa.subTok = bs->blockOff; pa.nEmitBlk = bs->nEmitBlk; pa.blockL1 = bs->blockL1;
         pa.chainLut = bs->chainLut; pa.idxOff = bs->idxOff; pa.nIdx = bs->nIdx;
-        if (!bs->fineIdx && hipMalloc(&bs->fineIdx, (size_t)B * bs->nIdx * 16) != hipSuccess) return -3;
-        if (!bs->idxVal3 && hipMalloc(&bs->idxVal3, (size_t)B * bs->nIdx * 8) != hipSuccess) return -3;
         // the uniform hint of k_decode_region: no flag of an earlier build survives, whichever kernels serve this one
-        const size_t boxBytes = (size_t)B * ((size_t)1 << (D - 12)) * sizeof(uint32_t);
-        if (!bs->boxUniform && hipMalloc(&bs->boxUniform, boxBytes) != hipSuccess) return -3;
-        if (hipMemsetAsync(bs->boxUniform, 0, boxBytes, st) != hipSuccess) return -1;
+        if (hipMemsetAsync(bs->boxUniform, 0, (size_t)B * (size_t)plan.boxes * sizeof(uint32_t), st) != hipSuccess) return -1;
         pa.fineIdx = (uint32_t *)bs->fineIdx; pa.boxUniform = bs->boxUniform;
-        pa.ctrlsR = mr ? bs->rng.ctrl : nullptr; pa.tempR = mr ? bs->rng.temp : nullptr; pa.codesR = mr ? bs->rng.codes : nullptr;
+        pa.ctrlsR = mr ? bs->rng.ctrl : nullptr; pa.tempR = tempR; pa.codesR = mr ? bs->rng.codes : nullptr;
         pa.rbR = rbR;
         pa.gap = bs->mid.tree; pa.gapR = mr ? bs->rng.tree : nullptr; pa.treeCap = bs->treeCap;
-        const dim3 peGrid((unsigned)((int64_t)1 << (D - 12)), B);
+        const dim3 peGrid(plan.pruneGrid, B);
         // constant blocks of a leafless SkipBlocks build have a closed form (k_prune_emit12_const); the two launches
         // write disjoint blocks, and heap nodes 1 .. 3 of a block, whose bytes neighbours share, only through cset3
-        pa.uniformBlocks = skipOn && bs->leafless && !mr && !bs->sw.noUniformBlocks;
-        if (pa.uniformBlocks)
-            hipLaunchKernelGGL(k_prune_emit12_const, dim3((unsigned)cdiv((int64_t)1 << (D - 12), PEC_BOXES), B), dim3(256), 0, st, pa);
-        if (bs->leafless) {
-            hipLaunchKernelGGL((k_prune_emit12<false, true>), peGrid, dim3(256), 0, st, pa);
-            if (mr) hipLaunchKernelGGL((k_prune_emit12<true, true>), peGrid, dim3(256), 0, st, pa);
-        } else {
-            hipLaunchKernelGGL((k_prune_emit12<false, false>), peGrid, dim3(256), 0, st, pa);
-            if (mr) hipLaunchKernelGGL((k_prune_emit12<true, false>), peGrid, dim3(256), 0, st, pa);
-        }
-        pruneFrom = D - 13;
+        pa.uniformBlocks = plan.uniformBlocks;
+        if (plan.uniformBlocks)
+            hipLaunchKernelGGL(k_prune_emit12_const, dim3(plan.uniformGrid, B), dim3(256), 0, st, pa);
+        hipLaunchKernelGGL((plan.leafless ? k_prune_emit12<false, true> : k_prune_emit12<false, false>), peGrid, dim3(256), 0, st, pa);
+        if (mr) hipLaunchKernelGGL((plan.leafless ? k_prune_emit12<true, true> : k_prune_emit12<true, false>), peGrid, dim3(256), 0, st, pa);
         bs->fineHas.assign((size_t)B, 1);
         fine_has_changed(*bs);
     } else
-        hipLaunchKernelGGL(k_prune_leaf, dim3(cdiv((int64_t)1 << D, 256), B), dim3(256), 0, st, D, kernel_tolerance(*bs),
+        hipLaunchKernelGGL(k_prune_leaf, dim3(plan.pruneGrid, B), dim3(256), 0, st, D, kernel_tolerance(*bs),
                            bs->mid.ctrl, bs->mid.temp, bs->mid.codes, mr ? bs->rng.codes : nullptr, bs->heapStride,
                            bs->codeStride, rb, bs->reconStride, bs->maxDepth, bs->blockL1, bs->nEmitBlk);
-    for (int d = pruneFrom; d >= 0; --d)
+    for (int d = plan.pruneFrom; d >= 0; --d)
         hipLaunchKernelGGL(k_prune_level, dim3(cdiv((int64_t)1 << d, 256), B), dim3(256), 0, st, d, bs->mid.ctrl, bs->mid.codes,
                            mr ? bs->rng.codes : nullptr, bs->codeStride);
     hipLaunchKernelGGL(k_fix_chain_distances, dim3(B), dim3(64), 0, st, D, bs->maxDepth, bs->mid.ctrl,
@@ -3704,36 +3615,29 @@ int encode_launch(BrickSet *bs, const uint8_t *vox, hipStream_t st)
     // ---- CONVERT
     EmitArgs a;
     fill_emit_args(bs, a);
-    const int64_t nblk = cdiv((int64_t)1 << D, fused ? 4096 : EMIT_RANKS_PER_BLOCK);
-    if (fused) hipLaunchKernelGGL(k_block_alive, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk, 12);   // + token counts
+    const int64_t nblk = plan.nblk;
+    if (plan.fused) hipLaunchKernelGGL(k_block_alive, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk, 12);   // + token counts
     else hipLaunchKernelGGL(k_emit_count, dim3((unsigned)nblk, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
     dbg_sync(st, "block_alive/count");
     hipLaunchKernelGGL(k_emit_scan, dim3(B), dim3(1024), 0, st, a, nblk);
     dbg_sync(st, "emit_scan");
     // fused: the strings stay in their slots of the gapped buffer, the decode index points there (k_index12); the
     // contiguous stream is made when the host asks for it (compact_launch)
-    bs->gapped = fused;
+    bs->gapped = plan.gapped;
     bs->compactValid = false;
-    // (k_index12 writes the index entries of constant bricks too; the per-block kernel leaves them to k_const_finish)
-    const bool idxBatched = fused && !bs->sw.indexPerBlock;
-    if (idxBatched) hipLaunchKernelGGL(k_index12, dim3(cdiv(nblk, IDX_BLOCKS), B), dim3(256), 0, st, a, (uint32_t)nblk);
-    else if (fused) hipLaunchKernelGGL(k_index12_block, dim3(cdiv(nblk, 4), B), dim3(256), 0, st, a, (uint32_t)nblk);
+    if (plan.index == VR_INDEX12) hipLaunchKernelGGL(k_index12, dim3(plan.indexGrid, B), dim3(256), 0, st, a, (uint32_t)nblk);
+    else if (plan.index == VR_INDEX12_BLOCK) hipLaunchKernelGGL(k_index12_block, dim3(plan.indexGrid, B), dim3(256), 0, st, a, (uint32_t)nblk);
     else {
         hipLaunchKernelGGL(k_emit_zero, dim3(cdiv(nblk, 256), B), dim3(256), 0, st, a, nblk);
-        hipLaunchKernelGGL(k_emit_write, dim3((unsigned)nblk, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
+        hipLaunchKernelGGL(k_emit_write, dim3(plan.indexGrid, B), dim3(EMIT_RANKS_PER_BLOCK), 0, st, a);
     }
-    // statistics records: one per 1024 leaves from k_prune_emit12, one per 256 from k_prune_leaf
-    hipLaunchKernelGGL(k_emit_stats, dim3(B), dim3(1024), 0, st, a, (int64_t)(D >= 12 ? cdiv((int64_t)1 << D, 1024) : cdiv((int64_t)1 << D, 256)));
-    if (idxBatched)
-        hipLaunchKernelGGL(k_const_finish, dim3(1, B), dim3(64), 0, st, D, bs->mid.ctrl, bs->mid.tree,
-                           bs->treeCap, bs->idxOff, bs->idxVal, (int64_t)0);
-    else
-        hipLaunchKernelGGL(k_const_finish, dim3(cdiv(bs->nIdx, 256), B), dim3(256), 0, st, D, bs->mid.ctrl, bs->mid.tree,
-                           bs->treeCap, bs->idxOff, bs->idxVal, bs->nIdx);
+    hipLaunchKernelGGL(k_emit_stats, dim3(B), dim3(1024), 0, st, a, plan.statRecords);
+    hipLaunchKernelGGL(k_const_finish, dim3(plan.constFinishGrid, B), dim3(plan.constFinishThreads), 0, st, D, bs->mid.ctrl, bs->mid.tree,
+                       bs->treeCap, bs->idxOff, bs->idxVal, plan.constFinishIdx);
     if (mr) hipLaunchKernelGGL(k_const_finish_range, dim3(B), dim3(64), 0, st, D, bs->rng.ctrl, bs->rng.tree, bs->treeCap);
     // the reference's build() ends with the contiguous stream (tree.swap(preorderTree), R.cpp:714-718): so does this one,
     // unless the caller turned it off (vr_brickset_set_compaction): the decoders read the block strings where they are
-    if (fused && bs->compactOnBuild) {
+    if (plan.compact) {
         const int rc = compact_launch(bs, st);
         if (rc != 0) return rc;
     }
