@@ -5,9 +5,13 @@ BrickSet.decode_lod against BrickSet.decode with HIP events (median of --reps, a
   full      every brick at max_tree_depth (the same kernels as decode: expected equal within noise)
   default   the start camera (0, 0, -0.75), fov 50, 1920 x 1080, cuts from select_lod at pixel tolerance 1
   inside    a camera at the cube's centre looking along +z: the bricks behind it and outside its fov are culled
-and reports decoded voxels per ms for each."""
+and reports decoded voxels per ms for each.
+
+--host-bricks B instead: the host time of one decode_lod call (planning, staging and enqueueing; the stream is idle when
+the call starts and is not waited for) on B bricks of 32^3 with cuts of every class, median and minimum in microseconds."""
 import argparse
 import json
+import time
 import os
 import sys
 
@@ -38,11 +42,39 @@ def timed(fn, reps):
     return float(np.median(ms)), ms
 
 
+def host_time(B, reps):
+    bd = (32, 32, 32)
+    V = bd[0] * bd[1] * bd[2]
+    g = torch.Generator(device="cuda").manual_seed(5)
+    ramp = (torch.arange(B * V, device="cuda") // 97 % 200).to(torch.uint8)
+    vox = ramp + torch.randint(0, 3, (B * V,), generator=g, device="cuda", dtype=torch.uint8)
+    bs = vr.BrickSet(B, bd, 1, 2)
+    bs.build(vox)
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    choices = [-1, 0, 3, D - 7, D - 6, D - 3, D - 1, D, M]
+    cuts = np.array([choices[b % len(choices)] for b in range(B)], np.int32)
+    out = torch.empty(B * V, dtype=torch.uint8, device="cuda")
+    us = []
+    for _ in range(reps + 5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bs.decode_lod(cuts, out=out)
+        us.append((time.perf_counter() - t0) * 1e6)
+    torch.cuda.synchronize()
+    us = us[5:]
+    print("decode_lod host time, %d bricks of %s, %d calls: median %.1f us, min %.1f us" % (B, bd, reps, float(np.median(us)), min(us)), flush=True)
+    print(json.dumps({"host_bricks": B, "median_us": float(np.median(us)), "min_us": min(us)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report (text + one JSON line) here")
     ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--host-bricks", type=int, default=0, help="only the host time of one decode_lod call on this many 32^3 bricks")
     args = ap.parse_args()
+    if args.host_bricks:
+        return host_time(args.host_bricks, args.reps)
     bd, gd, grid = (256, 256, 128), (2048, 2048, 1920), (8, 8, 15)
     vox4 = bench.make_volume_gpu(torch, gd, bd, seed=12345)
     B = vox4.shape[0]

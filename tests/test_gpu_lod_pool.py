@@ -372,6 +372,52 @@ def test_pool_back_to_back_one_stream_and_two_streams(vr, render_set):
             assert np.array_equal(t.cpu().numpy(), serial[i % 3][1]), i
 
 
+def test_skipped_and_refused_calls_leave_the_slot_ring(vr):
+    """A per-brick call in which every brick is skipped, and one refused for its misaligned pool, claim no slot of the
+    set's ring and touch none.  Made before and between calls that are still queued, on two streams and with one call
+    more than the ring has slots, they change nothing: every call still gives what it gives alone."""
+    import torch
+    shape, B, slots = (16, 16, 16), 4, 4                       # slots: VR_LOD_SLOTS
+    bs = vr.BrickSet(B, shape, 1, 2)
+    bs.build(np.stack([rm_like(shape, s) for s in range(B)]))
+    info = bs.info(0)
+    D, M = info["orig_tree_depth"], info["max_tree_depth"]
+    Ds = D - 6
+    ijk, grid = line_ijk(B)
+    # above the index level (the slot's cut values), coarse (staged and packed), full resolution, skipped
+    choices = [0, 3, Ds - 1, Ds, D - 3, D - 1, D, M, -1]
+    plans = [np.array([choices[(2 * r + 3 * b) % len(choices)] for b in range(B)], np.int32) for r in range(slots + 1)]
+    serial = []
+    for cuts in plans:
+        p, t = run_pool(vr, bs, cuts, ijk, grid)
+        torch.cuda.synchronize()
+        serial.append((p.cpu().numpy(), t.cpu().numpy()))
+    dense = torch.full((B * bs.voxels_per_brick,), FILL, dtype=torch.uint8, device="cuda")
+    odd = torch.full((B * bs.voxels_per_brick + 64,), FILL, dtype=torch.uint8, device="cuda")
+    tab = torch.full((B * 16,), 0x5A, dtype=torch.uint8, device="cuda")
+    coarse = np.full(B, D - 3, np.int32)                      # stored rows of 8 bytes: k_pool_pack writes words
+
+    def idle_calls():
+        bs.decode_lod(np.full(B, -1, np.int32), out=dense)
+        with pytest.raises(vr.VrError) as e:
+            bs.decode_lod_pool(coarse, ijk, grid, pool=odd[1:], table=tab)
+        assert e.value.status == -1
+
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    idle_calls()
+    outs = []
+    for i, cuts in enumerate(plans):
+        outs.append(run_pool(vr, bs, cuts, ijk, grid, stream=streams[i % 2]))
+        if i in (1, 3):
+            idle_calls()
+    torch.cuda.synchronize()
+    for i, (p, t) in enumerate(outs):
+        assert np.array_equal(p.cpu().numpy(), serial[i][0]), i
+        assert np.array_equal(t.cpu().numpy(), serial[i][1]), i
+    assert bool((dense == FILL).all()) and bool((odd == FILL).all()) and bool((tab == 0x5A).all())
+
+
 def test_full_size_start_camera(vr):
     """The bench volume at the start camera, 1920 x 1080: the pool frame is the dense LOD frame, the pool is the
     layout's size."""

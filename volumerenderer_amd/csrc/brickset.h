@@ -26,9 +26,10 @@ struct Stream2 {              // one 2-bit stream (mid, or MidRangeTree's half-r
 struct LodSlot {
     int32_t *dev = nullptr;        // 3B: the cuts of all B bricks, then the class lists (together at most 2B entries)
     int32_t *host = nullptr;       // 3B pinned: the same, staged for the copy
-    uint8_t *idxValCut = nullptr;  // B * nIdx: cut values of the bricks cut above depth Ds (first needed: allocated)
-    uint32_t *decTables = nullptr; // B * FD_TABLE_WORDS: k_decode_fine's tables at each brick's cut (first needed)
-    uint8_t *rankVals = nullptr;   // B * 2^D * 2: general-extent decode scratch (first needed)
+    // (the next three: made by capi.hip ensure_lod_slot for the first call whose LodPlan::needs names them)
+    uint8_t *idxValCut = nullptr;  // B * nIdx: cut values of the bricks cut above depth Ds
+    uint32_t *decTables = nullptr; // B * VR_FD_TABLE_WORDS: k_decode_fine's tables at each brick's cut
+    uint8_t *rankVals = nullptr;   // B * 2^D * 2: general-extent decode scratch
     int64_t *obDev = nullptr;      // 3B, pool decodes only: each list entry's output offset (B), then the pack
     int64_t *obHost = nullptr;     //   descriptors of the coarse bricks (2 per brick); 3B pinned: the same, staged
     vr_pool_entry *tabHost = nullptr;  // pool decodes with a table: its pinned host image (tabCap entries)
@@ -140,7 +141,7 @@ struct BrickSet {
     void *lastStream = nullptr;
     LodSlot lodSlot[VR_LOD_SLOTS];
     int lodNext = 0;
-    // vr_brickset_decode_lod_pool: VR_POOL_STAGE_BRICKS decoded coarse bricks (first needed), shared by the calls of
+    // vr_brickset_decode_lod_pool: VR_POOL_STAGE_BRICKS decoded coarse bricks (ensure_lod_slot, for the first staged plan), shared by the calls of
     // every stream; stageDone is recorded after a call's last read of it and waited for by the next call's stream
     uint8_t *poolStage = nullptr;
     hipEvent_t stageDone = nullptr;
@@ -174,12 +175,14 @@ int encode_launch(BrickSet *bs, const BuildPlan &plan, const uint8_t *voxDev, hi
 // fused builds: contiguous stream(s) into Stream2::treeCompact; -1 without its buffers (capi.hip ensure_compact_buffers)
 int compact_launch(BrickSet *bs, hipStream_t st);
 // kd_decode.hip
-// would the call store vectors to the caller's buffer (the tiled kernels, k_pool_pack)?  capi.hip asks before it launches
-bool decode_stores_vectors(const BrickSet *bs, int cutDepth, bool rangeStream);
-bool decode_lod_stores_vectors(const BrickSet *bs, const int32_t *cutsHost, const PoolDest *pool);
-int decode_launch(BrickSet *bs, uint8_t *outDev, int cutDepth, hipStream_t st, bool rangeStream = false);
-// per-brick cuts (-1: skip; 0 .. maxDepth, checked by the caller); foreign sets: hostCtrl must be current
-int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *outDev, hipStream_t st, const PoolDest *pool = nullptr);
+// execute a plan (host_plan.h): allocate nothing, create no event; capi.hip has made whatever the plan's `needs` names,
+// written the quad tables (chain_tables_launch, once per set) and filled the cut values a foreign set's plan leaves to it
+int chain_tables_launch(BrickSet *bs, hipStream_t st);
+int decode_launch(BrickSet *bs, const DecodePlan &plan, uint8_t *outDev, hipStream_t st);
+// per-brick cuts: lod_stage uploads the plan's lists, offsets and pool table through the slot the caller has claimed,
+// decode_lod_launch runs the classes (outDev: the caller's buffer, the pool of a pool decode) and records the slot's event
+int lod_stage(BrickSet *bs, const LodPlan &plan, LodSlot &slot, const vr_pool_entry *tab, vr_pool_entry *tabDev, hipStream_t st);
+int decode_lod_launch(BrickSet *bs, const LodPlan &plan, LodSlot &slot, uint8_t *outDev, hipStream_t st);
 void free_lod_slots(BrickSet *bs);
 // error_table.hip: per-brick error of two buffers of B bricks x V bytes, added into out[0 .. B) (cleared by the caller)
 int brick_error_launch(const uint8_t *a, const uint8_t *b, int64_t B, int64_t V, vr_brick_error *out, hipStream_t st);

@@ -30,6 +30,10 @@ static bool device_ok()
     return e == hipSuccess && n > 0;
 }
 
+// first need: a device / pinned host buffer that stays (false: it could not be made)
+template <class T> static bool ensure_dev(T *&p, size_t bytes) { return p || hipMalloc(&p, bytes) == hipSuccess; }
+template <class T> static bool ensure_pinned(T *&p, size_t bytes) { return p || hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess; }
+
 // a vr_projection (vrhip.h); vr_compositor_composite_proj (compositor.hip) makes the same check through raymarch.h
 namespace vr {
 bool projection_ok(const vr_projection *pj)
@@ -255,6 +259,76 @@ static int ensure_aux(BrickSet &b, int n)
     }
     b.aux = b.auxN[0]; b.evJoin = b.evJoinN[0];
     return have;
+}
+
+// ---- a decode call, in the order of a build: validate, plan (host_plan.h make_decode_plan / make_lod_plan), check the
+// caller's alignment from the plan, ensure every buffer its `needs` names (a per-brick call then waits for and claims its
+// ring slot), fill the cut values the plan leaves to the caller, launch.  A failure up to the claim has enqueued nothing
+// (but the quad tables, once per set), recorded no timing event and left the ring where it was.
+static DecodeInputs decode_inputs(const BrickSet &b, bool rangeStream)
+{
+    DecodeInputs in{};
+    in.D = b.D; in.Ds = b.Ds; in.B = b.B; in.nb0 = b.g.nb[0];
+    in.nIdx = b.nIdx; in.voxels = b.g.voxels; in.leafStride = b.leafStride; in.nEmitBlk = b.nEmitBlk;
+    in.generalGeom = b.generalGeom; in.idx64 = b.idx64;
+    in.tileOk = b.tile.ok; in.tiles = b.tile.tilesX * b.tile.tilesY * b.tile.tilesZ;
+    in.regionOk = b.region.ok; in.nreg = b.region.nreg;
+    in.fineAll = b.fineIdx && b.fineAll; in.idxVal3 = b.idxVal3 != nullptr; in.foreign = b.foreign; in.rangeStream = rangeStream;
+    in.decodeWalk = b.sw.decodeWalk; in.decodeFineV1 = b.sw.decodeFineV1; in.decodeQuad = b.sw.decodeQuad;
+    in.noUniformDecode = b.sw.noUniformDecode;
+    return in;
+}
+
+// k_decode_quad's tables, written once per set, by whichever call first needs them
+static vr_status ensure_chain_tables(BrickSet &b, hipStream_t st)
+{
+    if (b.chainTabReady) return VR_OK;
+    if (!ensure_dev(b.chainTab, (size_t)(VR_CHAIN_LEVELS + 1) * VR_QD_CHAIN_ENTRIES * 4)) return VR_ERR_OOM;
+    // (the first use may come from any stream: make the tables visible to all of them before going on)
+    if (chain_tables_launch(&b, st) != 0 || hipStreamSynchronize(st) != hipSuccess) return VR_ERR_NO_DEVICE;
+    b.chainTabReady = true;
+    return VR_OK;
+}
+
+// the scratch of a uniform decode (the set's) or of a per-brick one (its slot's); the quad tables last: nothing is
+// enqueued before the last allocation
+static vr_status ensure_decode_scratch(BrickSet &b, const DecodeNeeds &n, uint8_t *&idxValCut, uint32_t *&decTables, uint8_t *&rankVals,
+                                       hipStream_t st)
+{
+    const size_t B = (size_t)b.B;
+    if ((n.idxValCut && !ensure_dev(idxValCut, B * (size_t)b.nIdx)) || (n.decTables && !ensure_dev(decTables, B * VR_FD_TABLE_WORDS * 4)) ||
+        (n.rankVals && !ensure_dev(rankVals, B * (size_t)b.leafStride * 2))) {
+        (void)hipGetLastError();
+        return VR_ERR_OOM;
+    }
+    return n.chainTab ? ensure_chain_tables(b, st) : VR_OK;
+}
+
+// The next ring slot with everything the plan touches, claimed (lodNext advances) only when all of it exists.  The
+// slot's previous call (any stream) may still read its lists, cut values and tables: waited for first, on the host
+static vr_status ensure_lod_slot(BrickSet &b, const LodPlan &p, hipStream_t st, LodSlot *&slot)
+{
+    LodSlot &s = b.lodSlot[b.lodNext];
+    if (s.pending && hipEventSynchronize(s.done) != hipSuccess) return VR_ERR_NO_DEVICE;
+    s.pending = false;
+    const size_t B = (size_t)b.B;
+    bool ok = ensure_dev(s.dev, 3 * B * sizeof(int32_t)) && ensure_pinned(s.host, 3 * B * sizeof(int32_t));
+    if (!p.offsets.empty()) ok = ok && ensure_dev(s.obDev, 3 * B * sizeof(int64_t)) && ensure_pinned(s.obHost, 3 * B * sizeof(int64_t));
+    if (ok && s.tabCap < p.tableCells) {
+        if (s.tabHost) hipHostFree(s.tabHost);
+        s.tabHost = nullptr; s.tabCap = 0;
+        ok = ensure_pinned(s.tabHost, (size_t)p.tableCells * sizeof(vr_pool_entry));
+        if (ok) s.tabCap = p.tableCells;
+    }
+    if (p.staged) ok = ok && ensure_dev(b.poolStage, (size_t)VR_POOL_STAGE_BRICKS * b.g.voxels);
+    if (!ok) { (void)hipGetLastError(); return VR_ERR_OOM; }
+    if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return VR_ERR_NO_DEVICE;
+    if (p.staged && !b.stageDone && hipEventCreateWithFlags(&b.stageDone, hipEventDisableTiming) != hipSuccess) return VR_ERR_NO_DEVICE;
+    const vr_status rc = ensure_decode_scratch(b, p.needs, s.idxValCut, s.decTables, s.rankVals, st);
+    if (rc != VR_OK) return rc;
+    b.lodNext = (b.lodNext + 1) % VR_LOD_SLOTS;
+    slot = &s;
+    return VR_OK;
 }
 
 vr_status vr_brickset_destroy(vr_brickset *h)
@@ -605,6 +679,40 @@ vr_status vr_brickset_get_packed4(vr_brickset *h, int32_t brick, uint8_t *dst, i
     return VR_OK;
 }
 
+// The one route for "foreign set, cut above Ds": the scalar of every depth-Ds subtree's ancestor at the brick's cut,
+// into dst (B * nIdx).  cuts: per brick (only those in [0, Ds) are filled), or null: every brick at `cut`.  Bricks
+// installed by vr_brickset_set_trees: from the heap their install wrote, on the stream -- a uniform cut run by run; a
+// per-brick decode in one launch over the nTop bricks its uploaded image lists first (imageDev: LodPlan::image).  The
+// others: from the stream bytes kept at set_tree/open time, by blocking copies, after sync_ctrl (numActive, distanceMap)
+static vr_status foreign_cut_values(BrickSet &b, uint8_t *dst, const int32_t *cuts, int cut, const int32_t *imageDev, int nTop,
+                                    hipStream_t st)
+{
+    const auto host = [&](int br) { const int c = cuts ? cuts[br] : cut; return c >= 0 && c < b.Ds && !top_indexed(b, br); };
+    if (imageDev && cut_from_top_launch(&b, imageDev + b.B, imageDev, 0, nTop, 0, dst, st) != 0) return VR_ERR_NO_DEVICE;
+    for (int br = 0; !imageDev && br < b.B;) {
+        if (!top_indexed(b, br)) { ++br; continue; }
+        int e = br;
+        while (e < b.B && top_indexed(b, e)) ++e;
+        if (cut_from_top_launch(&b, nullptr, nullptr, br, e - br, cut, dst, st) != 0) return VR_ERR_NO_DEVICE;
+        br = e;
+    }
+    bool hostFill = false;
+    for (int br = 0; br < b.B; ++br) hostFill = hostFill || host(br);
+    const vr_status rc = hostFill ? sync_ctrl(b) : VR_OK;
+    if (rc != VR_OK) return rc;
+    std::vector<uint8_t> vals;
+    for (int br = 0; br < b.B; ++br) {
+        if (!host(br)) continue;
+        vals.assign((size_t)b.nIdx, 0);
+        if (br < (int)b.hostTree.size() && !b.hostTree[br].empty() &&
+            cut_values_from_stream(b.D, b.Ds, b.K, b.nIdx, b.hostTree[br].data(), (int64_t)b.hostCtrl[br].numActive,
+                                   b.hostCtrl[br].distanceMap, cuts ? cuts[br] : cut, vals) != 0)
+            return VR_ERR_FORMAT;
+        HIPCHK(hipMemcpy(dst + (size_t)br * b.nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice));
+    }
+    return VR_OK;
+}
+
 // rangeStream: a MidRangeTree's half-range stream (vr_brickset_decode_range)
 static vr_status decode_common(vr_brickset *h, int32_t cut_depth, uint8_t *out, void *stream, bool rangeStream)
 {
@@ -615,32 +723,14 @@ static vr_status decode_common(vr_brickset *h, int32_t cut_depth, uint8_t *out, 
     if (rangeStream && b.foreign) return VR_ERR_UNSUPPORTED;   // an opened file carries no BFS codes to seed the index scalars from
     if (cut_depth > b.maxDepth) return VR_ERR_INVALID;
     const int cut = cut_depth < 0 ? b.maxDepth : cut_depth;
-    if (decode_stores_vectors(&b, cut, rangeStream) && misaligned16(out)) return VR_ERR_INVALID;
-    if (cut < b.Ds && b.foreign) {
-        // ancestor scalars at the cut depth, from the stream bytes kept at set_tree/open time
-        // bricks installed by vr_brickset_set_trees: from the heap their install wrote, on the stream, run by run
-        bool hostFill = false;
-        for (int br = 0; br < b.B;) {
-            if (!top_indexed(b, br)) { hostFill = true; ++br; continue; }
-            int e = br;
-            while (e < b.B && top_indexed(b, e)) ++e;
-            if (cut_from_top_launch(&b, nullptr, nullptr, br, e - br, cut, b.idxValCut, (hipStream_t)stream) != 0) return VR_ERR_NO_DEVICE;
-            br = e;
-        }
-        vr_status rc = hostFill ? sync_ctrl(b) : VR_OK;
-        if (rc != VR_OK) return rc;
-        for (int br = 0; br < b.B; ++br) {
-            if (top_indexed(b, br)) continue;
-            std::vector<uint8_t> vals((size_t)b.nIdx, 0);
-            if (br < (int)b.hostTree.size() && !b.hostTree[br].empty() &&
-                cut_values_from_stream(b.D, b.Ds, b.K, b.nIdx, b.hostTree[br].data(), (int64_t)b.hostCtrl[br].numActive,
-                                       b.hostCtrl[br].distanceMap, cut, vals) != 0)
-                return VR_ERR_FORMAT;
-            HIPCHK(hipMemcpy(b.idxValCut + (size_t)br * b.nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice));
-        }
-    }
-    const int rc = decode_launch(&b, out, cut, (hipStream_t)stream, rangeStream);
-    if (rc != 0) return rc == -3 && !rangeStream ? VR_ERR_OOM : VR_ERR_NO_DEVICE;   // (the range decode never named out-of-memory)
+    const hipStream_t st = (hipStream_t)stream;
+    const DecodePlan plan = make_decode_plan(decode_inputs(b, rangeStream), cut);
+    if (plan.storesVectors && misaligned16(out)) return VR_ERR_INVALID;
+    vr_status rc = ensure_decode_scratch(b, plan.needs, b.idxValCut, b.decTables, b.rankVals, st);
+    if (rc != VR_OK) return rangeStream ? VR_ERR_NO_DEVICE : rc;      // (the range decode never named out-of-memory)
+    if (plan.cutValues == CutSource::CALLER) rc = foreign_cut_values(b, b.idxValCut, nullptr, cut, nullptr, 0, st);
+    if (rc != VR_OK) return rc;
+    if (decode_launch(&b, plan, out, st) != 0) return VR_ERR_NO_DEVICE;
     b.decodeTimingPending = true;
     b.lastStream = stream;
     return VR_OK;
@@ -659,15 +749,22 @@ vr_status vr_brickset_decode_range(vr_brickset *h, int32_t cut_depth, uint8_t *o
 // the launch of the two per-brick decodes (cuts checked); the caller's buffer is out or pool->pool
 static vr_status lod_decode(BrickSet &b, const int32_t *cuts, uint8_t *out, const PoolDest *pool, void *stream)
 {
-    if (decode_lod_stores_vectors(&b, cuts, pool) && misaligned16(pool ? pool->pool : out)) return VR_ERR_INVALID;
-    bool hostFill = false;
-    for (int br = 0; br < b.B; ++br) hostFill = hostFill || (cuts[br] >= 0 && cuts[br] < b.Ds && !top_indexed(b, br));
-    if (hostFill && b.foreign) {
-        vr_status rc = sync_ctrl(b);      // the host fill of the cut values reads every brick's numActive / distanceMap
-        if (rc != VR_OK) return rc;
-    }
-    const int rc = decode_lod_launch(&b, cuts, out, (hipStream_t)stream, pool);
-    if (rc != 0) return rc == -3 ? VR_ERR_OOM : (rc == -4 ? VR_ERR_FORMAT : VR_ERR_NO_DEVICE);
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t *dst = pool ? pool->pool : out;
+    std::vector<uint8_t> top;
+    for (int br = 0; b.foreign && br < b.B; ++br) top.push_back(top_indexed(b, br));
+    const LodPlan plan = make_lod_plan(decode_inputs(b, false), cuts, b.foreign ? top.data() : nullptr, pool ? pool->off : nullptr,
+                                       pool ? pool->shift : nullptr, pool && pool->tabDev ? pool->cells : 0);
+    if (plan.storesVectors && misaligned16(dst)) return VR_ERR_INVALID;
+    if (plan.nothing) return VR_OK;
+    LodSlot *s = nullptr;
+    vr_status rc = ensure_lod_slot(b, plan, st, s);
+    if (rc != VR_OK) return rc;
+    // from here on the slot is in use: decode_lod_launch ends with its event, and so does a failure in front of it
+    if (lod_stage(&b, plan, *s, pool ? pool->tab : nullptr, pool ? pool->tabDev : nullptr, st) != 0) rc = VR_ERR_NO_DEVICE;
+    if (rc == VR_OK && plan.cutValues == CutSource::CALLER) rc = foreign_cut_values(b, s->idxValCut, cuts, 0, s->dev, plan.nTop, st);
+    if (rc != VR_OK) { hipEventRecord(s->done, st); s->pending = true; return rc; }
+    if (decode_lod_launch(&b, plan, *s, dst, st) != 0) return VR_ERR_NO_DEVICE;
     b.decodeTimingPending = true;
     b.lastStream = stream;
     return VR_OK;
@@ -682,54 +779,6 @@ vr_status vr_brickset_decode_lod(vr_brickset *h, const int32_t *cuts, uint8_t *o
     return lod_decode(b, cuts, out, nullptr, stream);
 }
 
-// vr_lod_pool_layout's rule (vrhip.h).  off / shift: per brick (shift 3 bytes each); table: per grid cell, may be null.
-static vr_status pool_layout(const int64_t bd[3], int32_t nb, const int64_t *ijk, const int64_t grid[3], const int32_t *cuts,
-                             int32_t origDepth, int32_t maxDepth, int64_t *off, uint8_t *shift, vr_pool_entry *table,
-                             int64_t *total)
-{
-    if (!bd || !ijk || !grid || !cuts || !total || nb <= 0) return VR_ERR_INVALID;
-    int lg[3];
-    for (int k = 0; k < 3; ++k) {
-        if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || bd[k] >= (1ll << 31) || grid[k] <= 0) return VR_ERR_INVALID;
-        lg[k] = 0;
-        while (((int64_t)1 << lg[k]) < bd[k]) ++lg[k];
-    }
-    if (origDepth != lg[0] + lg[1] + lg[2] || maxDepth < origDepth) return VR_ERR_INVALID;
-    const int64_t cells = grid[0] * grid[1] * grid[2];
-    std::vector<int64_t> cellOf((size_t)nb);
-    const std::vector<std::array<int, 3>> splits = split_counts(bd, origDepth);
-    int64_t run = 0;
-    for (int32_t b = 0; b < nb; ++b) {
-        const int64_t *q = ijk + 3 * (int64_t)b;
-        for (int k = 0; k < 3; ++k) if (q[k] < 0 || q[k] >= grid[k]) return VR_ERR_INVALID;
-        const int c = cuts[b];
-        if (c < -1 || c > maxDepth) return VR_ERR_INVALID;
-        cellOf[(size_t)b] = q[0] + grid[0] * (q[1] + grid[1] * q[2]);
-        uint8_t sh[3] = {0, 0, 0};
-        if (c >= 0 && c < origDepth)
-            for (int k = 0; k < 3; ++k) sh[k] = (uint8_t)(lg[k] - splits[(size_t)c][(size_t)k]);
-        if (shift) for (int k = 0; k < 3; ++k) shift[3 * b + k] = sh[k];
-        int64_t o = -1;
-        if (c >= 0) {
-            o = (run + 255) & ~(int64_t)255;
-            run = o + ((bd[0] >> sh[0]) * (bd[1] >> sh[1]) * (bd[2] >> sh[2]));
-        }
-        if (off) off[b] = o;
-    }
-    std::vector<int64_t> cs = cellOf;       // two bricks on one cell: refused
-    std::sort(cs.begin(), cs.end());
-    if (std::adjacent_find(cs.begin(), cs.end()) != cs.end()) return VR_ERR_INVALID;
-    for (int64_t cell = 0; table && cell < cells; ++cell) { table[cell] = vr_pool_entry(); table[cell].offset = -1; }
-    for (int32_t b = 0; table && b < nb; ++b) {
-        if (cuts[b] < 0) continue;
-        vr_pool_entry &e = table[cellOf[(size_t)b]];
-        e.offset = off[b];
-        for (int k = 0; k < 3; ++k) e.shift[k] = shift[3 * b + k];
-    }
-    *total = run;
-    return VR_OK;
-}
-
 vr_status vr_lod_pool_layout(const int64_t brick_dims[3], int32_t num_bricks, const int64_t *brick_ijk, const int64_t grid[3],
                              const int32_t *cuts, int32_t orig_tree_depth, int32_t max_tree_depth, vr_pool_entry *table_out,
                              int64_t *pool_bytes)
@@ -737,8 +786,8 @@ vr_status vr_lod_pool_layout(const int64_t brick_dims[3], int32_t num_bricks, co
     if (!brick_dims || !brick_ijk || !grid || !cuts || !pool_bytes || num_bricks <= 0) return VR_ERR_INVALID;
     std::vector<int64_t> off((size_t)num_bricks);
     std::vector<uint8_t> sh((size_t)num_bricks * 3);
-    return pool_layout(brick_dims, num_bricks, brick_ijk, grid, cuts, orig_tree_depth, max_tree_depth, off.data(), sh.data(),
-                       table_out, pool_bytes);
+    return (vr_status)pool_layout(brick_dims, num_bricks, brick_ijk, grid, cuts, orig_tree_depth, max_tree_depth, off.data(),
+                                  sh.data(), table_out, pool_bytes);
 }
 
 vr_status vr_brickset_decode_lod_pool(vr_brickset *h, const int32_t *cuts, const int64_t *ijk, const int64_t grid[3],
@@ -755,7 +804,7 @@ vr_status vr_brickset_decode_lod_pool(vr_brickset *h, const int32_t *cuts, const
     std::vector<uint8_t> sh((size_t)b.B * 3);
     std::vector<vr_pool_entry> tab((size_t)cells);
     int64_t total = 0;
-    vr_status st = pool_layout(bd, b.B, ijk, grid, cuts, b.D, b.maxDepth, off.data(), sh.data(), tab.data(), &total);
+    const vr_status st = (vr_status)pool_layout(bd, b.B, ijk, grid, cuts, b.D, b.maxDepth, off.data(), sh.data(), tab.data(), &total);
     if (st != VR_OK) return st;
     if (pool_bytes < total) return VR_ERR_INVALID;
     PoolDest d;
@@ -1293,7 +1342,7 @@ vr_status vr_brickset_error_table(vr_brickset *h, const uint8_t *ref, uint8_t *s
     if (cut_lo < 0 || cut_hi > b.maxDepth || cut_lo > cut_hi) return VR_ERR_INVALID;
     if (!b.built) return VR_ERR_STATE;
     for (int c = cut_lo; c <= cut_hi; ++c)
-        if (decode_stores_vectors(&b, c, false) && misaligned16(scratch)) return VR_ERR_INVALID;
+        if (make_decode_plan(decode_inputs(b, false), c).storesVectors && misaligned16(scratch)) return VR_ERR_INVALID;
     const size_t row = (size_t)b.B * sizeof(vr_brick_error), bytes = row * (size_t)(cut_hi - cut_lo + 1);
     if (!b.errTable) HIPCHK(hipMalloc(&b.errTable, row * (size_t)(b.maxDepth + 1)));
     hipStream_t st = (hipStream_t)stream;

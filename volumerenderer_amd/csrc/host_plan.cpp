@@ -583,6 +583,197 @@ BuildLevel build_level(const BuildPlan &p, int d)
     return l;
 }
 
+// ---- a decode ----
+static_assert(VR_STAGE_BRICKS == VR_POOL_STAGE_BRICKS, "the staged batches are the header's");
+
+// the only place a decode kernel is chosen
+static DecodeKernel decode_kernel(const DecodeInputs &in, int cut)
+{
+    if (in.generalGeom) return DecodeKernel::GENERAL;
+    if (!in.tileOk) return DecodeKernel::LANE;
+    const bool fine = in.fineAll && !in.rangeStream && !in.decodeWalk;
+    // k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
+    // at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
+    if (fine && in.idxVal3 && cut >= in.D - 3 && !in.decodeFineV1)
+        return !in.decodeQuad && in.regionOk ? DecodeKernel::REGION : DecodeKernel::QUAD;
+    return fine ? DecodeKernel::FINE : DecodeKernel::TILE;
+}
+
+// the tiled kernels store 16-byte vectors to their destination, k_decode_lane and k_owner_gather bytes
+static bool stores_vectors(DecodeKernel k) { return k != DecodeKernel::GENERAL && k != DecodeKernel::LANE; }
+
+static DecodeLaunch decode_class(const DecodeInputs &in, DecodeKernel k, int rows, int cut, bool perBrick)
+{
+    DecodeLaunch l{};
+    l.kernel = k; l.rows = rows; l.cut = cut;
+    switch (k) {
+    case DecodeKernel::GENERAL:     // rank-domain decode, then every voxel takes its owner leaf's value
+        l.gatherGx = cdiv(in.voxels, 256);
+        [[fallthrough]];
+    case DecodeKernel::LANE:
+        l.gx = cdiv(in.nIdx, 64); l.threads = 64;
+        break;
+    case DecodeKernel::REGION:
+        // a workgroup decodes every VR_RG_PER-th region of its brick: enough regions to amortise its tables and the
+        // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
+        l.gx = cdiv(in.nreg, VR_RG_PER); l.threads = 64 * VR_RG_WAVES;
+        if ((int64_t)l.gx * rows < VR_RG_MIN_WGS) l.gx = (uint32_t)std::min<int64_t>(in.nreg, cdiv(VR_RG_MIN_WGS, rows));
+        break;
+    case DecodeKernel::QUAD:
+        l.gx = cdiv(in.tiles, VR_QD_WAVES * VR_QD_TPW); l.threads = 64 * VR_QD_WAVES;
+        l.chainLevels = perBrick ? 0 : std::min(std::max(cut - in.D, 0), VR_CHAIN_LEVELS);
+        break;
+    case DecodeKernel::FINE:
+        l.gx = cdiv(in.tiles, VR_FD_WAVES); l.threads = 64 * VR_FD_WAVES; l.fineTables = true;
+        break;
+    case DecodeKernel::TILE:
+        l.gx = cdiv(in.tiles, VR_DEC_WAVES); l.threads = 64 * VR_DEC_WAVES;
+        break;
+    }
+    return l;
+}
+
+static void class_needs(DecodeNeeds &n, DecodeKernel k)
+{
+    n.rankVals = n.rankVals || k == DecodeKernel::GENERAL;
+    n.decTables = n.decTables || k == DecodeKernel::FINE;       // (k_decode_quad's tables are chainTab; region and tile have none)
+    n.chainTab = n.chainTab || k == DecodeKernel::QUAD;
+}
+
+DecodePlan make_decode_plan(const DecodeInputs &in, int cut)
+{
+    DecodePlan p{};
+    const DecodeKernel k = decode_kernel(in, cut);
+    p.launch = decode_class(in, k, in.B, cut, false);
+    p.rangeStream = in.rangeStream;
+    // MidRangeTree's second stream has no index scalars of its own: they are its cut values at depth Ds
+    p.cutValues = cut < in.Ds || in.rangeStream ? (in.foreign ? CutSource::CALLER : CutSource::CODES) : CutSource::NONE;
+    p.cutAll = std::min(cut, in.Ds);
+    p.idxValFromCut = in.rangeStream;
+    // the uniform hint describes the mid stream of this handle's own last build (an installed stream has none)
+    p.uni = !in.foreign && !in.rangeStream && !in.noUniformDecode;
+    p.nBase = k == DecodeKernel::GENERAL && in.idx64 ? in.nEmitBlk : 0;
+    p.storesVectors = stores_vectors(k);
+    class_needs(p.needs, k);
+    p.needs.idxValCut = p.cutValues != CutSource::NONE;
+    return p;
+}
+
+LodPlan make_lod_plan(const DecodeInputs &in, const int32_t *cuts, const uint8_t *topIndexed, const int64_t *off,
+                      const uint8_t *shift, int64_t tableCells)
+{
+    LodPlan p{};
+    const int B = in.B;
+    const bool pool = off != nullptr;
+    p.image.reserve((size_t)3 * B);
+    p.image.assign(cuts, cuts + B);
+    std::vector<DecodeKernel> kern((size_t)B);      // each decoded brick's kernel, chosen once
+    for (int b = 0; b < B; ++b) if (cuts[b] >= 0) kern[(size_t)b] = decode_kernel(in, cuts[b]);
+    for (int top = 1; top >= 0; --top) {
+        for (int b = 0; b < B; ++b)
+            if (cuts[b] >= 0 && cuts[b] < in.Ds && (in.foreign && topIndexed && topIndexed[b]) == (top == 1)) p.image.push_back(b);
+        if (top) p.nTop = (int)p.image.size() - B;
+    }
+    p.nAbove = (int)p.image.size() - B;
+    // the passes: [0] full resolution (every decoded brick without a pool), then the staged batches
+    const auto coarse = [&](int b) { return pool && (shift[3 * b] | shift[3 * b + 1] | shift[3 * b + 2]) != 0; };
+    std::vector<std::vector<int>> passes(1);
+    passes[0].reserve((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        if (cuts[b] < 0) continue;
+        if (!coarse(b)) { passes[0].push_back(b); p.storesVectors = p.storesVectors || stores_vectors(kern[(size_t)b]); continue; }
+        if (passes.size() == 1 || (int)passes.back().size() == VR_STAGE_BRICKS) passes.emplace_back();
+        passes.back().push_back(b);
+        // k_pool_pack writes 32-bit words for stored rows of 4 bytes or more
+        p.storesVectors = p.storesVectors || in.nb0 - shift[3 * b] >= 2;
+    }
+    p.staged = passes.size() > 1;
+    if (pool) p.offsets.assign((size_t)B, 0);
+    for (int ps = 0; ps < (int)passes.size(); ++ps) {
+        const std::vector<int> &bricks = passes[(size_t)ps];
+        for (int c = 0; c < DECODE_KERNELS; ++c) {
+            const int first = (int)p.image.size();
+            int cut = 0;
+            for (int i = 0; i < (int)bricks.size(); ++i) {
+                const int b = bricks[(size_t)i];
+                if ((int)kern[(size_t)b] != c) continue;
+                if (pool) p.offsets[p.image.size() - (size_t)(B + p.nAbove)] = ps == 0 ? off[b] : (int64_t)i * in.voxels;
+                p.image.push_back(b);
+                cut = cuts[b];
+            }
+            const int n = (int)p.image.size() - first;
+            if (!n) continue;
+            DecodeLaunch l = decode_class(in, (DecodeKernel)c, n, cut, true);
+            l.pass = ps; l.first = first;
+            l.waitStage = ps == 1 && (p.launches.empty() || p.launches.back().pass == 0);
+            p.launches.push_back(l);
+            class_needs(p.needs, l.kernel);
+        }
+        if (ps == 0) continue;
+        p.launches.back().packRows = (int)bricks.size();
+        p.launches.back().packFirst = ((int)p.offsets.size() - B) / 2;
+        for (int b : bricks) {
+            p.offsets.push_back(off[b]);
+            p.offsets.push_back(shift[3 * b] | (shift[3 * b + 1] << 8) | (shift[3 * b + 2] << 16));
+        }
+    }
+    p.nRows = (int)p.image.size() - B - p.nAbove;
+    p.packGx = (uint32_t)std::min<int64_t>(1024, (in.voxels / 4 + 255) / 256);
+    p.cutValues = !p.nAbove ? CutSource::NONE : (in.foreign ? CutSource::CALLER : CutSource::CODES);
+    p.uni = !in.foreign && !in.noUniformDecode;
+    p.nBase = in.generalGeom && in.idx64 ? in.nEmitBlk : 0;
+    p.needs.idxValCut = p.nAbove != 0;
+    p.tableCells = tableCells;
+    p.nothing = p.nRows == 0 && p.nAbove == 0 && tableCells == 0;
+    return p;
+}
+
+int pool_layout(const int64_t bd[3], int32_t nb, const int64_t *ijk, const int64_t grid[3], const int32_t *cuts,
+                int32_t origDepth, int32_t maxDepth, int64_t *off, uint8_t *shift, vr_pool_entry *table, int64_t *total)
+{
+    if (!bd || !ijk || !grid || !cuts || !total || nb <= 0) return VR_ERR_INVALID;
+    int lg[3];
+    for (int k = 0; k < 3; ++k) {
+        if (bd[k] <= 0 || (bd[k] & (bd[k] - 1)) != 0 || bd[k] >= (1ll << 31) || grid[k] <= 0) return VR_ERR_INVALID;
+        lg[k] = 0;
+        while (((int64_t)1 << lg[k]) < bd[k]) ++lg[k];
+    }
+    if (origDepth != lg[0] + lg[1] + lg[2] || maxDepth < origDepth) return VR_ERR_INVALID;
+    const int64_t cells = grid[0] * grid[1] * grid[2];
+    std::vector<int64_t> cellOf((size_t)nb);
+    const std::vector<std::array<int, 3>> splits = split_counts(bd, origDepth);
+    int64_t run = 0;
+    for (int32_t b = 0; b < nb; ++b) {
+        const int64_t *q = ijk + 3 * (int64_t)b;
+        for (int k = 0; k < 3; ++k) if (q[k] < 0 || q[k] >= grid[k]) return VR_ERR_INVALID;
+        const int c = cuts[b];
+        if (c < -1 || c > maxDepth) return VR_ERR_INVALID;
+        cellOf[(size_t)b] = q[0] + grid[0] * (q[1] + grid[1] * q[2]);
+        uint8_t sh[3] = {0, 0, 0};
+        if (c >= 0 && c < origDepth)
+            for (int k = 0; k < 3; ++k) sh[k] = (uint8_t)(lg[k] - splits[(size_t)c][(size_t)k]);
+        if (shift) for (int k = 0; k < 3; ++k) shift[3 * b + k] = sh[k];
+        int64_t o = -1;
+        if (c >= 0) {
+            o = (run + 255) & ~(int64_t)255;
+            run = o + ((bd[0] >> sh[0]) * (bd[1] >> sh[1]) * (bd[2] >> sh[2]));
+        }
+        if (off) off[b] = o;
+    }
+    std::vector<int64_t> cs = cellOf;       // two bricks on one cell: refused
+    std::sort(cs.begin(), cs.end());
+    if (std::adjacent_find(cs.begin(), cs.end()) != cs.end()) return VR_ERR_INVALID;
+    for (int64_t cell = 0; table && cell < cells; ++cell) { table[cell] = vr_pool_entry(); table[cell].offset = -1; }
+    for (int32_t b = 0; table && b < nb; ++b) {
+        if (cuts[b] < 0) continue;
+        vr_pool_entry &e = table[cellOf[(size_t)b]];
+        e.offset = off[b];
+        for (int k = 0; k < 3; ++k) e.shift[k] = shift[3 * b + k];
+    }
+    *total = run;
+    return VR_OK;
+}
+
 } // namespace vr
 
 // ---- error-bounded selection of cuts: the rule is stated in vrhip.h ("error-bounded level of detail") ----

@@ -1,6 +1,7 @@
 // host_plan.h -- the codec's host logic that needs no device: the split rule and what follows from it, the launch
 // geometry of the tiled kernels (planned once per set, at vr_brickset_create), the debugging switches' one table, the
-// plan of a build (BuildPlan: every kernel, grid and brick range of vr_brickset_build), the walker of foreign streams and the
+// plan of a build (BuildPlan: every kernel, grid and brick range of vr_brickset_build), the plan of a decode call (DecodePlan /
+// LodPlan: the kernel, grids, class lists and buffers of the uniform and per-brick decodes), the walker of foreign streams and the
 // file header, the block tables and per-block index walker of installed streams (shared with kd_index.hip's kernel) and the
 // brick-set archive's parser and writer; and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
 // host_plan.cpp: a rule on a host table).  Includes no HIP header: compiles with a plain C++17 compiler (tests/host_plan_main.cpp links it
@@ -21,6 +22,8 @@
 #define VR_MAX_DEPTH 40     // origTreeDepth + 7 must stay below this
 #define VR_CHAIN_LEVELS 7   // maxAddLevels (R.cpp:22)
 #define VR_IDX_DEAD 0xFFFFFFFFu
+
+struct vr_pool_entry;       // vrhip.h
 
 namespace vr {
 
@@ -221,6 +224,85 @@ struct BuildLevel {
     uint32_t fillGrid;
 };
 BuildLevel build_level(const BuildPlan &p, int d);
+
+// ---- a decode (kd_decode.hip decode_launch / decode_lod_launch execute it; they decide nothing) ----
+// Every decision of a decode call from plain inputs, gathered from the set when the call arrives: which kernel, on
+// which grid, with which companions, where the cut values come from and which buffers the launches touch.  Contract with
+// the allocator (capi.hip ensure_decode_buffers / ensure_lod_slot): everything in `needs` exists, and the quad tables are
+// written, before the first launch.
+constexpr int VR_DEC_WAVES = 4, VR_FD_WAVES = 4, VR_FD_TABLE_WORDS = 1024 + 64 + 4;       // kd_decode.hip DEC_WAVES, FD_*, QD_*, RG_*
+constexpr int VR_QD_WAVES = 16, VR_QD_TPW = 16, VR_QD_CHAIN_ENTRIES = 16384, VR_RG_PER = 16, VR_RG_WAVES = 8;
+constexpr int VR_RG_MIN_WGS = 2048;         // k_decode_region: at least this many workgroups where the regions allow it
+constexpr int VR_STAGE_BRICKS = 32;         // vrhip.h VR_POOL_STAGE_BRICKS
+
+// the kernels, in the order a per-brick decode launches its classes
+enum class DecodeKernel { REGION, QUAD, FINE, TILE, GENERAL, LANE };
+constexpr int DECODE_KERNELS = (int)DecodeKernel::LANE + 1;
+// scalars above depth Ds: none needed; k_cut_values from the encoder's codes; or written before the launch by the
+// caller (a set of installed streams: capi.hip foreign_cut_values)
+enum class CutSource { NONE, CODES, CALLER };
+
+struct DecodeInputs {
+    int32_t D, Ds, B, nb0;      // nb0: log2 X
+    int64_t nIdx, voxels, leafStride, nEmitBlk;
+    bool generalGeom, idx64;
+    bool tileOk; int32_t tiles;         // TilePlan: ok, tilesX * tilesY * tilesZ
+    bool regionOk; int32_t nreg;        // RegionPlan
+    bool fineAll;               // every brick has the per-4-leaf side-car (fineIdx && fineAll)
+    bool idxVal3, foreign, rangeStream;
+    bool decodeWalk, decodeFineV1, decodeQuad, noUniformDecode;     // Switches, read per call
+};
+struct DecodeNeeds { bool rankVals, decTables, chainTab, idxValCut; };
+// one launch of a decode kernel on grid (gx, rows) x threads; a per-brick decode: over image[first .. first + rows)
+struct DecodeLaunch {
+    DecodeKernel kernel;
+    int32_t rows, cut;          // cut: the call's, or one of the class's (the kernels read each row's own)
+    uint32_t gx, threads;
+    uint32_t gatherGx;          // GENERAL: k_owner_gather on (gatherGx, rows) x 256 behind it
+    bool fineTables;            // FINE: k_fine_tables on rows x 256 in front
+    int32_t chainLevels;        // QUAD: the table of that many refining levels (a per-brick decode: 0, the kernel adds each row's)
+    int32_t pass, first;        // per-brick decode: 0 = to the caller's buffer, p >= 1 = staged batch p - 1
+    bool waitStage;             // the call's first staged launch: the staging buffer's previous reader comes first
+    int32_t packRows, packFirst;    // the batch's last class: k_pool_pack over packRows descriptors from packFirst follows
+};
+struct DecodePlan {
+    DecodeLaunch launch;
+    bool rangeStream;
+    CutSource cutValues;
+    int32_t cutAll;             // k_cut_values' depth: min(cut, Ds)
+    bool idxValFromCut;         // the range stream's index scalars are the cut values
+    bool uni;                   // k_decode_region gets the uniform-box hint
+    int64_t nBase;              // GENERAL with 64-bit offsets: block-relative index entries, this many bases per brick
+    bool storesVectors;         // 16-byte stores to the caller's buffer (vrhip.h "alignment of caller buffers")
+    DecodeNeeds needs;
+};
+DecodePlan make_decode_plan(const DecodeInputs &in, int cut);
+
+// vr_brickset_decode_lod / _lod_pool.  cuts: per brick, -1 = skipped.  topIndexed: per brick of a foreign set, its cut
+// values come from idxTop (null: of none).  off / shift: pool_layout's (null: no pool); tableCells: the pool table to
+// upload (0: none).  With a pool the full-resolution bricks go straight to their slots (pass 0), the coarse ones
+// VR_STAGE_BRICKS at a time, in index order, to the staging buffer, each batch followed by k_pool_pack.
+struct LodPlan {
+    std::vector<int32_t> image;     // cuts [0, B), the bricks cut above Ds (nTop from idxTop first), then the class lists
+    int32_t nAbove, nTop, nRows;    // nRows: decoded bricks
+    std::vector<DecodeLaunch> launches;
+    std::vector<int64_t> offsets;   // pool: each list entry's output offset [0, nRows), from B on the pack descriptors
+                                    // (slot offset, sx | sy << 8 | sz << 16), batch by batch; else empty
+    uint32_t packGx;
+    CutSource cutValues;
+    bool uni, staged, storesVectors;
+    int64_t nBase;
+    bool nothing;                   // every brick skipped and no table: nothing to launch
+    DecodeNeeds needs;              // of the slot (chainTab: the set's)
+    int64_t tableCells;
+};
+LodPlan make_lod_plan(const DecodeInputs &in, const int32_t *cuts, const uint8_t *topIndexed, const int64_t *off,
+                      const uint8_t *shift, int64_t tableCells);
+
+// vr_lod_pool_layout's rule (vrhip.h); returns a vr_status.  off / shift: per brick (shift 3 bytes each), may be null;
+// table: per grid cell, may be null.
+int pool_layout(const int64_t bd[3], int32_t nb, const int64_t *ijk, const int64_t grid[3], const int32_t *cuts,
+                int32_t origDepth, int32_t maxDepth, int64_t *off, uint8_t *shift, vr_pool_entry *table, int64_t *total);
 
 // ---- foreign streams (host): one preorder walk over the 2-bit tokens, grammar checked ----
 // Per tree token node(depth, path, pos, tok, val): val is the node's decoded scalar, refined down to depth `cut` only; then

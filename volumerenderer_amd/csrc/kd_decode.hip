@@ -1682,73 +1682,50 @@ k_cut_values(const uint8_t *__restrict__ codes, int64_t codeStride, const Ctrl *
     out[(int64_t)brick * nIdx + s] = (uint8_t)val;
 }
 
-// ---- the choice of decode kernel.  The kernels, in the order a per-brick decode launches its classes:
-enum class DecodeKernel { REGION, QUAD, FINE, TILE, GENERAL, LANE };
-constexpr int DECODE_KERNELS = (int)DecodeKernel::LANE + 1;
+// ---- decode driver: executes a DecodePlan / LodPlan (host_plan.h).  Decides nothing, allocates nothing and creates no
+// event: capi.hip has planned the call and made whatever the plan's `needs` names
+static_assert(DEC_WAVES == VR_DEC_WAVES && FD_WAVES == VR_FD_WAVES && FD_TABLE_WORDS == VR_FD_TABLE_WORDS, "host_plan.cpp sizes the grids and the tables");
+static_assert(QD_WAVES == VR_QD_WAVES && QD_TPW == VR_QD_TPW && QD_CHAIN_ENTRIES == VR_QD_CHAIN_ENTRIES, "host_plan.cpp sizes the grids and the tables");
+static_assert(RG_PER == VR_RG_PER && RG_WAVES == VR_RG_WAVES, "host_plan.cpp sizes the grids");
 
-// What the choice depends on besides the cut: the set's geometry (BrickSet::tile / region, planned at create), and what
-// can change from call to call: the stream, the switches and whether every brick has the per-4-leaf side-car.  Worked
-// out once per call (a per-brick decode classifies every brick with one plan); kernel() is the only place a kernel is
-// chosen.
-struct DecodePlan {
-    const BrickSet *bs;
-    bool fine;      // every brick has the per-4-leaf side-car (k_decode_fine / quad / region)
-    bool region;    // region geometry, and k_decode_quad was not asked for instead
-
-    DecodePlan(const BrickSet *b, bool rangeStream)
-        : bs(b), fine(b->tile.ok && b->fineIdx && b->fineAll && !rangeStream && !b->sw.decodeWalk),
-          region(fine && !b->sw.decodeQuad && b->region.ok) {}
-
-    DecodeKernel kernel(int cut) const
-    {
-        if (bs->generalGeom) return DecodeKernel::GENERAL;
-        if (!bs->tile.ok) return DecodeKernel::LANE;
-        // k_decode_region / k_decode_quad: cuts at or below depth D-3 (the third side-car holds the depth-(D-3) scalars
-        // at full precision); shallower progressive cuts keep k_decode_fine, which decodes the upper nodes itself
-        if (fine && bs->idxVal3 && cut >= bs->D - 3 && !bs->sw.decodeFineV1)
-            return region ? DecodeKernel::REGION : DecodeKernel::QUAD;
-        return fine ? DecodeKernel::FINE : DecodeKernel::TILE;
-    }
+// what a launch reads and writes beside the set's own arrays
+struct DecodeBufs {
+    const Stream2 *sm;          // the stream: mid, or MidRangeTree's half-range stream
+    uint8_t *out;
+    const int32_t *list, *cuts; // per-brick decode: the class's bricks (grid rows), the cuts of all B bricks; else null
+    const int64_t *obase;       // each row's output offset (pool decode); null: brick * voxels
+    const uint8_t *cutVals, *idxVals;
+    uint32_t *decTables;        // the call's own in a per-brick decode (LodSlot), as are cutVals and rankVals
+    uint8_t *rankVals;
+    const uint32_t *uni;
+    int64_t nBase;
 };
 
-// one launch class of a per-brick decode (launch_decode's `lod` argument)
-struct LodClass {
-    const int32_t *list = nullptr; // device: the class's bricks (grid rows)
-    int n = 0;
-    const int32_t *cuts = nullptr; // device: the cuts of all B bricks
-    uint8_t *idxValCut = nullptr;
-    uint32_t *decTables = nullptr;
-    uint8_t *rankVals = nullptr;
-    const int64_t *obase = nullptr; // device: each row's output offset (pool decode); null: brick * voxels
-};
-
-// One launch of kernel k.  lod: one class of a per-brick decode (decode_lod_launch): grid rows = the class's bricks,
-// each at its own cut; `cut` is one of theirs (the kernel is the class's).  The call's cut values, fine tables and rank
-// scratch are its own (LodSlot), and the caller records the timing events around all classes.
-static int launch_decode(BrickSet *bs, DecodeKernel k, uint8_t *out, int cut, hipStream_t st, bool rangeStream, const LodClass *lod)
+// the quad tables, one per number of refining levels, all written once (capi.hip ensure_chain_tables): two decodes of
+// one set on different streams at different cuts never rewrite a table the other is reading
+int chain_tables_launch(BrickSet *bs, hipStream_t st)
 {
-    if (!lod) hipEventRecord(bs->ev[5], st);
-    const unsigned rows = lod ? (unsigned)lod->n : (unsigned)bs->B;
-    const int32_t *list = lod ? lod->list : nullptr, *cuts = lod ? lod->cuts : nullptr;
-    const int64_t *obase = lod ? lod->obase : nullptr;
+    for (int lv = 0; lv <= VR_CHAIN_LEVELS; ++lv)
+        hipLaunchKernelGGL(k_chain_table, dim3(QD_CHAIN_ENTRIES / 256), dim3(256), 0, st, lv, bs->chainTab + (size_t)lv * QD_CHAIN_ENTRIES);
+    return launch_status("chain_table");
+}
+
+// One launch of the plan.  In a per-brick decode the grid rows are a class's bricks, each at its own cut; l.cut is one
+// of theirs.  The caller records the timing events around all launches.
+static int launch_class(BrickSet *bs, const DecodeLaunch &l, const DecodeBufs &d, hipStream_t st)
+{
+    const unsigned rows = (unsigned)l.rows;
+    const int cut = l.cut;
+    const int32_t *list = d.list, *cuts = d.cuts;
+    const int64_t *obase = d.obase;
+    uint8_t *out = d.out;
     // MidRangeTree's second stream is emitted in lock step with the first (M.cpp:871-982): same token positions,
     // so the same side-car offsets serve it; only the scalars (its own codes, its own distanceMap) differ
-    const Stream2 &sm = rangeStream ? bs->rng : bs->mid;
-    const uint8_t *cutVals = nullptr, *idxVals = bs->idxVal;
-    if (lod) {
-        cutVals = lod->idxValCut;  // filled before the classes (k_cut_values over the bricks cut above Ds, or the host)
-    } else if (cut < bs->Ds || rangeStream) {
-        if (!bs->idxValCut) return -2;
-        if (!bs->foreign)
-            hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), bs->B), dim3(256), 0, st,
-                               sm.codes, bs->codeStride, sm.ctrl, bs->Ds, cut < bs->Ds ? cut : bs->Ds, bs->nIdx, bs->idxValCut,
-                               nullptr, nullptr);
-        cutVals = bs->idxValCut;   // foreign streams: filled by the host from the bytes (capi)
-        if (rangeStream) idxVals = bs->idxValCut;
-    }
+    const Stream2 &sm = *d.sm;
+    const uint8_t *cutVals = d.cutVals;
     // the fields that TileArgs, RegionArgs and DecodeArgs share, under one name in all three
     const auto common = [&](auto &a, uint8_t *dst, const int64_t *dstBase) {
-        a.tree = sm.tree; a.treeCap = bs->treeCap; a.idxOff = bs->idxOff; a.idxVal = idxVals; a.nIdx = bs->nIdx;
+        a.tree = sm.tree; a.treeCap = bs->treeCap; a.idxOff = bs->idxOff; a.idxVal = d.idxVals; a.nIdx = bs->nIdx;
         a.ctrls = sm.ctrl; a.out = dst; a.D = bs->D; a.cut = cut; a.list = list; a.cuts = cuts; a.obase = dstBase;
     };
     const auto tile_args = [&]() {
@@ -1764,18 +1741,19 @@ static int launch_decode(BrickSet *bs, DecodeKernel k, uint8_t *out, int cut, hi
     const auto lane_args = [&](const unsigned long long *idxBase, const uint32_t *lut, uint8_t *dst, const int64_t *dstBase) {
         DecodeArgs a;
         common(a, dst, dstBase);
-        a.idxBase = idxBase; a.nBase = idxBase ? bs->nEmitBlk : 0; a.lut = lut; a.g = bs->g; a.K = bs->K; a.Ds = bs->Ds; a.idxValCut = cutVals;
+        a.idxBase = idxBase; a.nBase = idxBase ? d.nBase : 0; a.lut = lut; a.g = bs->g; a.K = bs->K; a.Ds = bs->Ds; a.idxValCut = cutVals;
         return a;
     };
-    switch (k) {
+    if ((l.kernel == DecodeKernel::GENERAL && !d.rankVals) || (l.kernel == DecodeKernel::QUAD && !bs->chainTabReady) ||
+        (l.fineTables && !d.decTables))
+        return -1;      // the plan's contract was not kept
+    switch (l.kernel) {
     case DecodeKernel::GENERAL: {
         // general extents: rank-domain decode, then every voxel takes its owner leaf's value
-        if (!lod && !bs->rankVals && hipMalloc(&bs->rankVals, (size_t)bs->B * bs->leafStride * 2) != hipSuccess) return -3;
-        uint8_t *rankVals = lod ? lod->rankVals : bs->rankVals;
-        const DecodeArgs a = lane_args(bs->idx64 ? bs->idxBase : nullptr, nullptr, rankVals, nullptr);
-        hipLaunchKernelGGL(k_decode_lane<true>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(k_owner_gather, dim3((unsigned)((bs->g.voxels + 255) / 256), rows), dim3(256), 0, st,
-                           (const uint16_t *)rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list, obase);
+        const DecodeArgs a = lane_args(d.nBase ? bs->idxBase : nullptr, nullptr, d.rankVals, nullptr);
+        hipLaunchKernelGGL(k_decode_lane<true>, dim3(l.gx, rows), dim3(l.threads), 0, st, a);
+        hipLaunchKernelGGL(k_owner_gather, dim3(l.gatherGx, rows), dim3(256), 0, st,
+                           (const uint16_t *)d.rankVals, bs->leafStride, bs->ownerRank, bs->ownerSurv, bs->g.voxels, out, list, obase);
         break;
     }
     case DecodeKernel::REGION: {
@@ -1788,89 +1766,55 @@ static int launch_decode(BrickSet *bs, DecodeKernel k, uint8_t *out, int cut, hi
         r.blkX = p.blkX; r.blkY = p.blkY; r.blkZ = p.blkZ; r.nreg = p.nreg;
         common(r, out, obase);
         r.fine = bs->fineIdx; r.val3 = bs->idxVal3; r.spread = bs->spread;
-        // the uniform hint describes the mid stream of this handle's own last build (an installed stream has none)
-        r.uni = bs->foreign || rangeStream || bs->sw.noUniformDecode ? nullptr : bs->boxUniform;
-        // a workgroup decodes every RG_PER-th region of its brick: enough regions to amortise its tables and the
-        // pipeline's fill, enough workgroups (a few thousand for the bench volume) to balance the chip
-        unsigned wgs = (unsigned)((r.nreg + RG_PER - 1) / RG_PER);
-        if ((int64_t)wgs * rows < 2048) wgs = (unsigned)std::min<int64_t>(r.nreg, (2048 + rows - 1) / rows);
-        hipLaunchKernelGGL(k_decode_region, dim3(wgs, rows), dim3(64 * RG_WAVES), 0, st, r);
+        r.uni = d.uni;
+        hipLaunchKernelGGL(k_decode_region, dim3(l.gx, rows), dim3(l.threads), 0, st, r);
         break;
     }
     case DecodeKernel::QUAD: {
         TileArgs t = tile_args();
-        const int ntiles = t.tilesX * t.tilesY * t.tilesZ;
-        const int levels = cut - bs->D < 0 ? 0 : (cut - bs->D > VR_CHAIN_LEVELS ? VR_CHAIN_LEVELS : cut - bs->D);
-        // one table per number of refining levels, all written once: two decodes of one set on different streams at
-        // different cuts never rewrite a table the other is reading
-        if (!bs->chainTab && hipMalloc(&bs->chainTab, (size_t)(VR_CHAIN_LEVELS + 1) * QD_CHAIN_ENTRIES * 4) != hipSuccess) return -3;
-        if (!bs->chainTabReady) {
-            for (int lv = 0; lv <= VR_CHAIN_LEVELS; ++lv)
-                hipLaunchKernelGGL(k_chain_table, dim3(QD_CHAIN_ENTRIES / 256), dim3(256), 0, st, lv, bs->chainTab + (size_t)lv * QD_CHAIN_ENTRIES);
-            // (the first use may come from any stream: make the tables visible to all of them before going on)
-            if (hipStreamSynchronize(st) != hipSuccess) return -1;
-            bs->chainTabReady = true;
-        }
-        t.tables = bs->chainTab + (lod ? (size_t)0 : (size_t)levels * QD_CHAIN_ENTRIES);   // lod: the kernel picks per brick
-        const int per = QD_WAVES * QD_TPW;
-        hipLaunchKernelGGL(k_decode_quad, dim3((unsigned)((ntiles + per - 1) / per), rows), dim3(64 * QD_WAVES), 0, st, t);
+        t.tables = bs->chainTab + (size_t)l.chainLevels * QD_CHAIN_ENTRIES;
+        hipLaunchKernelGGL(k_decode_quad, dim3(l.gx, rows), dim3(l.threads), 0, st, t);
         break;
     }
-    case DecodeKernel::FINE:
+    case DecodeKernel::FINE: {
+        TileArgs t = tile_args();
+        t.tables = d.decTables;
+        hipLaunchKernelGGL(k_fine_tables, dim3(rows), dim3(256), 0, st, bs->mid.ctrl, bs->D, bs->Ds, cut, d.decTables, list, cuts);
+        hipLaunchKernelGGL(k_decode_fine, dim3(l.gx, rows), dim3(l.threads), 0, st, t);
+        break;
+    }
     case DecodeKernel::TILE: {
         TileArgs t = tile_args();
-        const int ntiles = t.tilesX * t.tilesY * t.tilesZ;
-        const bool useFine = k == DecodeKernel::FINE;
-        if (useFine && !lod && !bs->decTables && hipMalloc(&bs->decTables, (size_t)bs->B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
-        uint32_t *decTables = lod ? lod->decTables : bs->decTables;
-        t.tables = decTables;
-        if (useFine) {
-            hipLaunchKernelGGL(k_fine_tables, dim3(rows), dim3(256), 0, st, bs->mid.ctrl, bs->D, bs->Ds, cut, decTables, list, cuts);
-            hipLaunchKernelGGL(k_decode_fine, dim3((unsigned)((ntiles + FD_WAVES - 1) / FD_WAVES), rows),
-                               dim3(64 * FD_WAVES), 0, st, t);
-        } else
-            hipLaunchKernelGGL(k_decode_tile, dim3((unsigned)((ntiles + DEC_WAVES - 1) / DEC_WAVES), rows),
-                               dim3(64 * DEC_WAVES), 0, st, t);
+        t.tables = d.decTables;     // (not read)
+        hipLaunchKernelGGL(k_decode_tile, dim3(l.gx, rows), dim3(l.threads), 0, st, t);
         break;
     }
     case DecodeKernel::LANE: {
         const DecodeArgs a = lane_args(nullptr, bs->lut, out, obase);
-        hipLaunchKernelGGL(k_decode_lane<false>, dim3((unsigned)((bs->nIdx + 63) / 64), rows), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_decode_lane<false>, dim3(l.gx, rows), dim3(l.threads), 0, st, a);
         break;
     }
     }
-    if (!lod) hipEventRecord(bs->ev[6], st);
     return launch_status("decode");
 }
 
-// The rule of vrhip.h ("alignment of caller buffers"): the tiled kernels store 16-byte vectors to the caller's buffer,
-// k_decode_lane and k_owner_gather bytes.  capi.hip refuses a misaligned buffer before anything is launched.
-static bool stores_vectors(DecodeKernel k)
+int decode_launch(BrickSet *bs, const DecodePlan &p, uint8_t *out, hipStream_t st)
 {
-    return k == DecodeKernel::REGION || k == DecodeKernel::QUAD || k == DecodeKernel::FINE || k == DecodeKernel::TILE;
-}
-
-bool decode_stores_vectors(const BrickSet *bs, int cut, bool rangeStream)
-{
-    return stores_vectors(DecodePlan(bs, rangeStream).kernel(cut));
-}
-
-// per-brick cuts.  Without a pool every decoded brick goes to the caller's buffer; with one, the full-resolution bricks
-// do (the coarse ones go to the set's staging buffer) and k_pool_pack writes 32-bit words for stored rows of 4 bytes or more
-bool decode_lod_stores_vectors(const BrickSet *bs, const int32_t *cutsHost, const PoolDest *pool)
-{
-    const DecodePlan plan(bs, false);
-    for (int b = 0; b < bs->B; ++b) {
-        if (cutsHost[b] < 0) continue;
-        const bool coarse = pool && (pool->shift[3 * b] | pool->shift[3 * b + 1] | pool->shift[3 * b + 2]) != 0;
-        if (coarse ? bs->g.nb[0] - pool->shift[3 * b] >= 2 : stores_vectors(plan.kernel(cutsHost[b]))) return true;
-    }
-    return false;
-}
-
-int decode_launch(BrickSet *bs, uint8_t *out, int cut, hipStream_t st, bool rangeStream)
-{
-    return launch_decode(bs, DecodePlan(bs, rangeStream).kernel(cut), out, cut, st, rangeStream, nullptr);
+    hipEventRecord(bs->ev[5], st);
+    DecodeBufs d{};
+    d.sm = p.rangeStream ? &bs->rng : &bs->mid;
+    d.out = out;
+    if (p.cutValues == CutSource::CODES)
+        hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), bs->B), dim3(256), 0, st,
+                           d.sm->codes, bs->codeStride, d.sm->ctrl, bs->Ds, p.cutAll, bs->nIdx, bs->idxValCut, nullptr, nullptr);
+    d.cutVals = p.cutValues != CutSource::NONE ? bs->idxValCut : nullptr;
+    d.idxVals = p.idxValFromCut ? bs->idxValCut : bs->idxVal;
+    d.decTables = bs->decTables; d.rankVals = bs->rankVals;
+    d.uni = p.uni ? bs->boxUniform : nullptr;
+    d.nBase = p.nBase;
+    const int rc = launch_class(bs, p.launch, d, st);
+    hipEventRecord(bs->ev[6], st);
+    return rc;
 }
 
 void free_lod_slots(BrickSet *bs)
@@ -1923,132 +1867,58 @@ k_pool_pack(const uint8_t *__restrict__ stage, int64_t voxels, int lx, int ly, c
     }
 }
 
-// pool: vr_brickset_decode_lod_pool.  The bricks then go in passes: the full-resolution ones straight to their pool
-// slots, the coarse ones VR_POOL_STAGE_BRICKS at a time (index order) to the set's staging buffer, each such pass
-// followed by k_pool_pack.  All passes of a call share its slot: its lists hold every brick at most once.
-int decode_lod_launch(BrickSet *bs, const int32_t *cutsHost, uint8_t *out, hipStream_t st, const PoolDest *pool)
+// A per-brick decode (LodPlan, host_plan.h).  With a pool the bricks go in passes: the full-resolution ones straight to
+// their pool slots, the coarse ones VR_POOL_STAGE_BRICKS at a time (index order) to the set's staging buffer, each such
+// pass followed by k_pool_pack.  All passes of a call share its slot: its lists hold every brick at most once.
+// lod_stage: the plan's host images into the slot's pinned ones, and their uploads.  The slot is the caller's (capi.hip
+// ensure_lod_slot: its previous call has ended); tab / tabDev: the pool table, where the plan has one.
+int lod_stage(BrickSet *bs, const LodPlan &p, LodSlot &s, const vr_pool_entry *tab, vr_pool_entry *tabDev, hipStream_t st)
+{
+    const size_t B = (size_t)bs->B;
+    if (p.tableCells) {
+        memcpy(s.tabHost, tab, (size_t)p.tableCells * sizeof(vr_pool_entry));
+        if (hipMemcpyAsync(tabDev, s.tabHost, (size_t)p.tableCells * sizeof(vr_pool_entry), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    }
+    if (p.image.size() > B) {
+        memcpy(s.host, p.image.data(), p.image.size() * sizeof(int32_t));
+        if (hipMemcpyAsync(s.dev, s.host, p.image.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    }
+    if (!p.offsets.empty() && p.nRows) {
+        memcpy(s.obHost, p.offsets.data(), p.offsets.size() * sizeof(int64_t));
+        if (hipMemcpyAsync(s.obDev, s.obHost, p.offsets.size() * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    }
+    return 0;
+}
+
+// out: the caller's buffer (the pool of a pool decode).  Always ends with the slot's event: whatever was enqueued
+// before a failure, lod_stage's copies included, has ended before the slot is written again.
+int decode_lod_launch(BrickSet *bs, const LodPlan &p, LodSlot &s, uint8_t *out, hipStream_t st)
 {
     const int B = bs->B;
-    LodSlot &s = bs->lodSlot[bs->lodNext];
-    // the slot's previous call (any stream) may still read its lists, cut values and tables
-    if (s.pending && hipEventSynchronize(s.done) != hipSuccess) return -1;
-    s.pending = false;
-    if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return -1;
-    if (!s.dev && hipMalloc(&s.dev, (size_t)3 * B * sizeof(int32_t)) != hipSuccess) return -3;
-    if (!s.host && hipHostMalloc(&s.host, (size_t)3 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return -3;
-    if (pool) {
-        if (!s.obDev && hipMalloc(&s.obDev, (size_t)3 * B * sizeof(int64_t)) != hipSuccess) return -3;
-        if (!s.obHost && hipHostMalloc(&s.obHost, (size_t)3 * B * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) return -3;
-        if (pool->tabDev && s.tabCap < pool->cells) {
-            if (s.tabHost) hipHostFree(s.tabHost);
-            s.tabHost = nullptr; s.tabCap = 0;
-            if (hipHostMalloc(&s.tabHost, (size_t)pool->cells * sizeof(vr_pool_entry), hipHostMallocDefault) != hipSuccess) return -3;
-            s.tabCap = pool->cells;
-        }
-    }
-    bs->lodNext = (bs->lodNext + 1) % VR_LOD_SLOTS;
-    // host image: cuts [0, B), bricks cut above Ds, then the passes' classes' lists
-    int32_t *H = s.host;
-    const DecodePlan plan(bs, false);
-    // (of a set of installed streams: first the bricks whose scalars come from idxTop, then those the host fills)
-    int nAbove = 0, nTop = 0;
-    for (int b = 0; b < B; ++b) H[b] = cutsHost[b];
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int b = 0; b < B; ++b)
-            if (cutsHost[b] >= 0 && cutsHost[b] < bs->Ds && (bs->foreign && top_indexed(*bs, b)) == (pass == 0)) H[B + nAbove++] = b;
-        if (pass == 0) nTop = nAbove;
-    }
-    // the passes: [0] full resolution (every decoded brick without a pool), then the staged batches
-    const auto coarse = [&](int b) { return pool && (pool->shift[3 * b] | pool->shift[3 * b + 1] | pool->shift[3 * b + 2]) != 0; };
-    std::vector<std::vector<int>> passes(1);
-    for (int b = 0; b < B; ++b) {
-        if (cutsHost[b] < 0) continue;
-        if (!coarse(b)) { passes[0].push_back(b); continue; }
-        if (passes.size() == 1 || passes.back().size() == VR_POOL_STAGE_BRICKS) passes.emplace_back();
-        passes.back().push_back(b);
-    }
-    struct Launch { int pass, cls, first, n, cut; };
-    std::vector<Launch> launches;
-    int at = B + nAbove;
-    for (int p = 0; p < (int)passes.size(); ++p) {
-        int nCls[DECODE_KERNELS] = {}, cutOf[DECODE_KERNELS] = {};
-        for (int b : passes[(size_t)p]) { const int c = (int)plan.kernel(cutsHost[b]); ++nCls[c]; cutOf[c] = cutsHost[b]; }
-        for (int c = 0; c < DECODE_KERNELS; ++c) {
-            if (!nCls[c]) continue;
-            launches.push_back({p, c, at, nCls[c], cutOf[c]});
-            for (int i = 0; i < (int)passes[(size_t)p].size(); ++i) {
-                const int b = passes[(size_t)p][(size_t)i];
-                if ((int)plan.kernel(cutsHost[b]) != c) continue;
-                if (pool) s.obHost[at - B - nAbove] = p == 0 ? pool->off[b] : (int64_t)i * bs->g.voxels;
-                H[at++] = b;
-            }
-        }
-    }
-    const int nRows = at - B - nAbove;
-    int nDesc = 0;                      // pack descriptors, batch by batch
-    for (int p = 1; p < (int)passes.size(); ++p)
-        for (int b : passes[(size_t)p]) {
-            s.obHost[B + 2 * nDesc] = pool->off[b];
-            s.obHost[B + 2 * nDesc + 1] = pool->shift[3 * b] | (pool->shift[3 * b + 1] << 8) | (pool->shift[3 * b + 2] << 16);
-            ++nDesc;
-        }
-    const bool table = pool && pool->tabDev;
-    if (at == B && !table) return 0;    // every brick skipped: nothing to launch
-    int nc[DECODE_KERNELS] = {};
-    for (const Launch &l : launches) nc[l.cls] += l.n;
-    if (nAbove && !s.idxValCut && hipMalloc(&s.idxValCut, (size_t)B * bs->nIdx) != hipSuccess) return -3;
-    if ((nc[(int)DecodeKernel::REGION] || nc[(int)DecodeKernel::QUAD] || nc[(int)DecodeKernel::FINE]) && !s.decTables && hipMalloc(&s.decTables, (size_t)B * FD_TABLE_WORDS * 4) != hipSuccess) return -3;
-    if (nc[(int)DecodeKernel::GENERAL] && !s.rankVals && hipMalloc(&s.rankVals, (size_t)B * bs->leafStride * 2) != hipSuccess) return -3;
-    if (passes.size() > 1) {
-        if (!bs->poolStage && hipMalloc(&bs->poolStage, (size_t)VR_POOL_STAGE_BRICKS * bs->g.voxels) != hipSuccess) return -3;
-        if (!bs->stageDone && hipEventCreateWithFlags(&bs->stageDone, hipEventDisableTiming) != hipSuccess) return -1;
-    }
-    if (nAbove && bs->foreign) {
-        // ancestor scalars at each brick's cut, from the stream bytes kept at set_tree/open time (as vr_brickset_decode)
-        std::vector<uint8_t> vals;
-        for (int i = nTop; i < nAbove; ++i) {
-            const int br = H[B + i];
-            vals.assign((size_t)bs->nIdx, 0);
-            if (br < (int)bs->hostTree.size() && !bs->hostTree[br].empty() &&
-                cut_values_from_stream(bs->D, bs->Ds, bs->K, bs->nIdx, bs->hostTree[br].data(),
-                                       (int64_t)bs->hostCtrl[br].numActive, bs->hostCtrl[br].distanceMap, cutsHost[br], vals) != 0)
-                return -4;
-            if (hipMemcpy(s.idxValCut + (size_t)br * bs->nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        }
-    }
     hipEventRecord(bs->ev[5], st);
-    if (table) {
-        memcpy(s.tabHost, pool->tab, (size_t)pool->cells * sizeof(vr_pool_entry));
-        if (hipMemcpyAsync(pool->tabDev, s.tabHost, (size_t)pool->cells * sizeof(vr_pool_entry), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    }
-    if (at > B && hipMemcpyAsync(s.dev, H, (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    if (pool && (nRows || nDesc) &&
-        hipMemcpyAsync(s.obDev, s.obHost, (size_t)(B + 2 * nDesc) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    if (nTop && cut_from_top_launch(bs, s.dev + B, s.dev, 0, nTop, 0, s.idxValCut, st) != 0) return -1;
-    if (nAbove && !bs->foreign)
-        hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), nAbove), dim3(256), 0, st,
+    if (p.cutValues == CutSource::CODES)
+        hipLaunchKernelGGL(k_cut_values, dim3((unsigned)((bs->nIdx + 255) / 256), p.nAbove), dim3(256), 0, st,
                            bs->mid.codes, bs->codeStride, bs->mid.ctrl, bs->Ds, 0, bs->nIdx, s.idxValCut, s.dev + B, s.dev);
-    int rc = 0, desc = 0;
-    for (size_t li = 0; li < launches.size() && rc == 0; ++li) {
-        const Launch &l = launches[li];
-        if (l.pass == 1 && (li == 0 || launches[li - 1].pass == 0) && bs->stagePending)
-            hipStreamWaitEvent(st, bs->stageDone, 0);     // an earlier call, on any stream, may still pack from staging
-        LodClass L;
-        L.list = s.dev + l.first; L.n = l.n; L.cuts = s.dev;
-        L.idxValCut = s.idxValCut; L.decTables = s.decTables; L.rankVals = s.rankVals;
-        L.obase = pool ? s.obDev + (l.first - B - nAbove) : nullptr;
-        rc = launch_decode(bs, (DecodeKernel)l.cls, l.pass == 0 ? (pool ? pool->pool : out) : bs->poolStage, l.cut, st,
-                           false, &L);
-        if (rc == 0 && l.pass > 0 && (li + 1 == launches.size() || launches[li + 1].pass != l.pass)) {
-            const int n = (int)passes[(size_t)l.pass].size();
-            const unsigned gx = (unsigned)std::min<int64_t>(1024, (bs->g.voxels / 4 + 255) / 256);
-            hipLaunchKernelGGL(k_pool_pack, dim3(gx, n), dim3(256), 0, st, bs->poolStage, bs->g.voxels, bs->g.nb[0], bs->g.nb[1],
-                               s.obDev + B + 2 * desc, pool->pool);
-            desc += n;
+    DecodeBufs d{};
+    d.sm = &bs->mid; d.cuts = s.dev;
+    d.cutVals = s.idxValCut; d.idxVals = bs->idxVal; d.decTables = s.decTables; d.rankVals = s.rankVals;
+    d.uni = p.uni ? bs->boxUniform : nullptr;
+    d.nBase = p.nBase;
+    int rc = 0;
+    for (const DecodeLaunch &l : p.launches) {
+        if (l.waitStage && bs->stagePending) hipStreamWaitEvent(st, bs->stageDone, 0);     // an earlier call, on any stream, may still pack from staging
+        d.out = l.pass == 0 ? out : bs->poolStage;
+        d.list = s.dev + l.first;
+        d.obase = p.offsets.empty() ? nullptr : s.obDev + (l.first - B - p.nAbove);
+        rc = launch_class(bs, l, d, st);
+        if (rc == 0 && l.packRows) {
+            hipLaunchKernelGGL(k_pool_pack, dim3(p.packGx, l.packRows), dim3(256), 0, st, bs->poolStage, bs->g.voxels, bs->g.nb[0], bs->g.nb[1],
+                               s.obDev + B + 2 * l.packFirst, out);
             rc = launch_status("pool_pack");
         }
+        if (rc != 0) break;
     }
-    if (passes.size() > 1) { hipEventRecord(bs->stageDone, st); bs->stagePending = true; }
+    if (p.staged) { hipEventRecord(bs->stageDone, st); bs->stagePending = true; }
     hipEventRecord(bs->ev[6], st);
     hipEventRecord(s.done, st);
     s.pending = true;
