@@ -260,7 +260,8 @@ vr_status vr_brickset_decode_range(vr_brickset *bs, int32_t cut_depth, uint8_t *
  * terminating 3 included, only what is left is written and the other cells are 0,
  * at every cut (a cut stops the scalar updates, not the halvings).
  * A stream that ends early, has tokens left over or ends inside a grown branch is
- * VR_ERR_FORMAT and leaves the set as it was.
+ * VR_ERR_FORMAT and leaves the set as it was.  Every status other than VR_OK and a
+ * device error (VR_ERR_NO_DEVICE) leaves the set unchanged, VR_ERR_OOM included.
  * Extents that the tiled decoders serve: k_decode_region and k_decode_quad hold the
  * grown-branch distances (map entries origTreeDepth + 1 .. + 7) as the constants
  * 64 >> i, so a brick whose map says otherwise is decoded by the walking kernel,

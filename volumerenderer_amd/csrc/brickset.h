@@ -127,7 +127,6 @@ struct BrickSet {
     int32_t *compactOverflow = nullptr;       // device flag: the streams did not fit compactCap (nothing was written; the host regrows and repeats)
     std::vector<unsigned long long> hostBrickOff;
     bool foreign = false;       // stream installed by set_tree/open (no encoder state)
-    std::vector<int64_t> openTreeBytes; // per brick: tree.bits size as the reference's open() would have it
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // MidRangeTree: the half-range stream's level loop runs on a stream of its own beside the mid stream's (fork / join
     // by events around the two compress_stream calls), with its own partial-sum and estimator scratch

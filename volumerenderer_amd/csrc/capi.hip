@@ -172,7 +172,6 @@ static vr_status alloc_encoder_buffers(BrickSet &b, const BuildPlan &plan)
         HIPCHK(hipMalloc(&b.blockErrR, 3 * B * (size_t)b.nErrBlk * sizeof(unsigned long long)));
         HIPCHK(hipMalloc(&b.estSummR, B * (size_t)b.estSummStride * 128));
     }
-    b.nEmitBlk = (((int64_t)1 << b.D) + 255) / 256;
     HIPCHK(hipMalloc(&b.blockL1, B * (size_t)b.nEmitBlk * sizeof(unsigned long long)));
     // (BuildPlan's contract: the flags exist exactly when the build is fused, the range stream's for a MidRangeTree)
     if (plan.fused) HIPCHK(hipMalloc(&b.blockFlag, B * (size_t)plan.boxes));
@@ -400,6 +399,7 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
         if (gappedBytes > b.treeCap) b.treeCap = gappedBytes;
     }
     b.nIdx = (int64_t)1 << b.Ds;
+    b.nEmitBlk = (b.leafStride + 255) / 256;
     make_plans(b.g, b.K, b.generalGeom, b.idx64, b.treeCap, b.tile, b.region, b.pyr12);
     vr_status rc = alloc_stream2(b, b.mid);
     if (rc == VR_OK) {
@@ -423,7 +423,6 @@ vr_status vr_brickset_create(vr_brickset **out, int32_t num_bricks, const int64_
     }
     if (rc != VR_OK) { vr_brickset_destroy(h); return rc; }
     b.hostCtrl.resize(b.B);
-    b.openTreeBytes.assign(b.B, -1);
     *out = h;
     return VR_OK;
 }
@@ -506,7 +505,6 @@ vr_status vr_brickset_build(vr_brickset *h, const uint8_t *vox, void *stream)
     b.hostCtrlValid = false;
     b.hostBrickOff.clear();
     b.foreign = false;
-    std::fill(b.openTreeBytes.begin(), b.openTreeBytes.end(), -1);
     b.plan = plan;
     if (encode_launch(&b, b.plan, vox, (hipStream_t)stream) != 0) return VR_ERR_NO_DEVICE;
     b.built = true;
@@ -590,6 +588,17 @@ static vr_status contiguous_stream(BrickSet &b, Stream2 &s, int brick, const uin
         if (attempt == 1) return VR_ERR_STATE;
     }
     *ptr = s.treeCompact + (size_t)b.hostBrickOff[(size_t)brick];
+    return VR_OK;
+}
+
+// the tokens' bytes of a brick's contiguous stream in a host vector (after sync_ctrl)
+static vr_status download_stream(BrickSet &b, Stream2 &s, int brick, std::vector<uint8_t> &out)
+{
+    const uint8_t *src = nullptr;
+    const vr_status rc = contiguous_stream(b, s, brick, &src);
+    if (rc != VR_OK) return rc;
+    out.resize((size_t)(((int64_t)b.hostCtrl[(size_t)brick].numActive + 3) / 4));
+    HIPCHK(hipMemcpy(out.data(), src, out.size(), hipMemcpyDeviceToHost));
     return VR_OK;
 }
 
@@ -884,145 +893,150 @@ vr_status vr_lod_select(const vr_camera *cam, const vr_render_params *P, int32_t
     return VR_OK;
 }
 
-vr_status vr_brickset_set_tree(vr_brickset *h, int32_t brick, const uint8_t *tree, int64_t tree_bytes,
-                               int64_t num_active, const uint8_t *dmap, int32_t map_len)
+// ---- an install, in the order of a build: plan (host_plan.h make_install_plan: every refusal), the host pass over each
+// stream or table (VR_ERR_FORMAT), ensure every buffer the plan's `needs` names (VR_ERR_OOM), and only then the first
+// write to the set or to device memory.  A return up to there leaves the set as it was.
+static InstallInputs install_inputs(const BrickSet &b, InstallEngine engine, int32_t count, const int32_t *bricks, const vr_tree_desc *descs)
 {
-    if (!h || !tree || !dmap || brick < 0 || brick >= h->s.B) return VR_ERR_INVALID;
-    BrickSet &b = h->s;
-    if (map_len < b.maxDepth + 1 || num_active <= 0) return VR_ERR_INVALID;
-    if (num_active >= (1ll << 32)) return VR_ERR_UNSUPPORTED;      // the host-side index of a foreign stream is 32-bit
-    if (b.built && !b.foreign) return VR_ERR_STATE;                // streams are installed into a fresh set, not beside built trees
-    const int64_t need = (num_active + 3) / 4;
-    if (tree_bytes < need || need > b.treeCap) return VR_ERR_FORMAT;
-    std::vector<uint32_t> offs;
-    std::vector<uint8_t> vals, fine, val3;
-    if (build_index_from_stream(b.D, b.Ds, b.K, b.nIdx, tree, num_active, dmap, offs, vals, fine, val3) != 0) return VR_ERR_FORMAT;
-    // the fine decoders take the grown-branch distances as the constants the reference writes (R.cpp:94-97); a
-    // file that says otherwise is decoded by the walking kernel, which reads them from the map
-    for (int i = 0; i < VR_CHAIN_LEVELS; ++i)
-        if (dmap[b.D + 1 + i] != (uint8_t)(64 >> i)) { fine.clear(); val3.clear(); }
-    if (!b.built) { // first foreign tree: other bricks stay empty until set
-        b.fineHas.assign((size_t)b.B, 1);   // (their index is all "pruned": no counts are read)
-        fine_has_changed(b);
-        HIPCHK(hipMemset(b.mid.ctrl, 0, (size_t)b.B * sizeof(Ctrl)));
-        std::vector<uint32_t> dead((size_t)b.B * b.nIdx, VR_IDX_DEAD);
-        HIPCHK(hipMemcpy(b.idxOff, dead.data(), dead.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(b.idxVal, 0, (size_t)b.B * b.nIdx));
-        for (auto &c : b.hostCtrl) memset(&c, 0, sizeof(Ctrl));
-    } else {
-        vr_status rc = sync_ctrl(b);
-        if (rc != VR_OK) return rc;
+    InstallInputs in{};
+    in.D = b.D; in.Ds = b.Ds; in.K = b.K; in.B = b.B; in.maxDepth = b.maxDepth; in.variant = b.variant;
+    in.nIdx = b.nIdx; in.treeCap = b.treeCap;
+    in.idx64 = b.idx64; in.built = b.built; in.foreign = b.foreign;
+    in.engine = engine; in.count = count; in.bricks = bricks; in.descs = descs;
+    return in;
+}
+
+// a new idxTop is zero-filled: entry 0 of a heap, and the heap of a brick never installed, are never written otherwise
+static vr_status ensure_install_buffers(BrickSet &b, const InstallPlan &p)
+{
+    const size_t B = (size_t)b.B, nIdx = (size_t)b.nIdx;
+    const InstallNeeds &n = p.needs;
+    if (n.idxTop && !b.idxTop) {
+        if (!ensure_dev(b.idxTop, B * nIdx * 2)) { (void)hipGetLastError(); return VR_ERR_OOM; }
+        if (hipMemset(b.idxTop, 0, B * nIdx * 2) != hipSuccess) { hipFree(b.idxTop); b.idxTop = nullptr; return VR_ERR_NO_DEVICE; }
     }
-    Ctrl &c = b.hostCtrl[brick];
-    memset(&c, 0, sizeof(Ctrl));
-    c.numActive = (unsigned long long)num_active;
-    memcpy(c.distanceMap, dmap, (size_t)b.maxDepth + 1);
-    HIPCHK(hipMemcpy(b.mid.ctrl + brick, &c, sizeof(Ctrl), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(b.mid.tree + (size_t)brick * b.treeCap, 0, (size_t)b.treeCap));
-    HIPCHK(hipMemcpy(b.mid.tree + (size_t)brick * b.treeCap, tree, (size_t)need, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b.idxOff + (size_t)brick * b.nIdx, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b.idxVal + (size_t)brick * b.nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice));
+    if ((n.instOff && !ensure_dev(b.instOff, B * (size_t)p.nBlk * sizeof(uint32_t))) || (n.instFlag && !ensure_dev(b.instFlag, B * sizeof(int32_t))) ||
+        (n.instList && !ensure_dev(b.instList, B * sizeof(int32_t))) || (n.fineIdx && !ensure_dev(b.fineIdx, B * nIdx * 16)) ||
+        (n.idxVal3 && !ensure_dev(b.idxVal3, B * nIdx * 8)) || (n.idxBase && !ensure_dev(b.idxBase, B * (size_t)b.nEmitBlk * sizeof(unsigned long long)))) {
+        (void)hipGetLastError();
+        return VR_ERR_OOM;
+    }
+    return VR_OK;
+}
+
+// The whole set to "never installed": host controls zero, every index offset dead, index scalars and side-cars zero
+// (k_index_reset over all bricks, on st).  The device's controls follow with the caller's upload of hostCtrl, whole.
+static vr_status never_installed(BrickSet &b, hipStream_t st)
+{
+    for (auto &c : b.hostCtrl) memset(&c, 0, sizeof(Ctrl));
+    b.fineHas.assign((size_t)b.B, 1);       // (every offset is dead: no counts are read)
+    return index_reset_launch(&b, nullptr, b.B, nullptr, false, st) == 0 ? VR_OK : VR_ERR_NO_DEVICE;
+}
+
+// the one place a set becomes one of installed streams
+static void mark_installed(BrickSet &b)
+{
     b.built = true;
     b.hostCtrlValid = true;
     b.foreign = true;
     b.gapped = false;          // an installed stream is the contiguous one; its index points into it
-    if (b.idx64) {      // absolute 32-bit offsets from the host parse: bases are zero
-        if (!b.idxBase) { b.nEmitBlk = (((int64_t)1 << b.D) + 255) / 256; HIPCHK(hipMalloc(&b.idxBase, (size_t)b.B * b.nEmitBlk * sizeof(unsigned long long))); }
-        HIPCHK(hipMemset(b.idxBase, 0, (size_t)b.B * b.nEmitBlk * sizeof(unsigned long long)));
-    }
-    if ((int)b.fineHas.size() != b.B) b.fineHas.assign((size_t)b.B, 0);
-    b.fineHas[(size_t)brick] = 0;
+    if (b.fineHas.size() != (size_t)b.B) b.fineHas.assign((size_t)b.B, 0);
+    if (b.hostTree.size() != (size_t)b.B) b.hostTree.assign((size_t)b.B, std::vector<uint8_t>());
+}
+
+// the buffers, then the first writes of an install: a fresh set starts out never installed, any other brings its host controls up to date
+static vr_status begin_install(BrickSet &b, const InstallPlan &p, hipStream_t st)
+{
+    vr_status rc = ensure_install_buffers(b, p);
+    if (rc == VR_OK) rc = p.firstInstall ? never_installed(b, st) : sync_ctrl(b);
+    if (rc == VR_OK) mark_installed(b);
+    return rc;
+}
+
+// a brick's new stream on the host: its control block; no host bytes and no fine side-car until the engine says so
+static void record_brick(BrickSet &b, size_t br, const vr_tree_desc &d)
+{
+    Ctrl &c = b.hostCtrl[br];
+    memset(&c, 0, sizeof(Ctrl));
+    c.numActive = (unsigned long long)d.num_active;
+    memcpy(c.distanceMap, d.distance_map, (size_t)b.maxDepth + 1);
+    std::vector<uint8_t>().swap(b.hostTree[br]);
+    b.fineHas[br] = 0;
+}
+
+// the host-parsed engine: blocking copies; the stream's bytes are kept for cuts above depth Ds
+vr_status vr_brickset_set_tree(vr_brickset *h, int32_t brick, const uint8_t *tree, int64_t tree_bytes,
+                               int64_t num_active, const uint8_t *dmap, int32_t map_len)
+{
+    if (!h) return VR_ERR_INVALID;
+    BrickSet &b = h->s;
+    const vr_tree_desc d = {tree, tree_bytes, num_active, dmap, map_len, nullptr, nullptr};
+    const InstallPlan p = make_install_plan(install_inputs(b, InstallEngine::HOST_PARSE, 1, &brick, &d));
+    if (p.status != VR_OK) return (vr_status)p.status;
+    const InstallBrick &pb = p.brick[0];
+    std::vector<uint32_t> offs;
+    std::vector<uint8_t> vals, fine, val3;
+    if (build_index_from_stream(b.D, b.Ds, b.K, b.nIdx, tree, num_active, dmap, offs, vals, fine, val3) != 0) return VR_ERR_FORMAT;
+    const vr_status rc = begin_install(b, p, nullptr);      // (the null stream: in front of the blocking copies)
+    if (rc != VR_OK) return rc;
+    const size_t br = (size_t)brick, nIdx = (size_t)b.nIdx;
+    record_brick(b, br, d);
     fine_has_changed(b);
-    if (!fine.empty()) {
-        if (!b.fineIdx) HIPCHK(hipMalloc(&b.fineIdx, (size_t)b.B * b.nIdx * 16));
-        HIPCHK(hipMemcpy(b.fineIdx + (size_t)brick * b.nIdx * 16, fine.data(), fine.size(), hipMemcpyHostToDevice));
-        if (!b.idxVal3) HIPCHK(hipMalloc(&b.idxVal3, (size_t)b.B * b.nIdx * 8));
-        HIPCHK(hipMemcpy(b.idxVal3 + (size_t)brick * b.nIdx * 8, val3.data(), val3.size(), hipMemcpyHostToDevice));
-        b.fineHas[(size_t)brick] = 1;
+    if (p.firstInstall) HIPCHK(hipMemcpy(b.mid.ctrl, b.hostCtrl.data(), (size_t)b.B * sizeof(Ctrl), hipMemcpyHostToDevice));
+    else HIPCHK(hipMemcpy(b.mid.ctrl + br, &b.hostCtrl[br], sizeof(Ctrl), hipMemcpyHostToDevice));
+    uint8_t *slot = b.mid.tree + br * (size_t)b.treeCap;
+    HIPCHK(hipMemset(slot, 0, (size_t)b.treeCap));
+    HIPCHK(hipMemcpy(slot, tree, (size_t)pb.need, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b.idxOff + br * nIdx, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b.idxVal + br * nIdx, vals.data(), vals.size(), hipMemcpyHostToDevice));
+    if (p.needs.idxBase) HIPCHK(hipMemset(b.idxBase, 0, (size_t)b.B * b.nEmitBlk * sizeof(unsigned long long)));
+    if (install_fine_has(pb, false)) {
+        HIPCHK(hipMemcpy(b.fineIdx + br * nIdx * 16, fine.data(), fine.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.idxVal3 + br * nIdx * 8, val3.data(), val3.size(), hipMemcpyHostToDevice));
+        b.fineHas[br] = 1;
         fine_has_changed(b);
     }
-    if ((int)b.hostTree.size() != b.B) b.hostTree.assign((size_t)b.B, std::vector<uint8_t>());
-    b.hostTree[brick].assign(tree, tree + need);
+    b.hostTree[br].assign(tree, tree + pb.need);
     return VR_OK;
 }
 
-// vrhip.h "compressed brick-set archives".  Everything that can refuse the call is checked first; then the copies and
-// the kernels of kd_index.hip go to `stream`, and one synchronisation reads the grammar flags.
+// vrhip.h "compressed brick-set archives": the device engine.  The copies and the kernels of kd_index.hip go to
+// `stream`, and one synchronisation reads the grammar flags.  No host bytes are kept: cuts above depth Ds come from idxTop.
 vr_status vr_brickset_set_trees(vr_brickset *h, int32_t count, const int32_t *bricks, const vr_tree_desc *descs, void *stream)
 {
-    if (!h || !bricks || !descs || count < 1 || count > h->s.B) return VR_ERR_INVALID;
+    if (!h) return VR_ERR_INVALID;
     BrickSet &b = h->s;
-    if (b.variant == VR_VARIANT_MIDRANGE || b.idx64) return VR_ERR_UNSUPPORTED;
-    if (b.built && !b.foreign) return VR_ERR_STATE;
-    const int Dc = block_depth(b.D);
-    const size_t nBlk = (size_t)1 << Dc, B = (size_t)b.B;
-    std::vector<uint8_t> named(B, 0);
-    for (int i = 0; i < count; ++i) {
-        const vr_tree_desc &d = descs[i];
-        if (bricks[i] < 0 || bricks[i] >= b.B || named[(size_t)bricks[i]]) return VR_ERR_INVALID;
-        named[(size_t)bricks[i]] = 1;
-        if (!d.tree || !d.distance_map || (d.block_off == nullptr) != (d.top_val == nullptr)) return VR_ERR_INVALID;
-        if (d.map_len < b.maxDepth + 1 || d.num_active <= 0) return VR_ERR_INVALID;
-        if (d.num_active >= (1ll << 32)) return VR_ERR_UNSUPPORTED;
-        const int64_t need = (d.num_active + 3) / 4;
-        if (d.tree_bytes < need || need > b.treeCap) return VR_ERR_FORMAT;
-    }
+    const InstallPlan p = make_install_plan(install_inputs(b, InstallEngine::DEVICE_INDEX, count, bricks, descs));
+    if (p.status != VR_OK) return (vr_status)p.status;
+    const size_t nBlk = (size_t)p.nBlk, B = (size_t)b.B;
     std::vector<std::vector<uint32_t>> madeOff((size_t)count);
     std::vector<std::vector<uint8_t>> madeTop((size_t)count);
     std::atomic<int> bad(0);
     parallel_for(count, [&](int i) {
         const vr_tree_desc &d = descs[i];
-        if (d.block_off) { if (!block_table_ok(b.D, d.num_active, d.block_off)) bad = 1; return; }
+        if (p.brick[(size_t)i].pass == HostPass::TABLE_CHECK) { if (!block_table_ok(b.D, d.num_active, d.block_off)) bad = 1; return; }
         madeOff[(size_t)i].resize(nBlk);
         madeTop[(size_t)i].resize(2 * nBlk);
         if (block_table_from_stream(b.D, d.tree, d.num_active, d.distance_map, madeOff[(size_t)i].data(), madeTop[(size_t)i].data()) != 0) bad = 1;
     });
     if (bad) return VR_ERR_FORMAT;
-    const bool wantFine = b.K == 6 && b.D >= 6;
-    if (!b.idxTop) {
-        HIPCHK(hipMalloc(&b.idxTop, B * (size_t)b.nIdx * 2));
-        HIPCHK(hipMemset(b.idxTop, 0, B * (size_t)b.nIdx * 2));
-    }
-    if (!b.instOff) HIPCHK(hipMalloc(&b.instOff, B * nBlk * sizeof(uint32_t)));
-    if (!b.instFlag) HIPCHK(hipMalloc(&b.instFlag, B * sizeof(int32_t)));
-    if (!b.instList) HIPCHK(hipMalloc(&b.instList, B * sizeof(int32_t)));
-    if (wantFine && !b.fineIdx) HIPCHK(hipMalloc(&b.fineIdx, B * (size_t)b.nIdx * 16));
-    if (wantFine && !b.idxVal3) HIPCHK(hipMalloc(&b.idxVal3, B * (size_t)b.nIdx * 8));
     hipStream_t st = (hipStream_t)stream;
-    if (!b.built) {     // a fresh set: every brick starts out never installed (as vr_brickset_set_tree's first call)
-        b.fineHas.assign(B, 1);
-        for (auto &c : b.hostCtrl) memset(&c, 0, sizeof(Ctrl));
-        if (index_reset_launch(&b, nullptr, b.B, nullptr, false, st) != 0) return VR_ERR_NO_DEVICE;
-        b.built = true;
-        b.hostCtrlValid = true;
-    } else {
-        vr_status rc = sync_ctrl(b);
-        if (rc != VR_OK) return rc;
-    }
-    b.foreign = true;
-    b.gapped = false;
+    const vr_status rc = begin_install(b, p, st);
+    if (rc != VR_OK) return rc;
     b.lastStream = stream;
-    if (b.fineHas.size() != B) b.fineHas.assign(B, 0);
-    if (b.hostTree.size() != B) b.hostTree.assign(B, std::vector<uint8_t>());
     for (int i = 0; i < count; ++i) {
         const vr_tree_desc &d = descs[i];
+        const InstallBrick &pb = p.brick[(size_t)i];
         const size_t br = (size_t)bricks[i];
-        Ctrl &c = b.hostCtrl[br];
-        memset(&c, 0, sizeof(Ctrl));
-        c.numActive = (unsigned long long)d.num_active;
-        memcpy(c.distanceMap, d.distance_map, (size_t)b.maxDepth + 1);
-        std::vector<uint8_t>().swap(b.hostTree[br]);       // no host copy: cuts above depth Ds come from idxTop
-        b.openTreeBytes[br] = -1;
-        const int64_t need = (d.num_active + 3) / 4;
-        // the decoders read past a stream's last token, never further than VR_TREE_TAIL bytes
-        const int64_t tail = std::min<int64_t>(VR_TREE_TAIL, b.treeCap - need);
+        record_brick(b, br, d);
         uint8_t *slot = b.mid.tree + br * (size_t)b.treeCap;
-        HIPCHK(hipMemcpyAsync(slot, d.tree, (size_t)need, hipMemcpyHostToDevice, st));
-        if (tail > 0) HIPCHK(hipMemsetAsync(slot + need, 0, (size_t)tail, st));
+        HIPCHK(hipMemcpyAsync(slot, d.tree, (size_t)pb.need, hipMemcpyHostToDevice, st));
+        if (pb.tail > 0) HIPCHK(hipMemsetAsync(slot + pb.need, 0, (size_t)pb.tail, st));
         HIPCHK(hipMemcpyAsync(b.instOff + br * nBlk, d.block_off ? d.block_off : madeOff[(size_t)i].data(), nBlk * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         // (the table's heap IS the top of the brick's: the same layout, depths 0 .. Dc)
         HIPCHK(hipMemcpyAsync(b.idxTop + br * (size_t)b.nIdx * 2, d.top_val ? d.top_val : madeTop[(size_t)i].data(), 2 * nBlk, hipMemcpyHostToDevice, st));
     }
+    fine_has_changed(b);
     HIPCHK(hipMemcpyAsync(b.mid.ctrl, b.hostCtrl.data(), B * sizeof(Ctrl), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b.instList, bricks, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(b.instFlag, 0, (size_t)count * sizeof(int32_t), st));
@@ -1035,9 +1049,7 @@ vr_status vr_brickset_set_trees(vr_brickset *h, int32_t count, const int32_t *br
     const bool failed = std::find_if(flags.begin(), flags.end(), [](int32_t f) { return f != 0; }) != flags.end();
     for (int i = 0; i < count; ++i) {
         const size_t br = (size_t)bricks[i];
-        bool fine = wantFine && !failed;
-        for (int k = 0; k < VR_CHAIN_LEVELS; ++k) fine = fine && descs[i].distance_map[b.D + 1 + k] == (uint8_t)(64 >> k);
-        b.fineHas[br] = failed ? 1 : (fine ? 1 : 0);        // (a brick never installed: no counts are read)
+        b.fineHas[br] = install_fine_has(p.brick[(size_t)i], failed);
         if (failed) memset(&b.hostCtrl[br], 0, sizeof(Ctrl));
     }
     fine_has_changed(b);
@@ -1153,12 +1165,9 @@ vr_status vr_brickset_save_set(vr_brickset *h, const char *path)
         const Ctrl &c = b.hostCtrl[(size_t)br];
         if (c.numActive == 0ull) continue;
         if (c.numActive >= (1ull << 32)) return VR_ERR_UNSUPPORTED;
-        const uint8_t *src = nullptr;
-        rc = contiguous_stream(b, b.mid, br, &src);
+        rc = download_stream(b, b.mid, br, trees[(size_t)br]);
         if (rc != VR_OK) return rc;
         if (b.hostCtrl[(size_t)br].emitOverflow) return VR_ERR_STATE;
-        trees[(size_t)br].resize((size_t)(((int64_t)c.numActive + 3) / 4));
-        HIPCHK(hipMemcpy(trees[(size_t)br].data(), src, trees[(size_t)br].size(), hipMemcpyDeviceToHost));
     }
     std::atomic<int> bad(0);
     parallel_for(b.B, [&](int br) {
@@ -1188,22 +1197,16 @@ vr_status vr_brickset_save(vr_brickset *h, int32_t brick, const char *path)
     const Ctrl &c = b.hostCtrl[brick];
     const int64_t bytes = ((int64_t)c.numActive + 3) / 4;
     if (bytes == 0) return VR_ERR_STATE;
-    std::vector<uint8_t> tree((size_t)bytes);
-    const uint8_t *baseM = nullptr;
-    rc = contiguous_stream(b, b.mid, brick, &baseM);
+    std::vector<uint8_t> tree, treeR;
+    rc = download_stream(b, b.mid, brick, tree);
     if (rc != VR_OK) return rc;
-    HIPCHK(hipMemcpy(tree.data(), baseM, (size_t)bytes, hipMemcpyDeviceToHost));
     // MidRangeTree::save (M.cpp:753-785): same header, then distanceMap, distanceMap_range, tree, tree_range
     const bool mrFile = b.variant == VR_VARIANT_MIDRANGE;
-    std::vector<uint8_t> treeR;
     Ctrl cr;
     if (mrFile) {
         if (b.foreign && !b.foreignRange) return VR_ERR_STATE;
-        treeR.resize((size_t)bytes);
-        const uint8_t *baseR = nullptr;
-        rc = contiguous_stream(b, b.rng, brick, &baseR);
+        rc = download_stream(b, b.rng, brick, treeR);     // (as many tokens as the mid stream's)
         if (rc != VR_OK) return rc;
-        HIPCHK(hipMemcpy(treeR.data(), baseR, (size_t)bytes, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(&cr, b.rng.ctrl + brick, sizeof(Ctrl), hipMemcpyDeviceToHost));
     }
     FILE *f = fopen(path, "wb");
@@ -1217,6 +1220,20 @@ vr_status vr_brickset_save(vr_brickset *h, int32_t brick, const char *path)
               (!mrFile || fwrite(treeR.data(), 1, (size_t)bytes, f) == (size_t)bytes);
     fclose(f);
     return ok ? VR_OK : VR_ERR_IO;
+}
+
+// a MidRangeTree file's half-range stream, beside the mid stream vr_brickset_set_tree installed (a 1-brick set: open_file)
+static vr_status install_range_stream(BrickSet &b, const uint8_t *tree, int64_t bytes, int64_t numActive, const uint8_t *dmap)
+{
+    if (!ensure_dev(b.rng.ctrl, (size_t)b.B * sizeof(Ctrl)) || !ensure_dev(b.rng.tree, (size_t)b.B * b.treeCap)) { (void)hipGetLastError(); return VR_ERR_OOM; }
+    Ctrl cr;
+    memset(&cr, 0, sizeof(Ctrl));
+    cr.numActive = (unsigned long long)numActive;
+    memcpy(cr.distanceMap, dmap, (size_t)b.maxDepth + 1);
+    if (hipMemcpy(b.rng.ctrl, &cr, sizeof(Ctrl), hipMemcpyHostToDevice) != hipSuccess || hipMemset(b.rng.tree, 0, (size_t)b.treeCap) != hipSuccess ||
+        hipMemcpy(b.rng.tree, tree, (size_t)bytes, hipMemcpyHostToDevice) != hipSuccess) return VR_ERR_NO_DEVICE;
+    b.foreignRange = true;
+    return VR_OK;
 }
 
 // VolumeKdtree::open (R.cpp:554-594) and, mr, MidRangeTree files (M.cpp:753-785).  A missing file is an error code here
@@ -1251,25 +1268,8 @@ static vr_status open_file(vr_brickset **out, const char *path, bool mr)
     BrickSet &b = h->s;
     if (b.D != hd.origDepth || b.maxDepth != mtd) { vr_brickset_destroy(h); return VR_ERR_FORMAT; }
     rc = vr_brickset_set_tree(h, 0, tree, T, na, dmap, (int32_t)mtd + 1);
+    if (rc == VR_OK && mr) rc = install_range_stream(b, treeR, T, na, dmapR);
     if (rc != VR_OK) { vr_brickset_destroy(h); return rc; }
-    if (!mr) {
-        // R.cpp:581 subtracts only three of the four int64 fields: tree.bits ends up 8 bytes
-        // longer than what was saved (SURVEY C-6); numActiveNodes is authoritative.
-        b.openTreeBytes[0] = fileSize - (2 * 24 + 2 * 4 + mtd + 1 + 3 * 8);
-    } else {
-        Ctrl cr;
-        memset(&cr, 0, sizeof(Ctrl));
-        cr.numActive = (unsigned long long)na;
-        memcpy(cr.distanceMap, dmapR, (size_t)mtd + 1);
-        hipError_t e = hipSuccess;
-        if (!b.rng.ctrl) e = hipMalloc(&b.rng.ctrl, sizeof(Ctrl));
-        if (e == hipSuccess && !b.rng.tree) e = hipMalloc(&b.rng.tree, (size_t)b.treeCap);
-        if (e == hipSuccess) e = hipMemcpy(b.rng.ctrl, &cr, sizeof(Ctrl), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(b.rng.tree, 0, (size_t)b.treeCap);
-        if (e == hipSuccess) e = hipMemcpy(b.rng.tree, treeR, (size_t)T, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { vr_brickset_destroy(h); return VR_ERR_NO_DEVICE; }
-        b.foreignRange = true;
-    }
     *out = h;
     return VR_OK;
 }

@@ -305,6 +305,51 @@ bool block_table_ok(int D, int64_t numActive, const uint32_t *blockOff)
     return true;
 }
 
+// ---- installing streams ----
+StreamCheck check_stream(int maxDepth, int64_t treeCap, const vr_tree_desc &d)
+{
+    if (!d.tree || !d.distance_map || (d.block_off == nullptr) != (d.top_val == nullptr)) return {VR_ERR_INVALID, 0, 0};
+    if (d.map_len < maxDepth + 1 || d.num_active <= 0) return {VR_ERR_INVALID, 0, 0};
+    if (d.num_active >= (1ll << 32)) return {VR_ERR_UNSUPPORTED, 0, 0};    // token offsets of an installed stream are 32-bit
+    const int64_t need = (d.num_active + 3) / 4;
+    if (d.tree_bytes < need || need > treeCap) return {VR_ERR_FORMAT, 0, 0};
+    return {VR_OK, need, std::min<int64_t>(VR_TREE_TAIL, treeCap - need)};
+}
+
+InstallPlan make_install_plan(const InstallInputs &in)
+{
+    InstallPlan p{};
+    const bool device = in.engine == InstallEngine::DEVICE_INDEX;
+    const bool beside = in.built && !in.foreign;    // streams are installed into a fresh set, not beside built trees
+    p.firstInstall = !in.built;
+    p.nBlk = (int64_t)1 << block_depth(in.D);
+    p.wantFine = in.K == 6 && in.D >= 6;
+    const auto refuse = [&](int status) { p.status = status; p.brick.clear(); return p; };
+    if (!in.bricks || !in.descs || in.count < 1 || in.count > in.B) return refuse(VR_ERR_INVALID);
+    if (device && (in.variant == VR_VARIANT_MIDRANGE || in.idx64)) return refuse(VR_ERR_UNSUPPORTED);
+    if (device && beside) return refuse(VR_ERR_STATE);
+    std::vector<uint8_t> named((size_t)in.B, 0);
+    bool anyFine = false;
+    for (int i = 0; i < in.count; ++i) {
+        const int32_t br = in.bricks[i];
+        if (br < 0 || br >= in.B || named[(size_t)br]) return refuse(VR_ERR_INVALID);
+        named[(size_t)br] = 1;
+        const vr_tree_desc &d = in.descs[i];
+        const StreamCheck c = check_stream(in.maxDepth, in.treeCap, d);
+        if (beside && (c.status == VR_OK || c.status == VR_ERR_FORMAT)) return refuse(VR_ERR_STATE);
+        if (c.status != VR_OK) return refuse(c.status);
+        const bool fineOk = p.wantFine && std_chain_distances(d.distance_map, in.D);
+        anyFine = anyFine || fineOk;
+        p.brick.push_back({c.need, c.tail, fineOk,
+                           !device ? HostPass::BUILD_INDEX : (d.block_off ? HostPass::TABLE_CHECK : HostPass::TABLE_FROM_STREAM)});
+    }
+    // the host parse uploads side-cars only where it made them; the kernels write them wherever the geometry has them
+    p.needs.idxTop = p.needs.instOff = p.needs.instFlag = p.needs.instList = device;
+    p.needs.fineIdx = p.needs.idxVal3 = device ? p.wantFine : anyFine;
+    p.needs.idxBase = !device && in.idx64;      // absolute 32-bit offsets from the host parse: the bases are zero
+    return p;
+}
+
 // ---- the brick-set archive ----
 static const char ARCHIVE_MAGIC[8] = {'V', 'R', 'B', 'S', 'E', 'T', '\r', '\n'};
 struct ArchiveHeader { char magic[8]; uint32_t version, variant; int64_t dims[3]; int32_t numBricks, D, maxDepth; uint32_t zero; int64_t fileBytes; };

@@ -3,7 +3,8 @@
 // plan of a build (BuildPlan: every kernel, grid and brick range of vr_brickset_build), the plan of a decode call (DecodePlan /
 // LodPlan: the kernel, grids, class lists and buffers of the uniform and per-brick decodes), the walker of foreign streams and the
 // file header, the block tables and per-block index walker of installed streams (shared with kd_index.hip's kernel) and the
-// brick-set archive's parser and writer; and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
+// brick-set archive's parser and writer, the plan of an install (InstallPlan: the refusals, host passes and buffers of
+// vr_brickset_set_tree / _set_trees); and the error-bounded selection of cuts, vr_lod_select_error (declared in vrhip.h, defined in
 // host_plan.cpp: a rule on a host table).  Includes no HIP header: compiles with a plain C++17 compiler (tests/host_plan_main.cpp links it
 // directly) and with hipcc.
 #pragma once
@@ -24,6 +25,7 @@
 #define VR_IDX_DEAD 0xFFFFFFFFu
 
 struct vr_pool_entry;       // vrhip.h
+struct vr_tree_desc;
 
 namespace vr {
 
@@ -372,8 +374,8 @@ bool block_table_ok(int D, int64_t numActive, const uint32_t *blockOff);
 // token `pos` of a stream read as aligned 32-bit words, sixteen tokens each (little-endian: cget's packing)
 VR_HD inline int wget(const uint32_t *W, uint32_t pos) { return (int)((W[pos >> 4] >> ((pos & 15u) * 2u)) & 3u); }
 
-// One brick's index arrays.  fine / val3 null: the brick gets none (K != 6, D < 6 or a map with other grown-branch
-// distances than 64 >> i).  top: 2 * nIdx bytes, a heap like topVal over depths 0 .. Ds.
+// One brick's index arrays.  fine / val3 null: the brick gets none (K != 6, D < 6 or a map that fails
+// std_chain_distances).  top: 2 * nIdx bytes, a heap like topVal over depths 0 .. Ds.
 struct BlockIndexOut { uint32_t *off; uint8_t *val, *fine, *val3, *top; };
 
 // The walker of one block: the index entries below block `blk`, byte for byte what build_index_from_stream gives them
@@ -467,6 +469,59 @@ VR_HD inline int block_gap_walk(const uint32_t *W, uint32_t numActive, int Dc, c
         } else { ++j; path <<= 1; }
     }
 }
+
+// ---- installing streams (capi.hip vr_brickset_set_tree / _set_trees execute it; they decide nothing) ----
+// Every refusal and every buffer of an install from plain inputs.  Two engines fill a brick's decode index: the host
+// parse of vr_brickset_set_tree (build_index_from_stream, uploaded) and kd_index.hip's kernels behind
+// vr_brickset_set_trees, from a block table that is the caller's (block_table_ok checks it) or made here
+// (block_table_from_stream).  Contract with capi.hip: everything in `needs` exists (ensure_install_buffers) before the
+// first write to the set or to device memory.
+
+// The grown-branch distances as the reference writes them (R.cpp:94-97), which the fine decoders hold as constants: a
+// brick whose map says otherwise gets no fine side-car and is decoded by the walking kernel, which reads the map
+VR_HD inline bool std_chain_distances(const uint8_t *dmap, int D)
+{
+    bool ok = true;
+    for (int i = 0; i < VR_CHAIN_LEVELS; ++i) ok = ok && dmap[D + 1 + i] == (uint8_t)(64 >> i);
+    return ok;
+}
+
+// One stream against its set.  status: VR_OK or, in this order, VR_ERR_INVALID (a null stream or map, one table pointer
+// without the other, a short map, no tokens), VR_ERR_UNSUPPORTED (2^32 tokens or more), VR_ERR_FORMAT (fewer bytes than
+// the tokens take, or more than a stream slot holds).  need: the tokens' bytes; tail: the bytes zeroed behind them (the
+// decoders read past a stream's last token, never further than VR_TREE_TAIL bytes: DESIGN.md 3.3).  Both 0 unless VR_OK.
+struct StreamCheck { int status; int64_t need, tail; };
+StreamCheck check_stream(int maxDepth, int64_t treeCap, const vr_tree_desc &d);
+
+enum class InstallEngine { HOST_PARSE, DEVICE_INDEX };      // vr_brickset_set_tree / vr_brickset_set_trees
+enum class HostPass { BUILD_INDEX, TABLE_FROM_STREAM, TABLE_CHECK };    // build_index_from_stream / block_table_from_stream / block_table_ok
+struct InstallInputs {
+    int32_t D, Ds, K, B, maxDepth, variant;
+    int64_t nIdx, treeCap;
+    bool idx64, built, foreign;
+    InstallEngine engine;
+    int32_t count;
+    const int32_t *bricks;          // count
+    const vr_tree_desc *descs;      // count
+};
+struct InstallNeeds { bool idxTop, instOff, instFlag, instList, fineIdx, idxVal3, idxBase; };   // beyond what vr_brickset_create makes
+struct InstallBrick { int64_t need, tail; bool fineOk; HostPass pass; };    // fineOk: wantFine and a map of the standard distances
+struct InstallPlan {
+    // VR_OK or the call's refusal (then nothing below `wantFine` is filled in).  DEVICE_INDEX: a null list or a count
+    // outside 1 .. B (INVALID), a MidRangeTree set or 64-bit offsets (UNSUPPORTED), a built set (STATE), then stream by
+    // stream: a brick out of range or named twice (INVALID), check_stream.  HOST_PARSE: the same per stream, but a built
+    // set's STATE comes behind a stream's INVALID and UNSUPPORTED and in front of its FORMAT, and no variant is refused.
+    int status;
+    bool firstInstall;              // a fresh set: the whole set goes to "never installed" first
+    int64_t nBlk;                   // blocks per brick, 2^block_depth(D)
+    bool wantFine;                  // the set's geometry has the fine side-car (K == 6 and D >= 6)
+    std::vector<InstallBrick> brick;    // per named brick
+    InstallNeeds needs;
+};
+InstallPlan make_install_plan(const InstallInputs &in);
+// a named brick's BrickSet::fineHas when the call ends.  failed: the device found a stream of the call outside the
+// grammar, and every named brick is left never installed (no counts are read: 1)
+inline uint8_t install_fine_has(const InstallBrick &b, bool failed) { return failed || b.fineOk ? 1 : 0; }
 
 // ---- the brick-set archive (layout: vrhip.h "compressed brick-set archives"); parsing and writing need no device ----
 constexpr int VR_ARCHIVE_HEADER_BYTES = 64, VR_ARCHIVE_ENTRY_BYTES = 32;

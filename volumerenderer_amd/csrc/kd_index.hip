@@ -24,14 +24,6 @@ struct IndexArgs {
     int32_t *flags;             // per row
 };
 
-// the standard grown-branch distances (the rule of vr_brickset_set_tree: other maps get no fine counts)
-__device__ __forceinline__ bool std_chain(const uint8_t *dmap, int D)
-{
-    bool ok = true;
-    for (int i = 0; i < VR_CHAIN_LEVELS; ++i) ok = ok && dmap[D + 1 + i] == (uint8_t)(64 >> i);
-    return ok;
-}
-
 // Index entries of the listed bricks back to "never installed": offsets dead, scalars and counts zero.  Not the heap
 // of scalars: its upper levels were just copied from the table and the walkers write every other entry.
 // onlyFlagged: the bricks whose flag is set (flags null: every listed brick), and then the heap and the control
@@ -76,7 +68,7 @@ k_index_from_stream(IndexArgs a)
         const uint32_t *W = (const uint32_t *)(a.tree + (int64_t)brick * a.treeCap);
         const uint32_t *tab = a.instOff + (int64_t)brick * a.nBlk;
         const int Dc = block_depth(a.D);
-        const bool fine = a.fine && a.K == 6 && a.D >= 6 && std_chain(dm, a.D);
+        const bool fine = a.fine && a.K == 6 && a.D >= 6 && std_chain_distances(dm, a.D);    // (host_plan.h: other maps get no fine counts)
         BlockIndexOut o;
         o.off = a.idxOff + (int64_t)brick * a.nIdx;
         o.val = a.idxVal + (int64_t)brick * a.nIdx;
